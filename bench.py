@@ -4,8 +4,14 @@
 Metric: effective TFLOP/s (nnz-FLOPs, 2 * nnz_elements * N per DSD call,
 reference sputnik/block/dsd/dsd_benchmark.cu:113-114) of DSD, block 128,
 M=K=N=4096, fp16 in / fp32 accumulate / fp16 out, at density 0.5 (the
-north-star point); densities 0.1/0.3/0.5/0.9 are reported in "by_density",
-each with its own roofline (MFMA- or HBM-bound by arithmetic intensity).
+north-star point), reported in "by_density" with its roofline (MFMA- or
+HBM-bound by arithmetic intensity). A run without `--full` sets up, warms
+up, times the steps and prints the line; with `--full` the densities
+0.1/0.3/0.9 are timed too (each its own "by_density" entry), and the dense
+anchor, the CPU baseline and the config-1 line below are measured.
+`--dump-outputs DIR` writes what the last timed step computed (the dense C)
+as DIR/c.npy, float32; the inputs depend only on the arguments, so two
+builds can be compared output for output.
 
 One step = one sputnik_dsd_ex call (C-ABI; NN, so no metadata work) over one
 synthetic BCSR matrix already resident in HBM. Protocol as the reference
@@ -29,11 +35,13 @@ matmul the device Transpose runs inside every DSD TN/TT and DDS NN/TN step)
 and transpose (the device Transpose alone).
 
 Extra JSON objects: "roofline" (dominant kernel vs its MFMA or HBM roof),
-"dense_anchor" (torch.matmul -> hipBLASLt on a dense GEMM of the same FLOPs,
-timed beside it: what this GPU's matrix cores reach under the same clocks),
-"cpu_baseline" (the CPU oracle on a bounded sample, 1 thread and all
-allotted threads, rank 0 at N=1), "config1" (BASELINE config 1: the host
-reference matmul at 512^3, 50%), "build" (library source hash vs the tree).
+"build" (library source hash vs the tree) and, for the dsd workload only
+with `--full` (null without it), "dense_anchor" (torch.matmul -> hipBLASLt
+on a dense GEMM of the same FLOPs, timed beside it: what this GPU's matrix
+cores reach under the same clocks), "cpu_baseline" (the CPU oracle on a
+bounded sample, 1 thread and all allotted threads, rank 0 at N=1) and
+"config1" (BASELINE config 1: the host reference matmul at 512^3, 50%).
+The other workloads time their dense anchor with or without `--full`.
 """
 
 import argparse
@@ -100,6 +108,17 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
                     help="per CPU-baseline leg (two legs)")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="dsd: beside the headline, also the other densities "
+                         "of --sweep (by_density), the hipBLASLt dense anchor, "
+                         "the CPU baseline and the config-1 host line. Without "
+                         "it a run sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "computed as DIR/<name>.npy (float32; a fixed seeded "
+                         "sample of rows where an output is large, at most "
+                         "64 MB in all)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) on a node; gloo only for tests that "
                          "run several ranks on one device")
@@ -111,6 +130,9 @@ def parse():
                     help="per-kernel PMC of the sdd_dds / moe / panel workloads "
                          "(scripts/pmc_workload.sh), keyed by workload and build hash")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload in ("sweep", "transpose"):
+        ap.error(f"--dump-outputs: --workload {args.workload} has no "
+                 "floating-point output to write")
     # per-workload defaults: config 3's 64-73 us step and config 5's 200 us
     # step need more steps than the headline's for >= 100 ms of load (config
     # 3: 100 + 100 steps 72.3-73.2 us, 1000 + 1000 steps 64.9 us on one box)
@@ -346,6 +368,9 @@ class DsdProblem:
         self._keep = (ca, cb, cc)
         return lambda: fn(*args)
 
+    def outputs(self):
+        return {"c": self.c_vals.view(self.m, self.n)}
+
 
 def dsd_panel(args, world, rank, device, density, m_total=None, seed_off=0):
     """The rank's row panel of one (world x m)-row BCSR matrix (or m_total
@@ -417,6 +442,31 @@ def time_steps(fn, steps, warmup, world):
     barrier(world)
     torch.cuda.synchronize()
     return start.elapsed_time(end)  # ms, this rank
+
+
+DUMP_BYTES = 48 << 20  # of float32 over every file of a run (the limit is 64 MB)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(outputs, path, rank, world):
+    """--dump-outputs: the arrays the last timed step left on the device,
+    {name: 2-D tensor}, as path/<name>.npy in float32 (<name>_rank<r>.npy at
+    N > 1: every rank writes its own panel). An output over its share of
+    DUMP_BYTES is cut to a sample of whole rows, drawn from a fixed seed, so
+    that two builds write the same rows."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // (world * len(outputs))
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, t in outputs.items():
+        rows, cols = t.shape
+        keep = max(1, share // (cols * 4))
+        if keep < rows:
+            sel = np.sort(rng.choice(rows, size=keep, replace=False))
+            t = t[torch.from_numpy(sel).to(t.device)]
+        if world > 1:
+            name = f"{name}_rank{rank}"
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def _reduce(x, world, op):
@@ -601,6 +651,11 @@ class PairProblem:
         self._keep = (cx, cw, cg, co, cC)
         return lambda: (L.sputnik_sdd(*a1), L.sputnik_dds_ex(*a2))
 
+    def outputs(self):
+        # (the SDD's blocks, one 128-wide block row per array row)
+        return {"sdd_values": self.cv.view(-1, BLOCK),
+                "dds_out": self.out.view(self.dim, self.dim)}
+
 
 class MoeProblem:
     """BASELINE config 4: MegaBlocks dMoE MLP, 8 experts, 8192 tokens,
@@ -664,6 +719,10 @@ class MoeProblem:
         assert L.sputnik_sdd(*a1) == 0 and L.sputnik_dsd_ex(*a2) == 0
         self._keep = (cx, c1, c2, cy, cH)
         return lambda: (L.sputnik_sdd(*a1), L.sputnik_dsd_ex(*a2))
+
+    def outputs(self):
+        return {"h_values": self.hv.view(-1, BLOCK),
+                "y": self.y.view(self.dims[0], self.dims[1])}
 
 
 class OpProblem:
@@ -745,6 +804,12 @@ class OpProblem:
         assert fn(*a) == 0
         self._keep = (cS, cx, co)
         return lambda: fn(*a)
+
+    def outputs(self):
+        if self.op == "sdd":
+            return {"sdd_values": self.sv.view(-1, BLOCK)}
+        d = int(self.S.rows)
+        return {"out": self.out.view(d, d)}
 
 
 class TransposeProblem:
@@ -856,6 +921,8 @@ def run_other(args, world, rank, device, build):
     fn = graph_step(prob) if args.graph else prob.launcher()
     ms = max_over_ranks(time_steps(fn, args.steps, args.warmup, world), world)
     per = ms / args.steps
+    if args.dump_outputs:
+        dump_outputs(prob.outputs(), args.dump_outputs, rank, world)
     flops_all = sum_over_ranks(prob.flops, world)
     extra = {}
     if args.workload == "transpose":
@@ -953,9 +1020,11 @@ def main():
             dist.destroy_process_group()
         return
 
-    # Headline density first, then the sweep.
-    densities = [args.density] + [float(d) for d in args.sweep.split(",")
-                                  if d and float(d) != args.density]
+    # Headline density first, then (--full) the sweep.
+    densities = [args.density]
+    if args.full:
+        densities += [float(d) for d in args.sweep.split(",")
+                      if d and float(d) != args.density]
     results = {}
     head = None
     m_total = args.m if args.scaling == "strong" else args.m * world
@@ -982,6 +1051,8 @@ def main():
                       "nnz_blocks_per_rank": prob.nb, "roofline": roof}
         if head is None:
             head = (prob, per_step, tflops, roof)
+            if args.dump_outputs:
+                dump_outputs(prob.outputs(), args.dump_outputs, rank, world)
         else:
             del prob
         torch.cuda.empty_cache()
@@ -991,7 +1062,7 @@ def main():
     prob, per_step, tflops, roof = head
 
     anchor = None
-    if rank == 0:
+    if rank == 0 and args.full:
         kd = max(BLOCK, int(round(args.k * args.density / BLOCK)) * BLOCK)
         anchor = dense_anchor(prob.m, args.n, kd, args.dtype, device)
         if "tflops" in anchor:
@@ -999,7 +1070,7 @@ def main():
 
     cpu = None
     config1 = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline(prob, args.cpu_seconds)
         config1 = config1_host_reference()
 
@@ -1035,6 +1106,7 @@ def main():
             "cpu_baseline": cpu,
             "config1": config1,
             "graph": args.graph,
+            "full": args.full,
             "build": build,
         })
 

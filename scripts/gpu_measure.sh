@@ -29,7 +29,7 @@ if [ "$SKIP_TESTS" = "0" ]; then
     --timeout 120 --timeout-method thread --junitxml=$OUT/junit.xml; rc=$?
   fatal $rc && exit $rc
 fi
-step bench 300 python bench.py; rc=$?
+step bench 300 python bench.py --full; rc=$?
 fatal $rc && exit $rc
 cd /tmp
 echo "== prof" | tee -a $OUT/steps.log

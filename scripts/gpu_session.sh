@@ -31,7 +31,7 @@ if [ "$TESTS" = "1" ]; then
     --timeout 120 --timeout-method thread --junitxml=$OUT/junit.xml; rc=$?
   fatal $rc && exit $rc
 fi
-step bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5; rc=$?
+step bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full; rc=$?
 fatal $rc && exit $rc
 cd /tmp
 echo "== prof_driver" | tee -a $OUT/steps.log

@@ -17,5 +17,5 @@ cp $O/pmc_workloads.json profiles/pmc_workloads.json
 for w in sdd_dds moe panel; do
   timeout -k 10 300 python bench.py --workload $w > $O/w_$w.json 2> $O/w_$w.err || exit $?
 done
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || exit $?
+timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err || exit $?
 cat $O/w_*.json
