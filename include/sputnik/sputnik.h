@@ -14,5 +14,6 @@
 #include "sputnik/block/dss/dss.h"
 #include "sputnik/block/row_indices/row_indices.h"
 #include "sputnik/block/transpose/transpose.h"
+#include "sputnik/block/workspace.h"
 
 #endif  // SPUTNIK_SPUTNIK_H_

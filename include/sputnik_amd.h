@@ -78,6 +78,83 @@ int sputnik_sdd(const sputnik_matrix_t *a, int transpose_a,
                 const sputnik_matrix_t *b, int transpose_b,
                 const sputnik_block_matrix_t *c, int dtype, void *stream);
 
+/* ---- Caller-owned workspaces for the transposed-B path
+ * SDD NT / TT, and DSD NT over a nearly dense A, transpose B once into a
+ * scratch buffer when B is at least "sdd_bt_min_mib" MiB and the product is
+ * dense enough, then run the N-major kernel. There are two routes.
+ *
+ * Library route (nothing supplied; the behaviour of earlier versions): the
+ * buffer is the library's, one per (device, stream). It is allocated inside
+ * the first such product, grown with a stream synchronize and a free when a
+ * larger B arrives, and kept until sputnik_release_workspaces(). A stream
+ * being captured, and hipStreamPerThread, keep the NT / TT kernel.
+ *
+ * Caller route: the caller supplies the memory, per call (the _ws entry
+ * points) or per stream (sputnik_set_stream_workspace). Such a product
+ * allocates, frees and synchronises nothing (sputnik_incall_events does not
+ * move), takes no library lock across the launch, and enqueues the same two
+ * launches eagerly, while `stream` is being captured, and on
+ * hipStreamPerThread. Memory that is smaller than the query below asks for,
+ * or not 16-byte aligned, keeps the NT / TT kernel for that product; it never
+ * falls back to the library's buffer.
+ *
+ * Lifetime: the memory must stay valid until all work enqueued with it has
+ * finished, and for a captured launch until the graph and every executable
+ * made from it are destroyed. A graph that captured it must not replay
+ * concurrently with other work that uses the same memory. */
+/* Bytes the transposed copy takes for this problem under the current knobs,
+ * rounded up to 256; 0 when the path does not apply (the product then needs
+ * no workspace). Host-only: ignores capture state, allocates and launches
+ * nothing. */
+size_t sputnik_sdd_workspace_bytes(const sputnik_matrix_t *a, int transpose_a,
+                                   const sputnik_matrix_t *b, int transpose_b,
+                                   const sputnik_block_matrix_t *c);
+size_t sputnik_dsd_workspace_bytes(const sputnik_block_matrix_t *a,
+                                   int transpose_a, const sputnik_matrix_t *b,
+                                   int transpose_b, const sputnik_matrix_t *c);
+/* Per-call route: sputnik_sdd / sputnik_dsd / sputnik_dsd_ex with `ws_bytes`
+ * bytes of device memory at `ws`. ws == NULL or ws_bytes == 0 means no
+ * workspace: exactly the plain entry point. */
+int sputnik_sdd_ws(const sputnik_matrix_t *a, int transpose_a,
+                   const sputnik_matrix_t *b, int transpose_b,
+                   const sputnik_block_matrix_t *c, int dtype, void *ws,
+                   size_t ws_bytes, void *stream);
+int sputnik_dsd_ws(const sputnik_block_matrix_t *a, int transpose_a,
+                   const sputnik_matrix_t *b, int transpose_b,
+                   const sputnik_matrix_t *c, int dtype, void *ws,
+                   size_t ws_bytes, void *stream);
+int sputnik_dsd_ex_ws(const sputnik_block_matrix_t *a, int transpose_a,
+                      const sputnik_matrix_t *b, int transpose_b,
+                      const sputnik_matrix_t *c, int dtype, void *ws,
+                      size_t ws_bytes, void *stream);
+/* Per-stream route, for callers bound to the reference's fixed signatures
+ * (the C++ Matmul / MatmulEx, and the plain entry points above): registers
+ * `bytes` of device memory at `ptr` for (current device, stream); ptr == NULL
+ * unregisters. The plain entry points look the registration up under a short
+ * lock, released before anything is enqueued, and then run the caller route;
+ * a stream with a registration never uses the library's buffer.
+ * hipErrorInvalidValue (1) for a pointer that is not 16-byte aligned, for
+ * bytes == 0 with a non-null pointer, and for hipStreamPerThread (one handle,
+ * a different stream in every thread); hipErrorOutOfMemory (2) when all 16
+ * entries are taken. */
+int sputnik_set_stream_workspace(void *stream, void *ptr, size_t bytes);
+/* Device memory the library holds on the current device: transposed-B
+ * buffers, eager and capture pair-balancing workspaces, persistent tile
+ * counters. Host-only query. */
+size_t sputnik_retained_bytes(void);
+/* Synchronises the current device, frees every library-owned transposed-B
+ * buffer on it and returns the bytes freed; a later product on the library
+ * route allocates again. Pair workspaces and tile counters are not touched
+ * (sputnik_capture_workspaces returns the captured ones). */
+size_t sputnik_release_workspaces(void);
+/* Two process-wide counters that only grow. incall_events: every hipMalloc,
+ * hipFree, hipStreamSynchronize and hipDeviceSynchronize the library executed
+ * inside a product call (the transposed-B buffer, pair workspaces, tile
+ * counters). bt_launches: every transpose of B enqueued for a product, by
+ * either route, eager or captured. */
+unsigned long long sputnik_incall_events(void);
+unsigned long long sputnik_bt_launches(void);
+
 /* ---- SSD: C_bcsr = op(A_bcsr) * op(B) at C's nonzero blocks
  *      (reference sputnik/block/ssd/ssd.h:10-22; needs c->row_indices, and
  *      a's transposed metadata when transpose_a) */
@@ -166,9 +243,11 @@ int sputnik_sdd_plan(const sputnik_matrix_t *a, int transpose_a,
 /* The SDD kernel behind that plan: 0 = the 8-wave k-split block tile,
  * 1 = grouped tiles on the 8-wave kernel, 2 = the 4-wave K-split, 3 =
  * grouped tiles on the 4-wave kernel, 4 = (NT / TT over a B past the
- * MALL) B transposed into a library buffer, then grouped tiles on the
- * 4-wave kernel (eager launches; a stream being captured keeps 3), -1 =
- * rejected. */
+ * MALL) B transposed into a scratch buffer, then grouped tiles on the
+ * 4-wave kernel, -1 = rejected. Answers for an eager launch on the null
+ * stream with no workspace registered; under capture, code 4 needs a
+ * caller-owned workspace (the _ws entry points or
+ * sputnik_set_stream_workspace) -- without one a captured launch runs 3. */
 int sputnik_sdd_kernel(const sputnik_matrix_t *a, int transpose_a,
                        const sputnik_matrix_t *b, int transpose_b,
                        const sputnik_block_matrix_t *c);

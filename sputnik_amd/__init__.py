@@ -122,6 +122,20 @@ _SIGNATURES = {
     "sputnik_dsd_plan": [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P],
     "sputnik_sdd_kernel": [_P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_dds_plan": [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P],
+    # caller-owned transposed-B workspaces
+    "sputnik_sdd_ws": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                       _P, ctypes.c_size_t, _P],
+    "sputnik_dsd_ws": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                       _P, ctypes.c_size_t, _P],
+    "sputnik_dsd_ex_ws": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                          _P, ctypes.c_size_t, _P],
+    "sputnik_sdd_workspace_bytes": [_P, ctypes.c_int, _P, ctypes.c_int, _P],
+    "sputnik_dsd_workspace_bytes": [_P, ctypes.c_int, _P, ctypes.c_int, _P],
+    "sputnik_set_stream_workspace": [_P, _P, ctypes.c_size_t],
+    "sputnik_retained_bytes": [],
+    "sputnik_release_workspaces": [],
+    "sputnik_incall_events": [],
+    "sputnik_bt_launches": [],
 }
 _RESTYPES = {
     "sputnik_abi_block_matrix_size": ctypes.c_size_t,
@@ -131,6 +145,12 @@ _RESTYPES = {
     "sputnik_build_hash": ctypes.c_char_p,
     "sputnik_bitmask_bytes": ctypes.c_size_t,
     "sputnik_debug_pair_fault": None,
+    "sputnik_sdd_workspace_bytes": ctypes.c_size_t,
+    "sputnik_dsd_workspace_bytes": ctypes.c_size_t,
+    "sputnik_retained_bytes": ctypes.c_size_t,
+    "sputnik_release_workspaces": ctypes.c_size_t,
+    "sputnik_incall_events": ctypes.c_ulonglong,
+    "sputnik_bt_launches": ctypes.c_ulonglong,
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -236,16 +256,42 @@ def _check(code: int, what: str) -> None:
         raise SputnikError(code, what)
 
 
-def _call(ex: bool, a, transpose_a: bool, b, transpose_b: bool, c, stream):
+def _workspace(ws):
+    """(pointer, bytes) of a caller-owned workspace tensor: any dtype, on
+    the device, contiguous. Raises before any HIP call otherwise."""
+    if not hasattr(ws, "data_ptr") or not hasattr(ws, "element_size"):
+        raise TypeError("workspace must be a torch tensor")
+    if not ws.is_cuda:
+        raise ValueError("workspace must be device memory (a cuda tensor), "
+                         f"not {ws.device}")
+    if not ws.is_contiguous():
+        raise ValueError("workspace must be contiguous")
+    return ws.data_ptr(), ws.numel() * ws.element_size()
+
+
+def _call(ex: bool, a, transpose_a: bool, b, transpose_b: bool, c, stream,
+          workspace=None):
+    ws = _workspace(workspace) if workspace is not None else None
     L = lib()
     ta, tb = int(bool(transpose_a)), int(bool(transpose_b))
     if isinstance(a, BlockMatrix) and isinstance(b, Matrix) and isinstance(c, Matrix):
         ca, cb, cc = a._c(), b._c(), c._c()
+        if ws is not None:
+            fn = L.sputnik_dsd_ex_ws if ex else L.sputnik_dsd_ws
+            code = fn(ctypes.byref(ca), ta, ctypes.byref(cb), tb,
+                      ctypes.byref(cc), _dtype_code(b.data), ws[0], ws[1],
+                      _stream(stream))
+            _check(code, "dsd")
+            return
         fn = L.sputnik_dsd_ex if ex else L.sputnik_dsd
         code = fn(ctypes.byref(ca), ta, ctypes.byref(cb), tb, ctypes.byref(cc),
                   _dtype_code(b.data), _stream(stream))
         _check(code, "dsd")
         return
+    if ws is not None and not (not ex and isinstance(a, Matrix)
+                               and isinstance(b, Matrix)
+                               and isinstance(c, BlockMatrix)):
+        raise TypeError("workspace applies to SDD and DSD only")
     if isinstance(a, Matrix) and isinstance(b, BlockMatrix) and isinstance(c, Matrix):
         ca, cb, cc = a._c(), b._c(), c._c()
         fn = L.sputnik_dds_ex if ex else L.sputnik_dds
@@ -256,6 +302,12 @@ def _call(ex: bool, a, transpose_a: bool, b, transpose_b: bool, c, stream):
     if (not ex and isinstance(a, Matrix) and isinstance(b, Matrix)
             and isinstance(c, BlockMatrix)):
         ca, cb, cc = a._c(), b._c(), c._c()
+        if ws is not None:
+            code = L.sputnik_sdd_ws(ctypes.byref(ca), ta, ctypes.byref(cb), tb,
+                                    ctypes.byref(cc), _dtype_code(a.data),
+                                    ws[0], ws[1], _stream(stream))
+            _check(code, "sdd")
+            return
         code = L.sputnik_sdd(ctypes.byref(ca), ta, ctypes.byref(cb), tb,
                              ctypes.byref(cc), _dtype_code(a.data),
                              _stream(stream))
@@ -288,16 +340,79 @@ def _call(ex: bool, a, transpose_a: bool, b, transpose_b: bool, c, stream):
     raise TypeError("no Matmul overload for these operand kinds")
 
 
-def Matmul(a, transpose_a, b, transpose_b, c, stream=None):  # noqa: N802
+def Matmul(a, transpose_a, b, transpose_b, c, stream=None,  # noqa: N802
+           workspace=None):
     """DSD / DDS / SDD / SSD / SDS / DSS by operand kinds, like the C++
-    overload set."""
-    _call(False, a, transpose_a, b, transpose_b, c, stream)
+    overload set. `workspace` (SDD and DSD): a device tensor of any dtype
+    with at least sdd_workspace_bytes / dsd_workspace_bytes bytes for the
+    transposed copy of B, so the call allocates and synchronises nothing
+    (include/sputnik_amd.h, "Caller-owned workspaces"); it must outlive the
+    work enqueued with it. None: the plain entry points."""
+    _call(False, a, transpose_a, b, transpose_b, c, stream, workspace)
 
 
-def MatmulEx(a, transpose_a, b, transpose_b, c, stream=None):  # noqa: N802
+def MatmulEx(a, transpose_a, b, transpose_b, c, stream=None,  # noqa: N802
+             workspace=None):
     """DSD / DDS / SSD / SDS / DSS with the transposed metadata already
-    present."""
-    _call(True, a, transpose_a, b, transpose_b, c, stream)
+    present. `workspace` (DSD) as in Matmul."""
+    _call(True, a, transpose_a, b, transpose_b, c, stream, workspace)
+
+
+def sdd_workspace_bytes(a, transpose_a, b, transpose_b, c) -> int:
+    """Bytes of transposed-B workspace this SDD would use (0: none needed;
+    sputnik_sdd_workspace_bytes). Host-only."""
+    ca, cb, cc = a._c(), b._c(), c._c()
+    return int(lib().sputnik_sdd_workspace_bytes(
+        ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
+        int(bool(transpose_b)), ctypes.byref(cc)))
+
+
+def dsd_workspace_bytes(a, transpose_a, b, transpose_b, c) -> int:
+    """Bytes of transposed-B workspace this DSD would use (0: none needed;
+    sputnik_dsd_workspace_bytes). Host-only."""
+    ca, cb, cc = a._c(), b._c(), c._c()
+    return int(lib().sputnik_dsd_workspace_bytes(
+        ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
+        int(bool(transpose_b)), ctypes.byref(cc)))
+
+
+def set_stream_workspace(stream, workspace) -> None:
+    """Registers `workspace` (a device tensor; None unregisters) as the
+    transposed-B workspace of `stream` (a torch stream, a raw handle, or
+    None for torch's current stream) on the current device
+    (sputnik_set_stream_workspace). The caller keeps the tensor alive while
+    it is registered and until the work enqueued with it has finished."""
+    handle = getattr(stream, "cuda_stream", stream)
+    ptr, nbytes = (None, 0) if workspace is None else _workspace(workspace)
+    if workspace is not None and nbytes == 0:
+        # (an empty tensor has no pointer to hand over, and a null pointer
+        # would unregister: the C entry point's answer for zero bytes)
+        raise SputnikError(hipErrorInvalidValue, "set_stream_workspace")
+    _check(lib().sputnik_set_stream_workspace(_stream(handle), ptr, nbytes),
+           "set_stream_workspace")
+
+
+def retained_bytes() -> int:
+    """Device memory the library holds on the current device
+    (sputnik_retained_bytes)."""
+    return int(lib().sputnik_retained_bytes())
+
+
+def release_workspaces() -> int:
+    """Frees the library-owned transposed-B buffers of the current device
+    after a device synchronize; bytes freed (sputnik_release_workspaces)."""
+    return int(lib().sputnik_release_workspaces())
+
+
+def incall_events() -> int:
+    """Allocations, frees and synchronizes the library has executed inside
+    product calls so far (sputnik_incall_events)."""
+    return int(lib().sputnik_incall_events())
+
+
+def bt_launches() -> int:
+    """Transposes of B enqueued for products so far (sputnik_bt_launches)."""
+    return int(lib().sputnik_bt_launches())
 
 
 def RowIndices(a: BlockMatrix, row_indices, stream=None):  # noqa: N802
@@ -503,6 +618,8 @@ __all__ = [
     "build_hash", "capture_workspaces", "pair_errors", "sdd_plan", "sdd_kernel",
     "dds_plan",
     "select_dsd_kernel", "dsd_plan", "tuning",
+    "set_stream_workspace", "sdd_workspace_bytes", "dsd_workspace_bytes",
+    "retained_bytes", "release_workspaces", "incall_events", "bt_launches",
     "BlockMatrix", "BlockSize", "ExpertTopology", "FreeRowIndicesBuffer",
     "MaskToBcsr",
     "FreeTransposeBuffers", "Matmul", "MatmulEx", "Matrix", "RowIndices",

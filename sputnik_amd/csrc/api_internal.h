@@ -2,6 +2,8 @@
 #ifndef SPUTNIK_AMD_API_INTERNAL_H_
 #define SPUTNIK_AMD_API_INTERNAL_H_
 
+#include <cstddef>
+
 #include "sputnik/block/arguments.h"
 
 namespace sputnik_amd {
@@ -18,17 +20,42 @@ enum class Status {
 using sputnik::block::BlockMatrix;
 using sputnik::block::Matrix;
 
+// Caller-owned device memory for the transposed copy of B (SDD NT / TT, DSD
+// NT; dispatch.cpp "caller-owned transposed-B workspaces"). Empty: none was
+// supplied with the call.
+struct Workspace {
+  void *ptr = nullptr;
+  size_t bytes = 0;
+};
+
 // Validate, optionally build transposed metadata, launch. A non-kOk *status
 // means nothing was launched.
 hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                   const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *status);
+                  hipStream_t stream, Status *status, Workspace ws = Workspace{});
 hipError_t RunDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
                   const Matrix &c, int dtype, bool build_meta,
                   hipStream_t stream, Status *status);
 hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, hipStream_t stream,
-                  Status *status);
+                  Status *status, Workspace ws = Workspace{});
+
+// Per-(current device, stream) registration of caller memory (ptr null:
+// unregister); the plain entry points look it up.
+hipError_t SetStreamWorkspace(hipStream_t stream, void *ptr, size_t bytes);
+// Bytes the transposed-B path would use for a problem (0: it does not apply).
+size_t SddWorkspaceBytes(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                         const BlockMatrix &c);
+size_t DsdWorkspaceBytes(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
+                         const Matrix &c);
+// Device memory the library holds on the current device; the transposed-B
+// buffers of it freed (after a device synchronize), bytes freed.
+size_t RetainedBytes();
+size_t ReleaseWorkspaces();
+// Monotonic process-wide counters: allocations / frees / synchronizes
+// executed inside a product call; transposed-B launches enqueued.
+unsigned long long InCallEvents();
+unsigned long long BtLaunches();
 
 hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, bool build_meta,

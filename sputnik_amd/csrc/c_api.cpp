@@ -51,27 +51,45 @@ int Code(hipError_t launch, int status_code) {
 
 extern "C" {
 
-int sputnik_dsd(const sputnik_block_matrix_t *a, int transpose_a,
-                const sputnik_matrix_t *b, int transpose_b,
-                const sputnik_matrix_t *c, int dtype, void *stream) {
+int sputnik_dsd_ws(const sputnik_block_matrix_t *a, int transpose_a,
+                   const sputnik_matrix_t *b, int transpose_b,
+                   const sputnik_matrix_t *c, int dtype, void *ws,
+                   size_t ws_bytes, void *stream) {
   if (!a || !b || !c) return hipErrorInvalidValue;
   const BlockMatrix ca = ToCpp(a);
   sputnik_amd::Status st;
   const hipError_t e = sputnik_amd::RunDsd(
       ca, transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      ca.create_metadata, static_cast<hipStream_t>(stream), &st);
+      ca.create_metadata, static_cast<hipStream_t>(stream), &st,
+      sputnik_amd::Workspace{ws, ws_bytes});
+  return Code(e, sputnik_amd::StatusCode(st));
+}
+
+int sputnik_dsd(const sputnik_block_matrix_t *a, int transpose_a,
+                const sputnik_matrix_t *b, int transpose_b,
+                const sputnik_matrix_t *c, int dtype, void *stream) {
+  return sputnik_dsd_ws(a, transpose_a, b, transpose_b, c, dtype, nullptr, 0,
+                        stream);
+}
+
+int sputnik_dsd_ex_ws(const sputnik_block_matrix_t *a, int transpose_a,
+                      const sputnik_matrix_t *b, int transpose_b,
+                      const sputnik_matrix_t *c, int dtype, void *ws,
+                      size_t ws_bytes, void *stream) {
+  if (!a || !b || !c) return hipErrorInvalidValue;
+  sputnik_amd::Status st;
+  const hipError_t e = sputnik_amd::RunDsd(
+      ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
+      false, static_cast<hipStream_t>(stream), &st,
+      sputnik_amd::Workspace{ws, ws_bytes});
   return Code(e, sputnik_amd::StatusCode(st));
 }
 
 int sputnik_dsd_ex(const sputnik_block_matrix_t *a, int transpose_a,
                    const sputnik_matrix_t *b, int transpose_b,
                    const sputnik_matrix_t *c, int dtype, void *stream) {
-  if (!a || !b || !c) return hipErrorInvalidValue;
-  sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunDsd(
-      ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      false, static_cast<hipStream_t>(stream), &st);
-  return Code(e, sputnik_amd::StatusCode(st));
+  return sputnik_dsd_ex_ws(a, transpose_a, b, transpose_b, c, dtype, nullptr,
+                           0, stream);
 }
 
 int sputnik_dds(const sputnik_matrix_t *a, int transpose_a,
@@ -97,15 +115,59 @@ int sputnik_dds_ex(const sputnik_matrix_t *a, int transpose_a,
   return Code(e, sputnik_amd::StatusCode(st));
 }
 
-int sputnik_sdd(const sputnik_matrix_t *a, int transpose_a,
-                const sputnik_matrix_t *b, int transpose_b,
-                const sputnik_block_matrix_t *c, int dtype, void *stream) {
+int sputnik_sdd_ws(const sputnik_matrix_t *a, int transpose_a,
+                   const sputnik_matrix_t *b, int transpose_b,
+                   const sputnik_block_matrix_t *c, int dtype, void *ws,
+                   size_t ws_bytes, void *stream) {
   if (!a || !b || !c) return hipErrorInvalidValue;
   sputnik_amd::Status st;
   const hipError_t e = sputnik_amd::RunSdd(
       ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      static_cast<hipStream_t>(stream), &st);
+      static_cast<hipStream_t>(stream), &st,
+      sputnik_amd::Workspace{ws, ws_bytes});
   return Code(e, sputnik_amd::StatusCode(st));
+}
+
+int sputnik_sdd(const sputnik_matrix_t *a, int transpose_a,
+                const sputnik_matrix_t *b, int transpose_b,
+                const sputnik_block_matrix_t *c, int dtype, void *stream) {
+  return sputnik_sdd_ws(a, transpose_a, b, transpose_b, c, dtype, nullptr, 0,
+                        stream);
+}
+
+size_t sputnik_sdd_workspace_bytes(const sputnik_matrix_t *a, int transpose_a,
+                                   const sputnik_matrix_t *b, int transpose_b,
+                                   const sputnik_block_matrix_t *c) {
+  if (!a || !b || !c) return 0;
+  return sputnik_amd::SddWorkspaceBytes(ToCpp(a), transpose_a != 0, ToCpp(b),
+                                        transpose_b != 0, ToCpp(c));
+}
+
+size_t sputnik_dsd_workspace_bytes(const sputnik_block_matrix_t *a,
+                                   int transpose_a, const sputnik_matrix_t *b,
+                                   int transpose_b, const sputnik_matrix_t *c) {
+  if (!a || !b || !c) return 0;
+  return sputnik_amd::DsdWorkspaceBytes(ToCpp(a), transpose_a != 0, ToCpp(b),
+                                        transpose_b != 0, ToCpp(c));
+}
+
+int sputnik_set_stream_workspace(void *stream, void *ptr, size_t bytes) {
+  return sputnik_amd::SetStreamWorkspace(static_cast<hipStream_t>(stream), ptr,
+                                         bytes);
+}
+
+size_t sputnik_retained_bytes(void) { return sputnik_amd::RetainedBytes(); }
+
+size_t sputnik_release_workspaces(void) {
+  return sputnik_amd::ReleaseWorkspaces();
+}
+
+unsigned long long sputnik_incall_events(void) {
+  return sputnik_amd::InCallEvents();
+}
+
+unsigned long long sputnik_bt_launches(void) {
+  return sputnik_amd::BtLaunches();
 }
 
 static int SparseInOut(bool ssd, bool ex, const void *a, int ta,

@@ -39,6 +39,29 @@ static unsigned long long *g_debug = nullptr;
 
 constexpr int kMaxDevices = 64;
 
+// ---- allocation / synchronisation accounting ------------------------------
+// g_incall_events: every hipMalloc, hipFree, hipStreamSynchronize and
+// hipDeviceSynchronize the library executes while a product entry point (a
+// Run* function) is on this thread's stack; g_bt_launches: every
+// LaunchTranspose16 enqueued for a product. Both only grow
+// (sputnik_incall_events / sputnik_bt_launches): a caller, or a test, reads
+// them around a call to see that the call allocated and synchronised nothing.
+static std::atomic<unsigned long long> g_incall_events{0};
+static std::atomic<unsigned long long> g_bt_launches{0};
+static thread_local int t_product_depth = 0;
+struct InProduct {
+  InProduct() { ++t_product_depth; }
+  ~InProduct() { --t_product_depth; }
+  InProduct(const InProduct &) = delete;
+  InProduct &operator=(const InProduct &) = delete;
+};
+// Called right before each such HIP call.
+static void InCallEvent() {
+  if (t_product_depth > 0) g_incall_events.fetch_add(1, std::memory_order_relaxed);
+}
+unsigned long long InCallEvents() { return g_incall_events.load(std::memory_order_relaxed); }
+unsigned long long BtLaunches() { return g_bt_launches.load(std::memory_order_relaxed); }
+
 // Compute units of a device, queried once per device (every SDD and every
 // pair-eligible DSD/DDS call needs it).
 static int DeviceCUs(int dev) {
@@ -226,10 +249,17 @@ static hipError_t AllocZeroed(void **ptr, size_t bytes, int dev) {
   hipStream_t side = nullptr;
   hipError_t e = SideStream(dev, &side);
   *ptr = nullptr;
-  if (e == hipSuccess) e = hipMalloc(ptr, bytes);
+  if (e == hipSuccess) {
+    InCallEvent();
+    e = hipMalloc(ptr, bytes);
+  }
   if (e == hipSuccess) e = hipMemsetAsync(*ptr, 0, bytes, side);
-  if (e == hipSuccess) e = hipStreamSynchronize(side);
+  if (e == hipSuccess) {
+    InCallEvent();
+    e = hipStreamSynchronize(side);
+  }
   if (e != hipSuccess && *ptr != nullptr) {
+    InCallEvent();
     (void)hipFree(*ptr);
     *ptr = nullptr;
   }
@@ -277,6 +307,7 @@ static void FreeQuiet(void *ptr) {
   if (ptr == nullptr) return;
   hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
   (void)hipThreadExchangeStreamCaptureMode(&mode);
+  InCallEvent();
   (void)hipFree(ptr);
   (void)hipThreadExchangeStreamCaptureMode(&mode);
 }
@@ -420,6 +451,15 @@ static void PreparePairs(GemmParams *p, long long blocks, hipStream_t stream,
   if (!PairsEnabled() || p->num_rows < 2 || p->num_rows > kLptRows) return;
   if (blocks * 4 < (long long)p->num_rows * SPUTNIK_PAIR_MIN_MEAN4) return;
   if (stream == hipStreamPerThread) return;  // many streams, one handle
+  // More tiles than resident workgroups never pair (the check on slot->slots
+  // below): decided here, before a workspace is looked up or allocated, so
+  // such a launch allocates nothing (e.g. DSD NT through a caller's
+  // transposed-B workspace, 16384 x 2048 out of a dense A).
+  {
+    int dev = 0;
+    const int cus = hipGetDevice(&dev) == hipSuccess ? DeviceCUs(dev) : 0;
+    if (cus > 0 && p->num_tiles > cus * CfgSparse::kWGs) return;
+  }
   std::lock_guard<std::mutex> lock(g_pairs_mu);
   PairSlot dry_slot;
   int capturing = 0;
@@ -1105,10 +1145,12 @@ static bool UseTallPipe(const GemmParams &p, long long blocks, long long row_max
 // of B (blocks 128^2 2 K / (K N 2) = 16384 blocks / N) >= kBtMinRatio, so
 // the copy is a small part of the launch (16384^3: 50% 8192, dense 16384,
 // 10% 1639 -- below; MegaBlocks' x.w1^T 1024 -- below); the N-major path
-// must be the 4-wave grouped kernel. Eager launches only: a stream being
-// captured keeps the NT / TT kernel (the buffer is allocated on first use).
-// One buffer per (device, stream), grown as needed, kept for the process
-// (INTEGRATION.md 3b); stream order makes it safe to reuse.
+// must be the 4-wave grouped kernel. On the library route, eager launches
+// only: a stream being captured keeps the NT / TT kernel (the buffer is
+// allocated on first use). One buffer per (device, stream), grown as needed,
+// kept until sputnik_release_workspaces(); stream order
+// makes it safe to reuse. A caller who supplies the memory (below) gets the
+// same two launches with none of this.
 constexpr long long kBtMinRatio = 3000;
 struct BtSlot {
   int device = -1;
@@ -1122,9 +1164,21 @@ static BtSlot g_bt[kMaxPairSlots];
 // stream in between; taken before g_pairs_mu, never while holding it.
 static std::mutex g_bt_mu;
 
-static bool UseBtTranspose(const Matrix &a, bool ta, const Matrix &b, bool tb,
-                           const BlockMatrix &c, hipStream_t stream) {
-  if (!tb || stream == hipStreamPerThread) return false;  // (many streams, one handle)
+// The gate has two parts. BtApplies*: the path applies to this problem
+// (sizes, density, alignment, the 4-wave kernel) -- all a caller-owned
+// workspace needs. BtLibraryStreamOk: this stream may use the library-owned
+// buffer -- not hipStreamPerThread (many streams, one handle) and not while
+// it is being captured (the buffer is allocated, grown and freed by eager
+// launches). UseBtTranspose* = both, the library route.
+static bool BtLibraryStreamOk(hipStream_t stream) {
+  if (stream == hipStreamPerThread) return false;
+  unsigned long long id = 0;
+  return CaptureState(stream, &id) == 0;
+}
+
+static bool BtAppliesSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                         const BlockMatrix &c) {
+  if (!tb) return false;
   const long long min_mib = Knob(kKnobSddBtMinMib);
   if (min_mib <= 0) return false;
   const long long n = b.rows, k = b.cols;  // B^T stored [N][K]
@@ -1134,12 +1188,15 @@ static bool UseBtTranspose(const Matrix &a, bool ta, const Matrix &b, bool tb,
     return false;
   const long long blocks = c.nonzeros / (kBlock * kBlock);
   if (blocks * 16384 < kBtMinRatio * n) return false;
-  unsigned long long id = 0;
-  if (CaptureState(stream, &id) != 0) return false;
   GemmParams p;
   const Matrix bt((int)k, (int)n, b.data);
   return PrepareSdd(a, ta, bt, false, c, &p) == Status::kOk && UseGroupedSdd(&p, c, false) &&
          Dsd4wEnabled() && Sdd4wApplies(p, true, ta, false, blocks);
+}
+
+static bool UseBtTranspose(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                           const BlockMatrix &c, hipStream_t stream) {
+  return BtAppliesSdd(a, ta, b, tb, c) && BtLibraryStreamOk(stream);
 }
 
 // The same for DSD NT over a nearly dense A (out = A . B with B^T stored
@@ -1148,9 +1205,8 @@ static bool UseBtTranspose(const Matrix &a, bool ta, const Matrix &b, bool tb,
 // the gate asks for >= kDsdBtMinRatio FLOPs per byte of B, 16384 blocks / K
 // (16384^3: dense 16384, 50% 8192).
 constexpr long long kDsdBtMinRatio = 15000;
-static bool UseBtTransposeDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
-                              hipStream_t stream) {
-  if (!tb || ta || stream == hipStreamPerThread) return false;
+static bool BtAppliesDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb) {
+  if (!tb || ta) return false;
   const long long min_mib = Knob(kKnobSddBtMinMib);
   if (min_mib <= 0) return false;
   const long long n = b.rows, k = b.cols;  // B^T stored [N][K]
@@ -1159,9 +1215,92 @@ static bool UseBtTransposeDsd(const BlockMatrix &a, bool ta, const Matrix &b, bo
       (reinterpret_cast<uintptr_t>(b.data) & 15) != 0)
     return false;
   const long long blocks = a.nonzeros / (kBlock * kBlock);
-  if (blocks * 16384 < kDsdBtMinRatio * k) return false;
-  unsigned long long id = 0;
-  return CaptureState(stream, &id) == 0;
+  return blocks * 16384 >= kDsdBtMinRatio * k;
+}
+
+static bool UseBtTransposeDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
+                              hipStream_t stream) {
+  return BtAppliesDsd(a, ta, b, tb) && BtLibraryStreamOk(stream);
+}
+
+// ---- caller-owned transposed-B workspaces ----------------------------------
+// The reference hands every workspace to the caller (arguments.h); here the
+// caller may hand over the memory of the transposed copy, per call (the *_ws
+// entry points) or per (device, stream) (sputnik_set_stream_workspace, for
+// callers bound to the reference's Matmul / MatmulEx signatures). With such
+// memory a product takes no g_bt_mu, touches no BtSlot, allocates, frees and
+// synchronises nothing, and runs the same two launches while `stream` is
+// being captured or is hipStreamPerThread. A stream with a registration
+// never uses the library-owned buffer: memory that is too small or not
+// 16-byte aligned keeps the NT / TT kernel.
+struct WsReg {
+  int device = -1;
+  hipStream_t stream = nullptr;
+  void *ptr = nullptr;  // nullptr: free entry
+  size_t bytes = 0;
+};
+static WsReg g_ws[kMaxPairSlots];
+static std::mutex g_ws_mu;  // held only around the table, never over a launch
+
+hipError_t SetStreamWorkspace(hipStream_t stream, void *ptr, size_t bytes) {
+  // (hipStreamPerThread names a different stream in every thread: there is
+  // no one stream whose order would protect the memory)
+  if (stream == hipStreamPerThread) return hipErrorInvalidValue;
+  if (ptr != nullptr && (bytes == 0 || (reinterpret_cast<uintptr_t>(ptr) & 15) != 0))
+    return hipErrorInvalidValue;
+  int dev = 0;
+  const hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(g_ws_mu);
+  WsReg *slot = nullptr;
+  for (WsReg &r : g_ws)
+    if (r.ptr != nullptr && r.device == dev && r.stream == stream) slot = &r;
+  if (ptr == nullptr) {
+    if (slot != nullptr) *slot = WsReg{};
+    return hipSuccess;
+  }
+  if (slot == nullptr)
+    for (WsReg &r : g_ws)
+      if (r.ptr == nullptr) {
+        slot = &r;
+        break;
+      }
+  if (slot == nullptr) return hipErrorOutOfMemory;
+  slot->device = dev;
+  slot->stream = stream;
+  slot->ptr = ptr;
+  slot->bytes = bytes;
+  return hipSuccess;
+}
+
+// The workspace of this call: the caller's own, else the one registered for
+// (current device, stream). false: neither (the library route).
+static bool CallerWorkspace(hipStream_t stream, Workspace given, Workspace *out) {
+  if (given.ptr != nullptr && given.bytes != 0) {
+    *out = given;
+    return true;
+  }
+  if (stream == hipStreamPerThread) return false;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  std::lock_guard<std::mutex> lock(g_ws_mu);
+  for (const WsReg &r : g_ws)
+    if (r.ptr != nullptr && r.device == dev && r.stream == stream) {
+      out->ptr = r.ptr;
+      out->bytes = r.bytes;
+      return true;
+    }
+  return false;
+}
+
+static bool WorkspaceFits(Workspace ws, size_t bytes) {
+  return ws.bytes >= bytes && (reinterpret_cast<uintptr_t>(ws.ptr) & 15) == 0;
+}
+
+// B^T ([rows][cols]) transposed into `out` on `stream`, counted.
+static hipError_t EnqueueBt(const Matrix &b, void *out, hipStream_t stream) {
+  g_bt_launches.fetch_add(1, std::memory_order_relaxed);
+  return LaunchTranspose16(b.data, b.rows, b.cols, out, stream);
 }
 
 // The transposed-B buffer of (device, stream), at least `bytes` (nullptr:
@@ -1183,11 +1322,13 @@ static void *BtBuffer(hipStream_t stream, size_t bytes) {
   if (slot->bytes < bytes) {
     if (slot->data != nullptr) {
       // the stream's earlier launches may still read the old buffer
+      InCallEvent();
       if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
       FreeQuiet(slot->data);
       slot->data = nullptr;
       slot->bytes = 0;
     }
+    InCallEvent();
     if (hipMalloc(&slot->data, bytes) != hipSuccess) {
       slot->data = nullptr;
       return nullptr;
@@ -1199,22 +1340,104 @@ static void *BtBuffer(hipStream_t stream, size_t bytes) {
   return slot->data;
 }
 
+// Bytes of the transposed copy the path would use for this problem under the
+// current knobs (a multiple of 256), 0 when the path does not apply. Host
+// only: ignores the capture state, allocates and launches nothing.
+static size_t BtBytes(const Matrix &b) {
+  return (((size_t)b.rows * b.cols * 2) + 255) & ~(size_t)255;
+}
+size_t SddWorkspaceBytes(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                         const BlockMatrix &c) {
+  GemmParams p;
+  if (PrepareSdd(a, ta, b, tb, c, &p) != Status::kOk) return 0;
+  return BtAppliesSdd(a, ta, b, tb, c) ? BtBytes(b) : 0;
+}
+size_t DsdWorkspaceBytes(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
+                         const Matrix &c) {
+  GemmParams p;
+  bool needs_meta = false;
+  if (PrepareDsd(a, ta, b, tb, c, &p, &needs_meta) != Status::kOk) return 0;
+  return BtAppliesDsd(a, ta, b, tb) ? BtBytes(b) : 0;
+}
+
+// Device memory the library holds on the current device: transposed-B
+// buffers, eager and capture pair workspaces, tile counters (host only).
+size_t RetainedBytes() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  size_t total = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_bt_mu);
+    for (const BtSlot &s : g_bt)
+      if (s.data != nullptr && s.device == dev) total += s.bytes;
+  }
+  std::lock_guard<std::mutex> lock(g_pairs_mu);
+  for (int i = 0; i < kMaxPairSlots + kMaxCaptureSlots; ++i) {
+    const PairSlot &s = i < kMaxPairSlots ? g_pairs[i] : g_capture_pairs[i - kMaxPairSlots];
+    if (s.partials == nullptr || s.device != dev) continue;
+    // (the sizes AcquirePairSlot allocates)
+    total += (size_t)s.slots * kBM * CfgSparse::kBN * sizeof(float) +
+             (size_t)(s.pairs + 3 + s.slots) * sizeof(unsigned);
+  }
+  for (int i = 0; i < kMaxPairSlots + kMaxCaptureSlots; ++i) {
+    const CounterSlot &c =
+        i < kMaxPairSlots ? g_counters[i] : g_capture_counters[i - kMaxPairSlots];
+    if (c.counter != nullptr && c.device == dev) total += 2 * sizeof(unsigned long long);
+  }
+  return total;
+}
+
+// Frees every library-owned transposed-B buffer of the current device after
+// one device-wide synchronize (the streams the buffers were made for may be
+// gone, as in PairErrors) and returns the bytes freed; the next library-route
+// launch allocates again. The lock is held across the synchronize, so no
+// library-route product can enqueue work on a buffer between the two. Pair
+// workspaces and tile counters stay: their epochs live in them.
+size_t ReleaseWorkspaces() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  std::lock_guard<std::mutex> lock(g_bt_mu);
+  if (hipDeviceSynchronize() != hipSuccess) return 0;
+  size_t freed = 0;
+  for (BtSlot &s : g_bt) {
+    if (s.data == nullptr || s.device != dev) continue;
+    FreeQuiet(s.data);
+    freed += s.bytes;
+    s = BtSlot{};
+  }
+  return freed;
+}
+
 hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                   const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *st_out) {
+                  hipStream_t stream, Status *st_out, Workspace ws) {
+  const InProduct in_product;
   GemmParams p;
   bool needs_meta = false;
   const Status st = PrepareDsd(a, ta, b, tb, c, &p, &needs_meta);
   *st_out = st;
   if (st != Status::kOk) return hipSuccess;
-  if (UseBtTransposeDsd(a, ta, b, tb, stream)) {
-    std::lock_guard<std::mutex> lock(g_bt_mu);
-    void *bt = BtBuffer(stream, (size_t)b.rows * b.cols * 2);
-    if (bt != nullptr) {
-      const hipError_t e = LaunchTranspose16(b.data, b.rows, b.cols, bt, stream);
-      if (e != hipSuccess) return e;
-      return RunDsd(a, ta, Matrix(b.cols, b.rows, bt), false, c, dtype, build_meta, stream,
-                    st_out);
+  if (BtAppliesDsd(a, ta, b, tb)) {
+    const size_t bt_bytes = (size_t)b.rows * b.cols * 2;
+    Workspace own;
+    if (CallerWorkspace(stream, ws, &own)) {
+      // the caller's memory: no lock, no slot, captured or not; memory that
+      // does not fit keeps the NT kernel below
+      if (WorkspaceFits(own, bt_bytes)) {
+        const hipError_t e = EnqueueBt(b, own.ptr, stream);
+        if (e != hipSuccess) return e;
+        return RunDsd(a, ta, Matrix(b.cols, b.rows, own.ptr), false, c, dtype, build_meta,
+                      stream, st_out, Workspace{});
+      }
+    } else if (BtLibraryStreamOk(stream)) {
+      std::lock_guard<std::mutex> lock(g_bt_mu);
+      void *bt = BtBuffer(stream, bt_bytes);
+      if (bt != nullptr) {
+        const hipError_t e = EnqueueBt(b, bt, stream);
+        if (e != hipSuccess) return e;
+        return RunDsd(a, ta, Matrix(b.cols, b.rows, bt), false, c, dtype, build_meta, stream,
+                      st_out, Workspace{});
+      }
     }
   }
   if (needs_meta && build_meta) {
@@ -1259,6 +1482,7 @@ hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
 hipError_t RunDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
                   const Matrix &c, int dtype, bool build_meta,
                   hipStream_t stream, Status *st_out) {
+  const InProduct in_product;
   GemmParams p;
   bool needs_meta = false;
   const Status st = PrepareDds(a, ta, b, tb, c, &p, &needs_meta);
@@ -1287,18 +1511,32 @@ hipError_t RunDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
 
 hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, hipStream_t stream,
-                  Status *st_out) {
+                  Status *st_out, Workspace ws) {
+  const InProduct in_product;
   GemmParams p;
   const Status st = PrepareSdd(a, ta, b, tb, c, &p);
   *st_out = st;
   if (st != Status::kOk) return hipSuccess;
-  if (UseBtTranspose(a, ta, b, tb, c, stream)) {
-    std::lock_guard<std::mutex> lock(g_bt_mu);
-    void *bt = BtBuffer(stream, (size_t)b.rows * b.cols * 2);
-    if (bt != nullptr) {
-      const hipError_t e = LaunchTranspose16(b.data, b.rows, b.cols, bt, stream);
-      if (e != hipSuccess) return e;
-      return RunSdd(a, ta, Matrix(b.cols, b.rows, bt), false, c, dtype, stream, st_out);
+  if (BtAppliesSdd(a, ta, b, tb, c)) {
+    const size_t bt_bytes = (size_t)b.rows * b.cols * 2;
+    Workspace own;
+    if (CallerWorkspace(stream, ws, &own)) {
+      // (as in RunDsd: the caller's memory, or the NT / TT kernel below)
+      if (WorkspaceFits(own, bt_bytes)) {
+        const hipError_t e = EnqueueBt(b, own.ptr, stream);
+        if (e != hipSuccess) return e;
+        return RunSdd(a, ta, Matrix(b.cols, b.rows, own.ptr), false, c, dtype, stream,
+                      st_out, Workspace{});
+      }
+    } else if (BtLibraryStreamOk(stream)) {
+      std::lock_guard<std::mutex> lock(g_bt_mu);
+      void *bt = BtBuffer(stream, bt_bytes);
+      if (bt != nullptr) {
+        const hipError_t e = EnqueueBt(b, bt, stream);
+        if (e != hipSuccess) return e;
+        return RunSdd(a, ta, Matrix(b.cols, b.rows, bt), false, c, dtype, stream, st_out,
+                      Workspace{});
+      }
     }
   }
   p.debug = g_debug;
@@ -1344,6 +1582,7 @@ hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
 hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, bool build_meta,
                   hipStream_t stream, Status *st_out) {
+  const InProduct in_product;
   GemmParams p;
   bool needs_meta = false;
   const Status st = PrepareSsd(a, ta, b, tb, c, &p, &needs_meta);
@@ -1361,6 +1600,7 @@ hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
 hipError_t RunSds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
                   const BlockMatrix &c, int dtype, bool build_meta,
                   hipStream_t stream, Status *st_out) {
+  const InProduct in_product;
   GemmParams p;
   bool needs_meta = false;
   const Status st = PrepareSds(a, ta, b, tb, c, &p, &needs_meta);
@@ -1378,6 +1618,7 @@ hipError_t RunSds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
 hipError_t RunDss(const BlockMatrix &a, bool ta, const BlockMatrix &b,
                   bool tb, const Matrix &c, int dtype, bool build_meta_a,
                   bool build_meta_b, hipStream_t stream, Status *st_out) {
+  const InProduct in_product;
   GemmParams p;
   bool meta_a = false, meta_b = false;
   const Status st = PrepareDss(a, ta, b, tb, c, &p, &meta_a, &meta_b);
@@ -1560,6 +1801,25 @@ hipError_t MatmulEx(const BlockMatrix a, bool transpose_a, const BlockMatrix b,
                     bool transpose_b, Matrix c, hipStream_t stream) {
   return MatmulEx(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
 }
+
+// Caller-owned workspaces (sputnik/block/workspace.h).
+hipError_t SetStreamWorkspace(hipStream_t stream, void *ptr, size_t bytes) {
+  return sputnik_amd::SetStreamWorkspace(stream, ptr, bytes);
+}
+
+size_t SddWorkspaceBytes(const Matrix a, bool transpose_a, const Matrix b,
+                         bool transpose_b, const BlockMatrix c) {
+  return sputnik_amd::SddWorkspaceBytes(a, transpose_a, b, transpose_b, c);
+}
+
+size_t DsdWorkspaceBytes(const BlockMatrix a, bool transpose_a, const Matrix b,
+                         bool transpose_b, const Matrix c) {
+  return sputnik_amd::DsdWorkspaceBytes(a, transpose_a, b, transpose_b, c);
+}
+
+size_t RetainedBytes() { return sputnik_amd::RetainedBytes(); }
+
+size_t ReleaseWorkspaces() { return sputnik_amd::ReleaseWorkspaces(); }
 
 hipError_t RowIndices(BlockMatrix a, short *row_indices, hipStream_t stream) {
   if (AsInt(a.block_size) == 0) return hipErrorNotSupported;

@@ -28,7 +28,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import (BlockMatrix, Matrix, Matmul, MatmulEx, RowIndices, Transpose,
-               AllocateRowIndicesBuffer, AllocateTransposeBuffers)
+               AllocateRowIndicesBuffer, AllocateTransposeBuffers,
+               dsd_workspace_bytes, sdd_workspace_bytes)
 
 BLOCK = 128
 
@@ -180,6 +181,17 @@ def _check_dtypes(*ts):
 
 # ---- raw products (no autograd) ----------------------------------------------
 
+def _bt_workspace(nbytes: int, device) -> Optional[torch.Tensor]:
+    """Memory for the transposed copy of B when a product asks for it: a
+    per-call temporary from torch's caching allocator, so the library never
+    allocates a buffer of its own for these ops. The allocator's stream
+    ordering makes its reuse safe in eager mode; under torch.cuda.graph it
+    comes from the graph's private pool and lives as long as the graph."""
+    if nbytes == 0:
+        return None
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def _dsd(a: SparseMatrix, b: torch.Tensor) -> torch.Tensor:
     _check_dtypes(a.data, b)
     if a.shape[1] != b.shape[0]:
@@ -188,8 +200,10 @@ def _dsd(a: SparseMatrix, b: torch.Tensor) -> torch.Tensor:
     out = torch.empty(a.shape[0], b.shape[1], dtype=b.dtype, device=b.device)
     if a.is_transposed():
         a._meta.ensure_transposed(a.data)
-    MatmulEx(a._descriptor(), a.is_transposed(), bm, tb,
-             Matrix(out.shape[0], out.shape[1], out))
+    ad, om = a._descriptor(), Matrix(out.shape[0], out.shape[1], out)
+    ws = _bt_workspace(dsd_workspace_bytes(ad, a.is_transposed(), bm, tb, om),
+                       b.device)
+    MatmulEx(ad, a.is_transposed(), bm, tb, om, workspace=ws)
     return out
 
 
@@ -221,7 +235,9 @@ def _sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix) -> torch.Tensor:
     data = torch.empty(topo.nnz_blocks, BLOCK, BLOCK, dtype=a.dtype,
                        device=a.device)
     topo._meta.ensure_row_indices(data)
-    Matmul(am, ta, bm, tb, topo._meta.descriptor(data))
+    cd = topo._meta.descriptor(data)
+    ws = _bt_workspace(sdd_workspace_bytes(am, ta, bm, tb, cd), a.device)
+    Matmul(am, ta, bm, tb, cd, workspace=ws)
     return data
 
 
