@@ -4,6 +4,7 @@
 #ifndef SPUTNIK_SPUTNIK_H_
 #define SPUTNIK_SPUTNIK_H_
 
+#include "sputnik/block/accumulate.h"
 #include "sputnik/block/arguments.h"
 #include "sputnik/block/bitmask/bitmask.h"
 #include "sputnik/block/dsd/dsd.h"

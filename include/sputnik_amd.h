@@ -72,6 +72,35 @@ int sputnik_dds_ex(const sputnik_matrix_t *a, int transpose_a,
                    const sputnik_block_matrix_t *b, int transpose_b,
                    const sputnik_matrix_t *c, int dtype, void *stream);
 
+/* ---- Accumulating DSD / DDS: C += op(A) * op(B) (sputnik/block/accumulate.h)
+ * C_out = round(acc_fp32 + C_in), rounded once after the add. c_type selects
+ * what c->data holds: SPUTNIK_OUT_OPERAND the operands' type (`dtype`),
+ * SPUTNIK_OUT_F32 rows x cols floats. Where the sparse operand has no blocks
+ * C is neither read nor written; every other element is read and written
+ * once. C must not overlap A or B. Always the 8-wave kernel (never the 4-wave
+ * kernel, split mode or a transposed-B workspace); otherwise as the plain
+ * calls. Any other c_type: hipErrorInvalidValue (1). They never abort. */
+enum {
+  SPUTNIK_OUT_OPERAND = 0,
+  SPUTNIK_OUT_F32 = 1,
+};
+int sputnik_dsd_acc(const sputnik_block_matrix_t *a, int transpose_a,
+                    const sputnik_matrix_t *b, int transpose_b,
+                    const sputnik_matrix_t *c, int dtype, int c_type,
+                    void *stream);
+int sputnik_dsd_ex_acc(const sputnik_block_matrix_t *a, int transpose_a,
+                       const sputnik_matrix_t *b, int transpose_b,
+                       const sputnik_matrix_t *c, int dtype, int c_type,
+                       void *stream);
+int sputnik_dds_acc(const sputnik_matrix_t *a, int transpose_a,
+                    const sputnik_block_matrix_t *b, int transpose_b,
+                    const sputnik_matrix_t *c, int dtype, int c_type,
+                    void *stream);
+int sputnik_dds_ex_acc(const sputnik_matrix_t *a, int transpose_a,
+                       const sputnik_block_matrix_t *b, int transpose_b,
+                       const sputnik_matrix_t *c, int dtype, int c_type,
+                       void *stream);
+
 /* ---- SDD: C_bcsr = op(A) * op(B) at C's nonzero blocks
  *      (reference sputnik/block/sdd/sdd.h:10-15; needs c->row_indices) */
 int sputnik_sdd(const sputnik_matrix_t *a, int transpose_a,

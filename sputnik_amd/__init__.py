@@ -93,6 +93,15 @@ _SIGNATURES = {
     "sputnik_dds": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_dds_ex": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_sdd": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
+    # accumulating DSD / DDS: (..., dtype, c_type, stream)
+    "sputnik_dsd_acc": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                        ctypes.c_int, _P],
+    "sputnik_dsd_ex_acc": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                           ctypes.c_int, _P],
+    "sputnik_dds_acc": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                        ctypes.c_int, _P],
+    "sputnik_dds_ex_acc": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                           ctypes.c_int, _P],
     "sputnik_ssd": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_ssd_ex": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_sds": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
@@ -356,6 +365,70 @@ def MatmulEx(a, transpose_a, b, transpose_b, c, stream=None,  # noqa: N802
     """DSD / DDS / SSD / SDS / DSS with the transposed metadata already
     present. `workspace` (DSD) as in Matmul."""
     _call(True, a, transpose_a, b, transpose_b, c, stream, workspace)
+
+
+SPUTNIK_OUT_OPERAND = 0
+SPUTNIK_OUT_F32 = 1
+
+
+def _acc_c_type(operand, c) -> int:
+    """c_type of an accumulating call from c's tensor dtype: the operands'
+    dtype or torch.float32. TypeError otherwise, before any library call."""
+    import torch
+
+    if not isinstance(c, Matrix):
+        raise TypeError("MatmulAccumulate needs a dense c (there is no "
+                        "accumulating SDD / SSD / SDS)")
+    cd = getattr(c.data, "dtype", None)
+    if cd == torch.float32:
+        return SPUTNIK_OUT_F32
+    if cd == operand.dtype:
+        return SPUTNIK_OUT_OPERAND
+    raise TypeError(f"c is {cd}: an accumulating product takes a c of the "
+                    f"operands' dtype ({operand.dtype}) or torch.float32")
+
+
+def _call_acc(ex: bool, a, transpose_a: bool, b, transpose_b: bool, c, stream):
+    ta, tb = int(bool(transpose_a)), int(bool(transpose_b))
+    if isinstance(c, BlockMatrix):
+        raise TypeError("MatmulAccumulate needs a dense c (there is no "
+                        "accumulating SDD / SSD / SDS)")
+    if isinstance(a, BlockMatrix) and isinstance(b, Matrix):
+        dtype = _dtype_code(b.data)
+        c_type = _acc_c_type(b.data, c)
+        L = lib()
+        ca, cb, cc = a._c(), b._c(), c._c()
+        fn = L.sputnik_dsd_ex_acc if ex else L.sputnik_dsd_acc
+        _check(fn(ctypes.byref(ca), ta, ctypes.byref(cb), tb, ctypes.byref(cc),
+                  dtype, c_type, _stream(stream)), "dsd (accumulate)")
+        return
+    if isinstance(a, Matrix) and isinstance(b, BlockMatrix):
+        dtype = _dtype_code(a.data)
+        c_type = _acc_c_type(a.data, c)
+        L = lib()
+        ca, cb, cc = a._c(), b._c(), c._c()
+        fn = L.sputnik_dds_ex_acc if ex else L.sputnik_dds_acc
+        _check(fn(ctypes.byref(ca), ta, ctypes.byref(cb), tb, ctypes.byref(cc),
+                  dtype, c_type, _stream(stream)), "dds (accumulate)")
+        return
+    raise TypeError("no MatmulAccumulate overload for these operand kinds "
+                    "(DSD and DDS only)")
+
+
+def MatmulAccumulate(a, transpose_a, b, transpose_b, c, stream=None):  # noqa: N802
+    """c += op(a) op(b) for DSD / DDS (by operand kinds, as Matmul), rounded
+    once after the add. c.data is a tensor of the operands' dtype or of
+    torch.float32 (rows x cols); anything else raises TypeError before the
+    library is called, and so does a sparse c. Where the sparse operand has
+    no blocks c is not touched; c must not overlap a or b. Always the 8-wave
+    kernel: no 4-wave kernel, split mode or transposed-B workspace
+    (sputnik/block/accumulate.h)."""
+    _call_acc(False, a, transpose_a, b, transpose_b, c, stream)
+
+
+def MatmulAccumulateEx(a, transpose_a, b, transpose_b, c, stream=None):  # noqa: N802
+    """MatmulAccumulate with the transposed metadata already present."""
+    _call_acc(True, a, transpose_a, b, transpose_b, c, stream)
 
 
 def sdd_workspace_bytes(a, transpose_a, b, transpose_b, c) -> int:
@@ -623,6 +696,7 @@ __all__ = [
     "BlockMatrix", "BlockSize", "ExpertTopology", "FreeRowIndicesBuffer",
     "MaskToBcsr",
     "FreeTransposeBuffers", "Matmul", "MatmulEx", "Matrix", "RowIndices",
+    "MatmulAccumulate", "MatmulAccumulateEx",
     "SputnikError", "Transpose", "can_implement", "lib", "version",
     "allgather_concat", "gather_row_panels", "gather_col_panels",
     "gather_block_runs",

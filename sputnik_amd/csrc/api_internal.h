@@ -28,14 +28,24 @@ struct Workspace {
   size_t bytes = 0;
 };
 
+// What a dense-output product does with C. kStore: overwrite it with the
+// operand type (the plain products). kAccT / kAccF32: C += op(A) op(B) into a
+// C of the operand type / of fp32, rounded once after the add; C is left
+// untouched where the sparse operand has no blocks. An accumulating call
+// always runs the 8-wave kernel (pairs or the tall configuration as the
+// plain call would, never split mode, never the transposed-B route).
+enum class OutMode { kStore = 0, kAccT = 1, kAccF32 = 2 };
+
 // Validate, optionally build transposed metadata, launch. A non-kOk *status
 // means nothing was launched.
 hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                   const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *status, Workspace ws = Workspace{});
+                  hipStream_t stream, Status *status, Workspace ws = Workspace{},
+                  OutMode out = OutMode::kStore);
 hipError_t RunDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
                   const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *status);
+                  hipStream_t stream, Status *status,
+                  OutMode out = OutMode::kStore);
 hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, hipStream_t stream,
                   Status *status, Workspace ws = Workspace{});

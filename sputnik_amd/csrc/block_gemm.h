@@ -568,11 +568,21 @@ constexpr unsigned long long kPairWaitTicks = 20000000;
 // kSparseOut: DSD / DDS (sparse S, dense output).
 // kSKC / kDKC: S / D are k-contiguous in memory (else m/n-contiguous).
 // kOutT: write O transposed (DDS).
+// kOutMode (dense output only): kOutStore overwrites C with T (the plain
+// products); kOutAccT / kOutAccF32 add the fp32 accumulators to the C that
+// is there, a T or an fp32 matrix, and round once after the add. The
+// accumulating modes never store a tile the sparse operand leaves empty.
+constexpr int kOutStore = 0, kOutAccT = 1, kOutAccF32 = 2;
 template <typename T, bool kSparseOut, bool kSKC, bool kDKC, bool kOutT,
-          class Cfg, bool kSparseIn = false, bool kSparseD = false>
+          class Cfg, bool kSparseIn = false, bool kSparseD = false,
+          int kOutMode = kOutStore>
 __global__ void __launch_bounds__(64 * Cfg::kWaves,
                                   Cfg::kWGs * Cfg::kWaves / 4)
     block_gemm_kernel(const GemmParams p) {
+  static_assert(kOutMode == kOutStore ||
+                    (!kSparseOut && !kSparseIn && !kSparseD &&
+                     Cfg::kKSplit == 1 && !Cfg::kSplitMode),
+                "accumulating output: DSD / DDS, not split mode");
   constexpr int kBN = Cfg::kBN;
   constexpr int kBK = Cfg::kBK;
   constexpr int kStages = Cfg::kStages;
@@ -1458,6 +1468,89 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
           for (int b = 0; b < kFN; ++b) acc[a][b] += xch[(a * kFN + b) * 64];
       }
     }
+    if constexpr (kOutMode != kOutStore) {
+      // Accumulating output: C comes in in the accumulator layout. Lane l of
+      // fragment (a, b) holds 4 consecutive elements of one output row (DSD:
+      // row i = l & 15, columns 4 (l >> 4) ..; DDS, transposed: output row
+      // j = l & 15, columns i = 4 (l >> 4) ..), 8 bytes of T or 16 of fp32.
+      // It is added to the fp32 accumulators before their single rounding.
+      // The j guard is per fragment column b (j_limit is a multiple of 8).
+      constexpr int kEsz = kOutMode == kOutAccF32 ? 4 : 2;
+      const int lr = lane & 15, lq = 4 * (lane >> 4);
+      char *c_lane;      // this lane's elements of fragment (0, 0)
+      long long st_a, st_b;  // byte steps to fragment (a + 1, b), (a, b + 1)
+      int j_lane;        // the lane's j in fragment column 0
+      if constexpr (kOutT) {
+        j_lane = j0 + col_w + lr;
+        c_lane = p.c_data + (long long)j_lane * p.c_ld +
+                 ((long long)srow * kBM + row_w + lq) * kEsz;
+        st_a = 16 * kEsz;
+        st_b = 16 * p.c_ld;
+      } else {
+        j_lane = j0 + col_w + lq;
+        c_lane = p.c_data + ((long long)srow * kBM + row_w + lr) * p.c_ld +
+                 (long long)j_lane * kEsz;
+        st_a = 16 * p.c_ld;
+        st_b = 16 * kEsz;
+      }
+      // A few fragment rows at a time (kRows x kFN loads in flight, 32
+      // registers): beside the accumulators and what the pipeline keeps live
+      // across the epilogue there is room for no more without spilling.
+      if constexpr (kOutMode == kOutAccT) {
+        typedef T t4 __attribute__((ext_vector_type(4)));
+        constexpr int kRows = kFM >= 2 ? 2 : 1;
+        static_assert(kFM % kRows == 0, "fragment rows");
+#pragma unroll
+        for (int a0 = 0; a0 < kFM; a0 += kRows) {
+          t4 old[kRows][kFN];
+#pragma unroll
+          for (int a = 0; a < kRows; ++a)
+#pragma unroll
+            for (int b = 0; b < kFN; ++b) {
+              old[a][b] = t4{(T)0.f, (T)0.f, (T)0.f, (T)0.f};
+              if (j_lane + 16 * b < p.j_limit)
+                old[a][b] = *reinterpret_cast<const t4 *>(
+                    c_lane + (a0 + a) * st_a + b * st_b);
+            }
+#pragma unroll
+          for (int a = 0; a < kRows; ++a)
+#pragma unroll
+            for (int b = 0; b < kFN; ++b) {
+              acc[a0 + a][b][0] += (float)old[a][b][0];
+              acc[a0 + a][b][1] += (float)old[a][b][1];
+              acc[a0 + a][b][2] += (float)old[a][b][2];
+              acc[a0 + a][b][3] += (float)old[a][b][3];
+            }
+        }
+        // ... and the sums take the plain product's staging and stores below
+      } else {
+        // fp32 C: read, add and store in the accumulator layout, 16 bytes per
+        // lane (4 lanes cover 64 contiguous bytes of a row).
+#pragma unroll
+        for (int a = 0; a < kFM; ++a) {
+          f32x4 old[kFN];
+#pragma unroll
+          for (int b = 0; b < kFN; ++b) {
+            old[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (j_lane + 16 * b < p.j_limit)
+              old[b] = *reinterpret_cast<const f32x4 *>(c_lane + a * st_a +
+                                                        b * st_b);
+          }
+#pragma unroll
+          for (int b = 0; b < kFN; ++b) {
+            if (j_lane + 16 * b >= p.j_limit) continue;
+            const f32x4 v = acc[a][b] + old[b];
+            char *dst = c_lane + a * st_a + b * st_b;
+            if constexpr (SPUTNIK_OUT_NT != 0)
+              __builtin_nontemporal_store(__builtin_bit_cast(v4u, v),
+                                          reinterpret_cast<v4u *>(dst));
+            else
+              *reinterpret_cast<f32x4 *>(dst) = v;
+          }
+        }
+        return;
+      }
+    }
     constexpr int kStLdNT = kBN * 2 + 16;  // straight staging row
     constexpr int kStLdT = kBM * 2 + 16;   // transposed staging row
     constexpr int kPasses =
@@ -1668,6 +1761,7 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
     int p_first = 0, p_steps = 0;  // scalar-index pipeline range
     int p_flush = -1;              // pair producer: end of the head segment
     bool do_collect = false;       // pair consumer
+    bool own_empty = false;        // accumulating pair producer, empty row
     bool use_pairs = false;
     if constexpr (kPairs) use_pairs = p.pair != 0;
     tl(7);
@@ -1785,6 +1879,9 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
         p_first = 0;
         p_steps = (hb + n_l) * kStepsPerBlock;
         p_flush = hb > 0 ? hb * kStepsPerBlock : -1;
+        // Accumulating: an empty light row that only ran the heavy row's
+        // head (published above) leaves its own tile alone.
+        if constexpr (kOutMode != kOutStore) own_empty = n_l == 0;
       } else {
         srow = rows.x;
         idx_base = e_h;
@@ -2031,8 +2128,9 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
     if (split_producer()) {
       // split mode: this chunk's partial is published; the tile is written
       // by its consumer
-    } else if (empty) {
-      write_zero_tile();
+    } else if (empty || own_empty) {
+      // (accumulating: C += 0, the tile is neither read nor written)
+      if constexpr (kOutMode == kOutStore) write_zero_tile();
     } else {
       write_tile(out_block);
     }
@@ -2114,6 +2212,12 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
 hipError_t LaunchBlockGemm(int dtype, bool sparse_out, bool s_kc, bool d_kc,
                            bool out_t, bool grouped, const GemmParams &params,
                            hipStream_t stream);
+// Accumulating DSD / DDS (defined in block_gemm_acc.hip): out_mode kOutAccT
+// or kOutAccF32, on CfgSparse (plain or paired; never split mode) or, tall,
+// on CfgTall. Anything else: hipErrorInvalidValue, nothing launched.
+hipError_t LaunchBlockGemmAcc(int dtype, bool s_kc, bool d_kc, bool out_t,
+                              bool tall, int out_mode,
+                              const GemmParams &params, hipStream_t stream);
 // DSS on CfgBlock: num_tiles = (M/128) x (N/128), num_jtiles = N/128.
 hipError_t LaunchBlockGemmDss(int dtype, bool s_kc, bool d_kc,
                               const GemmParams &params, hipStream_t stream);

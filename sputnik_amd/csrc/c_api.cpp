@@ -115,6 +115,80 @@ int sputnik_dds_ex(const sputnik_matrix_t *a, int transpose_a,
   return Code(e, sputnik_amd::StatusCode(st));
 }
 
+// Accumulating DSD / DDS. c_type: SPUTNIK_OUT_OPERAND / SPUTNIK_OUT_F32.
+static bool AccOutMode(int c_type, sputnik_amd::OutMode *out) {
+  if (c_type == SPUTNIK_OUT_OPERAND) {
+    *out = sputnik_amd::OutMode::kAccT;
+    return true;
+  }
+  if (c_type == SPUTNIK_OUT_F32) {
+    *out = sputnik_amd::OutMode::kAccF32;
+    return true;
+  }
+  return false;
+}
+
+static int DsdAcc(bool ex, const sputnik_block_matrix_t *a, int transpose_a,
+                  const sputnik_matrix_t *b, int transpose_b,
+                  const sputnik_matrix_t *c, int dtype, int c_type,
+                  void *stream) {
+  sputnik_amd::OutMode out;
+  if (!a || !b || !c || !AccOutMode(c_type, &out)) return hipErrorInvalidValue;
+  const BlockMatrix ca = ToCpp(a);
+  sputnik_amd::Status st;
+  const hipError_t e = sputnik_amd::RunDsd(
+      ca, transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
+      !ex && ca.create_metadata, static_cast<hipStream_t>(stream), &st,
+      sputnik_amd::Workspace{}, out);
+  return Code(e, sputnik_amd::StatusCode(st));
+}
+
+static int DdsAcc(bool ex, const sputnik_matrix_t *a, int transpose_a,
+                  const sputnik_block_matrix_t *b, int transpose_b,
+                  const sputnik_matrix_t *c, int dtype, int c_type,
+                  void *stream) {
+  sputnik_amd::OutMode out;
+  if (!a || !b || !c || !AccOutMode(c_type, &out)) return hipErrorInvalidValue;
+  const BlockMatrix cb = ToCpp(b);
+  sputnik_amd::Status st;
+  const hipError_t e = sputnik_amd::RunDds(
+      ToCpp(a), transpose_a != 0, cb, transpose_b != 0, ToCpp(c), dtype,
+      !ex && cb.create_metadata, static_cast<hipStream_t>(stream), &st, out);
+  return Code(e, sputnik_amd::StatusCode(st));
+}
+
+int sputnik_dsd_acc(const sputnik_block_matrix_t *a, int transpose_a,
+                    const sputnik_matrix_t *b, int transpose_b,
+                    const sputnik_matrix_t *c, int dtype, int c_type,
+                    void *stream) {
+  return DsdAcc(false, a, transpose_a, b, transpose_b, c, dtype, c_type,
+                stream);
+}
+
+int sputnik_dsd_ex_acc(const sputnik_block_matrix_t *a, int transpose_a,
+                       const sputnik_matrix_t *b, int transpose_b,
+                       const sputnik_matrix_t *c, int dtype, int c_type,
+                       void *stream) {
+  return DsdAcc(true, a, transpose_a, b, transpose_b, c, dtype, c_type,
+                stream);
+}
+
+int sputnik_dds_acc(const sputnik_matrix_t *a, int transpose_a,
+                    const sputnik_block_matrix_t *b, int transpose_b,
+                    const sputnik_matrix_t *c, int dtype, int c_type,
+                    void *stream) {
+  return DdsAcc(false, a, transpose_a, b, transpose_b, c, dtype, c_type,
+                stream);
+}
+
+int sputnik_dds_ex_acc(const sputnik_matrix_t *a, int transpose_a,
+                       const sputnik_block_matrix_t *b, int transpose_b,
+                       const sputnik_matrix_t *c, int dtype, int c_type,
+                       void *stream) {
+  return DdsAcc(true, a, transpose_a, b, transpose_b, c, dtype, c_type,
+                stream);
+}
+
 int sputnik_sdd_ws(const sputnik_matrix_t *a, int transpose_a,
                    const sputnik_matrix_t *b, int transpose_b,
                    const sputnik_block_matrix_t *c, int dtype, void *ws,

@@ -443,8 +443,10 @@ static void BindPairSlot(GemmParams *p, PairSlot *slot, int capturing) {
   p->ks_flags = slot->flags + slot->pairs + 3;
 }
 
+// allow_split = false (accumulating calls): pairs only, never split mode; the
+// tile widths and the grid stay those of the non-split launch.
 static void PreparePairs(GemmParams *p, long long blocks, hipStream_t stream,
-                         bool dry = false) {
+                         bool dry = false, bool allow_split = true) {
   p->pair = 0;
   if (!CfgSparse::kStagger || CfgSparse::kWGs != 1)
     return;
@@ -493,7 +495,8 @@ static void PreparePairs(GemmParams *p, long long blocks, hipStream_t stream,
   // workgroups each) still fit the slots, so a panel of few block-rows
   // fills the CUs (r03: M = 512 on 128-column tiles, M = 1024 on 256).
   int split = 1;
-  if (split_on != 0 && (long long)p->num_tiles * 2 <= slot->slots &&
+  if (allow_split && split_on != 0 &&
+      (long long)p->num_tiles * 2 <= slot->slots &&
       blocks >= 4LL * p->num_rows) {
     split = 2;
     int bn = CfgSparse::kBN;
@@ -1410,13 +1413,31 @@ size_t ReleaseWorkspaces() {
 
 hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                   const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *st_out, Workspace ws) {
+                  hipStream_t stream, Status *st_out, Workspace ws,
+                  OutMode out) {
   const InProduct in_product;
   GemmParams p;
   bool needs_meta = false;
   const Status st = PrepareDsd(a, ta, b, tb, c, &p, &needs_meta);
   *st_out = st;
   if (st != Status::kOk) return hipSuccess;
+  if (out != OutMode::kStore) {
+    // Accumulating: always the 8-wave kernel, with pairs where PreparePairs
+    // grants them (never split mode) or the tall configuration; op(B) = B^T
+    // runs the NT kernel directly (no transposed copy, no workspace).
+    if (needs_meta && build_meta) {
+      const hipError_t e = BuildTransposed(a, stream);
+      if (e != hipSuccess) return e;
+    }
+    if (out == OutMode::kAccF32) p.c_ld *= 2;  // ldc x 4 bytes
+    p.debug = g_debug;
+    PreparePairs(&p, a.nonzeros / (kBlock * kBlock), stream, /*dry=*/false,
+                 /*allow_split=*/false);
+    const bool tall = UseTall(&p, stream);
+    return LaunchBlockGemmAcc(dtype, !ta, tb, false, tall,
+                              out == OutMode::kAccF32 ? kOutAccF32 : kOutAccT,
+                              p, stream);
+  }
   if (BtAppliesDsd(a, ta, b, tb)) {
     const size_t bt_bytes = (size_t)b.rows * b.cols * 2;
     Workspace own;
@@ -1427,7 +1448,7 @@ hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
         const hipError_t e = EnqueueBt(b, own.ptr, stream);
         if (e != hipSuccess) return e;
         return RunDsd(a, ta, Matrix(b.cols, b.rows, own.ptr), false, c, dtype, build_meta,
-                      stream, st_out, Workspace{});
+                      stream, st_out, Workspace{}, OutMode::kStore);
       }
     } else if (BtLibraryStreamOk(stream)) {
       std::lock_guard<std::mutex> lock(g_bt_mu);
@@ -1436,7 +1457,7 @@ hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
         const hipError_t e = EnqueueBt(b, bt, stream);
         if (e != hipSuccess) return e;
         return RunDsd(a, ta, Matrix(b.cols, b.rows, bt), false, c, dtype, build_meta, stream,
-                      st_out, Workspace{});
+                      st_out, Workspace{}, OutMode::kStore);
       }
     }
   }
@@ -1481,7 +1502,7 @@ hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
 
 hipError_t RunDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
                   const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *st_out) {
+                  hipStream_t stream, Status *st_out, OutMode out) {
   const InProduct in_product;
   GemmParams p;
   bool needs_meta = false;
@@ -1493,6 +1514,17 @@ hipError_t RunDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
     if (e != hipSuccess) return e;
   }
   p.debug = g_debug;
+  if (out != OutMode::kStore) {
+    // Accumulating: the 8-wave kernel (RunDsd above).
+    if (out == OutMode::kAccF32) p.c_ld *= 2;  // ldc x 4 bytes
+    PreparePairs(&p, b.nonzeros / (kBlock * kBlock), stream, /*dry=*/false,
+                 /*allow_split=*/false);
+    const bool tall = UseTall(&p, stream);
+    return LaunchBlockGemmAcc(dtype, /*s_kc=*/tb, /*d_kc=*/!ta,
+                              /*out_t=*/true, tall,
+                              out == OutMode::kAccF32 ? kOutAccF32 : kOutAccT,
+                              p, stream);
+  }
   p.xcd_rows = Knob(kKnobXcdRows);
   PreparePairs(&p, b.nonzeros / (kBlock * kBlock), stream);
   const bool tall = UseTall(&p, stream);
@@ -1699,6 +1731,55 @@ hipError_t Matmul(const Matrix a, bool transpose_a, const BlockMatrix b,
 hipError_t MatmulEx(const Matrix a, bool transpose_a, const BlockMatrix b,
                     bool transpose_b, Matrix c, hipStream_t stream) {
   return MatmulEx(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+// ---- accumulating DSD / DDS (sputnik/block/accumulate.h) ----
+
+static sputnik_amd::OutMode AccMode(OutputType c_type) {
+  return c_type == OutputType::kF32 ? sputnik_amd::OutMode::kAccF32
+                                    : sputnik_amd::OutMode::kAccT;
+}
+
+hipError_t MatmulAccumulate(const BlockMatrix a, bool transpose_a,
+                            const Matrix b, bool transpose_b, Matrix c,
+                            DataType dtype, OutputType c_type,
+                            hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunDsd(
+      a, transpose_a, b, transpose_b, c, (int)dtype, a.create_metadata, stream,
+      &st, sputnik_amd::Workspace{}, AccMode(c_type));
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dsd (accumulate)");
+}
+
+hipError_t MatmulAccumulateEx(const BlockMatrix a, bool transpose_a,
+                              const Matrix b, bool transpose_b, Matrix c,
+                              DataType dtype, OutputType c_type,
+                              hipStream_t stream) {
+  BlockMatrix acp = a;
+  acp.create_metadata = false;
+  return MatmulAccumulate(acp, transpose_a, b, transpose_b, c, dtype, c_type,
+                          stream);
+}
+
+hipError_t MatmulAccumulate(const Matrix a, bool transpose_a,
+                            const BlockMatrix b, bool transpose_b, Matrix c,
+                            DataType dtype, OutputType c_type,
+                            hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunDds(
+      a, transpose_a, b, transpose_b, c, (int)dtype, b.create_metadata, stream,
+      &st, AccMode(c_type));
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dds (accumulate)");
+}
+
+hipError_t MatmulAccumulateEx(const Matrix a, bool transpose_a,
+                              const BlockMatrix b, bool transpose_b, Matrix c,
+                              DataType dtype, OutputType c_type,
+                              hipStream_t stream) {
+  BlockMatrix bcp = b;
+  bcp.create_metadata = false;
+  return MatmulAccumulate(a, transpose_a, bcp, transpose_b, c, dtype, c_type,
+                          stream);
 }
 
 hipError_t Matmul(const Matrix a, bool transpose_a, const Matrix b,

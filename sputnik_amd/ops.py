@@ -9,7 +9,11 @@ device the first time a product needs them, so every later call is a
     dds(a, b_sparse) -> Tensor        (a @ op(b))
 
 whose backward passes are again sdd / dsd / dds with transpose flags (the
-MegaBlocks forward/backward set, BASELINE config 3). Every product runs on
+MegaBlocks forward/backward set, BASELINE config 3). Each op takes optional
+gradient sinks (`a_grad_out` / `b_grad_out`) for its dense operands: backward
+then adds that operand's gradient into the sink with the accumulating product
+(C += op(A) op(B), `dsd_acc` / `dds_acc` below) instead of returning it, the
+Megatron `main_grad` convention. Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
 
@@ -27,7 +31,8 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import (BlockMatrix, Matrix, Matmul, MatmulEx, RowIndices, Transpose,
+from . import (BlockMatrix, Matrix, Matmul, MatmulAccumulateEx, MatmulEx,
+               RowIndices, Transpose,
                AllocateRowIndicesBuffer, AllocateTransposeBuffers,
                dsd_workspace_bytes, sdd_workspace_bytes)
 
@@ -241,12 +246,95 @@ def _sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix) -> torch.Tensor:
     return data
 
 
+# ---- accumulating products (no autograd) ---------------------------------------
+
+def _check_sink(out: torch.Tensor, rows: int, cols: int, dt, what: str):
+    if not isinstance(out, torch.Tensor) or out.dim() != 2:
+        raise TypeError(f"{what}: the sink must be a 2-D tensor")
+    if tuple(out.shape) != (rows, cols):
+        raise ValueError(f"{what}: sink shape {tuple(out.shape)}, expected "
+                         f"{(rows, cols)}")
+    if not out.is_contiguous():
+        raise ValueError(f"{what}: the sink must be contiguous")
+    if out.dtype not in (dt, torch.float32):
+        raise TypeError(f"{what}: sink dtype {out.dtype}, expected {dt} or "
+                        "torch.float32")
+
+
+def dsd_acc(a: SparseMatrix, b: torch.Tensor, out: torch.Tensor
+            ) -> torch.Tensor:
+    """out += op(a_sparse) @ b in place, rounded once after the add; `out`
+    is contiguous, of b's dtype or fp32, and must not overlap a or b. Rows of
+    `out` that meet no block of op(a) are not touched. Returns `out`."""
+    _check_dtypes(a.data, b)
+    if a.shape[1] != b.shape[0]:
+        raise ValueError(f"dsd shapes {a.shape} x {tuple(b.shape)}")
+    _check_sink(out, a.shape[0], b.shape[1], b.dtype, "dsd_acc")
+    bm, tb = _dense_operand(b)
+    if a.is_transposed():
+        a._meta.ensure_transposed(a.data)
+    MatmulAccumulateEx(a._descriptor(), a.is_transposed(), bm, tb,
+                       Matrix(out.shape[0], out.shape[1], out))
+    return out
+
+
+def dds_acc(a: torch.Tensor, b: SparseMatrix, out: torch.Tensor
+            ) -> torch.Tensor:
+    """out += a @ op(b_sparse) in place (as dsd_acc); columns of `out` that
+    meet no block of op(b) are not touched. Returns `out`."""
+    _check_dtypes(a, b.data)
+    if a.shape[1] != b.shape[0]:
+        raise ValueError(f"dds shapes {tuple(a.shape)} x {b.shape}")
+    _check_sink(out, a.shape[0], b.shape[1], a.dtype, "dds_acc")
+    am, ta = _dense_operand(a)
+    if not b.is_transposed():  # row n of op(B)^T is column n of B
+        b._meta.ensure_transposed(b.data)
+    MatmulAccumulateEx(am, ta, b._descriptor(), b.is_transposed(),
+                       Matrix(out.shape[0], out.shape[1], out))
+    return out
+
+
+class _Sink:
+    """A gradient sink of one dense operand. The sink belongs to the tensor
+    the caller holds: when the operand reached the op as a transposed view of
+    a contiguous tensor, the sink has that tensor's shape and receives the
+    transposed gradient."""
+
+    def __init__(self, out: torch.Tensor, operand: torch.Tensor, what: str):
+        self.out = out
+        self.transposed = (operand.dim() == 2 and not operand.is_contiguous()
+                           and operand.t().is_contiguous())
+        rows, cols = operand.shape
+        if self.transposed:
+            rows, cols = cols, rows
+        _check_sink(out, rows, cols, operand.dtype, what)
+
+    # (X Y)^T = Y^T X^T: the transposed product swaps DSD and DDS and flips
+    # both operands' flags, so no transposing copy is made.
+    def add_dsd(self, a: SparseMatrix, b: torch.Tensor):
+        if self.transposed:
+            dds_acc(b.t(), a.t(), self.out)
+        else:
+            dsd_acc(a, b, self.out)
+
+    def add_dds(self, a: torch.Tensor, b: SparseMatrix):
+        if self.transposed:
+            dsd_acc(b.t(), a.t(), self.out)
+        else:
+            dds_acc(a, b, self.out)
+
+
+def _sink(out, operand, what):
+    return None if out is None else _Sink(out, operand, what)
+
+
 # ---- autograd ---------------------------------------------------------------
 
 class _DSD(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a_data, b, a):
+    def forward(ctx, a_data, b, a, b_sink):
         ctx.a = a
+        ctx.b_sink = b_sink
         ctx.save_for_backward(a_data, b)
         return _dsd(a.with_data(a_data), b)
 
@@ -255,20 +343,23 @@ class _DSD(torch.autograd.Function):
         a_data, b = ctx.saved_tensors
         a = ctx.a.with_data(a_data)
         da = db = None
-        if ctx.needs_input_grad[1]:
+        if ctx.b_sink is not None:
+            ctx.b_sink.add_dsd(a.t(), dc)              # sink += op(A)^T dC
+        elif ctx.needs_input_grad[1]:
             db = _dsd(a.t(), dc)                       # op(A)^T dC
         if ctx.needs_input_grad[0]:
             # C = S B: dS = dC B^T;  C = S^T B: dS = B dC^T (at S's blocks)
             stored = a.t() if a.is_transposed() else a
             da = (_sdd(b, dc.t(), stored) if a.is_transposed()
                   else _sdd(dc, b.t(), stored))
-        return da, db, None
+        return da, db, None, None
 
 
 class _DDS(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b_data, b):
+    def forward(ctx, a, b_data, b, a_sink):
         ctx.b = b
+        ctx.a_sink = a_sink
         ctx.save_for_backward(a, b_data)
         return _dds(a, b.with_data(b_data))
 
@@ -277,20 +368,23 @@ class _DDS(torch.autograd.Function):
         a, b_data = ctx.saved_tensors
         b = ctx.b.with_data(b_data)
         da = db = None
-        if ctx.needs_input_grad[0]:
+        if ctx.a_sink is not None:
+            ctx.a_sink.add_dds(dc, b.t())              # sink += dC op(B)^T
+        elif ctx.needs_input_grad[0]:
             da = _dds(dc, b.t())                       # dC op(B)^T
         if ctx.needs_input_grad[1]:
             # C = A S: dS = A^T dC;  C = A S^T: dS = dC^T A (at S's blocks)
             stored = b.t() if b.is_transposed() else b
             db = (_sdd(dc.t(), a, stored) if b.is_transposed()
                   else _sdd(a.t(), dc, stored))
-        return da, db, None
+        return da, db, None, None
 
 
 class _SDD(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, topo):
+    def forward(ctx, a, b, topo, a_sink, b_sink):
         ctx.topo = topo
+        ctx.a_sink, ctx.b_sink = a_sink, b_sink
         ctx.save_for_backward(a, b)
         return _sdd(a, b, topo)
 
@@ -299,26 +393,44 @@ class _SDD(torch.autograd.Function):
         a, b = ctx.saved_tensors
         dc = ctx.topo.with_data(dc_data.contiguous())
         da = db = None
-        if ctx.needs_input_grad[0]:
+        if ctx.a_sink is not None:
+            ctx.a_sink.add_dsd(dc, b.t())              # sink += dC B^T
+        elif ctx.needs_input_grad[0]:
             da = _dsd(dc, b.t())                       # dC B^T
-        if ctx.needs_input_grad[1]:
+        if ctx.b_sink is not None:
+            ctx.b_sink.add_dds(a.t(), dc)              # sink += A^T dC
+        elif ctx.needs_input_grad[1]:
             db = _dds(a.t(), dc)                       # A^T dC
-        return da, db, None
+        return da, db, None, None, None
 
 
-def dsd(a: SparseMatrix, b: torch.Tensor) -> torch.Tensor:
+# Gradient sinks (`*_grad_out`): a contiguous tensor of the dense operand's
+# shape (of the tensor the caller holds when the operand is its .t() view),
+# in the operand's dtype or fp32. Backward adds the operand's gradient into
+# it with the accumulating product, allocates no gradient-sized temporary
+# and returns None for that operand, so its .grad stays unset. The sink must
+# not overlap any operand or the incoming gradient. Without sinks nothing
+# changes.
+
+def dsd(a: SparseMatrix, b: torch.Tensor,
+        b_grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dense = op(sparse) @ dense (reference dsd.h:10-22)."""
-    return _DSD.apply(a.data, b, a)
+    return _DSD.apply(a.data, b, a, _sink(b_grad_out, b, "dsd b_grad_out"))
 
 
-def dds(a: torch.Tensor, b: SparseMatrix) -> torch.Tensor:
+def dds(a: torch.Tensor, b: SparseMatrix,
+        a_grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dense = dense @ op(sparse) (reference dds.h:10-22)."""
-    return _DDS.apply(a, b.data, b)
+    return _DDS.apply(a, b.data, b, _sink(a_grad_out, a, "dds a_grad_out"))
 
 
-def sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix) -> SparseMatrix:
+def sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
+        a_grad_out: Optional[torch.Tensor] = None,
+        b_grad_out: Optional[torch.Tensor] = None) -> SparseMatrix:
     """Sparse (topo's blocks) = dense @ dense (reference sdd.h:10-15)."""
-    return topo.with_data(_SDD.apply(a, b, topo))
+    return topo.with_data(_SDD.apply(
+        a, b, topo, _sink(a_grad_out, a, "sdd a_grad_out"),
+        _sink(b_grad_out, b, "sdd b_grad_out")))
 
 
 def from_dense_mask(x: torch.Tensor, mask) -> SparseMatrix:
@@ -371,5 +483,5 @@ def expert_topology(padded_bins: torch.Tensor, blocks_per_expert: int,
                         data, offsets, indices)
 
 
-__all__ = ["SparseMatrix", "dds", "dsd", "expert_topology", "from_dense_mask",
-           "sdd", "topology_from_mask"]
+__all__ = ["SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
+           "expert_topology", "from_dense_mask", "sdd", "topology_from_mask"]
