@@ -5,6 +5,7 @@
 #define SPUTNIK_SPUTNIK_H_
 
 #include "sputnik/block/accumulate.h"
+#include "sputnik/block/activation.h"
 #include "sputnik/block/arguments.h"
 #include "sputnik/block/bitmask/bitmask.h"
 #include "sputnik/block/dsd/dsd.h"

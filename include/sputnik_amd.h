@@ -107,6 +107,57 @@ int sputnik_sdd(const sputnik_matrix_t *a, int transpose_a,
                 const sputnik_matrix_t *b, int transpose_b,
                 const sputnik_block_matrix_t *c, int dtype, void *stream);
 
+/* ---- SDD with an activation epilogue (sputnik/block/activation.h,
+ * INTEGRATION.md 3e). With acc the fp32 accumulator sputnik_sdd would round
+ * and T the operand type:
+ *   sputnik_sdd_act       Z = round_T(acc), H = round_T(act(float(Z)));
+ *                         H -> c->data, Z -> z when z != NULL
+ *   sputnik_sdd_act_grad  c->data = round_T(float(round_T(acc)) *
+ *                         act'(float(Z))), Z read from z (required)
+ * z holds c->nonzeros elements of T in c's storage order and must not overlap
+ * c->data, A or B. act: SPUTNIK_ACT_RELU, SPUTNIK_ACT_GELU (the tanh form)
+ * or SPUTNIK_ACT_SILU, evaluated in fp32 (formulas in activation.h); every
+ * finite Z gives a finite result, NaN / inf in Z what the fp32 formula
+ * yields. Two routes give the same bits: the 8-wave kernel's fused epilogue,
+ * or sputnik_sdd as it stands followed by the elementwise kernel below (knob
+ * "sdd_act_route"). `ws`, `ws_bytes`: as sputnik_sdd_ws (used on the
+ * two-kernel route only; the fused route never takes the transposed-B path,
+ * and sputnik_sdd_workspace_bytes answers as for sputnik_sdd).
+ * They never abort: an unknown act, a null operand, a null z in the grad
+ * form, or z == c->data: hipErrorInvalidValue (1); block size != 128:
+ * hipErrorNotSupported; a shape sputnik_sdd rejects is rejected the same
+ * way. */
+enum {
+  SPUTNIK_ACT_RELU = 0,
+  SPUTNIK_ACT_GELU = 1,
+  SPUTNIK_ACT_SILU = 2,
+};
+int sputnik_sdd_act(const sputnik_matrix_t *a, int transpose_a,
+                    const sputnik_matrix_t *b, int transpose_b,
+                    const sputnik_block_matrix_t *c, int act, void *z,
+                    int dtype, void *ws, size_t ws_bytes, void *stream);
+int sputnik_sdd_act_grad(const sputnik_matrix_t *a, int transpose_a,
+                         const sputnik_matrix_t *b, int transpose_b,
+                         const sputnik_block_matrix_t *c, int act,
+                         const void *z, int dtype, void *ws, size_t ws_bytes,
+                         void *stream);
+/* The elementwise stage alone, over n elements of block data (dtype 0 fp16,
+ * 1 bf16): h[i] = round_T(act(float(z[i]))), and the gate
+ * out[i] = round_T(float(g[i]) * act'(float(z[i]))). h may be z, out may be
+ * g or z (in place). 16-byte accesses when every buffer is 16-byte aligned.
+ * hipErrorInvalidValue for an unknown act or dtype, n < 0, or a null buffer
+ * with n > 0. */
+int sputnik_block_activation(const void *z, void *h, long long n, int act,
+                             int dtype, void *stream);
+int sputnik_block_activation_grad(const void *g, const void *z, void *out,
+                                  long long n, int act, int dtype,
+                                  void *stream);
+/* Diagnostic: the route sputnik_sdd_act[_grad] would take for this problem
+ * now, 1 = fused, 2 = two kernels, -1 = rejected. */
+int sputnik_sdd_act_route(const sputnik_matrix_t *a, int transpose_a,
+                          const sputnik_matrix_t *b, int transpose_b,
+                          const sputnik_block_matrix_t *c);
+
 /* ---- Caller-owned workspaces for the transposed-B path
  * SDD NT / TT, and DSD NT over a nearly dense A, transpose B once into a
  * scratch buffer when B is at least "sdd_bt_min_mib" MiB and the product is
@@ -341,7 +392,10 @@ int sputnik_select_dsd_kernel(int four_wave);
  * "tall4w" (1: the tall DSD NN pipeline), "tall_flush_w" (4: a tile
  * store's weight in quarter blocks for the pipeline's work split),
  * "tall_odd_share" (120: an odd XCD's workgroup share in percent of an even
- * one's). An environment value that does not parse or is out of range
+ * one's), "sdd_act_route" (0: auto -- the SDD activation products run fused
+ * where the plain SDD would run the 8-wave kernel, as two kernels otherwise;
+ * 1 fused, 2 two kernels; same results either way).
+ * An environment value that does not parse or is out of range
  * means the default. get returns the value,
  * set the previous value; both return INT_MIN for an unknown name, set also
  * for a value out of the knob's range (nothing changes then). */

@@ -102,6 +102,19 @@ _SIGNATURES = {
                         ctypes.c_int, _P],
     "sputnik_dds_ex_acc": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
                            ctypes.c_int, _P],
+    # SDD activation products: (a, ta, b, tb, c, act, z, dtype, ws, ws_bytes,
+    # stream); the elementwise stage alone: (z, h, n, act, dtype, stream) and
+    # (g, z, out, n, act, dtype, stream)
+    "sputnik_sdd_act": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                        _P, ctypes.c_int, _P, ctypes.c_size_t, _P],
+    "sputnik_sdd_act_grad": [_P, ctypes.c_int, _P, ctypes.c_int, _P,
+                             ctypes.c_int, _P, ctypes.c_int, _P,
+                             ctypes.c_size_t, _P],
+    "sputnik_block_activation": [_P, _P, ctypes.c_longlong, ctypes.c_int,
+                                 ctypes.c_int, _P],
+    "sputnik_block_activation_grad": [_P, _P, _P, ctypes.c_longlong,
+                                      ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_sdd_act_route": [_P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_ssd": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_ssd_ex": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_sds": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
@@ -431,6 +444,147 @@ def MatmulAccumulateEx(a, transpose_a, b, transpose_b, c, stream=None):  # noqa:
     _call_acc(True, a, transpose_a, b, transpose_b, c, stream)
 
 
+SPUTNIK_ACT_RELU = 0
+SPUTNIK_ACT_GELU = 1
+SPUTNIK_ACT_SILU = 2
+_ACT_NAMES = {"relu": SPUTNIK_ACT_RELU, "gelu": SPUTNIK_ACT_GELU,
+              "silu": SPUTNIK_ACT_SILU}
+
+
+def _act_code(activation) -> int:
+    """SPUTNIK_ACT_* from a constant or a name ("relu", "gelu": the tanh
+    form, "silu"). ValueError otherwise, before any library call."""
+    if isinstance(activation, str):
+        if activation in _ACT_NAMES:
+            return _ACT_NAMES[activation]
+    elif isinstance(activation, int) and not isinstance(activation, bool):
+        if activation in _ACT_NAMES.values():
+            return int(activation)
+    raise ValueError(f"unknown activation {activation!r}: one of "
+                     f"{sorted(_ACT_NAMES)} or SPUTNIK_ACT_RELU/GELU/SILU")
+
+
+def _act_buffer(t, dtype, numel: int, what: str):
+    """A block-data buffer of an activation call: `dtype`, `numel` elements,
+    contiguous. Raises before any library call."""
+    td = getattr(t, "dtype", None)
+    if td != dtype:
+        raise TypeError(f"{what} is {td}, expected {dtype}")
+    if int(t.numel()) != numel:
+        raise ValueError(f"{what} holds {int(t.numel())} elements, expected "
+                         f"{numel}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+
+
+def _sdd_act_operands(a, b, c, what: str) -> int:
+    if not (isinstance(a, Matrix) and isinstance(b, Matrix)
+            and isinstance(c, BlockMatrix)):
+        raise TypeError(f"{what} is an SDD: dense a and b, sparse c")
+    dtype = _dtype_code(a.data)
+    for name, m in (("b", b), ("c", c)):
+        md = getattr(m.data, "dtype", None)
+        if md != a.data.dtype:
+            raise TypeError(f"{what}: {name} is {md}, a is {a.data.dtype}")
+    return dtype
+
+
+def _call_sdd_act(grad: bool, a, transpose_a, b, transpose_b, c, activation,
+                  pre_activation, stream, workspace):
+    what = "MatmulActivationGrad" if grad else "MatmulActivation"
+    act = _act_code(activation)
+    dtype = _sdd_act_operands(a, b, c, what)
+    if pre_activation is None:
+        if grad:
+            raise TypeError(f"{what} needs the pre-activation the forward "
+                            "call stored")
+    else:
+        _act_buffer(pre_activation, a.data.dtype, int(c.nonzeros),
+                    "pre_activation")
+    ws = _workspace(workspace) if workspace is not None else (None, 0)
+    L = lib()
+    ca, cb, cc = a._c(), b._c(), c._c()
+    fn = L.sputnik_sdd_act_grad if grad else L.sputnik_sdd_act
+    _check(fn(ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
+              int(bool(transpose_b)), ctypes.byref(cc), act,
+              _ptr(pre_activation), dtype, ws[0], ws[1], _stream(stream)),
+           "sdd (activation grad)" if grad else "sdd (activation)")
+
+
+def MatmulActivation(a, transpose_a, b, transpose_b, c, activation,  # noqa: N802
+                     pre_activation=None, stream=None, workspace=None):
+    """SDD with the activation fused: c.data = H = act(Z), Z = op(a) op(b)
+    rounded to the operand type, at c's blocks. `pre_activation` (optional):
+    a contiguous tensor of c.nonzeros elements of the operands' dtype that
+    receives Z in c's storage order. `activation`: "relu", "gelu" (the tanh
+    form), "silu" or a SPUTNIK_ACT_* constant. H equals act(Z) of the stored
+    Z bit for bit, whichever kernel runs (sputnik/block/activation.h).
+    `workspace` as in Matmul. Type and size errors are raised before the
+    library is called."""
+    _call_sdd_act(False, a, transpose_a, b, transpose_b, c, activation,
+                  pre_activation, stream, workspace)
+
+
+def MatmulActivationGrad(a, transpose_a, b, transpose_b, c, activation,  # noqa: N802
+                         pre_activation, stream=None, workspace=None):
+    """SDD gated by the activation's derivative: c.data = round(op(a) op(b))
+    * act'(Z) at c's blocks, Z = `pre_activation` as MatmulActivation stored
+    it (required; it must not be c.data)."""
+    _call_sdd_act(True, a, transpose_a, b, transpose_b, c, activation,
+                  pre_activation, stream, workspace)
+
+
+def BlockActivation(z, activation, out=None, stream=None):  # noqa: N802
+    """out = act(z) elementwise over block data (sputnik_block_activation):
+    the second kernel of MatmulActivation's two-kernel route, bit-identical
+    to its fused route. `out` defaults to a new tensor; it may be `z`."""
+    import torch
+
+    act = _act_code(activation)
+    dtype = _dtype_code(z)
+    if not z.is_contiguous():
+        raise ValueError("z must be contiguous")
+    if out is None:
+        out = torch.empty_like(z)
+    else:
+        _act_buffer(out, z.dtype, int(z.numel()), "out")
+    _check(lib().sputnik_block_activation(_ptr(z), _ptr(out), int(z.numel()),
+                                          act, dtype, _stream(stream)),
+           "block activation")
+    return out
+
+
+def BlockActivationGrad(g, z, activation, out=None, stream=None):  # noqa: N802
+    """out = g * act'(z) elementwise over block data
+    (sputnik_block_activation_grad), rounded once. `out` defaults to a new
+    tensor; it may be `g`."""
+    import torch
+
+    act = _act_code(activation)
+    dtype = _dtype_code(z)
+    if not z.is_contiguous():
+        raise ValueError("z must be contiguous")
+    _act_buffer(g, z.dtype, int(z.numel()), "g")
+    if out is None:
+        out = torch.empty_like(g)
+    else:
+        _act_buffer(out, z.dtype, int(z.numel()), "out")
+    _check(lib().sputnik_block_activation_grad(
+        _ptr(g), _ptr(z), _ptr(out), int(z.numel()), act, dtype,
+        _stream(stream)), "block activation grad")
+    return out
+
+
+def sdd_act_route(a, transpose_a, b, transpose_b, c) -> int:
+    """Route MatmulActivation[Grad] would take for this problem now: 1 the
+    fused epilogue of the 8-wave kernel, 2 plain SDD plus the elementwise
+    kernel, -1 rejected (sputnik_sdd_act_route; knob "sdd_act_route")."""
+    ca, cb, cc = a._c(), b._c(), c._c()
+    return int(lib().sputnik_sdd_act_route(
+        ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
+        int(bool(transpose_b)), ctypes.byref(cc)))
+
+
 def sdd_workspace_bytes(a, transpose_a, b, transpose_b, c) -> int:
     """Bytes of transposed-B workspace this SDD would use (0: none needed;
     sputnik_sdd_workspace_bytes). Host-only."""
@@ -697,6 +851,9 @@ __all__ = [
     "MaskToBcsr",
     "FreeTransposeBuffers", "Matmul", "MatmulEx", "Matrix", "RowIndices",
     "MatmulAccumulate", "MatmulAccumulateEx",
+    "MatmulActivation", "MatmulActivationGrad", "BlockActivation",
+    "BlockActivationGrad", "SPUTNIK_ACT_RELU", "SPUTNIK_ACT_GELU",
+    "SPUTNIK_ACT_SILU", "sdd_act_route",
     "SputnikError", "Transpose", "can_implement", "lib", "version",
     "allgather_concat", "gather_row_panels", "gather_col_panels",
     "gather_block_runs",

@@ -1,0 +1,167 @@
+// sputnik-amd: the activation math of the SDD activation products
+// (sputnik/block/activation.h), evaluated in fp32. One definition, used by
+// the 8-wave kernel's epilogue (block_gemm.h kOutAct / kOutActGrad) and by
+// the elementwise kernel (block_act.hip): the two routes must agree bit for
+// bit, so floating-point contraction is off in every function here (the
+// compiler forms no fma on its own, whatever the surrounding code looks like)
+// and the only transcendental steps are the hardware's exp2 and reciprocal.
+//
+//   relu   max(x, 0)                        relu'  x > 0 ? 1 : 0
+//   gelu   x s, s = 1 / (1 + exp(-2u)),     gelu'  s + x s (1 - s) 2 c
+//          u = c (x + 0.044715 x^3),                 (1 + 0.134145 x^2)
+//          c = sqrt(2 / pi)   (the tanh form, written as a sigmoid)
+//   silu   x s, s = 1 / (1 + exp(-x))       silu'  s (1 + x (1 - s))
+//
+// Every finite x gives a finite result: the argument of s and of the
+// derivative is clamped to where s is already exactly 0 or 1 in fp32 (gelu
+// |x| <= 11, silu |x| <= 100: exp overflows to inf, or drops below 2^-24,
+// long before), so x^2 and x^3 never overflow; the forward x s uses the
+// unclamped x. NaN or +-inf in x gives what these formulas yield (NaN for
+// gelu / silu of -inf, since -inf * 0).
+#ifndef SPUTNIK_AMD_ACT_MATH_H_
+#define SPUTNIK_AMD_ACT_MATH_H_
+
+#include <hip/hip_runtime.h>
+
+namespace sputnik_amd {
+
+constexpr int kActRelu = 0, kActGelu = 1, kActSilu = 2;
+
+// Every function below is written once for F = float and F = act_f2 (two
+// elements side by side): the pair form compiles to the packed fp32
+// multiplies and adds, which round exactly as the scalar ones, so a value
+// gets the same bits whichever form evaluates it.
+typedef float act_f2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float act_exp2(float x) {
+  return __builtin_amdgcn_exp2f(x);
+}
+__device__ __forceinline__ act_f2 act_exp2(act_f2 x) {
+  return act_f2{__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
+}
+__device__ __forceinline__ float act_rcp(float x) {
+  return __builtin_amdgcn_rcpf(x);
+}
+__device__ __forceinline__ act_f2 act_rcp(act_f2 x) {
+  return act_f2{__builtin_amdgcn_rcpf(x.x), __builtin_amdgcn_rcpf(x.y)};
+}
+__device__ __forceinline__ float act_clamp(float x, float lim) {
+  return __builtin_amdgcn_fmed3f(x, -lim, lim);
+}
+__device__ __forceinline__ act_f2 act_clamp(act_f2 x, float lim) {
+  return act_f2{act_clamp(x.x, lim), act_clamp(x.y, lim)};
+}
+template <typename F>
+__device__ __forceinline__ F act_splat(float v);
+template <>
+__device__ __forceinline__ float act_splat<float>(float v) {
+  return v;
+}
+template <>
+__device__ __forceinline__ act_f2 act_splat<act_f2>(float v) {
+  return act_f2{v, v};
+}
+// x > 0 ? a : b
+__device__ __forceinline__ float act_pos(float x, float a, float b) {
+  return x > 0.0f ? a : b;
+}
+__device__ __forceinline__ act_f2 act_pos(act_f2 x, act_f2 a, act_f2 b) {
+  return act_f2{x.x > 0.0f ? a.x : b.x, x.y > 0.0f ? a.y : b.y};
+}
+
+// 1 / (1 + exp(-t)); t = -inf .. inf gives 0 .. 1.
+template <typename F>
+__device__ __forceinline__ F act_sigmoid(F t) {
+#pragma clang fp contract(off)
+  const F e = act_exp2(t * -1.44269504088896340736f);
+  return act_rcp(1.0f + e);
+}
+
+// s of gelu at the clamped argument xc.
+template <typename F>
+__device__ __forceinline__ F act_gelu_s(F xc) {
+#pragma clang fp contract(off)
+  const F x3 = xc * xc * xc;
+  const F u = 0.7978845608028654f * (xc + 0.044715f * x3);
+  return act_sigmoid<F>(2.0f * u);
+}
+
+template <typename F>
+__device__ __forceinline__ F act_apply(int act, F x) {
+#pragma clang fp contract(off)
+  if (act == kActRelu) return act_pos(x, x, act_splat<F>(0.0f));
+  if (act == kActGelu) return x * act_gelu_s<F>(act_clamp(x, 11.0f));
+  return x * act_sigmoid<F>(act_clamp(x, 100.0f));
+}
+
+template <typename F>
+__device__ __forceinline__ F act_grad(int act, F x) {
+#pragma clang fp contract(off)
+  if (act == kActRelu)
+    return act_pos(x, act_splat<F>(1.0f), act_splat<F>(0.0f));
+  if (act == kActGelu) {
+    const F xc = act_clamp(x, 11.0f);
+    const F s = act_gelu_s<F>(xc);
+    const F poly = 1.0f + 0.134145f * (xc * xc);
+    return s + xc * s * (1.0f - s) * (2.0f * 0.7978845608028654f) * poly;
+  }
+  const F xc = act_clamp(x, 100.0f);
+  const F s = act_sigmoid<F>(xc);
+  return s * (1.0f + xc * (1.0f - s));
+}
+
+// The two elementwise stages, on values of the operand type T:
+//   H = round_T(act(float(Z)))       C = round_T(float(G) act'(float(Z)))
+// + 0.0f before the rounding makes an exact zero +0 whatever its factors'
+// signs: the compiler may fuse a multiply and the conversion to fp16 into
+// one mixed-precision fma with a +0 addend where it sees a single element,
+// and not where it sees a pair, and -0 + +0 = +0 only there. With the add
+// spelled out both forms give +0. (A result that merely underflows to zero
+// in T keeps its sign in both.)
+template <typename T>
+__device__ __forceinline__ T act_forward(int act, T z) {
+#pragma clang fp contract(off)
+  return (T)(act_apply<float>(act, (float)z) + 0.0f);
+}
+template <typename T>
+__device__ __forceinline__ T act_gate(int act, T g, T z) {
+#pragma clang fp contract(off)
+  return (T)((float)g * act_grad<float>(act, (float)z) + 0.0f);
+}
+
+// ... and on 8 of them (one 16-byte chunk), as 4 pairs.
+template <typename T>
+using act_t8 = T __attribute__((ext_vector_type(8)));
+
+template <typename T>
+__device__ __forceinline__ act_t8<T> act_forward8(int act, act_t8<T> z) {
+#pragma clang fp contract(off)
+  act_t8<T> r;
+#pragma unroll
+  for (int i = 0; i < 8; i += 2) {
+    const act_f2 h =
+        act_apply<act_f2>(act, act_f2{(float)z[i], (float)z[i + 1]}) + 0.0f;
+    r[i] = (T)h.x;
+    r[i + 1] = (T)h.y;
+  }
+  return r;
+}
+template <typename T>
+__device__ __forceinline__ act_t8<T> act_gate8(int act, act_t8<T> g,
+                                               act_t8<T> z) {
+#pragma clang fp contract(off)
+  act_t8<T> r;
+#pragma unroll
+  for (int i = 0; i < 8; i += 2) {
+    const act_f2 d =
+        act_grad<act_f2>(act, act_f2{(float)z[i], (float)z[i + 1]});
+    const act_f2 c = act_f2{(float)g[i], (float)g[i + 1]} * d + 0.0f;
+    r[i] = (T)c.x;
+    r[i + 1] = (T)c.y;
+  }
+  return r;
+}
+
+}  // namespace sputnik_amd
+
+#endif  // SPUTNIK_AMD_ACT_MATH_H_

@@ -50,6 +50,33 @@ hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, hipStream_t stream,
                   Status *status, Workspace ws = Workspace{});
 
+// SDD activation products (sputnik/block/activation.h). grad = false:
+// c.data = H = act(Z), Z = round(A B), also stored to `z` when that is not
+// null; grad = true: c.data = round(A B) * act'(z), `z` required (null:
+// hipErrorInvalidValue). act: kActRelu / kActGelu / kActSilu (act_math.h;
+// anything else: hipErrorInvalidValue). Two routes, bit-identical (knob
+// "sdd_act_route": 0 auto, 1 fused, 2 two kernels): fused, the 8-wave
+// kernel's activation epilogue (never the transposed-B path); two kernels,
+// RunSdd as it stands into `z` (or c.data) and LaunchBlockAct behind it.
+// Auto: fused where the plain call would run the 8-wave kernel alone
+// (SddKernel 0 / 1), decided once from the prepared params
+// (dispatch.cpp SddActDecide); two kernels wherever the transposed-B path
+// applies to the problem.
+hipError_t RunSddAct(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                     const BlockMatrix &c, int dtype, int act, void *z,
+                     bool grad, hipStream_t stream, Status *status,
+                     Workspace ws = Workspace{});
+// The route RunSddAct would take now: 1 fused, 2 two kernels, -1 rejected.
+int SddActRoute(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                const BlockMatrix &c);
+// The elementwise stage alone over n elements (block_act.hip): g null:
+// out = act(z); else out = g * act'(z). out may be z or g. Validates act and
+// the pointers (hipErrorInvalidValue).
+hipError_t RunBlockAct(int dtype, int act, const void *g, const void *z,
+                       void *out, long long n, bool gate, hipStream_t stream);
+hipError_t LaunchBlockAct(int dtype, int act, const void *g, const void *z,
+                          void *out, long long n, int cus, hipStream_t stream);
+
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.
 hipError_t SetStreamWorkspace(hipStream_t stream, void *ptr, size_t bytes);
@@ -143,6 +170,7 @@ enum KnobId {
   kKnobSddSpread,
   kKnobSddBtMinMib,
   kKnobSddTailMinK,
+  kKnobSddActRoute,
   kNumKnobs
 };
 int Knob(KnobId k);

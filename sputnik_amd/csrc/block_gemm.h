@@ -43,6 +43,8 @@
 
 #include <type_traits>
 
+#include "act_math.h"
+
 // Ablation switches for performance experiments only (scripts/exp_build.sh);
 // the shipped library is built with SPUTNIK_EXP == 0.
 //   1: skip the MFMAs (keep LDS reads)   2: skip the operand DMA
@@ -235,6 +237,12 @@ struct GemmParams {
   // is not a few groups on an idle chip. tail_cus: the CUs (the round size).
   int sdd_tail;
   int tail_cus;
+  // SDD activation products (kOutAct / kOutActGrad, block_gemm_act.hip).
+  // z_data: the pre-activation Z in C's storage order -- kOutAct: where Z is
+  // stored as well (nullptr: not stored); kOutActGrad: the Z to gate with.
+  // act: kActRelu / kActGelu / kActSilu (act_math.h).
+  char *z_data;
+  int act;
 };
 
 // XOR key of the m/n-contiguous image: spreads the 8 k-rows one
@@ -572,17 +580,27 @@ constexpr unsigned long long kPairWaitTicks = 20000000;
 // products); kOutAccT / kOutAccF32 add the fp32 accumulators to the C that
 // is there, a T or an fp32 matrix, and round once after the add. The
 // accumulating modes never store a tile the sparse operand leaves empty.
+// SDD only (sparse output from dense operands): kOutAct stores
+// H = round_T(act(float(Z))) with Z = round_T(acc), and Z itself to
+// p.z_data when that is set; kOutActGrad stores
+// round_T(float(round_T(acc)) * act'(float(Z))) with Z read from p.z_data.
+// Both work on the staged tile, in the store loop of write_tile.
 constexpr int kOutStore = 0, kOutAccT = 1, kOutAccF32 = 2;
+constexpr int kOutAct = 3, kOutActGrad = 4;
 template <typename T, bool kSparseOut, bool kSKC, bool kDKC, bool kOutT,
           class Cfg, bool kSparseIn = false, bool kSparseD = false,
           int kOutMode = kOutStore>
 __global__ void __launch_bounds__(64 * Cfg::kWaves,
                                   Cfg::kWGs * Cfg::kWaves / 4)
     block_gemm_kernel(const GemmParams p) {
-  static_assert(kOutMode == kOutStore ||
+  static_assert(kOutMode == kOutStore || kOutMode == kOutAct ||
+                    kOutMode == kOutActGrad ||
                     (!kSparseOut && !kSparseIn && !kSparseD &&
                      Cfg::kKSplit == 1 && !Cfg::kSplitMode),
                 "accumulating output: DSD / DDS, not split mode");
+  static_assert((kOutMode != kOutAct && kOutMode != kOutActGrad) ||
+                    (kSparseOut && !kSparseIn && !kSparseD && !kOutT),
+                "activation output: SDD");
   constexpr int kBN = Cfg::kBN;
   constexpr int kBK = Cfg::kBK;
   constexpr int kStages = Cfg::kStages;
@@ -1468,7 +1486,7 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
           for (int b = 0; b < kFN; ++b) acc[a][b] += xch[(a * kFN + b) * 64];
       }
     }
-    if constexpr (kOutMode != kOutStore) {
+    if constexpr (kOutMode == kOutAccT || kOutMode == kOutAccF32) {
       // Accumulating output: C comes in in the accumulator layout. Lane l of
       // fragment (a, b) holds 4 consecutive elements of one output row (DSD:
       // row i = l & 15, columns 4 (l >> 4) ..; DDS, transposed: output row
@@ -1599,7 +1617,7 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
       for (int id = tid; id < kChunks; id += kThreads) {
         const int row = id / kChunksPerRow;
         const int cc = id % kChunksPerRow;
-        const uint4 v =
+        uint4 v =
             *reinterpret_cast<const uint4 *>(st + row * kStLd + cc * 16);
         char *dst;
         if constexpr (kSparseOut && kOutT) {
@@ -1623,6 +1641,28 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
           if (jcol >= p.j_limit) continue;
           dst = p.c_data + ((long long)srow * kBM + row) * p.c_ld +
                 (long long)jcol * 2;
+        }
+        if constexpr (kOutMode == kOutAct || kOutMode == kOutActGrad) {
+          // SDD activation products, applied here, on the staged image, so
+          // every thread of the workgroup shares the work (the accumulators
+          // live in half of the waves of a k-split tile) and the tile is
+          // staged once. The chunk is 8 elements of round_T(acc): Z (stored
+          // to p.z_data at the same offset when that is set, then H =
+          // act(Z) goes out), or the product G to gate with act'(Z), Z read
+          // from p.z_data at the chunk's offset, 16 coalesced bytes.
+          typedef T t8 __attribute__((ext_vector_type(8)));
+          const long long off = dst - p.c_data;
+          const int act = p.act;
+          t8 x = __builtin_bit_cast(t8, v);
+          if constexpr (kOutMode == kOutAct) {
+            if (p.z_data != nullptr)
+              *reinterpret_cast<uint4 *>(p.z_data + off) = v;
+            x = act_forward8<T>(act, x);
+          } else {
+            const t8 zv = *reinterpret_cast<const t8 *>(p.z_data + off);
+            x = act_gate8<T>(act, x, zv);
+          }
+          v = __builtin_bit_cast(uint4, x);
         }
         if constexpr (kSparseOut ? SPUTNIK_SPARSE_OUT_NT != 0
                                  : SPUTNIK_OUT_NT != 0)
@@ -2218,6 +2258,12 @@ hipError_t LaunchBlockGemm(int dtype, bool sparse_out, bool s_kc, bool d_kc,
 hipError_t LaunchBlockGemmAcc(int dtype, bool s_kc, bool d_kc, bool out_t,
                               bool tall, int out_mode,
                               const GemmParams &params, hipStream_t stream);
+// SDD activation products (defined in block_gemm_act.hip): out_mode kOutAct
+// or kOutActGrad on CfgSdd or, grouped, CfgSddGrouped; params.act and
+// params.z_data set. Anything else: hipErrorInvalidValue, nothing launched.
+hipError_t LaunchBlockGemmAct(int dtype, bool s_kc, bool d_kc, bool grouped,
+                              int out_mode, const GemmParams &params,
+                              hipStream_t stream);
 // DSS on CfgBlock: num_tiles = (M/128) x (N/128), num_jtiles = N/128.
 hipError_t LaunchBlockGemmDss(int dtype, bool s_kc, bool d_kc,
                               const GemmParams &params, hipStream_t stream);

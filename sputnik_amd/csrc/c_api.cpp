@@ -202,6 +202,62 @@ int sputnik_sdd_ws(const sputnik_matrix_t *a, int transpose_a,
   return Code(e, sputnik_amd::StatusCode(st));
 }
 
+// SDD activation products (sputnik/block/activation.h).
+static int SddAct(const sputnik_matrix_t *a, int transpose_a,
+                  const sputnik_matrix_t *b, int transpose_b,
+                  const sputnik_block_matrix_t *c, int act, void *z, bool grad,
+                  int dtype, void *ws, size_t ws_bytes, void *stream) {
+  if (!a || !b || !c) return hipErrorInvalidValue;
+  if (act != SPUTNIK_ACT_RELU && act != SPUTNIK_ACT_GELU &&
+      act != SPUTNIK_ACT_SILU)
+    return hipErrorInvalidValue;
+  if (grad && z == nullptr) return hipErrorInvalidValue;
+  sputnik_amd::Status st;
+  const hipError_t e = sputnik_amd::RunSddAct(
+      ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
+      act, z, grad, static_cast<hipStream_t>(stream), &st,
+      sputnik_amd::Workspace{ws, ws_bytes});
+  return Code(e, sputnik_amd::StatusCode(st));
+}
+
+int sputnik_sdd_act(const sputnik_matrix_t *a, int transpose_a,
+                    const sputnik_matrix_t *b, int transpose_b,
+                    const sputnik_block_matrix_t *c, int act, void *z,
+                    int dtype, void *ws, size_t ws_bytes, void *stream) {
+  return SddAct(a, transpose_a, b, transpose_b, c, act, z, false, dtype, ws,
+                ws_bytes, stream);
+}
+
+int sputnik_sdd_act_grad(const sputnik_matrix_t *a, int transpose_a,
+                         const sputnik_matrix_t *b, int transpose_b,
+                         const sputnik_block_matrix_t *c, int act,
+                         const void *z, int dtype, void *ws, size_t ws_bytes,
+                         void *stream) {
+  return SddAct(a, transpose_a, b, transpose_b, c, act, const_cast<void *>(z),
+                true, dtype, ws, ws_bytes, stream);
+}
+
+int sputnik_block_activation(const void *z, void *h, long long n, int act,
+                             int dtype, void *stream) {
+  return sputnik_amd::RunBlockAct(dtype, act, nullptr, z, h, n, false,
+                                  static_cast<hipStream_t>(stream));
+}
+
+int sputnik_block_activation_grad(const void *g, const void *z, void *out,
+                                  long long n, int act, int dtype,
+                                  void *stream) {
+  return sputnik_amd::RunBlockAct(dtype, act, g, z, out, n, true,
+                                  static_cast<hipStream_t>(stream));
+}
+
+int sputnik_sdd_act_route(const sputnik_matrix_t *a, int transpose_a,
+                          const sputnik_matrix_t *b, int transpose_b,
+                          const sputnik_block_matrix_t *c) {
+  if (!a || !b || !c) return -1;
+  return sputnik_amd::SddActRoute(ToCpp(a), transpose_a != 0, ToCpp(b),
+                                  transpose_b != 0, ToCpp(c));
+}
+
 int sputnik_sdd(const sputnik_matrix_t *a, int transpose_a,
                 const sputnik_matrix_t *b, int transpose_b,
                 const sputnik_block_matrix_t *c, int dtype, void *stream) {

@@ -156,6 +156,9 @@ static const KnobDef kKnobs[kNumKnobs] = {
     // (grouped 4-wave SDD with K >= this: the rows past the groups' full
     // rounds go to an 8-wave launch of a block per workgroup; 0 off)
     {"sdd_tail_min_k", "SPUTNIK_AMD_SDD_TAIL_MIN_K", 8192, 0, 1 << 30},
+    // (SDD activation products, RunSddAct: 0 auto, 1 the fused epilogue of
+    // the 8-wave kernel, 2 plain SDD plus the elementwise kernel)
+    {"sdd_act_route", "SPUTNIK_AMD_SDD_ACT_ROUTE", 0, 0, 2},
 };
 constexpr int kKnobUnset = -0x7fffffff - 1;
 static std::atomic<int> g_knobs[kNumKnobs];
@@ -1611,6 +1614,87 @@ hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                          grouped, p, stream);
 }
 
+// ---- SDD activation products (sputnik/block/activation.h) ----
+
+static bool ActOk(int act) {
+  return act == kActRelu || act == kActGelu || act == kActSilu;
+}
+
+hipError_t RunBlockAct(int dtype, int act, const void *g, const void *z,
+                       void *out, long long n, bool gate, hipStream_t stream) {
+  if (!ActOk(act) || (dtype != 0 && dtype != 1) || n < 0)
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (z == nullptr || out == nullptr || (gate && g == nullptr))
+    return hipErrorInvalidValue;
+  int dev = 0;
+  const int cus = hipGetDevice(&dev) == hipSuccess ? DeviceCUs(dev) : 0;
+  return LaunchBlockAct(dtype, act, gate ? g : nullptr, z, out, n, cus, stream);
+}
+
+// The route of one call, decided once from the prepared params, in the order
+// RunSdd decides: 2 (two kernels) where the plain call would or might leave
+// the 8-wave kernel -- the transposed-B path applies to the problem (whether
+// it is then taken depends on the stream and the workspace: RunSdd's
+// business), the 4-wave K-split, grouped tiles on the 4-wave kernel (with or
+// without the tail split) -- and 1 (fused) otherwise, the 8-wave k-split tile
+// or grouped tile. On return *p and *grouped are what the fused launch needs
+// (UseGroupedSdd applied). profiles/sdd_activation has the A/B behind the
+// boundary.
+static int SddActDecide(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                        const BlockMatrix &c, hipStream_t stream,
+                        GemmParams *p, bool *grouped) {
+  const int knob = Knob(kKnobSddActRoute);
+  if (knob == 2) return 2;
+  const long long blocks = p->num_tiles;
+  *grouped = UseGroupedSdd(p, c, tb);
+  if (knob == 1) return 1;
+  if (BtAppliesSdd(a, ta, b, tb, c)) return 2;
+  if (!*grouped) {
+    GemmParams q = *p;
+    if (PrepareSddKsplit(&q, c, ta, tb, stream, /*dry=*/true)) return 2;
+  }
+  if (Dsd4wEnabled() && Sdd4wApplies(*p, *grouped, ta, tb, blocks)) return 2;
+  return 1;
+}
+
+int SddActRoute(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                const BlockMatrix &c) {
+  GemmParams p;
+  bool grouped = false;
+  if (PrepareSdd(a, ta, b, tb, c, &p) != Status::kOk) return -1;
+  return SddActDecide(a, ta, b, tb, c, nullptr, &p, &grouped);
+}
+
+hipError_t RunSddAct(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                     const BlockMatrix &c, int dtype, int act, void *z,
+                     bool grad, hipStream_t stream, Status *st_out,
+                     Workspace ws) {
+  GemmParams p;
+  const Status st = PrepareSdd(a, ta, b, tb, c, &p);
+  *st_out = st;
+  if (st != Status::kOk) return hipSuccess;
+  if (!ActOk(act) || (grad && z == nullptr) || (z != nullptr && z == c.data))
+    return hipErrorInvalidValue;
+  bool grouped = false;
+  if (SddActDecide(a, ta, b, tb, c, stream, &p, &grouped) == 2) {
+    // Two kernels: the plain SDD, whatever it runs, into Z (forward, when Z
+    // is wanted) or C, and the elementwise stage behind it on the stream.
+    BlockMatrix prod = c;
+    if (!grad && z != nullptr) prod.data = z;
+    const hipError_t e = RunSdd(a, ta, b, tb, prod, dtype, stream, st_out, ws);
+    if (e != hipSuccess || *st_out != Status::kOk) return e;
+    return RunBlockAct(dtype, act, grad ? c.data : nullptr,
+                       grad ? z : prod.data, c.data, c.nonzeros, grad, stream);
+  }
+  const InProduct in_product;
+  p.debug = g_debug;
+  p.act = act;
+  p.z_data = static_cast<char *>(z);
+  return LaunchBlockGemmAct(dtype, /*s_kc=*/!ta, /*d_kc=*/tb, grouped,
+                            grad ? kOutActGrad : kOutAct, p, stream);
+}
+
 hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, bool build_meta,
                   hipStream_t stream, Status *st_out) {
@@ -1794,6 +1878,32 @@ hipError_t Matmul(const Matrix a, bool transpose_a, const Matrix b,
 hipError_t Matmul(const Matrix a, bool transpose_a, const Matrix b,
                   bool transpose_b, BlockMatrix c, hipStream_t stream) {
   return Matmul(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+// ---- SDD activation products (sputnik/block/activation.h) ----
+
+hipError_t MatmulActivation(const Matrix a, bool transpose_a, const Matrix b,
+                            bool transpose_b, BlockMatrix c,
+                            Activation activation, void *pre_activation,
+                            DataType dtype, hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunSddAct(
+      a, transpose_a, b, transpose_b, c, (int)dtype, (int)activation,
+      pre_activation, /*grad=*/false, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sdd (activation)");
+}
+
+hipError_t MatmulActivationGrad(const Matrix a, bool transpose_a,
+                                const Matrix b, bool transpose_b,
+                                BlockMatrix c, Activation activation,
+                                const void *pre_activation, DataType dtype,
+                                hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunSddAct(
+      a, transpose_a, b, transpose_b, c, (int)dtype, (int)activation,
+      const_cast<void *>(pre_activation), /*grad=*/true, stream, &st);
+  return st == Status::kOk ? e
+                           : sputnik_amd::OrAbort(st, "sdd (activation grad)");
 }
 
 // SSD (reference sputnik/block/ssd/ssd.h:10-22) and SDS (sds.h:10-22).

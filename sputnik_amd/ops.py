@@ -13,7 +13,11 @@ MegaBlocks forward/backward set, BASELINE config 3). Each op takes optional
 gradient sinks (`a_grad_out` / `b_grad_out`) for its dense operands: backward
 then adds that operand's gradient into the sink with the accumulating product
 (C += op(A) op(B), `dsd_acc` / `dds_acc` below) instead of returning it, the
-Megatron `main_grad` convention. Every product runs on
+Megatron `main_grad` convention.
+`sdd_act(a, b, topo, activation)` is sdd with the activation
+fused into the product, and `mlp(x, w1, w2, topo, activation)` the expert MLP
+dsd(act(sdd(x, w1, topo)), w2) as one autograd function
+(sputnik/block/activation.h). Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
 
@@ -31,8 +35,9 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import (BlockMatrix, Matrix, Matmul, MatmulAccumulateEx, MatmulEx,
-               RowIndices, Transpose,
+from . import (BlockActivation, BlockActivationGrad, BlockMatrix, Matrix,
+               Matmul, MatmulAccumulateEx, MatmulActivation,
+               MatmulActivationGrad, MatmulEx, RowIndices, Transpose, _act_code,
                AllocateRowIndicesBuffer, AllocateTransposeBuffers,
                dsd_workspace_bytes, sdd_workspace_bytes)
 
@@ -225,10 +230,11 @@ def _dds(a: torch.Tensor, b: SparseMatrix) -> torch.Tensor:
     return out
 
 
-def _sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix) -> torch.Tensor:
-    """Block values of (a @ b) at topo's nonzero blocks, in topo's storage
-    order. A transposed topo view means the product is stored transposed:
-    (a @ b)^T = b^T @ a^T is computed instead."""
+def _sdd_setup(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix):
+    """What every SDD form passes to the library: (am, ta, bm, tb, cd, ws,
+    data), `data` the new block values cd describes. A transposed topo view
+    means the product is stored transposed: (a @ b)^T = b^T @ a^T is computed
+    instead."""
     _check_dtypes(a, b)
     if a.shape[1] != b.shape[0] or (a.shape[0], b.shape[1]) != topo.shape:
         raise ValueError(f"sdd shapes {tuple(a.shape)} x {tuple(b.shape)} "
@@ -242,8 +248,30 @@ def _sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix) -> torch.Tensor:
     topo._meta.ensure_row_indices(data)
     cd = topo._meta.descriptor(data)
     ws = _bt_workspace(sdd_workspace_bytes(am, ta, bm, tb, cd), a.device)
+    return am, ta, bm, tb, cd, ws, data
+
+
+def _sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix) -> torch.Tensor:
+    """Block values of (a @ b) at topo's nonzero blocks, in topo's storage
+    order."""
+    am, ta, bm, tb, cd, ws, data = _sdd_setup(a, b, topo)
     Matmul(am, ta, bm, tb, cd, workspace=ws)
     return data
+
+
+def _sdd_act(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix, act: int,
+             z: Optional[torch.Tensor] = None, grad: bool = False,
+             keep_z: bool = False):
+    """_sdd with the activation epilogue (MatmulActivation[Grad]). Forward
+    (grad False): returns (H, Z), Z None unless keep_z. Gradient: returns
+    round(a @ b) * act'(z) at topo's blocks."""
+    am, ta, bm, tb, cd, ws, data = _sdd_setup(a, b, topo)
+    if grad:
+        MatmulActivationGrad(am, ta, bm, tb, cd, act, z, workspace=ws)
+        return data
+    z = torch.empty_like(data) if keep_z else None
+    MatmulActivation(am, ta, bm, tb, cd, act, z, workspace=ws)
+    return data, z
 
 
 # ---- accumulating products (no autograd) ---------------------------------------
@@ -404,6 +432,78 @@ class _SDD(torch.autograd.Function):
         return da, db, None, None, None
 
 
+class _SDDAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, topo, act, a_sink, b_sink):
+        ctx.topo, ctx.act = topo, act
+        ctx.a_sink, ctx.b_sink = a_sink, b_sink
+        # (Z is stored only when a backward pass can follow)
+        keep = (any(ctx.needs_input_grad[:2]) or a_sink is not None
+                or b_sink is not None)
+        h, z = _sdd_act(a, b, topo, act, keep_z=keep)
+        if keep:
+            ctx.save_for_backward(a, b, z)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh_data):
+        a, b, z = ctx.saved_tensors
+        # dZ = dH * act'(Z), then as _SDD.backward
+        dz = BlockActivationGrad(dh_data.contiguous(), z, ctx.act)
+        dc = ctx.topo.with_data(dz)
+        da = db = None
+        if ctx.a_sink is not None:
+            ctx.a_sink.add_dsd(dc, b.t())              # sink += dZ B^T
+        elif ctx.needs_input_grad[0]:
+            da = _dsd(dc, b.t())                       # dZ B^T
+        if ctx.b_sink is not None:
+            ctx.b_sink.add_dds(a.t(), dc)              # sink += A^T dZ
+        elif ctx.needs_input_grad[1]:
+            db = _dds(a.t(), dc)                       # A^T dZ
+        return da, db, None, None, None, None
+
+
+class _MLP(torch.autograd.Function):
+    """y = dsd(act(sdd(x, w1, topo)), w2). Keeps Z, not H: H = act(Z) is
+    recomputed in backward, bit for bit what forward multiplied by w2."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, topo, act, w1_sink, w2_sink):
+        ctx.topo, ctx.act = topo, act
+        ctx.w1_sink, ctx.w2_sink = w1_sink, w2_sink
+        keep = (any(ctx.needs_input_grad[:3]) or w1_sink is not None
+                or w2_sink is not None)
+        h, z = _sdd_act(x, w1, topo, act, keep_z=keep)
+        if keep:
+            ctx.save_for_backward(x, w1, w2, z)
+        return _dsd(topo.with_data(h), w2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, w2, z = ctx.saved_tensors
+        topo = ctx.topo
+        dx = dw1 = dw2 = None
+        if ctx.w2_sink is not None or ctx.needs_input_grad[2]:
+            h = topo.with_data(BlockActivation(z, ctx.act))
+            if ctx.w2_sink is not None:
+                ctx.w2_sink.add_dsd(h.t(), dy)         # sink += H^T dY
+            else:
+                dw2 = _dsd(h.t(), dy)                  # H^T dY
+            del h
+        if (ctx.w1_sink is not None or ctx.needs_input_grad[0]
+                or ctx.needs_input_grad[1]):
+            # dZ = (dY W2^T) * act'(Z), one product
+            dz = topo.with_data(_sdd_act(dy, w2.t(), topo, ctx.act, z=z,
+                                         grad=True))
+            if ctx.needs_input_grad[0]:
+                dx = _dsd(dz, w1.t())                  # dZ W1^T
+            if ctx.w1_sink is not None:
+                ctx.w1_sink.add_dds(x.t(), dz)         # sink += X^T dZ
+            elif ctx.needs_input_grad[1]:
+                dw1 = _dds(x.t(), dz)                  # X^T dZ
+        return dx, dw1, dw2, None, None, None, None
+
+
 # Gradient sinks (`*_grad_out`): a contiguous tensor of the dense operand's
 # shape (of the tensor the caller holds when the operand is its .t() view),
 # in the operand's dtype or fp32. Backward adds the operand's gradient into
@@ -431,6 +531,33 @@ def sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
     return topo.with_data(_SDD.apply(
         a, b, topo, _sink(a_grad_out, a, "sdd a_grad_out"),
         _sink(b_grad_out, b, "sdd b_grad_out")))
+
+
+def sdd_act(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
+            activation, a_grad_out: Optional[torch.Tensor] = None,
+            b_grad_out: Optional[torch.Tensor] = None) -> SparseMatrix:
+    """Sparse (topo's blocks) = act(dense @ dense), the activation fused into
+    the product (MatmulActivation; "relu", "gelu": the tanh form, "silu").
+    The pre-activation is kept for backward, which gates the incoming
+    gradient with act' and proceeds as sdd's. Sinks as in sdd."""
+    return topo.with_data(_SDDAct.apply(
+        a, b, topo, _act_code(activation),
+        _sink(a_grad_out, a, "sdd_act a_grad_out"),
+        _sink(b_grad_out, b, "sdd_act b_grad_out")))
+
+
+def mlp(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+        topo: SparseMatrix, activation="gelu",
+        w1_grad_out: Optional[torch.Tensor] = None,
+        w2_grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The expert MLP y = dsd(act(sdd(x, w1, topo)), w2) as one autograd
+    function: forward is the fused sdd_act and one dsd; backward computes
+    dZ = (dy @ w2^T) * act'(Z) with one MatmulActivationGrad, then dw2 =
+    H^T dy, dx = dZ w1^T and dw1 = x^T dZ. Only Z is kept between the passes.
+    `w1_grad_out` / `w2_grad_out`: gradient sinks as in sdd / dsd."""
+    return _MLP.apply(x, w1, w2, topo, _act_code(activation),
+                      _sink(w1_grad_out, w1, "mlp w1_grad_out"),
+                      _sink(w2_grad_out, w2, "mlp w2_grad_out"))
 
 
 def from_dense_mask(x: torch.Tensor, mask) -> SparseMatrix:
@@ -484,4 +611,5 @@ def expert_topology(padded_bins: torch.Tensor, blocks_per_expert: int,
 
 
 __all__ = ["SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
-           "expert_topology", "from_dense_mask", "sdd", "topology_from_mask"]
+           "expert_topology", "from_dense_mask", "mlp", "sdd", "sdd_act",
+           "topology_from_mask"]
