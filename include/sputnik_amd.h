@@ -158,6 +158,49 @@ int sputnik_sdd_act_route(const sputnik_matrix_t *a, int transpose_a,
                           const sputnik_matrix_t *b, int transpose_b,
                           const sputnik_block_matrix_t *c);
 
+/* ---- SDD with a gated (GLU) epilogue (sputnik/block/gated.h,
+ * INTEGRATION.md 3f). With acc the fp32 accumulator sputnik_sdd would round
+ * and T the operand type:
+ *   sputnik_sdd_gated       U = round_T(acc),
+ *                           H = round_T(float(U) * act(float(G)));
+ *                           H -> c->data, U -> up when up != NULL,
+ *                           G read from gate (required)
+ *   sputnik_sdd_gated_grad  D = round_T(acc),
+ *                           up_grad = round_T(float(D) * act(float(G))),
+ *                           c->data = round_T((float(D) * float(U)) *
+ *                           act'(float(G))); G read from gate, U from up,
+ *                           all three required
+ * gate, up and up_grad hold c->nonzeros elements of T in c's storage order.
+ * up_grad may be exactly up (in place); otherwise none of gate, up, up_grad,
+ * c->data, A, B may overlap. act, the routes, the knob "sdd_act_route",
+ * sputnik_sdd_act_route, `ws` and `ws_bytes`: as sputnik_sdd_act.
+ * They never abort: an unknown act, a null operand, a null required buffer,
+ * or a buffer that equals one it must not overlap: hipErrorInvalidValue (1),
+ * nothing launched; block size != 128: hipErrorNotSupported; a shape
+ * sputnik_sdd rejects is rejected the same way. */
+int sputnik_sdd_gated(const sputnik_matrix_t *a, int transpose_a,
+                      const sputnik_matrix_t *b, int transpose_b,
+                      const sputnik_block_matrix_t *c, int act,
+                      const void *gate, void *up, int dtype, void *ws,
+                      size_t ws_bytes, void *stream);
+int sputnik_sdd_gated_grad(const sputnik_matrix_t *a, int transpose_a,
+                           const sputnik_matrix_t *b, int transpose_b,
+                           const sputnik_block_matrix_t *c, int act,
+                           const void *gate, const void *up, void *up_grad,
+                           int dtype, void *ws, size_t ws_bytes, void *stream);
+/* The elementwise stages alone, over n elements of block data (dtype 0 fp16,
+ * 1 bf16): out[i] = round_T(float(u[i]) * act(float(g[i]))), and the pair
+ * du[i] = round_T(float(d[i]) * act(float(g[i]))), dg[i] = round_T((float(d[i])
+ * * float(u[i])) * act'(float(g[i]))). out may be u or g, dg may be d, du may
+ * be u (in place). 16-byte accesses when every buffer is 16-byte aligned.
+ * hipErrorInvalidValue for an unknown act or dtype, n < 0, a null buffer
+ * with n > 0, or dg == du. */
+int sputnik_block_gate(const void *u, const void *g, void *out, long long n,
+                       int act, int dtype, void *stream);
+int sputnik_block_gate_grad(const void *d, const void *g, const void *u,
+                            void *dg, void *du, long long n, int act,
+                            int dtype, void *stream);
+
 /* ---- Caller-owned workspaces for the transposed-B path
  * SDD NT / TT, and DSD NT over a nearly dense A, transpose B once into a
  * scratch buffer when B is at least "sdd_bt_min_mib" MiB and the product is

@@ -115,6 +115,18 @@ _SIGNATURES = {
     "sputnik_block_activation_grad": [_P, _P, _P, ctypes.c_longlong,
                                       ctypes.c_int, ctypes.c_int, _P],
     "sputnik_sdd_act_route": [_P, ctypes.c_int, _P, ctypes.c_int, _P],
+    # gated SDD products: (a, ta, b, tb, c, act, gate, up[, up_grad], dtype,
+    # ws, ws_bytes, stream); the elementwise stages alone: (u, g, out, n, act,
+    # dtype, stream) and (d, g, u, dg, du, n, act, dtype, stream)
+    "sputnik_sdd_gated": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int,
+                          _P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P],
+    "sputnik_sdd_gated_grad": [_P, ctypes.c_int, _P, ctypes.c_int, _P,
+                               ctypes.c_int, _P, _P, _P, ctypes.c_int, _P,
+                               ctypes.c_size_t, _P],
+    "sputnik_block_gate": [_P, _P, _P, ctypes.c_longlong, ctypes.c_int,
+                           ctypes.c_int, _P],
+    "sputnik_block_gate_grad": [_P, _P, _P, _P, _P, ctypes.c_longlong,
+                                ctypes.c_int, ctypes.c_int, _P],
     "sputnik_ssd": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_ssd_ex": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_sds": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
@@ -575,6 +587,113 @@ def BlockActivationGrad(g, z, activation, out=None, stream=None):  # noqa: N802
     return out
 
 
+def _call_sdd_gated(grad: bool, a, transpose_a, b, transpose_b, c, activation,
+                    gate, up, up_grad, stream, workspace):
+    what = "MatmulGatedGrad" if grad else "MatmulGated"
+    act = _act_code(activation)
+    dtype = _sdd_act_operands(a, b, c, what)
+    numel = int(c.nonzeros)
+    if gate is None:
+        raise TypeError(f"{what} needs the gate")
+    _act_buffer(gate, a.data.dtype, numel, "gate")
+    if grad and (up is None or up_grad is None):
+        raise TypeError(f"{what} needs up, as MatmulGated stored it, and "
+                        "up_grad")
+    if up is not None:
+        _act_buffer(up, a.data.dtype, numel, "up")
+    if grad:
+        _act_buffer(up_grad, a.data.dtype, numel, "up_grad")
+    ws = _workspace(workspace) if workspace is not None else (None, 0)
+    L = lib()
+    ca, cb, cc = a._c(), b._c(), c._c()
+    head = (ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
+            int(bool(transpose_b)), ctypes.byref(cc), act, _ptr(gate),
+            _ptr(up))
+    tail = (dtype, ws[0], ws[1], _stream(stream))
+    if grad:
+        _check(L.sputnik_sdd_gated_grad(*head, _ptr(up_grad), *tail),
+               "sdd (gated grad)")
+    else:
+        _check(L.sputnik_sdd_gated(*head, *tail), "sdd (gated)")
+
+
+def MatmulGated(a, transpose_a, b, transpose_b, c, activation, gate,  # noqa: N802
+                up=None, stream=None, workspace=None):
+    """SDD with a gate fused: c.data = H = U * act(G), U = op(a) op(b)
+    rounded to the operand type, at c's blocks; G = `gate` (required), a
+    contiguous tensor of c.nonzeros elements of the operands' dtype in c's
+    storage order. `up` (optional): a tensor of the same kind that receives
+    U. `activation` as in MatmulActivation. H equals BlockGate of the stored
+    (U, G) bit for bit, whichever kernel runs (sputnik/block/gated.h). gate
+    and up must not be c.data, a, b or each other. Type and size errors are
+    raised before the library is called."""
+    _call_sdd_gated(False, a, transpose_a, b, transpose_b, c, activation,
+                    gate, up, None, stream, workspace)
+
+
+def MatmulGatedGrad(a, transpose_a, b, transpose_b, c, activation, gate,  # noqa: N802
+                    up, up_grad, stream=None, workspace=None):
+    """The gradient pair of MatmulGated from one product: with D = op(a)
+    op(b) rounded to the operand type, up_grad = D * act(G) and c.data =
+    D * U * act'(G), G = `gate`, U = `up` as MatmulGated stored it (all three
+    required). `up_grad` may be `up` itself (in place); no other two buffers
+    may coincide."""
+    _call_sdd_gated(True, a, transpose_a, b, transpose_b, c, activation,
+                    gate, up, up_grad, stream, workspace)
+
+
+def BlockGate(u, g, activation, out=None, stream=None):  # noqa: N802
+    """out = u * act(g) elementwise over block data (sputnik_block_gate),
+    rounded once: the second kernel of MatmulGated's two-kernel route,
+    bit-identical to its fused route. `out` defaults to a new tensor; it may
+    be `u` or `g`."""
+    import torch
+
+    act = _act_code(activation)
+    dtype = _dtype_code(u)
+    if not u.is_contiguous():
+        raise ValueError("u must be contiguous")
+    _act_buffer(g, u.dtype, int(u.numel()), "g")
+    if out is None:
+        out = torch.empty_like(u)
+    else:
+        _act_buffer(out, u.dtype, int(u.numel()), "out")
+    _check(lib().sputnik_block_gate(_ptr(u), _ptr(g), _ptr(out),
+                                    int(u.numel()), act, dtype,
+                                    _stream(stream)), "block gate")
+    return out
+
+
+def BlockGateGrad(d, g, u, activation, dg=None, du=None, stream=None):  # noqa: N802
+    """(dg, du) with dg = d * u * act'(g) and du = d * act(g) elementwise over
+    block data (sputnik_block_gate_grad), each rounded once. `dg` and `du`
+    default to new tensors; dg may be `d`, du may be `u` (in place); they
+    must be two tensors."""
+    import torch
+
+    act = _act_code(activation)
+    dtype = _dtype_code(d)
+    if not d.is_contiguous():
+        raise ValueError("d must be contiguous")
+    n = int(d.numel())
+    _act_buffer(g, d.dtype, n, "g")
+    _act_buffer(u, d.dtype, n, "u")
+    if dg is None:
+        dg = torch.empty_like(d)
+    else:
+        _act_buffer(dg, d.dtype, n, "dg")
+    if du is None:
+        du = torch.empty_like(d)
+    else:
+        _act_buffer(du, d.dtype, n, "du")
+    if dg is du:
+        raise ValueError("dg and du must be two tensors")
+    _check(lib().sputnik_block_gate_grad(
+        _ptr(d), _ptr(g), _ptr(u), _ptr(dg), _ptr(du), n, act, dtype,
+        _stream(stream)), "block gate grad")
+    return dg, du
+
+
 def sdd_act_route(a, transpose_a, b, transpose_b, c) -> int:
     """Route MatmulActivation[Grad] would take for this problem now: 1 the
     fused epilogue of the 8-wave kernel, 2 plain SDD plus the elementwise
@@ -854,6 +973,7 @@ __all__ = [
     "MatmulActivation", "MatmulActivationGrad", "BlockActivation",
     "BlockActivationGrad", "SPUTNIK_ACT_RELU", "SPUTNIK_ACT_GELU",
     "SPUTNIK_ACT_SILU", "sdd_act_route",
+    "MatmulGated", "MatmulGatedGrad", "BlockGate", "BlockGateGrad",
     "SputnikError", "Transpose", "can_implement", "lib", "version",
     "allgather_concat", "gather_row_panels", "gather_col_panels",
     "gather_block_runs",

@@ -162,6 +162,72 @@ __device__ __forceinline__ act_t8<T> act_gate8(int act, act_t8<T> g,
   return r;
 }
 
+// The gated (GLU) stages (sputnik/block/gated.h), on values of T:
+//   H  = round_T(float(U) act(float(G)))
+//   dU = round_T(float(D) act(float(G)))
+//   dG = round_T((float(D) float(U)) act'(float(G)))
+// float(D) float(U) is exact in fp32 (two 8- or 11-bit significands). The
+// gradient calls act_apply and act_grad as they stand, so each output has the
+// bits those give on their own; where both evaluate the same sigmoid of the
+// same clamped argument the compiler may keep one copy, which changes nothing.
+template <typename F>
+__device__ __forceinline__ F gate_mul(int act, F u, F g) {
+#pragma clang fp contract(off)
+  return u * act_apply<F>(act, g) + 0.0f;
+}
+template <typename F>
+__device__ __forceinline__ F gate_mul_grad(int act, F d, F u, F g) {
+#pragma clang fp contract(off)
+  return (d * u) * act_grad<F>(act, g) + 0.0f;
+}
+
+template <typename T>
+__device__ __forceinline__ T gate_forward(int act, T u, T g) {
+  return (T)gate_mul<float>(act, (float)u, (float)g);
+}
+template <typename T>
+__device__ __forceinline__ void gate_grad(int act, T d, T g, T u, T *dg,
+                                          T *du) {
+  const float df = (float)d, gf = (float)g, uf = (float)u;
+  *du = (T)gate_mul<float>(act, df, gf);
+  *dg = (T)gate_mul_grad<float>(act, df, uf, gf);
+}
+
+template <typename T>
+__device__ __forceinline__ act_t8<T> gate_forward8(int act, act_t8<T> u,
+                                                   act_t8<T> g) {
+  act_t8<T> r;
+#pragma unroll
+  for (int i = 0; i < 8; i += 2) {
+    const act_f2 h =
+        gate_mul<act_f2>(act, act_f2{(float)u[i], (float)u[i + 1]},
+                         act_f2{(float)g[i], (float)g[i + 1]});
+    r[i] = (T)h.x;
+    r[i + 1] = (T)h.y;
+  }
+  return r;
+}
+template <typename T>
+__device__ __forceinline__ void gate_grad8(int act, act_t8<T> d, act_t8<T> g,
+                                           act_t8<T> u, act_t8<T> *dg,
+                                           act_t8<T> *du) {
+  act_t8<T> rg, ru;
+#pragma unroll
+  for (int i = 0; i < 8; i += 2) {
+    const act_f2 df = act_f2{(float)d[i], (float)d[i + 1]};
+    const act_f2 gf = act_f2{(float)g[i], (float)g[i + 1]};
+    const act_f2 uf = act_f2{(float)u[i], (float)u[i + 1]};
+    const act_f2 a = gate_mul<act_f2>(act, df, gf);
+    const act_f2 b = gate_mul_grad<act_f2>(act, df, uf, gf);
+    ru[i] = (T)a.x;
+    ru[i + 1] = (T)a.y;
+    rg[i] = (T)b.x;
+    rg[i + 1] = (T)b.y;
+  }
+  *dg = rg;
+  *du = ru;
+}
+
 }  // namespace sputnik_amd
 
 #endif  // SPUTNIK_AMD_ACT_MATH_H_

@@ -77,6 +77,36 @@ hipError_t RunBlockAct(int dtype, int act, const void *g, const void *z,
 hipError_t LaunchBlockAct(int dtype, int act, const void *g, const void *z,
                           void *out, long long n, int cus, hipStream_t stream);
 
+// Gated SDD products (sputnik/block/gated.h). grad = false: c.data = H =
+// U * act(G), U = round(A B) also stored to `up` when that is not null, G
+// read from `gate`; grad = true: D = round(A B), `up_grad` = D * act(G),
+// c.data = D * U * act'(G), U read from `up`. A null required pointer, or a
+// pointer that equals one it must not overlap (only up_grad == up is
+// allowed), is hipErrorInvalidValue before anything is launched. Routes and
+// knob as RunSddAct (the same SddActDecide): fused, the 8-wave kernel's
+// kOutGate / kOutGateGrad epilogue; two kernels, RunSdd as it stands into
+// `up` (forward, when given) or c.data and LaunchBlockGate[Grad] behind it.
+hipError_t RunSddGated(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                       const BlockMatrix &c, int dtype, int act,
+                       const void *gate, void *up, void *up_grad, bool grad,
+                       hipStream_t stream, Status *status,
+                       Workspace ws = Workspace{});
+// The elementwise stages alone over n elements (block_gate.hip):
+// out = u * act(g) (out may be u or g), and du = d * act(g), dg = d * u *
+// act'(g) (dg may be d, du may be u). Validate act, dtype and the pointers
+// (hipErrorInvalidValue).
+hipError_t RunBlockGate(int dtype, int act, const void *u, const void *g,
+                        void *out, long long n, hipStream_t stream);
+hipError_t RunBlockGateGrad(int dtype, int act, const void *d, const void *g,
+                            const void *u, void *dg, void *du, long long n,
+                            hipStream_t stream);
+hipError_t LaunchBlockGate(int dtype, int act, const void *u, const void *g,
+                           void *out, long long n, int cus,
+                           hipStream_t stream);
+hipError_t LaunchBlockGateGrad(int dtype, int act, const void *d, const void *g,
+                               const void *u, void *dg, void *du, long long n,
+                               int cus, hipStream_t stream);
+
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.
 hipError_t SetStreamWorkspace(hipStream_t stream, void *ptr, size_t bytes);

@@ -243,6 +243,13 @@ struct GemmParams {
   // act: kActRelu / kActGelu / kActSilu (act_math.h).
   char *z_data;
   int act;
+  // Gated SDD products (kOutGate / kOutGateGrad, block_gemm_gate.hip), all in
+  // C's storage order; the gate G is read from z_data. kOutGate: u_data,
+  // where U = round_T(acc) is stored as well (nullptr: not stored).
+  // kOutGateGrad: u_data, the U to multiply with; du_data, where dU goes (it
+  // may be u_data).
+  char *u_data;
+  char *du_data;
 };
 
 // XOR key of the m/n-contiguous image: spreads the 8 k-rows one
@@ -586,21 +593,30 @@ constexpr unsigned long long kPairWaitTicks = 20000000;
 // round_T(float(round_T(acc)) * act'(float(Z))) with Z read from p.z_data.
 // Both work on the staged tile, in the store loop of write_tile.
 constexpr int kOutStore = 0, kOutAccT = 1, kOutAccF32 = 2;
+// kOutGate stores H = round_T(float(U) * act(float(G))) with U = round_T(acc)
+// and G read from p.z_data, and U itself to p.u_data when that is set;
+// kOutGateGrad, with D = round_T(acc), stores dG = round_T((float(D) *
+// float(U)) * act'(float(G))) to C and dU = round_T(float(D) * act(float(G)))
+// to p.du_data, G read from p.z_data and U from p.u_data.
 constexpr int kOutAct = 3, kOutActGrad = 4;
+constexpr int kOutGate = 5, kOutGateGrad = 6;
+constexpr bool OutModeIsSddEpilogue(int m) {
+  return m == kOutAct || m == kOutActGrad || m == kOutGate ||
+         m == kOutGateGrad;
+}
 template <typename T, bool kSparseOut, bool kSKC, bool kDKC, bool kOutT,
           class Cfg, bool kSparseIn = false, bool kSparseD = false,
           int kOutMode = kOutStore>
 __global__ void __launch_bounds__(64 * Cfg::kWaves,
                                   Cfg::kWGs * Cfg::kWaves / 4)
     block_gemm_kernel(const GemmParams p) {
-  static_assert(kOutMode == kOutStore || kOutMode == kOutAct ||
-                    kOutMode == kOutActGrad ||
+  static_assert(kOutMode == kOutStore || OutModeIsSddEpilogue(kOutMode) ||
                     (!kSparseOut && !kSparseIn && !kSparseD &&
                      Cfg::kKSplit == 1 && !Cfg::kSplitMode),
                 "accumulating output: DSD / DDS, not split mode");
-  static_assert((kOutMode != kOutAct && kOutMode != kOutActGrad) ||
+  static_assert(!OutModeIsSddEpilogue(kOutMode) ||
                     (kSparseOut && !kSparseIn && !kSparseD && !kOutT),
-                "activation output: SDD");
+                "activation / gated output: SDD");
   constexpr int kBN = Cfg::kBN;
   constexpr int kBK = Cfg::kBK;
   constexpr int kStages = Cfg::kStages;
@@ -1664,6 +1680,31 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
           }
           v = __builtin_bit_cast(uint4, x);
         }
+        if constexpr (kOutMode == kOutGate || kOutMode == kOutGateGrad) {
+          // Gated SDD products, at the same place and for the same reasons.
+          // The chunk is 8 elements of round_T(acc): U, multiplied by act(G)
+          // (and stored to p.u_data when that is set), or D, which gives dU =
+          // D act(G) for p.du_data and dG = D U act'(G) for C. G and U are
+          // read at the chunk's offset, 16 coalesced bytes each, before
+          // anything is stored, so p.du_data may be p.u_data.
+          typedef T t8 __attribute__((ext_vector_type(8)));
+          const long long off = dst - p.c_data;
+          const int act = p.act;
+          t8 x = __builtin_bit_cast(t8, v);
+          const t8 gv = *reinterpret_cast<const t8 *>(p.z_data + off);
+          if constexpr (kOutMode == kOutGate) {
+            if (p.u_data != nullptr)
+              *reinterpret_cast<uint4 *>(p.u_data + off) = v;
+            x = gate_forward8<T>(act, x, gv);
+          } else {
+            const t8 uv = *reinterpret_cast<const t8 *>(p.u_data + off);
+            t8 dg, du;
+            gate_grad8<T>(act, x, gv, uv, &dg, &du);
+            *reinterpret_cast<t8 *>(p.du_data + off) = du;
+            x = dg;
+          }
+          v = __builtin_bit_cast(uint4, x);
+        }
         if constexpr (kSparseOut ? SPUTNIK_SPARSE_OUT_NT != 0
                                  : SPUTNIK_OUT_NT != 0)
           __builtin_nontemporal_store(__builtin_bit_cast(v4u, v), reinterpret_cast<v4u *>(dst));
@@ -2264,6 +2305,13 @@ hipError_t LaunchBlockGemmAcc(int dtype, bool s_kc, bool d_kc, bool out_t,
 hipError_t LaunchBlockGemmAct(int dtype, bool s_kc, bool d_kc, bool grouped,
                               int out_mode, const GemmParams &params,
                               hipStream_t stream);
+// Gated SDD products (defined in block_gemm_gate.hip): out_mode kOutGate or
+// kOutGateGrad on CfgSdd or, grouped, CfgSddGrouped; params.act, z_data (the
+// gate) and u_data / du_data set. Anything else: hipErrorInvalidValue,
+// nothing launched.
+hipError_t LaunchBlockGemmGate(int dtype, bool s_kc, bool d_kc, bool grouped,
+                               int out_mode, const GemmParams &params,
+                               hipStream_t stream);
 // DSS on CfgBlock: num_tiles = (M/128) x (N/128), num_jtiles = N/128.
 hipError_t LaunchBlockGemmDss(int dtype, bool s_kc, bool d_kc,
                               const GemmParams &params, hipStream_t stream);

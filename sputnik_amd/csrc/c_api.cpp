@@ -250,6 +250,60 @@ int sputnik_block_activation_grad(const void *g, const void *z, void *out,
                                   static_cast<hipStream_t>(stream));
 }
 
+// Gated SDD products (sputnik/block/gated.h).
+static int SddGated(const sputnik_matrix_t *a, int transpose_a,
+                    const sputnik_matrix_t *b, int transpose_b,
+                    const sputnik_block_matrix_t *c, int act, const void *gate,
+                    void *up, void *up_grad, bool grad, int dtype, void *ws,
+                    size_t ws_bytes, void *stream) {
+  if (!a || !b || !c) return hipErrorInvalidValue;
+  if (act != SPUTNIK_ACT_RELU && act != SPUTNIK_ACT_GELU &&
+      act != SPUTNIK_ACT_SILU)
+    return hipErrorInvalidValue;
+  if (gate == nullptr) return hipErrorInvalidValue;
+  if (grad && (up == nullptr || up_grad == nullptr))
+    return hipErrorInvalidValue;
+  sputnik_amd::Status st;
+  const hipError_t e = sputnik_amd::RunSddGated(
+      ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
+      act, gate, up, up_grad, grad, static_cast<hipStream_t>(stream), &st,
+      sputnik_amd::Workspace{ws, ws_bytes});
+  return Code(e, sputnik_amd::StatusCode(st));
+}
+
+int sputnik_sdd_gated(const sputnik_matrix_t *a, int transpose_a,
+                      const sputnik_matrix_t *b, int transpose_b,
+                      const sputnik_block_matrix_t *c, int act,
+                      const void *gate, void *up, int dtype, void *ws,
+                      size_t ws_bytes, void *stream) {
+  return SddGated(a, transpose_a, b, transpose_b, c, act, gate, up, nullptr,
+                  false, dtype, ws, ws_bytes, stream);
+}
+
+int sputnik_sdd_gated_grad(const sputnik_matrix_t *a, int transpose_a,
+                           const sputnik_matrix_t *b, int transpose_b,
+                           const sputnik_block_matrix_t *c, int act,
+                           const void *gate, const void *up, void *up_grad,
+                           int dtype, void *ws, size_t ws_bytes,
+                           void *stream) {
+  return SddGated(a, transpose_a, b, transpose_b, c, act, gate,
+                  const_cast<void *>(up), up_grad, true, dtype, ws, ws_bytes,
+                  stream);
+}
+
+int sputnik_block_gate(const void *u, const void *g, void *out, long long n,
+                       int act, int dtype, void *stream) {
+  return sputnik_amd::RunBlockGate(dtype, act, u, g, out, n,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int sputnik_block_gate_grad(const void *d, const void *g, const void *u,
+                            void *dg, void *du, long long n, int act,
+                            int dtype, void *stream) {
+  return sputnik_amd::RunBlockGateGrad(dtype, act, d, g, u, dg, du, n,
+                                       static_cast<hipStream_t>(stream));
+}
+
 int sputnik_sdd_act_route(const sputnik_matrix_t *a, int transpose_a,
                           const sputnik_matrix_t *b, int transpose_b,
                           const sputnik_block_matrix_t *c) {

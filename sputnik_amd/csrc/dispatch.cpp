@@ -1695,6 +1695,86 @@ hipError_t RunSddAct(const Matrix &a, bool ta, const Matrix &b, bool tb,
                             grad ? kOutActGrad : kOutAct, p, stream);
 }
 
+// ---- Gated SDD products (sputnik/block/gated.h) ----
+
+hipError_t RunBlockGate(int dtype, int act, const void *u, const void *g,
+                        void *out, long long n, hipStream_t stream) {
+  if (!ActOk(act) || (dtype != 0 && dtype != 1) || n < 0)
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (u == nullptr || g == nullptr || out == nullptr)
+    return hipErrorInvalidValue;
+  int dev = 0;
+  const int cus = hipGetDevice(&dev) == hipSuccess ? DeviceCUs(dev) : 0;
+  return LaunchBlockGate(dtype, act, u, g, out, n, cus, stream);
+}
+
+hipError_t RunBlockGateGrad(int dtype, int act, const void *d, const void *g,
+                            const void *u, void *dg, void *du, long long n,
+                            hipStream_t stream) {
+  if (!ActOk(act) || (dtype != 0 && dtype != 1) || n < 0)
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (d == nullptr || g == nullptr || u == nullptr || dg == nullptr ||
+      du == nullptr || dg == du)
+    return hipErrorInvalidValue;
+  int dev = 0;
+  const int cus = hipGetDevice(&dev) == hipSuccess ? DeviceCUs(dev) : 0;
+  return LaunchBlockGateGrad(dtype, act, d, g, u, dg, du, n, cus, stream);
+}
+
+// The buffer rules of gated.h: required pointers set, and no two of gate,
+// up, up_grad, c.data, A, B equal, up_grad == up excepted.
+static bool GatedBuffersOk(const Matrix &a, const Matrix &b,
+                           const BlockMatrix &c, const void *gate,
+                           const void *up, const void *up_grad, bool grad) {
+  if (gate == nullptr) return false;
+  if (grad && (up == nullptr || up_grad == nullptr)) return false;
+  const void *fixed[3] = {c.data, a.data, b.data};
+  const void *side[3] = {gate, up, grad ? up_grad : nullptr};
+  for (const void *s : side)
+    for (const void *f : fixed)
+      if (s != nullptr && s == f) return false;
+  if (up != nullptr && up == gate) return false;
+  if (grad && up_grad == gate) return false;
+  return true;
+}
+
+hipError_t RunSddGated(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                       const BlockMatrix &c, int dtype, int act,
+                       const void *gate, void *up, void *up_grad, bool grad,
+                       hipStream_t stream, Status *st_out, Workspace ws) {
+  GemmParams p;
+  const Status st = PrepareSdd(a, ta, b, tb, c, &p);
+  *st_out = st;
+  if (st != Status::kOk) return hipSuccess;
+  if (!ActOk(act) || !GatedBuffersOk(a, b, c, gate, up, up_grad, grad))
+    return hipErrorInvalidValue;
+  bool grouped = false;
+  if (SddActDecide(a, ta, b, tb, c, stream, &p, &grouped) == 2) {
+    // Two kernels: the plain SDD, whatever it runs, into U (forward, when U
+    // is wanted) or C, and the elementwise stage behind it on the stream
+    // (the gradient turns D in C into dG in place).
+    BlockMatrix prod = c;
+    if (!grad && up != nullptr) prod.data = up;
+    const hipError_t e = RunSdd(a, ta, b, tb, prod, dtype, stream, st_out, ws);
+    if (e != hipSuccess || *st_out != Status::kOk) return e;
+    if (grad)
+      return RunBlockGateGrad(dtype, act, c.data, gate, up, c.data, up_grad,
+                              c.nonzeros, stream);
+    return RunBlockGate(dtype, act, prod.data, gate, c.data, c.nonzeros,
+                        stream);
+  }
+  const InProduct in_product;
+  p.debug = g_debug;
+  p.act = act;
+  p.z_data = static_cast<char *>(const_cast<void *>(gate));
+  p.u_data = static_cast<char *>(up);
+  p.du_data = static_cast<char *>(up_grad);
+  return LaunchBlockGemmGate(dtype, /*s_kc=*/!ta, /*d_kc=*/tb, grouped,
+                             grad ? kOutGateGrad : kOutGate, p, stream);
+}
+
 hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, bool build_meta,
                   hipStream_t stream, Status *st_out) {
@@ -1904,6 +1984,31 @@ hipError_t MatmulActivationGrad(const Matrix a, bool transpose_a,
       const_cast<void *>(pre_activation), /*grad=*/true, stream, &st);
   return st == Status::kOk ? e
                            : sputnik_amd::OrAbort(st, "sdd (activation grad)");
+}
+
+// ---- Gated SDD products (sputnik/block/gated.h) ----
+
+hipError_t MatmulGated(const Matrix a, bool transpose_a, const Matrix b,
+                       bool transpose_b, BlockMatrix c, Activation activation,
+                       const void *gate, void *up, DataType dtype,
+                       hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunSddGated(
+      a, transpose_a, b, transpose_b, c, (int)dtype, (int)activation, gate, up,
+      nullptr, /*grad=*/false, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sdd (gated)");
+}
+
+hipError_t MatmulGatedGrad(const Matrix a, bool transpose_a, const Matrix b,
+                           bool transpose_b, BlockMatrix c,
+                           Activation activation, const void *gate,
+                           const void *up, void *up_grad, DataType dtype,
+                           hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunSddGated(
+      a, transpose_a, b, transpose_b, c, (int)dtype, (int)activation, gate,
+      const_cast<void *>(up), up_grad, /*grad=*/true, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sdd (gated grad)");
 }
 
 // SSD (reference sputnik/block/ssd/ssd.h:10-22) and SDS (sds.h:10-22).

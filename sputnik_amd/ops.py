@@ -17,7 +17,11 @@ Megatron `main_grad` convention.
 `sdd_act(a, b, topo, activation)` is sdd with the activation
 fused into the product, and `mlp(x, w1, w2, topo, activation)` the expert MLP
 dsd(act(sdd(x, w1, topo)), w2) as one autograd function
-(sputnik/block/activation.h). Every product runs on
+(sputnik/block/activation.h). `sdd_gated(a, b, topo, gate, activation)` is
+sdd multiplied by act(gate) in the product's epilogue, and `glu_mlp(x, w1, v1,
+w2, topo, activation)` the gated expert MLP
+dsd(act(sdd(x, w1, topo)) * sdd(x, v1, topo), w2) as one autograd function
+(sputnik/block/gated.h). Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
 
@@ -35,9 +39,10 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import (BlockActivation, BlockActivationGrad, BlockMatrix, Matrix,
-               Matmul, MatmulAccumulateEx, MatmulActivation,
-               MatmulActivationGrad, MatmulEx, RowIndices, Transpose, _act_code,
+from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
+               BlockMatrix, Matrix, Matmul, MatmulAccumulateEx,
+               MatmulActivation, MatmulActivationGrad, MatmulEx, MatmulGated,
+               MatmulGatedGrad, RowIndices, Transpose, _act_code,
                AllocateRowIndicesBuffer, AllocateTransposeBuffers,
                dsd_workspace_bytes, sdd_workspace_bytes)
 
@@ -274,6 +279,21 @@ def _sdd_act(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix, act: int,
     return data, z
 
 
+def _sdd_gated(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix, act: int,
+               gate: torch.Tensor, up: Optional[torch.Tensor] = None,
+               grad: bool = False, keep_up: bool = False):
+    """_sdd with the gated epilogue (MatmulGated[Grad]); `gate` is G's block
+    data. Forward (grad False): returns (H, U), U None unless keep_up.
+    Gradient: returns (dG, dU) of D = a @ b, dU written over `up`."""
+    am, ta, bm, tb, cd, ws, data = _sdd_setup(a, b, topo)
+    if grad:
+        MatmulGatedGrad(am, ta, bm, tb, cd, act, gate, up, up, workspace=ws)
+        return data, up
+    up = torch.empty_like(data) if keep_up else None
+    MatmulGated(am, ta, bm, tb, cd, act, gate, up, workspace=ws)
+    return data, up
+
+
 # ---- accumulating products (no autograd) ---------------------------------------
 
 def _check_sink(out: torch.Tensor, rows: int, cols: int, dt, what: str):
@@ -504,6 +524,94 @@ class _MLP(torch.autograd.Function):
         return dx, dw1, dw2, None, None, None, None
 
 
+class _SDDGated(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, gate_data, topo, act, a_sink, b_sink):
+        ctx.topo, ctx.act = topo, act
+        ctx.a_sink, ctx.b_sink = a_sink, b_sink
+        # (U is stored only when a backward pass can follow)
+        keep = (any(ctx.needs_input_grad[:3]) or a_sink is not None
+                or b_sink is not None)
+        g = gate_data.contiguous()
+        h, u = _sdd_gated(a, b, topo, act, g, keep_up=keep)
+        if keep:
+            ctx.save_for_backward(a, b, g, u)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh_data):
+        a, b, g, u = ctx.saved_tensors
+        # dG = dH U act'(G), dU = dH act(G), then as _SDD.backward on dU
+        dg, du = BlockGateGrad(dh_data.contiguous(), g, u, ctx.act)
+        dc = ctx.topo.with_data(du)
+        da = db = None
+        if ctx.a_sink is not None:
+            ctx.a_sink.add_dsd(dc, b.t())              # sink += dU B^T
+        elif ctx.needs_input_grad[0]:
+            da = _dsd(dc, b.t())                       # dU B^T
+        if ctx.b_sink is not None:
+            ctx.b_sink.add_dds(a.t(), dc)              # sink += A^T dU
+        elif ctx.needs_input_grad[1]:
+            db = _dds(a.t(), dc)                       # A^T dU
+        if not ctx.needs_input_grad[2]:
+            dg = None
+        return da, db, dg, None, None, None, None
+
+
+class _GLUMLP(torch.autograd.Function):
+    """y = dsd(act(sdd(x, w1)) * sdd(x, v1), w2). Keeps Z1 = x w1 and
+    Z2 = x v1, not H: H is recomputed from them in backward, bit for bit what
+    forward multiplied by w2, and dZ2 is written over Z2."""
+
+    @staticmethod
+    def forward(ctx, x, w1, v1, w2, topo, act, w1_sink, v1_sink, w2_sink):
+        ctx.topo, ctx.act = topo, act
+        ctx.w1_sink, ctx.v1_sink, ctx.w2_sink = w1_sink, v1_sink, w2_sink
+        keep = (any(ctx.needs_input_grad[:4]) or w1_sink is not None
+                or v1_sink is not None or w2_sink is not None)
+        z1 = _sdd(x, w1, topo)
+        h, z2 = _sdd_gated(x, v1, topo, act, z1, keep_up=keep)
+        if keep:
+            ctx.save_for_backward(x, w1, v1, w2, z1, z2)
+        return _dsd(topo.with_data(h), w2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, v1, w2, z1, z2 = ctx.saved_tensors
+        topo = ctx.topo
+        dx = dw1 = dv1 = dw2 = None
+        if ctx.w2_sink is not None or ctx.needs_input_grad[3]:
+            h = topo.with_data(BlockGate(z2, z1, ctx.act))
+            if ctx.w2_sink is not None:
+                ctx.w2_sink.add_dsd(h.t(), dy)         # sink += H^T dY
+            else:
+                dw2 = _dsd(h.t(), dy)                  # H^T dY
+            del h
+        if (ctx.w1_sink is not None or ctx.v1_sink is not None
+                or any(ctx.needs_input_grad[:3])):
+            # D = dY W2^T: dZ1 = D Z2 act'(Z1), dZ2 = D act(Z1) over Z2, one
+            # product. Z2 is gone after it, so this node runs backward once.
+            if getattr(ctx, "z2_consumed", False):
+                raise RuntimeError("glu_mlp: backward ran before and wrote "
+                                   "dZ2 over the saved Z2; call glu_mlp again")
+            ctx.z2_consumed = True
+            dz1, dz2 = _sdd_gated(dy, w2.t(), topo, ctx.act, z1, up=z2,
+                                  grad=True)
+            dz1, dz2 = topo.with_data(dz1), topo.with_data(dz2)
+            if ctx.needs_input_grad[0]:
+                dx = _dsd(dz1, w1.t())                 # dZ1 W1^T
+                dsd_acc(dz2, v1.t(), dx)               # += dZ2 V1^T
+            if ctx.w1_sink is not None:
+                ctx.w1_sink.add_dds(x.t(), dz1)        # sink += X^T dZ1
+            elif ctx.needs_input_grad[1]:
+                dw1 = _dds(x.t(), dz1)                 # X^T dZ1
+            if ctx.v1_sink is not None:
+                ctx.v1_sink.add_dds(x.t(), dz2)        # sink += X^T dZ2
+            elif ctx.needs_input_grad[2]:
+                dv1 = _dds(x.t(), dz2)                 # X^T dZ2
+        return dx, dw1, dv1, dw2, None, None, None, None, None
+
+
 # Gradient sinks (`*_grad_out`): a contiguous tensor of the dense operand's
 # shape (of the tensor the caller holds when the operand is its .t() view),
 # in the operand's dtype or fp32. Backward adds the operand's gradient into
@@ -560,6 +668,44 @@ def mlp(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
                       _sink(w2_grad_out, w2, "mlp w2_grad_out"))
 
 
+def sdd_gated(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
+              gate: SparseMatrix, activation,
+              a_grad_out: Optional[torch.Tensor] = None,
+              b_grad_out: Optional[torch.Tensor] = None) -> SparseMatrix:
+    """Sparse (topo's blocks) = (dense @ dense) * act(gate), the gate applied
+    in the product's epilogue (MatmulGated). `gate` is a SparseMatrix of
+    topo's topology and storage order. Differentiable in a, b and gate.data:
+    the product U is kept, backward is one BlockGateGrad giving (dG, dU) and
+    then sdd's backward on dU. Sinks as in sdd."""
+    if not isinstance(gate, SparseMatrix):
+        raise TypeError("sdd_gated: gate must be a SparseMatrix")
+    if (gate.shape != topo.shape or gate.is_transposed() != topo.is_transposed()
+            or gate.data.shape != topo.data.shape):
+        raise ValueError("sdd_gated: gate must have topo's shape and blocks")
+    return topo.with_data(_SDDGated.apply(
+        a, b, gate.data, topo, _act_code(activation),
+        _sink(a_grad_out, a, "sdd_gated a_grad_out"),
+        _sink(b_grad_out, b, "sdd_gated b_grad_out")))
+
+
+def glu_mlp(x: torch.Tensor, w1: torch.Tensor, v1: torch.Tensor,
+            w2: torch.Tensor, topo: SparseMatrix, activation="silu",
+            w1_grad_out: Optional[torch.Tensor] = None,
+            v1_grad_out: Optional[torch.Tensor] = None,
+            w2_grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gated expert MLP y = dsd(act(sdd(x, w1)) * sdd(x, v1), w2) as one
+    autograd function: forward is Z1 = sdd(x, w1), the fused MatmulGated
+    (x, v1, gate Z1, Z2 kept) and one dsd; backward recomputes H for dw2 =
+    H^T dy, computes (dZ1, dZ2) with one MatmulGatedGrad of dy @ w2^T (dZ2
+    over Z2), then dw1 = x^T dZ1, dv1 = x^T dZ2 and dx = dZ1 w1^T with
+    dZ2 v1^T accumulated into it. Only Z1 and Z2 are kept between the passes.
+    `*_grad_out`: gradient sinks as in sdd / dsd."""
+    return _GLUMLP.apply(x, w1, v1, w2, topo, _act_code(activation),
+                         _sink(w1_grad_out, w1, "glu_mlp w1_grad_out"),
+                         _sink(v1_grad_out, v1, "glu_mlp v1_grad_out"),
+                         _sink(w2_grad_out, w2, "glu_mlp w2_grad_out"))
+
+
 def from_dense_mask(x: torch.Tensor, mask) -> SparseMatrix:
     """SparseMatrix holding x's blocks where the [rows/128, cols/128] block
     mask is true (row-major, sorted columns: the reference's mask -> BCSR
@@ -611,5 +757,5 @@ def expert_topology(padded_bins: torch.Tensor, blocks_per_expert: int,
 
 
 __all__ = ["SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
-           "expert_topology", "from_dense_mask", "mlp", "sdd", "sdd_act",
-           "topology_from_mask"]
+           "expert_topology", "from_dense_mask", "glu_mlp", "mlp", "sdd",
+           "sdd_act", "sdd_gated", "topology_from_mask"]
