@@ -21,6 +21,8 @@ Shapes (gelu):
     c4_bwd    its dy . w2^T with w2 stored [8 x 14336, 4096]: NT, gradient
     tile_fwd  f16, 2048 x 2048 at 50% (128 blocks), K = 1024: the plain SDD
     tile_bwd  runs the 8-wave k-split tile (sdd_kernel 0); forward / gradient
+    g8_fwd    f16, 6144 x 6144 at 50% (1152 blocks), K = 960 (no multiple of
+    g8_bwd    128): the plain SDD runs the 8-wave grouped tile (sdd_kernel 1)
 
 The three library arms must agree bit for bit; today's arm agrees within
 tests/helpers.RTOL (torch evaluates gelu with its own tanh). One JSON line
@@ -86,8 +88,9 @@ def main():
                 return "bf16", x, False, w, True, off, idx, tokens, ne * dff, dm, True
             w = sp.Matrix(dm, ne * dff, normal(dm, ne * dff, dt, 1 / 64))
             return "bf16", x, False, w, False, off, idx, tokens, ne * dff, dm, False
-        assert shape.startswith("tile_"), shape
-        dt, d, k = torch.float16, 2048, 1024
+        assert shape.startswith(("tile_", "g8_")), shape
+        d, k = (2048, 1024) if shape.startswith("tile_") else (6144, 960)
+        dt = torch.float16
         rng = np.random.default_rng(3)
         nb = mu.nonzeros_for_density(d, d, 0.5) // (128 * 128)
         off, idx = mu.random_topology(d // 128, d // 128, nb, rng)

@@ -501,26 +501,36 @@ def _sdd_act_operands(a, b, c, what: str) -> int:
     return dtype
 
 
-def _call_sdd_act(grad: bool, a, transpose_a, b, transpose_b, c, activation,
-                  pre_activation, stream, workspace):
-    what = "MatmulActivationGrad" if grad else "MatmulActivation"
+# The SDD epilogue products: Python name -> (C entry point, error label).
+_SDD_EPILOGUES = {
+    "MatmulActivation": ("sputnik_sdd_act", "sdd (activation)"),
+    "MatmulActivationGrad": ("sputnik_sdd_act_grad", "sdd (activation grad)"),
+    "MatmulGated": ("sputnik_sdd_gated", "sdd (gated)"),
+    "MatmulGatedGrad": ("sputnik_sdd_gated_grad", "sdd (gated grad)"),
+}
+
+
+def _call_sdd_epilogue(what: str, a, transpose_a, b, transpose_b, c,
+                       activation, sides, stream, workspace):
+    """One SDD epilogue product. `sides`: its side buffers in the C entry
+    point's order, as (name, tensor, message); a tensor that is None raises
+    TypeError(message) where there is a message, and is optional otherwise
+    (buffers that share a message are required together, at the first)."""
     act = _act_code(activation)
     dtype = _sdd_act_operands(a, b, c, what)
-    if pre_activation is None:
-        if grad:
-            raise TypeError(f"{what} needs the pre-activation the forward "
-                            "call stored")
-    else:
-        _act_buffer(pre_activation, a.data.dtype, int(c.nonzeros),
-                    "pre_activation")
+    for i, (name, t, needs) in enumerate(sides):
+        if needs and any(u is None for _, u, m in sides[i:] if m == needs):
+            raise TypeError(needs)
+        if t is not None:
+            _act_buffer(t, a.data.dtype, int(c.nonzeros), name)
     ws = _workspace(workspace) if workspace is not None else (None, 0)
-    L = lib()
+    fn, label = _SDD_EPILOGUES[what]
     ca, cb, cc = a._c(), b._c(), c._c()
-    fn = L.sputnik_sdd_act_grad if grad else L.sputnik_sdd_act
-    _check(fn(ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
-              int(bool(transpose_b)), ctypes.byref(cc), act,
-              _ptr(pre_activation), dtype, ws[0], ws[1], _stream(stream)),
-           "sdd (activation grad)" if grad else "sdd (activation)")
+    _check(getattr(lib(), fn)(
+        ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
+        int(bool(transpose_b)), ctypes.byref(cc), act,
+        *(_ptr(t) for _, t, _ in sides), dtype, ws[0], ws[1],
+        _stream(stream)), label)
 
 
 def MatmulActivation(a, transpose_a, b, transpose_b, c, activation,  # noqa: N802
@@ -533,8 +543,10 @@ def MatmulActivation(a, transpose_a, b, transpose_b, c, activation,  # noqa: N80
     Z bit for bit, whichever kernel runs (sputnik/block/activation.h).
     `workspace` as in Matmul. Type and size errors are raised before the
     library is called."""
-    _call_sdd_act(False, a, transpose_a, b, transpose_b, c, activation,
-                  pre_activation, stream, workspace)
+    _call_sdd_epilogue("MatmulActivation", a, transpose_a, b, transpose_b, c,
+                       activation,
+                       [("pre_activation", pre_activation, None)], stream,
+                       workspace)
 
 
 def MatmulActivationGrad(a, transpose_a, b, transpose_b, c, activation,  # noqa: N802
@@ -542,79 +554,59 @@ def MatmulActivationGrad(a, transpose_a, b, transpose_b, c, activation,  # noqa:
     """SDD gated by the activation's derivative: c.data = round(op(a) op(b))
     * act'(Z) at c's blocks, Z = `pre_activation` as MatmulActivation stored
     it (required; it must not be c.data)."""
-    _call_sdd_act(True, a, transpose_a, b, transpose_b, c, activation,
-                  pre_activation, stream, workspace)
+    what = "MatmulActivationGrad"
+    _call_sdd_epilogue(what, a, transpose_a, b, transpose_b, c, activation,
+                       [("pre_activation", pre_activation,
+                         f"{what} needs the pre-activation the forward call "
+                         "stored")], stream, workspace)
+
+
+def _block_epilogue(fn: str, label: str, activation, ref: str, ins: dict,
+                    outs: dict, stream):
+    """One elementwise stage: `ins` / `outs` are its named buffers in the C
+    entry point's order. ins[ref] sets the dtype and the size every other
+    buffer must have; an output that is None is allocated like the first
+    input. Raises before any library call. Returns the outputs."""
+    import torch
+
+    act = _act_code(activation)
+    r = ins[ref]
+    dtype = _dtype_code(r)
+    if not r.is_contiguous():
+        raise ValueError(f"{ref} must be contiguous")
+    n = int(r.numel())
+    for name, t in ins.items():
+        if name != ref:
+            _act_buffer(t, r.dtype, n, name)
+    res = []
+    for name, t in outs.items():
+        if t is None:
+            t = torch.empty_like(next(iter(ins.values())))
+        else:
+            _act_buffer(t, r.dtype, n, name)
+        res.append(t)
+    if len(res) == 2 and res[0] is res[1]:
+        raise ValueError(f"{' and '.join(outs)} must be two tensors")
+    _check(getattr(lib(), fn)(*(_ptr(t) for t in (*ins.values(), *res)), n,
+                              act, dtype, _stream(stream)), label)
+    return res
 
 
 def BlockActivation(z, activation, out=None, stream=None):  # noqa: N802
     """out = act(z) elementwise over block data (sputnik_block_activation):
     the second kernel of MatmulActivation's two-kernel route, bit-identical
     to its fused route. `out` defaults to a new tensor; it may be `z`."""
-    import torch
-
-    act = _act_code(activation)
-    dtype = _dtype_code(z)
-    if not z.is_contiguous():
-        raise ValueError("z must be contiguous")
-    if out is None:
-        out = torch.empty_like(z)
-    else:
-        _act_buffer(out, z.dtype, int(z.numel()), "out")
-    _check(lib().sputnik_block_activation(_ptr(z), _ptr(out), int(z.numel()),
-                                          act, dtype, _stream(stream)),
-           "block activation")
-    return out
+    return _block_epilogue("sputnik_block_activation", "block activation",
+                           activation, "z", {"z": z}, {"out": out}, stream)[0]
 
 
 def BlockActivationGrad(g, z, activation, out=None, stream=None):  # noqa: N802
     """out = g * act'(z) elementwise over block data
     (sputnik_block_activation_grad), rounded once. `out` defaults to a new
     tensor; it may be `g`."""
-    import torch
-
-    act = _act_code(activation)
-    dtype = _dtype_code(z)
-    if not z.is_contiguous():
-        raise ValueError("z must be contiguous")
-    _act_buffer(g, z.dtype, int(z.numel()), "g")
-    if out is None:
-        out = torch.empty_like(g)
-    else:
-        _act_buffer(out, z.dtype, int(z.numel()), "out")
-    _check(lib().sputnik_block_activation_grad(
-        _ptr(g), _ptr(z), _ptr(out), int(z.numel()), act, dtype,
-        _stream(stream)), "block activation grad")
-    return out
-
-
-def _call_sdd_gated(grad: bool, a, transpose_a, b, transpose_b, c, activation,
-                    gate, up, up_grad, stream, workspace):
-    what = "MatmulGatedGrad" if grad else "MatmulGated"
-    act = _act_code(activation)
-    dtype = _sdd_act_operands(a, b, c, what)
-    numel = int(c.nonzeros)
-    if gate is None:
-        raise TypeError(f"{what} needs the gate")
-    _act_buffer(gate, a.data.dtype, numel, "gate")
-    if grad and (up is None or up_grad is None):
-        raise TypeError(f"{what} needs up, as MatmulGated stored it, and "
-                        "up_grad")
-    if up is not None:
-        _act_buffer(up, a.data.dtype, numel, "up")
-    if grad:
-        _act_buffer(up_grad, a.data.dtype, numel, "up_grad")
-    ws = _workspace(workspace) if workspace is not None else (None, 0)
-    L = lib()
-    ca, cb, cc = a._c(), b._c(), c._c()
-    head = (ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
-            int(bool(transpose_b)), ctypes.byref(cc), act, _ptr(gate),
-            _ptr(up))
-    tail = (dtype, ws[0], ws[1], _stream(stream))
-    if grad:
-        _check(L.sputnik_sdd_gated_grad(*head, _ptr(up_grad), *tail),
-               "sdd (gated grad)")
-    else:
-        _check(L.sputnik_sdd_gated(*head, *tail), "sdd (gated)")
+    return _block_epilogue("sputnik_block_activation_grad",
+                           "block activation grad", activation, "z",
+                           {"g": g, "z": z}, {"out": out}, stream)[0]
 
 
 def MatmulGated(a, transpose_a, b, transpose_b, c, activation, gate,  # noqa: N802
@@ -627,8 +619,10 @@ def MatmulGated(a, transpose_a, b, transpose_b, c, activation, gate,  # noqa: N8
     (U, G) bit for bit, whichever kernel runs (sputnik/block/gated.h). gate
     and up must not be c.data, a, b or each other. Type and size errors are
     raised before the library is called."""
-    _call_sdd_gated(False, a, transpose_a, b, transpose_b, c, activation,
-                    gate, up, None, stream, workspace)
+    what = "MatmulGated"
+    _call_sdd_epilogue(what, a, transpose_a, b, transpose_b, c, activation,
+                       [("gate", gate, f"{what} needs the gate"),
+                        ("up", up, None)], stream, workspace)
 
 
 def MatmulGatedGrad(a, transpose_a, b, transpose_b, c, activation, gate,  # noqa: N802
@@ -638,8 +632,12 @@ def MatmulGatedGrad(a, transpose_a, b, transpose_b, c, activation, gate,  # noqa
     D * U * act'(G), G = `gate`, U = `up` as MatmulGated stored it (all three
     required). `up_grad` may be `up` itself (in place); no other two buffers
     may coincide."""
-    _call_sdd_gated(True, a, transpose_a, b, transpose_b, c, activation,
-                    gate, up, up_grad, stream, workspace)
+    what = "MatmulGatedGrad"
+    both = f"{what} needs up, as MatmulGated stored it, and up_grad"
+    _call_sdd_epilogue(what, a, transpose_a, b, transpose_b, c, activation,
+                       [("gate", gate, f"{what} needs the gate"),
+                        ("up", up, both), ("up_grad", up_grad, both)], stream,
+                       workspace)
 
 
 def BlockGate(u, g, activation, out=None, stream=None):  # noqa: N802
@@ -647,21 +645,8 @@ def BlockGate(u, g, activation, out=None, stream=None):  # noqa: N802
     rounded once: the second kernel of MatmulGated's two-kernel route,
     bit-identical to its fused route. `out` defaults to a new tensor; it may
     be `u` or `g`."""
-    import torch
-
-    act = _act_code(activation)
-    dtype = _dtype_code(u)
-    if not u.is_contiguous():
-        raise ValueError("u must be contiguous")
-    _act_buffer(g, u.dtype, int(u.numel()), "g")
-    if out is None:
-        out = torch.empty_like(u)
-    else:
-        _act_buffer(out, u.dtype, int(u.numel()), "out")
-    _check(lib().sputnik_block_gate(_ptr(u), _ptr(g), _ptr(out),
-                                    int(u.numel()), act, dtype,
-                                    _stream(stream)), "block gate")
-    return out
+    return _block_epilogue("sputnik_block_gate", "block gate", activation,
+                           "u", {"u": u, "g": g}, {"out": out}, stream)[0]
 
 
 def BlockGateGrad(d, g, u, activation, dg=None, du=None, stream=None):  # noqa: N802
@@ -669,28 +654,9 @@ def BlockGateGrad(d, g, u, activation, dg=None, du=None, stream=None):  # noqa: 
     block data (sputnik_block_gate_grad), each rounded once. `dg` and `du`
     default to new tensors; dg may be `d`, du may be `u` (in place); they
     must be two tensors."""
-    import torch
-
-    act = _act_code(activation)
-    dtype = _dtype_code(d)
-    if not d.is_contiguous():
-        raise ValueError("d must be contiguous")
-    n = int(d.numel())
-    _act_buffer(g, d.dtype, n, "g")
-    _act_buffer(u, d.dtype, n, "u")
-    if dg is None:
-        dg = torch.empty_like(d)
-    else:
-        _act_buffer(dg, d.dtype, n, "dg")
-    if du is None:
-        du = torch.empty_like(d)
-    else:
-        _act_buffer(du, d.dtype, n, "du")
-    if dg is du:
-        raise ValueError("dg and du must be two tensors")
-    _check(lib().sputnik_block_gate_grad(
-        _ptr(d), _ptr(g), _ptr(u), _ptr(dg), _ptr(du), n, act, dtype,
-        _stream(stream)), "block gate grad")
+    dg, du = _block_epilogue("sputnik_block_gate_grad", "block gate grad",
+                             activation, "d", {"d": d, "g": g, "u": u},
+                             {"dg": dg, "du": du}, stream)
     return dg, du
 
 

@@ -1,7 +1,8 @@
-// sputnik-amd: the activation math of the SDD activation products
-// (sputnik/block/activation.h), evaluated in fp32. One definition, used by
-// the 8-wave kernel's epilogue (block_gemm.h kOutAct / kOutActGrad) and by
-// the elementwise kernel (block_act.hip): the two routes must agree bit for
+// sputnik-amd: the activation math of the SDD activation and gated products
+// (sputnik/block/activation.h, gated.h), evaluated in fp32, and the table of
+// SDD epilogue ops built on it (SddEpilogue, at the end). One definition,
+// used by the 8-wave kernel's epilogue (block_gemm.h kOutMode) and by the
+// elementwise kernel (block_epilogue.hip): the two routes must agree bit for
 // bit, so floating-point contraction is off in every function here (the
 // compiler forms no fma on its own, whatever the surrounding code looks like)
 // and the only transcendental steps are the hardware's exp2 and reciprocal.
@@ -226,6 +227,121 @@ __device__ __forceinline__ void gate_grad8(int act, act_t8<T> d, act_t8<T> g,
   }
   *dg = rg;
   *du = ru;
+}
+
+// ---- The SDD epilogue ops ----
+//
+// An epilogue op turns x = round_T(A B) and up to two side buffers s0, s1
+// (block data in C's storage order) into C (o0) and, for one op, a second
+// output o1. The 8-wave kernel applies it to the staged tile (block_gemm.h
+// kOutMode, x = round_T(acc)); the elementwise kernel (block_epilogue.hip)
+// applies it to an x the plain SDD stored. Both go through the trait below,
+// so an op is described once:
+//
+//   mode          x   s0   s1   o0   o1    x kept to
+//   kOutAct       Z             H          z     o0 = act(x)
+//   kOutActGrad   G   Z         C                o0 = x act'(s0)
+//   kOutGate      U   G         H          up    o0 = x act(s0)
+//   kOutGateGrad  D   G    U    dG   dU          o0 = x s1 act'(s0),
+//                                                o1 = x act(s0)
+//
+// kKeepsX: the fused route also stores x itself, on request, to the first
+// side slot the op does not read (GemmParams z_data for kOutAct, u_data for
+// kOutGate); the two-kernel route has the plain SDD write x there instead.
+constexpr int kOutAct = 3, kOutActGrad = 4;
+constexpr int kOutGate = 5, kOutGateGrad = 6;
+constexpr bool OutModeIsSddEpilogue(int m) {
+  return m == kOutAct || m == kOutActGrad || m == kOutGate ||
+         m == kOutGateGrad;
+}
+
+template <int kMode>
+struct SddEpilogue;
+
+template <>
+struct SddEpilogue<kOutAct> {
+  static constexpr int kMode = kOutAct;
+  static constexpr int kSideInputs = 0;
+  static constexpr bool kKeepsX = true, kSecondOutput = false;
+  template <typename T>
+  __device__ __forceinline__ static void apply8(int act, act_t8<T> x,
+                                                act_t8<T>, act_t8<T>,
+                                                act_t8<T> *o0, act_t8<T> *) {
+    *o0 = act_forward8<T>(act, x);
+  }
+  template <typename T>
+  __device__ __forceinline__ static void apply(int act, T x, T, T, T *o0,
+                                               T *) {
+    *o0 = act_forward<T>(act, x);
+  }
+};
+
+template <>
+struct SddEpilogue<kOutActGrad> {
+  static constexpr int kMode = kOutActGrad;
+  static constexpr int kSideInputs = 1;
+  static constexpr bool kKeepsX = false, kSecondOutput = false;
+  template <typename T>
+  __device__ __forceinline__ static void apply8(int act, act_t8<T> x,
+                                                act_t8<T> s0, act_t8<T>,
+                                                act_t8<T> *o0, act_t8<T> *) {
+    *o0 = act_gate8<T>(act, x, s0);
+  }
+  template <typename T>
+  __device__ __forceinline__ static void apply(int act, T x, T s0, T, T *o0,
+                                               T *) {
+    *o0 = act_gate<T>(act, x, s0);
+  }
+};
+
+template <>
+struct SddEpilogue<kOutGate> {
+  static constexpr int kMode = kOutGate;
+  static constexpr int kSideInputs = 1;
+  static constexpr bool kKeepsX = true, kSecondOutput = false;
+  template <typename T>
+  __device__ __forceinline__ static void apply8(int act, act_t8<T> x,
+                                                act_t8<T> s0, act_t8<T>,
+                                                act_t8<T> *o0, act_t8<T> *) {
+    *o0 = gate_forward8<T>(act, x, s0);
+  }
+  template <typename T>
+  __device__ __forceinline__ static void apply(int act, T x, T s0, T, T *o0,
+                                               T *) {
+    *o0 = gate_forward<T>(act, x, s0);
+  }
+};
+
+template <>
+struct SddEpilogue<kOutGateGrad> {
+  static constexpr int kMode = kOutGateGrad;
+  static constexpr int kSideInputs = 2;
+  static constexpr bool kKeepsX = false, kSecondOutput = true;
+  template <typename T>
+  __device__ __forceinline__ static void apply8(int act, act_t8<T> x,
+                                                act_t8<T> s0, act_t8<T> s1,
+                                                act_t8<T> *o0, act_t8<T> *o1) {
+    gate_grad8<T>(act, x, s0, s1, o0, o1);
+  }
+  template <typename T>
+  __device__ __forceinline__ static void apply(int act, T x, T s0, T s1,
+                                               T *o0, T *o1) {
+    gate_grad<T>(act, x, s0, s1, o0, o1);
+  }
+};
+
+// f(SddEpilogue<mode>{}) for a mode known at run time: the one place that
+// lists the ops for the host code (launchers, dispatch). Not an epilogue
+// mode: `otherwise`.
+template <typename R, typename F>
+R WithSddEpilogue(int mode, R otherwise, F &&f) {
+  switch (mode) {
+    case kOutAct: return f(SddEpilogue<kOutAct>{});
+    case kOutActGrad: return f(SddEpilogue<kOutActGrad>{});
+    case kOutGate: return f(SddEpilogue<kOutGate>{});
+    case kOutGateGrad: return f(SddEpilogue<kOutGateGrad>{});
+  }
+  return otherwise;
 }
 
 }  // namespace sputnik_amd

@@ -50,62 +50,47 @@ hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, hipStream_t stream,
                   Status *status, Workspace ws = Workspace{});
 
-// SDD activation products (sputnik/block/activation.h). grad = false:
-// c.data = H = act(Z), Z = round(A B), also stored to `z` when that is not
-// null; grad = true: c.data = round(A B) * act'(z), `z` required (null:
-// hipErrorInvalidValue). act: kActRelu / kActGelu / kActSilu (act_math.h;
-// anything else: hipErrorInvalidValue). Two routes, bit-identical (knob
-// "sdd_act_route": 0 auto, 1 fused, 2 two kernels): fused, the 8-wave
-// kernel's activation epilogue (never the transposed-B path); two kernels,
-// RunSdd as it stands into `z` (or c.data) and LaunchBlockAct behind it.
-// Auto: fused where the plain call would run the 8-wave kernel alone
-// (SddKernel 0 / 1), decided once from the prepared params
-// (dispatch.cpp SddActDecide); two kernels wherever the transposed-B path
-// applies to the problem.
-hipError_t RunSddAct(const Matrix &a, bool ta, const Matrix &b, bool tb,
-                     const BlockMatrix &c, int dtype, int act, void *z,
-                     bool grad, hipStream_t stream, Status *status,
-                     Workspace ws = Workspace{});
-// The route RunSddAct would take now: 1 fused, 2 two kernels, -1 rejected.
+// SDD epilogue products (sputnik/block/activation.h, sputnik/block/gated.h):
+// c.data = op(round(A B), side buffers), `mode` one of kOutAct, kOutActGrad,
+// kOutGate, kOutGateGrad (act_math.h SddEpilogue has the table). The side
+// buffers are GemmParams' z_data, u_data and du_data:
+//   kOutAct       side0 = z, receives Z = round(A B) when not null
+//   kOutActGrad   side0 = z, the Z to gate with (required)
+//   kOutGate      side0 = gate (required); side1 = up, receives U when not
+//                 null
+//   kOutGateGrad  side0 = gate, side1 = up, out1 = up_grad (all required)
+// act: kActRelu / kActGelu / kActSilu (act_math.h). A bad act, a null
+// required pointer or two buffers that must not coincide (activation: z ==
+// c.data; gated: any two of gate, up, up_grad, c.data, A, B, up_grad == up
+// excepted) is hipErrorInvalidValue before anything is launched. Two routes,
+// bit-identical (knob "sdd_act_route": 0 auto, 1 fused, 2 two kernels):
+// fused, the 8-wave kernel's epilogue (never the transposed-B path); two
+// kernels, RunSdd as it stands into the buffer that keeps x (or c.data) and
+// RunBlockEpilogue behind it. Auto: fused where the plain call would run the
+// 8-wave kernel alone (SddKernel 0 / 1), decided once from the prepared
+// params (dispatch.cpp SddActDecide); two kernels wherever the transposed-B
+// path applies to the problem.
+hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                          const BlockMatrix &c, int dtype, int act, int mode,
+                          void *side0, void *side1, void *out1,
+                          hipStream_t stream, Status *status,
+                          Workspace ws = Workspace{});
+// The route RunSddEpilogue would take now: 1 fused, 2 two kernels, -1
+// rejected.
 int SddActRoute(const Matrix &a, bool ta, const Matrix &b, bool tb,
                 const BlockMatrix &c);
-// The elementwise stage alone over n elements (block_act.hip): g null:
-// out = act(z); else out = g * act'(z). out may be z or g. Validates act and
-// the pointers (hipErrorInvalidValue).
-hipError_t RunBlockAct(int dtype, int act, const void *g, const void *z,
-                       void *out, long long n, bool gate, hipStream_t stream);
-hipError_t LaunchBlockAct(int dtype, int act, const void *g, const void *z,
-                          void *out, long long n, int cus, hipStream_t stream);
-
-// Gated SDD products (sputnik/block/gated.h). grad = false: c.data = H =
-// U * act(G), U = round(A B) also stored to `up` when that is not null, G
-// read from `gate`; grad = true: D = round(A B), `up_grad` = D * act(G),
-// c.data = D * U * act'(G), U read from `up`. A null required pointer, or a
-// pointer that equals one it must not overlap (only up_grad == up is
-// allowed), is hipErrorInvalidValue before anything is launched. Routes and
-// knob as RunSddAct (the same SddActDecide): fused, the 8-wave kernel's
-// kOutGate / kOutGateGrad epilogue; two kernels, RunSdd as it stands into
-// `up` (forward, when given) or c.data and LaunchBlockGate[Grad] behind it.
-hipError_t RunSddGated(const Matrix &a, bool ta, const Matrix &b, bool tb,
-                       const BlockMatrix &c, int dtype, int act,
-                       const void *gate, void *up, void *up_grad, bool grad,
-                       hipStream_t stream, Status *status,
-                       Workspace ws = Workspace{});
-// The elementwise stages alone over n elements (block_gate.hip):
-// out = u * act(g) (out may be u or g), and du = d * act(g), dg = d * u *
-// act'(g) (dg may be d, du may be u). Validate act, dtype and the pointers
-// (hipErrorInvalidValue).
-hipError_t RunBlockGate(int dtype, int act, const void *u, const void *g,
-                        void *out, long long n, hipStream_t stream);
-hipError_t RunBlockGateGrad(int dtype, int act, const void *d, const void *g,
-                            const void *u, void *dg, void *du, long long n,
-                            hipStream_t stream);
-hipError_t LaunchBlockGate(int dtype, int act, const void *u, const void *g,
-                           void *out, long long n, int cus,
-                           hipStream_t stream);
-hipError_t LaunchBlockGateGrad(int dtype, int act, const void *d, const void *g,
-                               const void *u, void *dg, void *du, long long n,
-                               int cus, hipStream_t stream);
+// The elementwise stage alone over n elements (block_epilogue.hip), in the
+// trait's argument order: (o0, o1) = op(x, s0, s1), buffers the mode does
+// not have null. An output may be an input (act_math.h); o0 == o1 is
+// rejected. Validates act, dtype, n and the pointers (hipErrorInvalidValue);
+// n == 0 succeeds whatever the pointers.
+hipError_t RunBlockEpilogue(int dtype, int act, int mode, const void *x,
+                            const void *s0, const void *s1, void *o0,
+                            void *o1, long long n, hipStream_t stream);
+hipError_t LaunchBlockEpilogue(int dtype, int mode, int act, const void *x,
+                               const void *s0, const void *s1, void *o0,
+                               void *o1, long long n, int cus,
+                               hipStream_t stream);
 
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.

@@ -237,20 +237,23 @@ struct GemmParams {
   // is not a few groups on an idle chip. tail_cus: the CUs (the round size).
   int sdd_tail;
   int tail_cus;
-  // SDD activation products (kOutAct / kOutActGrad, block_gemm_act.hip).
-  // z_data: the pre-activation Z in C's storage order -- kOutAct: where Z is
-  // stored as well (nullptr: not stored); kOutActGrad: the Z to gate with.
+  // SDD epilogue ops (act_math.h SddEpilogue, block_gemm_epilogue.hip), all
+  // in C's storage order. z_data, u_data: the op's side inputs s0, s1; the
+  // first of the two the op does not read is where x = round_T(acc) is stored
+  // as well when the op keeps it (nullptr: not stored). du_data: the second
+  // output. So kOutAct: z_data, where Z goes; kOutActGrad: z_data, the Z to
+  // gate with; kOutGate: z_data, the gate G, and u_data, where U goes;
+  // kOutGateGrad: z_data, G, u_data, the U to multiply with, and du_data,
+  // where dU goes (it may be u_data).
   // act: kActRelu / kActGelu / kActSilu (act_math.h).
   char *z_data;
   int act;
-  // Gated SDD products (kOutGate / kOutGateGrad, block_gemm_gate.hip), all in
-  // C's storage order; the gate G is read from z_data. kOutGate: u_data,
-  // where U = round_T(acc) is stored as well (nullptr: not stored).
-  // kOutGateGrad: u_data, the U to multiply with; du_data, where dU goes (it
-  // may be u_data).
   char *u_data;
   char *du_data;
 };
+// The kernels read these fields at fixed offsets of the kernel argument:
+// growing or reordering the struct changes the code of every instantiation.
+static_assert(sizeof(GemmParams) == 320, "GemmParams changed");
 
 // XOR key of the m/n-contiguous image: spreads the 8 k-rows one
 // ds_read_b64_tr_b16 half-wave touches over 8 distinct 32-byte bank sectors.
@@ -597,13 +600,8 @@ constexpr int kOutStore = 0, kOutAccT = 1, kOutAccF32 = 2;
 // and G read from p.z_data, and U itself to p.u_data when that is set;
 // kOutGateGrad, with D = round_T(acc), stores dG = round_T((float(D) *
 // float(U)) * act'(float(G))) to C and dU = round_T(float(D) * act(float(G)))
-// to p.du_data, G read from p.z_data and U from p.u_data.
-constexpr int kOutAct = 3, kOutActGrad = 4;
-constexpr int kOutGate = 5, kOutGateGrad = 6;
-constexpr bool OutModeIsSddEpilogue(int m) {
-  return m == kOutAct || m == kOutActGrad || m == kOutGate ||
-         m == kOutGateGrad;
-}
+// to p.du_data, G read from p.z_data and U from p.u_data. (These four are
+// the SDD epilogue ops: constants and traits in act_math.h.)
 template <typename T, bool kSparseOut, bool kSKC, bool kDKC, bool kOutT,
           class Cfg, bool kSparseIn = false, bool kSparseD = false,
           int kOutMode = kOutStore>
@@ -1658,52 +1656,34 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
           dst = p.c_data + ((long long)srow * kBM + row) * p.c_ld +
                 (long long)jcol * 2;
         }
-        if constexpr (kOutMode == kOutAct || kOutMode == kOutActGrad) {
-          // SDD activation products, applied here, on the staged image, so
-          // every thread of the workgroup shares the work (the accumulators
-          // live in half of the waves of a k-split tile) and the tile is
-          // staged once. The chunk is 8 elements of round_T(acc): Z (stored
-          // to p.z_data at the same offset when that is set, then H =
-          // act(Z) goes out), or the product G to gate with act'(Z), Z read
-          // from p.z_data at the chunk's offset, 16 coalesced bytes.
+        if constexpr (OutModeIsSddEpilogue(kOutMode)) {
+          // SDD epilogue ops (act_math.h SddEpilogue), applied here, on the
+          // staged image, so every thread of the workgroup shares the work
+          // (the accumulators live in half of the waves of a k-split tile)
+          // and the tile is staged once. The chunk is x, 8 elements of
+          // round_T(acc). The side inputs are read at the chunk's offset, 16
+          // coalesced bytes each, before anything is stored, so p.du_data
+          // may be p.u_data; then x itself is stored where the op keeps it,
+          // then the second output, and o0 goes out to C.
+          using E = SddEpilogue<kOutMode>;
           typedef T t8 __attribute__((ext_vector_type(8)));
           const long long off = dst - p.c_data;
           const int act = p.act;
-          t8 x = __builtin_bit_cast(t8, v);
-          if constexpr (kOutMode == kOutAct) {
-            if (p.z_data != nullptr)
-              *reinterpret_cast<uint4 *>(p.z_data + off) = v;
-            x = act_forward8<T>(act, x);
-          } else {
-            const t8 zv = *reinterpret_cast<const t8 *>(p.z_data + off);
-            x = act_gate8<T>(act, x, zv);
+          char *const side[2] = {p.z_data, p.u_data};
+          const t8 x = __builtin_bit_cast(t8, v);
+          t8 s0 = x, s1 = x, o0, o1;
+          if constexpr (E::kSideInputs >= 1)
+            s0 = *reinterpret_cast<const t8 *>(side[0] + off);
+          if constexpr (E::kSideInputs >= 2)
+            s1 = *reinterpret_cast<const t8 *>(side[1] + off);
+          if constexpr (E::kKeepsX) {
+            if (side[E::kSideInputs] != nullptr)
+              *reinterpret_cast<uint4 *>(side[E::kSideInputs] + off) = v;
           }
-          v = __builtin_bit_cast(uint4, x);
-        }
-        if constexpr (kOutMode == kOutGate || kOutMode == kOutGateGrad) {
-          // Gated SDD products, at the same place and for the same reasons.
-          // The chunk is 8 elements of round_T(acc): U, multiplied by act(G)
-          // (and stored to p.u_data when that is set), or D, which gives dU =
-          // D act(G) for p.du_data and dG = D U act'(G) for C. G and U are
-          // read at the chunk's offset, 16 coalesced bytes each, before
-          // anything is stored, so p.du_data may be p.u_data.
-          typedef T t8 __attribute__((ext_vector_type(8)));
-          const long long off = dst - p.c_data;
-          const int act = p.act;
-          t8 x = __builtin_bit_cast(t8, v);
-          const t8 gv = *reinterpret_cast<const t8 *>(p.z_data + off);
-          if constexpr (kOutMode == kOutGate) {
-            if (p.u_data != nullptr)
-              *reinterpret_cast<uint4 *>(p.u_data + off) = v;
-            x = gate_forward8<T>(act, x, gv);
-          } else {
-            const t8 uv = *reinterpret_cast<const t8 *>(p.u_data + off);
-            t8 dg, du;
-            gate_grad8<T>(act, x, gv, uv, &dg, &du);
-            *reinterpret_cast<t8 *>(p.du_data + off) = du;
-            x = dg;
-          }
-          v = __builtin_bit_cast(uint4, x);
+          E::template apply8<T>(act, x, s0, s1, &o0, &o1);
+          if constexpr (E::kSecondOutput)
+            *reinterpret_cast<t8 *>(p.du_data + off) = o1;
+          v = __builtin_bit_cast(uint4, o0);
         }
         if constexpr (kSparseOut ? SPUTNIK_SPARSE_OUT_NT != 0
                                  : SPUTNIK_OUT_NT != 0)
@@ -2299,19 +2279,15 @@ hipError_t LaunchBlockGemm(int dtype, bool sparse_out, bool s_kc, bool d_kc,
 hipError_t LaunchBlockGemmAcc(int dtype, bool s_kc, bool d_kc, bool out_t,
                               bool tall, int out_mode,
                               const GemmParams &params, hipStream_t stream);
-// SDD activation products (defined in block_gemm_act.hip): out_mode kOutAct
-// or kOutActGrad on CfgSdd or, grouped, CfgSddGrouped; params.act and
-// params.z_data set. Anything else: hipErrorInvalidValue, nothing launched.
-hipError_t LaunchBlockGemmAct(int dtype, bool s_kc, bool d_kc, bool grouped,
-                              int out_mode, const GemmParams &params,
-                              hipStream_t stream);
-// Gated SDD products (defined in block_gemm_gate.hip): out_mode kOutGate or
-// kOutGateGrad on CfgSdd or, grouped, CfgSddGrouped; params.act, z_data (the
-// gate) and u_data / du_data set. Anything else: hipErrorInvalidValue,
-// nothing launched.
-hipError_t LaunchBlockGemmGate(int dtype, bool s_kc, bool d_kc, bool grouped,
-                               int out_mode, const GemmParams &params,
-                               hipStream_t stream);
+// SDD epilogue ops (defined in block_gemm_epilogue.hip): out_mode kOutAct,
+// kOutActGrad, kOutGate or kOutGateGrad on CfgSdd or, grouped,
+// CfgSddGrouped; params.act and the pointers the mode needs (z_data, u_data,
+// du_data: GemmParams) set. Anything else: hipErrorInvalidValue, nothing
+// launched.
+hipError_t LaunchBlockGemmEpilogue(int dtype, bool s_kc, bool d_kc,
+                                   bool grouped, int out_mode,
+                                   const GemmParams &params,
+                                   hipStream_t stream);
 // DSS on CfgBlock: num_tiles = (M/128) x (N/128), num_jtiles = N/128.
 hipError_t LaunchBlockGemmDss(int dtype, bool s_kc, bool d_kc,
                               const GemmParams &params, hipStream_t stream);

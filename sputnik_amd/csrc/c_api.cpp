@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstring>
 
+#include "act_math.h"
 #include "api_internal.h"
 #include "sputnik/sputnik.h"
 #include "metadata.h"
@@ -202,20 +203,31 @@ int sputnik_sdd_ws(const sputnik_matrix_t *a, int transpose_a,
   return Code(e, sputnik_amd::StatusCode(st));
 }
 
-// SDD activation products (sputnik/block/activation.h).
-static int SddAct(const sputnik_matrix_t *a, int transpose_a,
-                  const sputnik_matrix_t *b, int transpose_b,
-                  const sputnik_block_matrix_t *c, int act, void *z, bool grad,
-                  int dtype, void *ws, size_t ws_bytes, void *stream) {
+// SDD epilogue products (sputnik/block/activation.h, sputnik/block/gated.h):
+// mode and side buffers as RunSddEpilogue takes them.
+static int SddEpilogueCall(const sputnik_matrix_t *a, int transpose_a,
+                           const sputnik_matrix_t *b, int transpose_b,
+                           const sputnik_block_matrix_t *c, int act, int mode,
+                           const void *side0, const void *side1, void *out1,
+                           int dtype, void *ws, size_t ws_bytes,
+                           void *stream) {
   if (!a || !b || !c) return hipErrorInvalidValue;
   if (act != SPUTNIK_ACT_RELU && act != SPUTNIK_ACT_GELU &&
       act != SPUTNIK_ACT_SILU)
     return hipErrorInvalidValue;
-  if (grad && z == nullptr) return hipErrorInvalidValue;
+  const bool required_set =
+      sputnik_amd::WithSddEpilogue(mode, false, [&](auto e) {
+        using E = decltype(e);
+        return !(E::kSideInputs >= 1 && side0 == nullptr) &&
+               !(E::kSideInputs >= 2 && side1 == nullptr) &&
+               !(E::kSecondOutput && out1 == nullptr);
+      });
+  if (!required_set) return hipErrorInvalidValue;
   sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunSddAct(
+  const hipError_t e = sputnik_amd::RunSddEpilogue(
       ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      act, z, grad, static_cast<hipStream_t>(stream), &st,
+      act, mode, const_cast<void *>(side0), const_cast<void *>(side1), out1,
+      static_cast<hipStream_t>(stream), &st,
       sputnik_amd::Workspace{ws, ws_bytes});
   return Code(e, sputnik_amd::StatusCode(st));
 }
@@ -224,8 +236,9 @@ int sputnik_sdd_act(const sputnik_matrix_t *a, int transpose_a,
                     const sputnik_matrix_t *b, int transpose_b,
                     const sputnik_block_matrix_t *c, int act, void *z,
                     int dtype, void *ws, size_t ws_bytes, void *stream) {
-  return SddAct(a, transpose_a, b, transpose_b, c, act, z, false, dtype, ws,
-                ws_bytes, stream);
+  return SddEpilogueCall(a, transpose_a, b, transpose_b, c, act,
+                         sputnik_amd::kOutAct, z, nullptr, nullptr, dtype, ws,
+                         ws_bytes, stream);
 }
 
 int sputnik_sdd_act_grad(const sputnik_matrix_t *a, int transpose_a,
@@ -233,42 +246,9 @@ int sputnik_sdd_act_grad(const sputnik_matrix_t *a, int transpose_a,
                          const sputnik_block_matrix_t *c, int act,
                          const void *z, int dtype, void *ws, size_t ws_bytes,
                          void *stream) {
-  return SddAct(a, transpose_a, b, transpose_b, c, act, const_cast<void *>(z),
-                true, dtype, ws, ws_bytes, stream);
-}
-
-int sputnik_block_activation(const void *z, void *h, long long n, int act,
-                             int dtype, void *stream) {
-  return sputnik_amd::RunBlockAct(dtype, act, nullptr, z, h, n, false,
-                                  static_cast<hipStream_t>(stream));
-}
-
-int sputnik_block_activation_grad(const void *g, const void *z, void *out,
-                                  long long n, int act, int dtype,
-                                  void *stream) {
-  return sputnik_amd::RunBlockAct(dtype, act, g, z, out, n, true,
-                                  static_cast<hipStream_t>(stream));
-}
-
-// Gated SDD products (sputnik/block/gated.h).
-static int SddGated(const sputnik_matrix_t *a, int transpose_a,
-                    const sputnik_matrix_t *b, int transpose_b,
-                    const sputnik_block_matrix_t *c, int act, const void *gate,
-                    void *up, void *up_grad, bool grad, int dtype, void *ws,
-                    size_t ws_bytes, void *stream) {
-  if (!a || !b || !c) return hipErrorInvalidValue;
-  if (act != SPUTNIK_ACT_RELU && act != SPUTNIK_ACT_GELU &&
-      act != SPUTNIK_ACT_SILU)
-    return hipErrorInvalidValue;
-  if (gate == nullptr) return hipErrorInvalidValue;
-  if (grad && (up == nullptr || up_grad == nullptr))
-    return hipErrorInvalidValue;
-  sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunSddGated(
-      ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      act, gate, up, up_grad, grad, static_cast<hipStream_t>(stream), &st,
-      sputnik_amd::Workspace{ws, ws_bytes});
-  return Code(e, sputnik_amd::StatusCode(st));
+  return SddEpilogueCall(a, transpose_a, b, transpose_b, c, act,
+                         sputnik_amd::kOutActGrad, z, nullptr, nullptr, dtype,
+                         ws, ws_bytes, stream);
 }
 
 int sputnik_sdd_gated(const sputnik_matrix_t *a, int transpose_a,
@@ -276,8 +256,9 @@ int sputnik_sdd_gated(const sputnik_matrix_t *a, int transpose_a,
                       const sputnik_block_matrix_t *c, int act,
                       const void *gate, void *up, int dtype, void *ws,
                       size_t ws_bytes, void *stream) {
-  return SddGated(a, transpose_a, b, transpose_b, c, act, gate, up, nullptr,
-                  false, dtype, ws, ws_bytes, stream);
+  return SddEpilogueCall(a, transpose_a, b, transpose_b, c, act,
+                         sputnik_amd::kOutGate, gate, up, nullptr, dtype, ws,
+                         ws_bytes, stream);
 }
 
 int sputnik_sdd_gated_grad(const sputnik_matrix_t *a, int transpose_a,
@@ -286,22 +267,41 @@ int sputnik_sdd_gated_grad(const sputnik_matrix_t *a, int transpose_a,
                            const void *gate, const void *up, void *up_grad,
                            int dtype, void *ws, size_t ws_bytes,
                            void *stream) {
-  return SddGated(a, transpose_a, b, transpose_b, c, act, gate,
-                  const_cast<void *>(up), up_grad, true, dtype, ws, ws_bytes,
-                  stream);
+  return SddEpilogueCall(a, transpose_a, b, transpose_b, c, act,
+                         sputnik_amd::kOutGateGrad, gate, up, up_grad, dtype,
+                         ws, ws_bytes, stream);
+}
+
+// The elementwise stages alone, in the trait's argument order (x, s0, s1;
+// o0, o1).
+int sputnik_block_activation(const void *z, void *h, long long n, int act,
+                             int dtype, void *stream) {
+  return sputnik_amd::RunBlockEpilogue(
+      dtype, act, sputnik_amd::kOutAct, z, nullptr, nullptr, h, nullptr, n,
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_block_activation_grad(const void *g, const void *z, void *out,
+                                  long long n, int act, int dtype,
+                                  void *stream) {
+  return sputnik_amd::RunBlockEpilogue(
+      dtype, act, sputnik_amd::kOutActGrad, g, z, nullptr, out, nullptr, n,
+      static_cast<hipStream_t>(stream));
 }
 
 int sputnik_block_gate(const void *u, const void *g, void *out, long long n,
                        int act, int dtype, void *stream) {
-  return sputnik_amd::RunBlockGate(dtype, act, u, g, out, n,
-                                   static_cast<hipStream_t>(stream));
+  return sputnik_amd::RunBlockEpilogue(
+      dtype, act, sputnik_amd::kOutGate, u, g, nullptr, out, nullptr, n,
+      static_cast<hipStream_t>(stream));
 }
 
 int sputnik_block_gate_grad(const void *d, const void *g, const void *u,
                             void *dg, void *du, long long n, int act,
                             int dtype, void *stream) {
-  return sputnik_amd::RunBlockGateGrad(dtype, act, d, g, u, dg, du, n,
-                                       static_cast<hipStream_t>(stream));
+  return sputnik_amd::RunBlockEpilogue(
+      dtype, act, sputnik_amd::kOutGateGrad, d, g, u, dg, du, n,
+      static_cast<hipStream_t>(stream));
 }
 
 int sputnik_sdd_act_route(const sputnik_matrix_t *a, int transpose_a,

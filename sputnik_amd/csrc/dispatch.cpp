@@ -156,7 +156,7 @@ static const KnobDef kKnobs[kNumKnobs] = {
     // (grouped 4-wave SDD with K >= this: the rows past the groups' full
     // rounds go to an 8-wave launch of a block per workgroup; 0 off)
     {"sdd_tail_min_k", "SPUTNIK_AMD_SDD_TAIL_MIN_K", 8192, 0, 1 << 30},
-    // (SDD activation products, RunSddAct: 0 auto, 1 the fused epilogue of
+    // (SDD epilogue products, RunSddEpilogue: 0 auto, 1 the fused epilogue of
     // the 8-wave kernel, 2 plain SDD plus the elementwise kernel)
     {"sdd_act_route", "SPUTNIK_AMD_SDD_ACT_ROUTE", 0, 0, 2},
 };
@@ -1614,22 +1614,40 @@ hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                          grouped, p, stream);
 }
 
-// ---- SDD activation products (sputnik/block/activation.h) ----
+// ---- SDD epilogue products (sputnik/block/activation.h, gated.h) ----
 
 static bool ActOk(int act) {
   return act == kActRelu || act == kActGelu || act == kActSilu;
 }
 
-hipError_t RunBlockAct(int dtype, int act, const void *g, const void *z,
-                       void *out, long long n, bool gate, hipStream_t stream) {
-  if (!ActOk(act) || (dtype != 0 && dtype != 1) || n < 0)
+// What the host code needs of SddEpilogue<mode>; side_inputs < 0: not an
+// epilogue mode.
+struct EpilogueShape {
+  int side_inputs;
+  bool keeps_x, second_output;
+};
+static EpilogueShape ShapeOf(int mode) {
+  return WithSddEpilogue(mode, EpilogueShape{-1, false, false}, [](auto e) {
+    using E = decltype(e);
+    return EpilogueShape{E::kSideInputs, E::kKeepsX, E::kSecondOutput};
+  });
+}
+
+hipError_t RunBlockEpilogue(int dtype, int act, int mode, const void *x,
+                            const void *s0, const void *s1, void *o0,
+                            void *o1, long long n, hipStream_t stream) {
+  const EpilogueShape e = ShapeOf(mode);
+  if (!ActOk(act) || e.side_inputs < 0 || (dtype != 0 && dtype != 1) || n < 0)
     return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  if (z == nullptr || out == nullptr || (gate && g == nullptr))
+  if (x == nullptr || o0 == nullptr || (e.side_inputs >= 1 && s0 == nullptr) ||
+      (e.side_inputs >= 2 && s1 == nullptr) ||
+      (e.second_output && o1 == nullptr) || o0 == o1)
     return hipErrorInvalidValue;
   int dev = 0;
   const int cus = hipGetDevice(&dev) == hipSuccess ? DeviceCUs(dev) : 0;
-  return LaunchBlockAct(dtype, act, gate ? g : nullptr, z, out, n, cus, stream);
+  return LaunchBlockEpilogue(dtype, mode, act, x, s0, s1, o0, o1, n, cus,
+                             stream);
 }
 
 // The route of one call, decided once from the prepared params, in the order
@@ -1666,63 +1684,6 @@ int SddActRoute(const Matrix &a, bool ta, const Matrix &b, bool tb,
   return SddActDecide(a, ta, b, tb, c, nullptr, &p, &grouped);
 }
 
-hipError_t RunSddAct(const Matrix &a, bool ta, const Matrix &b, bool tb,
-                     const BlockMatrix &c, int dtype, int act, void *z,
-                     bool grad, hipStream_t stream, Status *st_out,
-                     Workspace ws) {
-  GemmParams p;
-  const Status st = PrepareSdd(a, ta, b, tb, c, &p);
-  *st_out = st;
-  if (st != Status::kOk) return hipSuccess;
-  if (!ActOk(act) || (grad && z == nullptr) || (z != nullptr && z == c.data))
-    return hipErrorInvalidValue;
-  bool grouped = false;
-  if (SddActDecide(a, ta, b, tb, c, stream, &p, &grouped) == 2) {
-    // Two kernels: the plain SDD, whatever it runs, into Z (forward, when Z
-    // is wanted) or C, and the elementwise stage behind it on the stream.
-    BlockMatrix prod = c;
-    if (!grad && z != nullptr) prod.data = z;
-    const hipError_t e = RunSdd(a, ta, b, tb, prod, dtype, stream, st_out, ws);
-    if (e != hipSuccess || *st_out != Status::kOk) return e;
-    return RunBlockAct(dtype, act, grad ? c.data : nullptr,
-                       grad ? z : prod.data, c.data, c.nonzeros, grad, stream);
-  }
-  const InProduct in_product;
-  p.debug = g_debug;
-  p.act = act;
-  p.z_data = static_cast<char *>(z);
-  return LaunchBlockGemmAct(dtype, /*s_kc=*/!ta, /*d_kc=*/tb, grouped,
-                            grad ? kOutActGrad : kOutAct, p, stream);
-}
-
-// ---- Gated SDD products (sputnik/block/gated.h) ----
-
-hipError_t RunBlockGate(int dtype, int act, const void *u, const void *g,
-                        void *out, long long n, hipStream_t stream) {
-  if (!ActOk(act) || (dtype != 0 && dtype != 1) || n < 0)
-    return hipErrorInvalidValue;
-  if (n == 0) return hipSuccess;
-  if (u == nullptr || g == nullptr || out == nullptr)
-    return hipErrorInvalidValue;
-  int dev = 0;
-  const int cus = hipGetDevice(&dev) == hipSuccess ? DeviceCUs(dev) : 0;
-  return LaunchBlockGate(dtype, act, u, g, out, n, cus, stream);
-}
-
-hipError_t RunBlockGateGrad(int dtype, int act, const void *d, const void *g,
-                            const void *u, void *dg, void *du, long long n,
-                            hipStream_t stream) {
-  if (!ActOk(act) || (dtype != 0 && dtype != 1) || n < 0)
-    return hipErrorInvalidValue;
-  if (n == 0) return hipSuccess;
-  if (d == nullptr || g == nullptr || u == nullptr || dg == nullptr ||
-      du == nullptr || dg == du)
-    return hipErrorInvalidValue;
-  int dev = 0;
-  const int cus = hipGetDevice(&dev) == hipSuccess ? DeviceCUs(dev) : 0;
-  return LaunchBlockGateGrad(dtype, act, d, g, u, dg, du, n, cus, stream);
-}
-
 // The buffer rules of gated.h: required pointers set, and no two of gate,
 // up, up_grad, c.data, A, B equal, up_grad == up excepted.
 static bool GatedBuffersOk(const Matrix &a, const Matrix &b,
@@ -1740,39 +1701,49 @@ static bool GatedBuffersOk(const Matrix &a, const Matrix &b,
   return true;
 }
 
-hipError_t RunSddGated(const Matrix &a, bool ta, const Matrix &b, bool tb,
-                       const BlockMatrix &c, int dtype, int act,
-                       const void *gate, void *up, void *up_grad, bool grad,
-                       hipStream_t stream, Status *st_out, Workspace ws) {
+hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                          const BlockMatrix &c, int dtype, int act, int mode,
+                          void *side0, void *side1, void *out1,
+                          hipStream_t stream, Status *st_out, Workspace ws) {
   GemmParams p;
   const Status st = PrepareSdd(a, ta, b, tb, c, &p);
   *st_out = st;
   if (st != Status::kOk) return hipSuccess;
-  if (!ActOk(act) || !GatedBuffersOk(a, b, c, gate, up, up_grad, grad))
-    return hipErrorInvalidValue;
+  const EpilogueShape e = ShapeOf(mode);
+  if (!ActOk(act) || e.side_inputs < 0) return hipErrorInvalidValue;
+  // (activation.h: Z required by the gradient, and never C itself)
+  const bool buffers_ok =
+      mode == kOutGate || mode == kOutGateGrad
+          ? GatedBuffersOk(a, b, c, side0, side1, out1, mode == kOutGateGrad)
+          : !(mode == kOutActGrad && side0 == nullptr) &&
+                !(side0 != nullptr && side0 == c.data);
+  if (!buffers_ok) return hipErrorInvalidValue;
+  void *const side[2] = {side0, side1};
   bool grouped = false;
   if (SddActDecide(a, ta, b, tb, c, stream, &p, &grouped) == 2) {
-    // Two kernels: the plain SDD, whatever it runs, into U (forward, when U
-    // is wanted) or C, and the elementwise stage behind it on the stream
-    // (the gradient turns D in C into dG in place).
+    // Two kernels: the plain SDD, whatever it runs, into the buffer that
+    // keeps x (when the op has one and it is wanted) or C, and the
+    // elementwise stage behind it on the stream, in place where x is in C.
     BlockMatrix prod = c;
-    if (!grad && up != nullptr) prod.data = up;
-    const hipError_t e = RunSdd(a, ta, b, tb, prod, dtype, stream, st_out, ws);
-    if (e != hipSuccess || *st_out != Status::kOk) return e;
-    if (grad)
-      return RunBlockGateGrad(dtype, act, c.data, gate, up, c.data, up_grad,
-                              c.nonzeros, stream);
-    return RunBlockGate(dtype, act, prod.data, gate, c.data, c.nonzeros,
-                        stream);
+    if (e.keeps_x && side[e.side_inputs] != nullptr)
+      prod.data = side[e.side_inputs];
+    const hipError_t err =
+        RunSdd(a, ta, b, tb, prod, dtype, stream, st_out, ws);
+    if (err != hipSuccess || *st_out != Status::kOk) return err;
+    return RunBlockEpilogue(dtype, act, mode, prod.data,
+                            e.side_inputs >= 1 ? side0 : nullptr,
+                            e.side_inputs >= 2 ? side1 : nullptr, c.data,
+                            e.second_output ? out1 : nullptr, c.nonzeros,
+                            stream);
   }
   const InProduct in_product;
   p.debug = g_debug;
   p.act = act;
-  p.z_data = static_cast<char *>(const_cast<void *>(gate));
-  p.u_data = static_cast<char *>(up);
-  p.du_data = static_cast<char *>(up_grad);
-  return LaunchBlockGemmGate(dtype, /*s_kc=*/!ta, /*d_kc=*/tb, grouped,
-                             grad ? kOutGateGrad : kOutGate, p, stream);
+  p.z_data = static_cast<char *>(side0);
+  p.u_data = static_cast<char *>(side1);
+  p.du_data = static_cast<char *>(out1);
+  return LaunchBlockGemmEpilogue(dtype, /*s_kc=*/!ta, /*d_kc=*/tb, grouped,
+                                 mode, p, stream);
 }
 
 hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
@@ -1960,17 +1931,28 @@ hipError_t Matmul(const Matrix a, bool transpose_a, const Matrix b,
   return Matmul(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
 }
 
-// ---- SDD activation products (sputnik/block/activation.h) ----
+// ---- SDD epilogue products (sputnik/block/activation.h, gated.h) ----
+
+static hipError_t MatmulEpilogue(const char *what, const Matrix &a, bool ta,
+                                 const Matrix &b, bool tb,
+                                 const BlockMatrix &c, Activation activation,
+                                 int mode, const void *side0,
+                                 const void *side1, void *out1, DataType dtype,
+                                 hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunSddEpilogue(
+      a, ta, b, tb, c, (int)dtype, (int)activation, mode,
+      const_cast<void *>(side0), const_cast<void *>(side1), out1, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, what);
+}
 
 hipError_t MatmulActivation(const Matrix a, bool transpose_a, const Matrix b,
                             bool transpose_b, BlockMatrix c,
                             Activation activation, void *pre_activation,
                             DataType dtype, hipStream_t stream) {
-  Status st;
-  const hipError_t e = sputnik_amd::RunSddAct(
-      a, transpose_a, b, transpose_b, c, (int)dtype, (int)activation,
-      pre_activation, /*grad=*/false, stream, &st);
-  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sdd (activation)");
+  return MatmulEpilogue("sdd (activation)", a, transpose_a, b, transpose_b, c,
+                        activation, sputnik_amd::kOutAct, pre_activation,
+                        nullptr, nullptr, dtype, stream);
 }
 
 hipError_t MatmulActivationGrad(const Matrix a, bool transpose_a,
@@ -1978,25 +1960,18 @@ hipError_t MatmulActivationGrad(const Matrix a, bool transpose_a,
                                 BlockMatrix c, Activation activation,
                                 const void *pre_activation, DataType dtype,
                                 hipStream_t stream) {
-  Status st;
-  const hipError_t e = sputnik_amd::RunSddAct(
-      a, transpose_a, b, transpose_b, c, (int)dtype, (int)activation,
-      const_cast<void *>(pre_activation), /*grad=*/true, stream, &st);
-  return st == Status::kOk ? e
-                           : sputnik_amd::OrAbort(st, "sdd (activation grad)");
+  return MatmulEpilogue("sdd (activation grad)", a, transpose_a, b,
+                        transpose_b, c, activation, sputnik_amd::kOutActGrad,
+                        pre_activation, nullptr, nullptr, dtype, stream);
 }
-
-// ---- Gated SDD products (sputnik/block/gated.h) ----
 
 hipError_t MatmulGated(const Matrix a, bool transpose_a, const Matrix b,
                        bool transpose_b, BlockMatrix c, Activation activation,
                        const void *gate, void *up, DataType dtype,
                        hipStream_t stream) {
-  Status st;
-  const hipError_t e = sputnik_amd::RunSddGated(
-      a, transpose_a, b, transpose_b, c, (int)dtype, (int)activation, gate, up,
-      nullptr, /*grad=*/false, stream, &st);
-  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sdd (gated)");
+  return MatmulEpilogue("sdd (gated)", a, transpose_a, b, transpose_b, c,
+                        activation, sputnik_amd::kOutGate, gate, up, nullptr,
+                        dtype, stream);
 }
 
 hipError_t MatmulGatedGrad(const Matrix a, bool transpose_a, const Matrix b,
@@ -2004,11 +1979,9 @@ hipError_t MatmulGatedGrad(const Matrix a, bool transpose_a, const Matrix b,
                            Activation activation, const void *gate,
                            const void *up, void *up_grad, DataType dtype,
                            hipStream_t stream) {
-  Status st;
-  const hipError_t e = sputnik_amd::RunSddGated(
-      a, transpose_a, b, transpose_b, c, (int)dtype, (int)activation, gate,
-      const_cast<void *>(up), up_grad, /*grad=*/true, stream, &st);
-  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sdd (gated grad)");
+  return MatmulEpilogue("sdd (gated grad)", a, transpose_a, b, transpose_b, c,
+                        activation, sputnik_amd::kOutGateGrad, gate, up,
+                        up_grad, dtype, stream);
 }
 
 // SSD (reference sputnik/block/ssd/ssd.h:10-22) and SDS (sds.h:10-22).

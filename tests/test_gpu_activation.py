@@ -221,6 +221,10 @@ def test_exhaustive_elementwise(dtype, act):
         ds = sp.BlockActivationGrad(unaligned(gt, 1), unaligned(z, 3), act,
                                     out=unaligned(gt, 5))   # scalar gate
         assert torch.equal(ds.view(torch.int16), d[:n].view(torch.int16))
+        if g == 1.0:
+            zc = z.clone()
+            sp.BlockActivationGrad(gt, zc, act, out=zc)  # in place over z
+            assert torch.equal(zc.view(torch.int16), d.view(torch.int16))
         sp.BlockActivationGrad(gt, z, act, out=gt)       # in place over g
         assert torch.equal(gt.view(torch.int16), d.view(torch.int16))
     zc = z.clone()

@@ -188,9 +188,9 @@ def test_exhaustive_up_with_relu(dtype, r, route):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_exhaustive_elementwise(dtype, act):
     """BlockGate / BlockGateGrad called directly over every finite G: out of
-    place, in place (dG over D, dU over U), buffers that are not 16-byte
-    aligned with an odd length (the scalar loop, bit for bit what the vector
-    loop gave), aligned buffers with n % 8 != 0, and n = 0."""
+    place, in place (H over U, H over G; dG over D, dU over U), buffers that
+    are not 16-byte aligned with an odd length (the scalar loop, bit for bit
+    what the vector loop gave), aligned buffers with n % 8 != 0, and n = 0."""
     bits, g64 = _exhaustive(dtype)
     g = _from_bits(bits, dtype)
     n = g.numel() - 1                                    # odd length
@@ -217,6 +217,10 @@ def test_exhaustive_elementwise(dtype, act):
         uc = u.clone()
         sp.BlockGate(uc, g, act, out=uc)                 # in place over u
         assert _same(uc, h)
+        if f == FORWARD_FACTORS[0]:
+            gc = g.clone()
+            sp.BlockGate(u, gc, act, out=gc)             # in place over g
+            assert _same(gc, h)
     for d, uval in GRAD_FACTORS:
         dt, ut = torch.full_like(g, d), torch.full_like(g, uval)
         dg, du = sp.BlockGateGrad(dt, g, ut, act)
