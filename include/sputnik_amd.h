@@ -340,6 +340,80 @@ int sputnik_expert_topology(const int32_t *padded_bins, int num_experts,
                             int block_rows, int blocks_per_expert,
                             int32_t *offsets, int16_t *indices, void *stream);
 
+/* ---- MoE token permutation (sputnik/block/moe.h): the
+ * counterparts of MegaBlocks' padded_gather, padded_scatter and
+ * padded_scatter_wgrad, and the routing metadata behind them. With T the
+ * operand type, n = tokens * top_k assignments (assignment a = t * top_k + k)
+ * and the int32 routing tensors of MegaBlocks' indices_and_padded_bins
+ * (bin_ids, indices: the stable ascending sort of top_experts.flatten();
+ * bins / padded_bins: inclusive cumsums of the per-expert counts / of the
+ * counts rounded up to multiples of 128; all of num_experts entries):
+ *   sputnik_moe_bins        bins, tokens_per_expert, padded_bins from the
+ *                           sorted bin_ids[n] (one workgroup; the sort is
+ *                           the caller's)
+ *   sputnik_moe_row_map     row_of[indices[i]] = padded_bins[e-1] +
+ *                           (i - bins[e-1]), e = bin_ids[i] (index -1 read
+ *                           as 0): the padded row of every assignment; -1
+ *                           where the bin id is outside [0, num_experts) or
+ *                           the row outside [0, rows); a position whose
+ *                           index is outside [0, n) is skipped
+ *   sputnik_padded_gather   x [tokens, hidden] -> out [rows, hidden]:
+ *                           out[row(i)] = x[indices[i] / top_k] bit for bit,
+ *                           or round_T(float(w[indices[i]]) * float(x[..]))
+ *                           with weights; every other row of out (padding
+ *                           inside a bin, rows from padded_bins[E-1] to
+ *                           rows) is written as +0 by the same kernel: out
+ *                           needs no initialisation
+ *   sputnik_padded_scatter  y [rows, hidden] -> out [tokens, hidden]:
+ *                           out[t] = round_T(sum_k float(w[t top_k + k]) *
+ *                           float(y[row_of[t top_k + k]])), summed in fp32
+ *                           from 0 in ascending k, rounded once; no
+ *                           atomics, no [n, hidden] intermediate, bitwise
+ *                           reproducible
+ *   sputnik_padded_scatter_wgrad
+ *                           dw[a] = sum_h float(dout[a / top_k, h]) *
+ *                           float(y[row_of[a], h]), fp32 accumulation in a
+ *                           free order, stored in the weights' type
+ * weights: n elements indexed by assignment, of T (weights_dtype
+ * SPUTNIK_WEIGHTS_OPERAND) or float (SPUTNIK_WEIGHTS_F32); NULL means
+ * unweighted (weights_dtype is then ignored). dw is of weights_dtype. The
+ * gradients are these same calls: d gather / dx is the unweighted scatter,
+ * d scatter / dy the gather of dout with the weights, d scatter / dw the
+ * wgrad. Every index read from device memory is range-checked before it is
+ * used as an address; an entry out of range contributes zeros, so no kernel
+ * reads or writes outside its buffers whatever the metadata holds. 16-byte
+ * accesses when hidden % 8 == 0 and the row buffers are 16-byte aligned.
+ * Stream-ordered; no call allocates or synchronises.
+ * They never abort: a null required buffer, a negative size, top_k < 1,
+ * rows % 128 != 0, an unknown dtype or weights_dtype, tokens * top_k or
+ * n + 127 * num_experts past INT_MAX, or an output that equals an input:
+ * hipErrorInvalidValue (1), nothing launched. Zero-sized work (no output
+ * element) succeeds whatever the pointers. */
+enum {
+  SPUTNIK_WEIGHTS_OPERAND = 0,
+  SPUTNIK_WEIGHTS_F32 = 1,
+};
+int sputnik_moe_bins(const int32_t *bin_ids, int n, int num_experts,
+                     int32_t *bins, int32_t *tokens_per_expert,
+                     int32_t *padded_bins, void *stream);
+int sputnik_moe_row_map(const int32_t *indices, const int32_t *bin_ids,
+                        const int32_t *bins, const int32_t *padded_bins,
+                        int n, int num_experts, int rows, int32_t *row_of,
+                        void *stream);
+int sputnik_padded_gather(const void *x, const int32_t *indices,
+                          const int32_t *bins, const int32_t *padded_bins,
+                          const void *weights, void *out, int tokens,
+                          int hidden, int top_k, int num_experts, int rows,
+                          int dtype, int weights_dtype, void *stream);
+int sputnik_padded_scatter(const void *y, const int32_t *row_of,
+                           const void *weights, void *out, int tokens,
+                           int hidden, int top_k, int rows, int dtype,
+                           int weights_dtype, void *stream);
+int sputnik_padded_scatter_wgrad(const void *dout, const void *y,
+                                 const int32_t *row_of, void *dw, int tokens,
+                                 int hidden, int top_k, int rows, int dtype,
+                                 int weights_dtype, void *stream);
+
 /* ---- Host-only queries (no GPU work; safe without a device) */
 /* 1 when the reference would accept the problem (same rules as
  * can_launch_* + ValidMatmul), 0 otherwise. op: 0=DSD 1=DDS 2=SDD. */

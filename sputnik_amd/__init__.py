@@ -138,6 +138,24 @@ _SIGNATURES = {
     "sputnik_mask_to_bcsr": [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P],
     "sputnik_expert_topology": [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                 _P, _P, _P],
+    # MoE token permutation: (bin_ids, n, experts, bins, tokens_per_expert,
+    # padded_bins, stream); (indices, bin_ids, bins, padded_bins, n, experts,
+    # rows, row_of, stream); (x, indices, bins, padded_bins, weights, out,
+    # tokens, hidden, top_k, experts, rows, dtype, weights_dtype, stream);
+    # (y, row_of, weights, out, tokens, hidden, top_k, rows, dtype,
+    # weights_dtype, stream); (dout, y, row_of, dw, tokens, ..., stream)
+    "sputnik_moe_bins": [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P],
+    "sputnik_moe_row_map": [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
+                            ctypes.c_int, _P, _P],
+    "sputnik_padded_gather": [_P, _P, _P, _P, _P, _P, ctypes.c_int,
+                              ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                              ctypes.c_int, ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_padded_scatter": [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
+                               ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                               ctypes.c_int, _P],
+    "sputnik_padded_scatter_wgrad": [_P, _P, _P, _P, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, _P],
     "sputnik_can_implement": [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_abi_block_matrix_size": [],
     "sputnik_abi_block_matrix_offset": [ctypes.c_int],
@@ -761,6 +779,167 @@ def ExpertTopology(padded_bins, block_rows, blocks_per_expert, offsets,  # noqa:
         _stream(stream)), "ExpertTopology")
 
 
+SPUTNIK_WEIGHTS_OPERAND = 0
+SPUTNIK_WEIGHTS_F32 = 1
+
+
+def _moe_meta(t, numel, what: str) -> None:
+    """An int32 routing tensor of `numel` elements (None: any), contiguous.
+    Raises before any library call."""
+    import torch
+
+    td = getattr(t, "dtype", None)
+    if td != torch.int32:
+        raise TypeError(f"{what} is {td}, expected torch.int32")
+    if numel is not None and int(t.numel()) != numel:
+        raise ValueError(f"{what} holds {int(t.numel())} elements, expected "
+                         f"{numel}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+
+
+def _moe_matrix(t, dtype, cols, what: str) -> None:
+    """A [*, cols] row matrix of a permutation call: 2-D, `dtype` (None:
+    fp16 or bf16), contiguous. Raises before any library call."""
+    if dtype is None:
+        _dtype_code(t)
+    elif getattr(t, "dtype", None) != dtype:
+        raise TypeError(f"{what} is {getattr(t, 'dtype', None)}, expected "
+                        f"{dtype}")
+    if t.dim() != 2 or (cols is not None and int(t.shape[1]) != cols):
+        raise ValueError(f"{what} has shape {tuple(t.shape)}, expected "
+                         f"[rows, {'hidden' if cols is None else cols}]")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+
+
+def _moe_sizes(tokens: int, top_k, rows: int, what: str) -> int:
+    """top_k as an int >= 1 and rows a multiple of 128, or ValueError."""
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1:
+        raise ValueError(f"{what}: top_k must be an int >= 1, not {top_k!r}")
+    if rows % 128:
+        raise ValueError(f"{what}: {rows} padded rows, not a multiple of 128")
+    return tokens * top_k
+
+
+def _moe_weights(w, operand_dtype, n: int, what: str) -> int:
+    """SPUTNIK_WEIGHTS_* of a per-assignment weight tensor ([tokens, top_k]
+    or flat, n elements, the operand dtype or fp32, contiguous)."""
+    import torch
+
+    wd = getattr(w, "dtype", None)
+    if wd == torch.float32:
+        code = SPUTNIK_WEIGHTS_F32
+    elif wd == operand_dtype:
+        code = SPUTNIK_WEIGHTS_OPERAND
+    else:
+        raise TypeError(f"{what} is {wd}, expected {operand_dtype} or "
+                        "torch.float32")
+    if int(w.numel()) != n:
+        raise ValueError(f"{what} holds {int(w.numel())} elements, expected "
+                         f"tokens * top_k = {n}")
+    if not w.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return code
+
+
+def MoeBins(bin_ids, num_experts, bins, tokens_per_expert, padded_bins,  # noqa: N802
+            stream=None):
+    """bins, tokens_per_expert and padded_bins (int32 [num_experts]) from the
+    sorted bin_ids (int32 [n]) on the device (sputnik_moe_bins;
+    sputnik/block/moe.h)."""
+    e = int(num_experts)
+    _moe_meta(bin_ids, None, "bin_ids")
+    for name, t in (("bins", bins), ("tokens_per_expert", tokens_per_expert),
+                    ("padded_bins", padded_bins)):
+        _moe_meta(t, e, name)
+    _check(lib().sputnik_moe_bins(
+        _ptr(bin_ids), int(bin_ids.numel()), e, _ptr(bins),
+        _ptr(tokens_per_expert), _ptr(padded_bins), _stream(stream)),
+        "MoeBins")
+
+
+def MoeRowMap(indices, bin_ids, bins, padded_bins, rows, row_of,  # noqa: N802
+              stream=None):
+    """row_of (int32 [n]): the padded row of every assignment, -1 where the
+    routing tensors put it outside [0, rows) (sputnik_moe_row_map)."""
+    n, e = int(indices.numel()), int(bins.numel())
+    _moe_meta(indices, None, "indices")
+    _moe_meta(bin_ids, n, "bin_ids")
+    _moe_meta(bins, None, "bins")
+    _moe_meta(padded_bins, e, "padded_bins")
+    _moe_meta(row_of, n, "row_of")
+    if int(rows) % 128:
+        raise ValueError(f"MoeRowMap: {rows} padded rows, not a multiple of "
+                         "128")
+    _check(lib().sputnik_moe_row_map(
+        _ptr(indices), _ptr(bin_ids), _ptr(bins), _ptr(padded_bins), n, e,
+        int(rows), _ptr(row_of), _stream(stream)), "MoeRowMap")
+
+
+def PaddedGather(x, indices, bins, padded_bins, out, top_k, weights=None,  # noqa: N802
+                 stream=None):
+    """out [rows, hidden] = the rows of x [tokens, hidden] in padded expert
+    order: out[row(i)] = x[indices[i] // top_k], bit for bit, or times
+    weights[indices[i]] (rounded once) with `weights` ([tokens, top_k] or
+    flat, x's dtype or fp32). Every other row of `out` is written as +0:
+    `out` needs no initialisation (sputnik_padded_gather). Type and shape
+    errors are raised before the library is called."""
+    _moe_matrix(x, None, None, "x")
+    dtype = _dtype_code(x)
+    tokens, hidden = int(x.shape[0]), int(x.shape[1])
+    _moe_matrix(out, x.dtype, hidden, "out")
+    rows = int(out.shape[0])
+    n = _moe_sizes(tokens, top_k, rows, "PaddedGather")
+    _moe_meta(indices, n, "indices")
+    _moe_meta(bins, None, "bins")
+    _moe_meta(padded_bins, int(bins.numel()), "padded_bins")
+    wcode = (SPUTNIK_WEIGHTS_OPERAND if weights is None
+             else _moe_weights(weights, x.dtype, n, "weights"))
+    _check(lib().sputnik_padded_gather(
+        _ptr(x), _ptr(indices), _ptr(bins), _ptr(padded_bins), _ptr(weights),
+        _ptr(out), tokens, hidden, top_k, int(bins.numel()), rows, dtype,
+        wcode, _stream(stream)), "PaddedGather")
+
+
+def PaddedScatter(y, row_of, out, top_k, weights=None, stream=None):  # noqa: N802
+    """out [tokens, hidden] = for every token the sum over its top_k padded
+    rows of y [rows, hidden], read through row_of (int32 [tokens * top_k])
+    and multiplied by `weights` when given; fp32 sum in ascending k, rounded
+    once, no atomics (sputnik_padded_scatter). Type and shape errors are
+    raised before the library is called."""
+    _moe_matrix(y, None, None, "y")
+    dtype = _dtype_code(y)
+    rows, hidden = int(y.shape[0]), int(y.shape[1])
+    _moe_matrix(out, y.dtype, hidden, "out")
+    tokens = int(out.shape[0])
+    n = _moe_sizes(tokens, top_k, rows, "PaddedScatter")
+    _moe_meta(row_of, n, "row_of")
+    wcode = (SPUTNIK_WEIGHTS_OPERAND if weights is None
+             else _moe_weights(weights, y.dtype, n, "weights"))
+    _check(lib().sputnik_padded_scatter(
+        _ptr(y), _ptr(row_of), _ptr(weights), _ptr(out), tokens, hidden,
+        top_k, rows, dtype, wcode, _stream(stream)), "PaddedScatter")
+
+
+def PaddedScatterWeightGrad(dout, y, row_of, dw, top_k, stream=None):  # noqa: N802
+    """dw[a] = dot(dout[a // top_k], y[row_of[a]]) in fp32, stored in dw's
+    dtype (the operands' or fp32): the gradient of PaddedScatter with respect
+    to its weights (sputnik_padded_scatter_wgrad). Type and shape errors are
+    raised before the library is called."""
+    _moe_matrix(dout, None, None, "dout")
+    dtype = _dtype_code(dout)
+    tokens, hidden = int(dout.shape[0]), int(dout.shape[1])
+    _moe_matrix(y, dout.dtype, hidden, "y")
+    rows = int(y.shape[0])
+    n = _moe_sizes(tokens, top_k, rows, "PaddedScatterWeightGrad")
+    _moe_meta(row_of, n, "row_of")
+    wcode = _moe_weights(dw, dout.dtype, n, "dw")
+    _check(lib().sputnik_padded_scatter_wgrad(
+        _ptr(dout), _ptr(y), _ptr(row_of), _ptr(dw), tokens, hidden, top_k,
+        rows, dtype, wcode, _stream(stream)), "PaddedScatterWeightGrad")
+
+
 def Bitmask(m: BlockMatrix, stream=None):  # noqa: N802
     """reference sputnik/block/bitmask/bitmask.h:10 (on the device): the
     BitMatrix of m's topology, over the transposed order when m.offsets_t is
@@ -940,6 +1119,9 @@ __all__ = [
     "BlockActivationGrad", "SPUTNIK_ACT_RELU", "SPUTNIK_ACT_GELU",
     "SPUTNIK_ACT_SILU", "sdd_act_route",
     "MatmulGated", "MatmulGatedGrad", "BlockGate", "BlockGateGrad",
+    "MoeBins", "MoeRowMap", "PaddedGather", "PaddedScatter",
+    "PaddedScatterWeightGrad", "SPUTNIK_WEIGHTS_OPERAND",
+    "SPUTNIK_WEIGHTS_F32",
     "SputnikError", "Transpose", "can_implement", "lib", "version",
     "allgather_concat", "gather_row_panels", "gather_col_panels",
     "gather_block_runs",

@@ -10,6 +10,7 @@
 #include "api_internal.h"
 #include "sputnik/sputnik.h"
 #include "metadata.h"
+#include "moe_permute.h"
 #include "sputnik_amd.h"
 
 using sputnik::block::BlockMatrix;
@@ -489,6 +490,53 @@ int sputnik_expert_topology(const int32_t *padded_bins, int num_experts,
   return sputnik_amd::LaunchExpertTopology(
       padded_bins, num_experts, block_rows, blocks_per_expert, offsets,
       indices, static_cast<hipStream_t>(stream));
+}
+
+// MoE token permutation (sputnik/block/moe.h): moe_permute.hip validates.
+int sputnik_moe_bins(const int32_t *bin_ids, int n, int num_experts,
+                     int32_t *bins, int32_t *tokens_per_expert,
+                     int32_t *padded_bins, void *stream) {
+  return sputnik_amd::RunMoeBins(bin_ids, n, num_experts, bins,
+                                 tokens_per_expert, padded_bins,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int sputnik_moe_row_map(const int32_t *indices, const int32_t *bin_ids,
+                        const int32_t *bins, const int32_t *padded_bins,
+                        int n, int num_experts, int rows, int32_t *row_of,
+                        void *stream) {
+  return sputnik_amd::RunMoeRowMap(indices, bin_ids, bins, padded_bins, n,
+                                   num_experts, rows, row_of,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int sputnik_padded_gather(const void *x, const int32_t *indices,
+                          const int32_t *bins, const int32_t *padded_bins,
+                          const void *weights, void *out, int tokens,
+                          int hidden, int top_k, int num_experts, int rows,
+                          int dtype, int weights_dtype, void *stream) {
+  return sputnik_amd::RunPaddedGather(
+      x, indices, bins, padded_bins, weights, out, tokens, hidden, top_k,
+      num_experts, rows, dtype, weights_dtype,
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_padded_scatter(const void *y, const int32_t *row_of,
+                           const void *weights, void *out, int tokens,
+                           int hidden, int top_k, int rows, int dtype,
+                           int weights_dtype, void *stream) {
+  return sputnik_amd::RunPaddedScatter(y, row_of, weights, out, tokens, hidden,
+                                       top_k, rows, dtype, weights_dtype,
+                                       static_cast<hipStream_t>(stream));
+}
+
+int sputnik_padded_scatter_wgrad(const void *dout, const void *y,
+                                 const int32_t *row_of, void *dw, int tokens,
+                                 int hidden, int top_k, int rows, int dtype,
+                                 int weights_dtype, void *stream) {
+  return sputnik_amd::RunPaddedScatterWgrad(
+      dout, y, row_of, dw, tokens, hidden, top_k, rows, dtype, weights_dtype,
+      static_cast<hipStream_t>(stream));
 }
 
 int sputnik_can_implement(int op, const void *a, int transpose_a,

@@ -21,7 +21,11 @@ dsd(act(sdd(x, w1, topo)), w2) as one autograd function
 sdd multiplied by act(gate) in the product's epilogue, and `glu_mlp(x, w1, v1,
 w2, topo, activation)` the gated expert MLP
 dsd(act(sdd(x, w1, topo)) * sdd(x, v1, topo), w2) as one autograd function
-(sputnik/block/gated.h). Every product runs on
+(sputnik/block/gated.h). `moe_route`, `padded_gather` and `padded_scatter`
+are the token permutation on either side of those MLPs (MegaBlocks'
+padded_gather / padded_scatter; sputnik/block/moe.h), and `moe_mlp` the whole
+layer behind a router: route, gather, expert topology, mlp / glu_mlp,
+weighted scatter. Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
 
@@ -35,6 +39,7 @@ columns; `offsets_t` / `indices_t` / `block_offsets` are what
 
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
@@ -42,7 +47,9 @@ import torch
 from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                BlockMatrix, Matrix, Matmul, MatmulAccumulateEx,
                MatmulActivation, MatmulActivationGrad, MatmulEx, MatmulGated,
-               MatmulGatedGrad, RowIndices, Transpose, _act_code,
+               MatmulGatedGrad, MoeBins, MoeRowMap, PaddedGather,
+               PaddedScatter, PaddedScatterWeightGrad, RowIndices, Transpose,
+               _act_code,
                AllocateRowIndicesBuffer, AllocateTransposeBuffers,
                dsd_workspace_bytes, sdd_workspace_bytes)
 
@@ -168,7 +175,7 @@ class SparseMatrix:
         return self._meta.descriptor(self.data)
 
 
-# ---- dense operand plumbing --------------------------------------------------
+# ---- dense operand plumbing -------------------------------------------------
 
 def _dense_operand(x: torch.Tensor) -> Tuple[Matrix, bool]:
     """(stored matrix, transpose flag) for a 2-D tensor: a transposed view of
@@ -194,7 +201,7 @@ def _check_dtypes(*ts):
             raise TypeError("operands must share one dtype")
 
 
-# ---- raw products (no autograd) ----------------------------------------------
+# ---- raw products (no autograd) ---------------------------------------------
 
 def _bt_workspace(nbytes: int, device) -> Optional[torch.Tensor]:
     """Memory for the transposed copy of B when a product asks for it: a
@@ -294,7 +301,7 @@ def _sdd_gated(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix, act: int,
     return data, up
 
 
-# ---- accumulating products (no autograd) ---------------------------------------
+# ---- accumulating products (no autograd) ------------------------------------
 
 def _check_sink(out: torch.Tensor, rows: int, cols: int, dt, what: str):
     if not isinstance(out, torch.Tensor) or out.dim() != 2:
@@ -756,6 +763,284 @@ def expert_topology(padded_bins: torch.Tensor, blocks_per_expert: int,
                         data, offsets, indices)
 
 
-__all__ = ["SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
-           "expert_topology", "from_dense_mask", "glu_mlp", "mlp", "sdd",
-           "sdd_act", "sdd_gated", "topology_from_mask"]
+# ---- MoE token permutation --------------------------------------------------
+
+def moe_rows_bound(n: int, num_experts: int) -> int:
+    """The smallest multiple of 128 that is >= n + 127 * num_experts: the
+    worst case of padded_bins[-1] for n assignments (every expert's count one
+    past a multiple of 128), so a buffer of that many rows always fits."""
+    n, e = int(n), int(num_experts)
+    if n < 0 or e < 0:
+        raise ValueError("moe_rows_bound: negative n or num_experts")
+    return (n + 127 * e + 127) // BLOCK * BLOCK
+
+
+def _route_rows(rows, n: int, num_experts: int, padded_bins) -> int:
+    """Padded rows of a route: the exact size read from the device (one host
+    sync) when `rows` is None; else `rows` checked against the bound."""
+    if rows is None:
+        return int(padded_bins[-1].item()) if num_experts else 0
+    if isinstance(rows, bool) or not isinstance(rows, int):
+        raise TypeError("rows must be an int or None")
+    if rows % BLOCK or rows < moe_rows_bound(n, num_experts):
+        raise ValueError(
+            f"rows = {rows} must be a multiple of 128 and >= moe_rows_bound"
+            f"({n}, {num_experts}) = {moe_rows_bound(n, num_experts)}")
+    return rows
+
+
+@dataclass
+class MoeRoute:
+    """One routing decision in MegaBlocks' indices_and_padded_bins layout,
+    all int32 on the device: `bin_ids` / `indices` the stable ascending sort
+    of top_experts.flatten() (indices[i] the assignment t * top_k + k at
+    sorted position i), `bins` / `padded_bins` the inclusive cumsums of the
+    per-expert counts / of the counts rounded up to multiples of 128,
+    `tokens_per_expert` the counts, and `row_of` the padded row of every
+    assignment. `rows` is the row count of the padded matrix."""
+
+    indices: torch.Tensor
+    bin_ids: torch.Tensor
+    bins: torch.Tensor
+    padded_bins: torch.Tensor
+    tokens_per_expert: torch.Tensor
+    row_of: torch.Tensor
+    top_k: int
+    tokens: int
+    rows: int
+
+    @property
+    def num_experts(self) -> int:
+        return int(self.bins.numel())
+
+    @classmethod
+    def from_megablocks(cls, indices, bin_ids, bins, padded_bins, top_k,
+                        rows=None) -> "MoeRoute":
+        """A route from the tensors MegaBlocks' indices_and_padded_bins
+        returns (any integer dtype; converted to int32). `rows` as in
+        moe_route."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1:
+            raise ValueError(f"top_k must be an int >= 1, not {top_k!r}")
+        for name, t in (("indices", indices), ("bin_ids", bin_ids),
+                        ("bins", bins), ("padded_bins", padded_bins)):
+            if (not isinstance(t, torch.Tensor) or t.dim() != 1
+                    or t.dtype.is_floating_point or t.dtype == torch.bool):
+                raise TypeError(f"{name} must be a 1-D integer tensor")
+        n, e = int(indices.numel()), int(bins.numel())
+        if int(bin_ids.numel()) != n or int(padded_bins.numel()) != e:
+            raise ValueError("indices / bin_ids and bins / padded_bins must "
+                             "pair up in length")
+        if n % top_k:
+            raise ValueError(f"{n} assignments are not a multiple of top_k = "
+                             f"{top_k}")
+        if rows is not None:
+            _route_rows(rows, n, e, None)
+        indices, bin_ids, bins, padded_bins = (
+            t.to(torch.int32).contiguous()
+            for t in (indices, bin_ids, bins, padded_bins))
+        tpe = bins.clone()
+        tpe[1:] -= bins[:-1]
+        rows = _route_rows(rows, n, e, padded_bins)
+        row_of = torch.empty(n, dtype=torch.int32, device=indices.device)
+        MoeRowMap(indices, bin_ids, bins, padded_bins, rows, row_of)
+        return cls(indices, bin_ids, bins, padded_bins, tpe, row_of, top_k,
+                   n // top_k, rows)
+
+
+def _top_experts(top_experts, num_experts):
+    if (not isinstance(top_experts, torch.Tensor)
+            or top_experts.dtype.is_floating_point
+            or top_experts.dtype == torch.bool):
+        raise TypeError("top_experts must be an integer tensor")
+    if top_experts.dim() not in (1, 2):
+        raise ValueError("top_experts is [tokens, top_k] or [tokens]")
+    if (isinstance(num_experts, bool) or not isinstance(num_experts, int)
+            or num_experts < 1):
+        raise ValueError(f"num_experts must be an int >= 1, not "
+                         f"{num_experts!r}")
+    tokens = int(top_experts.shape[0])
+    top_k = int(top_experts.shape[1]) if top_experts.dim() == 2 else 1
+    if top_k < 1:
+        raise ValueError("top_experts has no expert per token")
+    return tokens, top_k
+
+
+def moe_route(top_experts: torch.Tensor, num_experts: int,
+              rows: Optional[int] = None) -> MoeRoute:
+    """The route of a router's `top_experts` ([tokens, top_k] expert ids, or
+    [tokens] for top_k = 1). The sort is torch.sort(stable=True); bins,
+    padded bins and the row map are built on the device. `rows` None: the
+    padded row count is read back once (one host sync; the exact size).
+    Explicit `rows`: a multiple of 128 that is >= moe_rows_bound(tokens *
+    top_k, num_experts), else ValueError; the route is then built without a
+    host sync, and the rows past padded_bins[-1] are zero rows, which
+    expert_topology assigns to the last expert."""
+    tokens, top_k = _top_experts(top_experts, num_experts)
+    n = tokens * top_k
+    if rows is not None:
+        _route_rows(rows, n, num_experts, None)
+    dev = top_experts.device
+    bin_ids, indices = torch.sort(top_experts.reshape(-1), stable=True)
+    bin_ids = bin_ids.to(torch.int32)
+    indices = indices.to(torch.int32)
+    bins, tpe, padded_bins = (torch.empty(num_experts, dtype=torch.int32,
+                                          device=dev) for _ in range(3))
+    MoeBins(bin_ids, num_experts, bins, tpe, padded_bins)
+    rows = _route_rows(rows, n, num_experts, padded_bins)
+    row_of = torch.empty(n, dtype=torch.int32, device=dev)
+    MoeRowMap(indices, bin_ids, bins, padded_bins, rows, row_of)
+    return MoeRoute(indices, bin_ids, bins, padded_bins, tpe, row_of, top_k,
+                    tokens, rows)
+
+
+def _check_route(route, what: str):
+    if not isinstance(route, MoeRoute):
+        raise TypeError(f"{what}: route must be a MoeRoute")
+
+
+def _check_rows(t, rows: int, what: str):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError(f"{what} must be a 2-D tensor")
+    _check_dtypes(t)
+    if int(t.shape[0]) != rows:
+        raise ValueError(f"{what} has {int(t.shape[0])} rows, the route "
+                         f"{rows}")
+
+
+def _check_weights(w, t, route: MoeRoute, what: str):
+    if not isinstance(w, torch.Tensor):
+        raise TypeError(f"{what}: weights must be a tensor")
+    if w.dtype not in (t.dtype, torch.float32):
+        raise TypeError(f"{what}: weights are {w.dtype}, expected {t.dtype} "
+                        "or torch.float32")
+    if (tuple(w.shape) != (route.tokens, route.top_k)
+            and tuple(w.shape) != (route.tokens * route.top_k,)):
+        raise ValueError(f"{what}: weights have shape {tuple(w.shape)}, "
+                         f"expected {(route.tokens, route.top_k)} or flat")
+
+
+def _gather(x: torch.Tensor, route: MoeRoute, weights) -> torch.Tensor:
+    out = torch.empty(route.rows, x.shape[1], dtype=x.dtype, device=x.device)
+    PaddedGather(x.contiguous(), route.indices, route.bins, route.padded_bins,
+                 out, route.top_k,
+                 None if weights is None else weights.contiguous())
+    return out
+
+
+def _scatter(y: torch.Tensor, route: MoeRoute, weights) -> torch.Tensor:
+    out = torch.empty(route.tokens, y.shape[1], dtype=y.dtype, device=y.device)
+    PaddedScatter(y.contiguous(), route.row_of, out, route.top_k,
+                  None if weights is None else weights.contiguous())
+    return out
+
+
+class _PaddedGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, route):
+        ctx.route = route
+        return _gather(x, route, None)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _scatter(dout, ctx.route, None), None  # sum over the copies
+
+
+class _PaddedScatter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, weights, route):
+        ctx.route = route
+        ctx.save_for_backward(y, weights)
+        return _scatter(y, route, weights)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, weights = ctx.saved_tensors
+        route = ctx.route
+        dy = dw = None
+        dout = dout.contiguous()
+        if ctx.needs_input_grad[0]:
+            dy = _gather(dout, route, weights)         # w[a] dout[a / top_k]
+        if weights is not None and ctx.needs_input_grad[1]:
+            dw = torch.empty_like(weights,
+                                  memory_format=torch.contiguous_format)
+            PaddedScatterWeightGrad(dout, y.contiguous(), route.row_of, dw,
+                                    route.top_k)
+        return dy, dw, None
+
+
+def padded_gather(x: torch.Tensor, route: MoeRoute) -> torch.Tensor:
+    """x [tokens, hidden] -> [route.rows, hidden] in padded expert order
+    (MegaBlocks' padded_gather): row_of[t * top_k + k] holds a copy of x[t],
+    every other row is +0. Backward is the unweighted padded_scatter."""
+    _check_route(route, "padded_gather")
+    _check_rows(x, route.tokens, "padded_gather: x")
+    return _PaddedGather.apply(x, route)
+
+
+def padded_scatter(y: torch.Tensor, route: MoeRoute,
+                   weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [route.rows, hidden] -> [tokens, hidden] (MegaBlocks'
+    padded_scatter): out[t] = sum_k weights[t, k] * y[row_of[t * top_k + k]],
+    summed in fp32 in ascending k and rounded once; a plain sum without
+    `weights` ([tokens, top_k] or flat, y's dtype or fp32). Differentiable
+    in y (a padded_gather of the incoming gradient with the weights) and in
+    weights (PaddedScatterWeightGrad)."""
+    _check_route(route, "padded_scatter")
+    _check_rows(y, route.rows, "padded_scatter: y")
+    if weights is not None:
+        _check_weights(weights, y, route, "padded_scatter")
+    return _PaddedScatter.apply(y, weights, route)
+
+
+def moe_mlp(x: torch.Tensor, top_experts: torch.Tensor,
+            expert_weights: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+            num_experts: int, activation=None,
+            v1: Optional[torch.Tensor] = None,
+            rows: Optional[int] = None) -> torch.Tensor:
+    """A dropless MoE layer behind its router: moe_route(top_experts) ->
+    padded_gather(x) -> expert_topology -> mlp (glu_mlp when `v1` is given)
+    -> padded_scatter with `expert_weights`. x [tokens, d_model]; w1 (and
+    v1) [d_model, num_experts * ffn], w2 [num_experts * ffn, d_model], ffn a
+    multiple of 128, expert e owning columns / rows [e * ffn, (e + 1) * ffn).
+    `activation` None: the MLP's default ("gelu" for mlp, "silu" for
+    glu_mlp). `rows` as in moe_route (None: one host sync for the exact
+    padded size; moe_rows_bound(tokens * top_k, num_experts) or more: none).
+    Differentiable in x, expert_weights, w1, v1 and w2."""
+    tokens, top_k = _top_experts(top_experts, num_experts)
+    _check_rows(x, tokens, "moe_mlp: x")
+    ws = (w1, w2) if v1 is None else (w1, v1, w2)
+    _check_dtypes(x, *ws)
+    d_model = int(x.shape[1])
+    if any(w.dim() != 2 for w in ws):
+        raise ValueError("moe_mlp: the expert weights are 2-D")
+    hidden = int(w1.shape[1])
+    if (int(w1.shape[0]) != d_model or tuple(w2.shape) != (hidden, d_model)
+            or (v1 is not None and v1.shape != w1.shape)):
+        raise ValueError("moe_mlp: w1 / v1 [d_model, E * ffn], w2 [E * ffn, "
+                         "d_model]")
+    if hidden == 0 or hidden % (num_experts * BLOCK):
+        raise ValueError(f"moe_mlp: {hidden} hidden columns are not "
+                         f"{num_experts} experts of a multiple of 128")
+    if (not isinstance(expert_weights, torch.Tensor)
+            or expert_weights.dtype not in (x.dtype, torch.float32)):
+        raise TypeError(f"moe_mlp: expert_weights must be {x.dtype} or "
+                        "torch.float32")
+    if int(expert_weights.numel()) != tokens * top_k:
+        raise ValueError("moe_mlp: one expert weight per (token, k)")
+    act = None if activation is None else _act_code(activation)
+    route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    if v1 is None:
+        y = mlp(xp, w1, w2, topo, "gelu" if act is None else act)
+    else:
+        y = glu_mlp(xp, w1, v1, w2, topo, "silu" if act is None else act)
+    return padded_scatter(y, route, expert_weights)
+
+
+__all__ = ["MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
+           "expert_topology", "from_dense_mask", "glu_mlp", "mlp",
+           "moe_mlp", "moe_route", "moe_rows_bound", "padded_gather",
+           "padded_scatter", "sdd", "sdd_act", "sdd_gated",
+           "topology_from_mask"]
