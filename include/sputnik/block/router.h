@@ -1,0 +1,108 @@
+// sputnik-amd: the MoE router in front of the token permutation (moe.h): the
+// fused softmax / top-k of the router logits with its gradient, and the
+// device sort that turns the router's choice into MegaBlocks' routing tensors
+// in one call. The counterparts of MegaBlocks' LearnedRouter arithmetic and
+// of its sort / histogram ops. No counterpart in the reference.
+//
+// Notation: L the logits' type (RouterType), E = num_experts, k = top_k,
+// n = tokens * top_k assignments, assignment a = t * top_k + k. W is the type
+// of weights, scores and their gradients: L (WeightType::kOperand) or float
+// (WeightType::kF32).
+//
+//   RouterTopK      logits [tokens, E] -> top_experts int32 [tokens, k],
+//                   weights W [tokens, k] and, when `scores` is not null,
+//                   scores W [tokens, E].
+//                   Selection is on the logits themselves: the k largest in
+//                   descending order, equal values to the lower expert index
+//                   (-0 equals +0), NaN below -inf (NaNs among themselves by
+//                   index). Every row yields k distinct ids in [0, E) whatever
+//                   the logits hold.
+//                   Arithmetic in fp32: p_e = exp(l_e - m) / sum_j exp(l_j - m)
+//                   with m the value of the first pick (the row maximum);
+//                   w_k = p_{sel k}, or with `normalize`
+//                   w_k = p_{sel k} / sum_k' p_{sel k'}; scores = p. Each
+//                   output is rounded once to W. A row holding NaN, +inf or
+//                   only -inf gets what that formula gives; only its ids are
+//                   pinned.
+//   RouterTopKGrad  dlogits L [tokens, E] from the logits, top_experts,
+//                   dweights W [tokens, k] and an optional dscores W
+//                   [tokens, E]. The softmax is recomputed (the forward pass
+//                   saves nothing): dp = dscores (or 0) plus, at each selected
+//                   column, dw_k, or with `normalize` (dw_k - sum_j dw_j w_j)
+//                   / S with S = sum_k p_{sel k}; dlogits_j = p_j (dp_j -
+//                   sum_i dp_i p_i). fp32, rounded once. A top_experts entry
+//                   outside [0, E) contributes nothing (neither to dp nor to
+//                   S); a duplicated entry adds twice.
+//   MoeSort         top_experts.flatten() int32 [n] -> indices, bin_ids [n],
+//                   bins, tokens_per_expert, padded_bins [E] and row_of [n] as
+//                   moe.h defines them: a stable counting sort by expert. For
+//                   ids in [0, E) every output is bit-identical to a stable
+//                   sort followed by MoeBins and MoeRowMap. An id outside
+//                   [0, E) is counted in no bin, gets row_of = -1 and takes
+//                   the sorted positions from bins[E-1] on, in assignment
+//                   order, with bin_ids = E (PaddedGather ignores positions
+//                   past bins[E-1]). `rows` as in MoeRowMap: a multiple of
+//                   128; a row at or past it maps to -1.
+//                   Three launches over chunks of kMoeSortChunk assignments:
+//                   per-chunk histograms (LDS integer adds), one workgroup
+//                   that scans [chunks, E + 1] counts into first positions and
+//                   writes bins / tokens_per_expert / padded_bins, and the
+//                   placement, which ranks an assignment among its chunk's
+//                   equal ids by position (no global atomics). The result
+//                   depends on the input alone.
+//                   workspace: MoeSortWorkspaceBytes(n, E) =
+//                   ceil(n / kMoeSortChunk) * (E + 1) * 4 bytes, the caller's,
+//                   4-byte aligned, no initialisation needed.
+//
+// Limits: 1 <= E <= 1024; RouterTopK / RouterTopKGrad 1 <= k <= min(E, 32).
+// Element offsets are long long (tokens * E may pass 2^31).
+//
+// Bounds: every id read from device memory (top_experts in RouterTopKGrad and
+// MoeSort) is range-checked before it forms an address.
+//
+// Stream-ordered; no call allocates or synchronises. They never abort:
+// hipErrorInvalidValue, with nothing launched, for a null required buffer, a
+// size outside the limits, an unknown type, rows % 128 != 0, n + 127 E past
+// INT_MAX, a workspace that is too small, or an output that is one of the
+// inputs or another output. Zero-sized work succeeds (MoeSort with n = 0
+// still writes the E zero counts).
+#ifndef SPUTNIK_BLOCK_ROUTER_H_
+#define SPUTNIK_BLOCK_ROUTER_H_
+
+#include <cstddef>
+
+#include "sputnik/block/arguments.h"
+#include "sputnik/block/moe.h"
+
+namespace sputnik {
+namespace block {
+
+enum class RouterType { kF16 = 0, kBF16 = 1, kF32 = 2 };
+
+// Assignments per histogram / placement workgroup of MoeSort.
+constexpr int kMoeSortChunk = 1024;
+
+hipError_t RouterTopK(const void *logits, int *top_experts, void *weights,
+                      void *scores, int tokens, int num_experts, int top_k,
+                      bool normalize, RouterType logits_type,
+                      WeightType weights_type, hipStream_t stream);
+
+hipError_t RouterTopKGrad(const void *logits, const int *top_experts,
+                          const void *dweights, const void *dscores,
+                          void *dlogits, int tokens, int num_experts,
+                          int top_k, bool normalize, RouterType logits_type,
+                          WeightType weights_type, hipStream_t stream);
+
+// 0 for sizes MoeSort rejects.
+size_t MoeSortWorkspaceBytes(int n, int num_experts);
+
+hipError_t MoeSort(const int *top_experts, int n, int num_experts, int rows,
+                   int *indices, int *bin_ids, int *bins,
+                   int *tokens_per_expert, int *padded_bins, int *row_of,
+                   void *workspace, size_t workspace_bytes,
+                   hipStream_t stream);
+
+}  // namespace block
+}  // namespace sputnik
+
+#endif  // SPUTNIK_BLOCK_ROUTER_H_

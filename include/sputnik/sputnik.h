@@ -11,6 +11,7 @@
 #include "sputnik/block/dsd/dsd.h"
 #include "sputnik/block/gated.h"
 #include "sputnik/block/moe.h"
+#include "sputnik/block/router.h"
 #include "sputnik/block/dds/dds.h"
 #include "sputnik/block/sdd/sdd.h"
 #include "sputnik/block/ssd/ssd.h"

@@ -414,6 +414,63 @@ int sputnik_padded_scatter_wgrad(const void *dout, const void *y,
                                  int hidden, int top_k, int rows, int dtype,
                                  int weights_dtype, void *stream);
 
+/* ---- MoE router and device sort (sputnik/block/router.h, INTEGRATION.md
+ * 3h): what stands in front of the permutation above. L is the logits' type
+ * (logits_dtype SPUTNIK_ROUTER_F16 / _BF16 / _F32), W the type of weights,
+ * scores and their gradients: L (SPUTNIK_WEIGHTS_OPERAND) or float
+ * (SPUTNIK_WEIGHTS_F32).
+ *   sputnik_router_topk       logits L [tokens, E] -> top_experts int32
+ *                             [tokens, top_k], weights W [tokens, top_k] and,
+ *                             with scores != NULL, scores W [tokens, E]. The
+ *                             picks are the top_k largest logits in
+ *                             descending order, equal values to the lower
+ *                             index, NaN below -inf: always top_k distinct
+ *                             ids in [0, E). fp32 arithmetic: p = softmax of
+ *                             the row (max subtracted), weights = p at the
+ *                             picks, divided by their sum with normalize;
+ *                             each output rounded once.
+ *   sputnik_router_topk_grad  dlogits L [tokens, E] from logits, top_experts,
+ *                             dweights W [tokens, top_k] and an optional
+ *                             dscores W [tokens, E] (NULL: zero); the softmax
+ *                             is recomputed. An id outside [0, E)
+ *                             contributes nothing, a duplicated id twice.
+ *   sputnik_moe_sort          top_experts.flatten() int32 [n] -> indices,
+ *                             bin_ids [n], bins, tokens_per_expert,
+ *                             padded_bins [E], row_of [n]: a stable counting
+ *                             sort in three launches, for ids in [0, E)
+ *                             bit-identical to a stable sort + moe_bins +
+ *                             moe_row_map. An id out of range: no bin, row_of
+ *                             -1, sorted behind bins[E-1] with bin_ids = E.
+ *                             workspace: sputnik_moe_sort_workspace_bytes(n,
+ *                             E) = ceil(n / 1024) * (E + 1) * 4 bytes, no
+ *                             initialisation needed.
+ * 1 <= E <= 1024, 1 <= top_k <= min(E, 32), rows % 128 == 0. Every id read
+ * from device memory is range-checked before it forms an address.
+ * Stream-ordered; no call allocates, synchronises or aborts: a null required
+ * buffer, a size outside the limits, an unknown type, n + 127 E past INT_MAX,
+ * a workspace too small or an output equal to an input or another output:
+ * hipErrorInvalidValue (1), nothing launched. Zero-sized work succeeds. */
+enum {
+  SPUTNIK_ROUTER_F16 = 0,
+  SPUTNIK_ROUTER_BF16 = 1,
+  SPUTNIK_ROUTER_F32 = 2,
+};
+int sputnik_router_topk(const void *logits, int32_t *top_experts,
+                        void *weights, void *scores, int tokens,
+                        int num_experts, int top_k, int normalize,
+                        int logits_dtype, int weights_dtype, void *stream);
+int sputnik_router_topk_grad(const void *logits, const int32_t *top_experts,
+                             const void *dweights, const void *dscores,
+                             void *dlogits, int tokens, int num_experts,
+                             int top_k, int normalize, int logits_dtype,
+                             int weights_dtype, void *stream);
+size_t sputnik_moe_sort_workspace_bytes(int n, int num_experts);
+int sputnik_moe_sort(const int32_t *top_experts, int n, int num_experts,
+                     int rows, int32_t *indices, int32_t *bin_ids,
+                     int32_t *bins, int32_t *tokens_per_expert,
+                     int32_t *padded_bins, int32_t *row_of, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
 /* ---- Host-only queries (no GPU work; safe without a device) */
 /* 1 when the reference would accept the problem (same rules as
  * can_launch_* + ValidMatmul), 0 otherwise. op: 0=DSD 1=DDS 2=SDD. */

@@ -156,6 +156,20 @@ _SIGNATURES = {
     "sputnik_padded_scatter_wgrad": [_P, _P, _P, _P, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, _P],
+    # MoE router and device sort: (logits, top_experts, weights, scores,
+    # tokens, experts, top_k, normalize, logits_dtype, weights_dtype, stream);
+    # (logits, top_experts, dweights, dscores, dlogits, tokens, ..., stream);
+    # (top_experts, n, experts, rows, indices, bin_ids, bins,
+    # tokens_per_expert, padded_bins, row_of, workspace, bytes, stream)
+    "sputnik_router_topk": [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
+                            ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                            ctypes.c_int, _P],
+    "sputnik_router_topk_grad": [_P, _P, _P, _P, _P, ctypes.c_int,
+                                 ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_moe_sort_workspace_bytes": [ctypes.c_int, ctypes.c_int],
+    "sputnik_moe_sort": [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P,
+                         _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "sputnik_can_implement": [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_abi_block_matrix_size": [],
     "sputnik_abi_block_matrix_offset": [ctypes.c_int],
@@ -199,6 +213,7 @@ _RESTYPES = {
     "sputnik_debug_pair_fault": None,
     "sputnik_sdd_workspace_bytes": ctypes.c_size_t,
     "sputnik_dsd_workspace_bytes": ctypes.c_size_t,
+    "sputnik_moe_sort_workspace_bytes": ctypes.c_size_t,
     "sputnik_retained_bytes": ctypes.c_size_t,
     "sputnik_release_workspaces": ctypes.c_size_t,
     "sputnik_incall_events": ctypes.c_ulonglong,
@@ -940,6 +955,170 @@ def PaddedScatterWeightGrad(dout, y, row_of, dw, top_k, stream=None):  # noqa: N
         rows, dtype, wcode, _stream(stream)), "PaddedScatterWeightGrad")
 
 
+SPUTNIK_ROUTER_F16 = 0
+SPUTNIK_ROUTER_BF16 = 1
+SPUTNIK_ROUTER_F32 = 2
+ROUTER_MAX_EXPERTS = 1024
+ROUTER_MAX_TOP_K = 32
+MOE_SORT_CHUNK = 1024
+
+
+def _router_logits(t, what: str):
+    """(SPUTNIK_ROUTER_* code, tokens, experts) of a [tokens, E] matrix of
+    fp16, bf16 or fp32, contiguous, 1 <= E <= 1024. Raises before any library
+    call."""
+    import torch
+
+    code = {torch.float16: SPUTNIK_ROUTER_F16,
+            torch.bfloat16: SPUTNIK_ROUTER_BF16,
+            torch.float32: SPUTNIK_ROUTER_F32}.get(getattr(t, "dtype", None))
+    if code is None:
+        raise TypeError(f"{what} is {getattr(t, 'dtype', None)}, expected "
+                        "torch.float16, torch.bfloat16 or torch.float32")
+    if t.dim() != 2:
+        raise ValueError(f"{what} has shape {tuple(t.shape)}, expected "
+                         "[tokens, num_experts]")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    tokens, e = int(t.shape[0]), int(t.shape[1])
+    if not 1 <= e <= ROUTER_MAX_EXPERTS:
+        raise ValueError(f"{what}: {e} experts, outside [1, "
+                         f"{ROUTER_MAX_EXPERTS}]")
+    return code, tokens, e
+
+
+def _router_picks(top_experts, tokens: int, e: int, what: str) -> int:
+    """top_k of an int32 [tokens, top_k] tensor, 1 <= top_k <= min(E, 32)."""
+    _moe_meta(top_experts, None, "top_experts")
+    if top_experts.dim() != 2 or int(top_experts.shape[0]) != tokens:
+        raise ValueError(f"{what}: top_experts has shape "
+                         f"{tuple(top_experts.shape)}, expected [{tokens}, "
+                         "top_k]")
+    k = int(top_experts.shape[1])
+    if not 1 <= k <= min(e, ROUTER_MAX_TOP_K):
+        raise ValueError(f"{what}: top_k = {k}, outside [1, min({e}, "
+                         f"{ROUTER_MAX_TOP_K})]")
+    return k
+
+
+def _router_values(t, logits, shape, code, what: str) -> int:
+    """SPUTNIK_WEIGHTS_* of a weights / scores tensor of `shape`: the logits'
+    dtype or fp32, the same choice (`code`, None: free) as its companions."""
+    import torch
+
+    td = getattr(t, "dtype", None)
+    if td == logits.dtype and code in (None, SPUTNIK_WEIGHTS_OPERAND):
+        got = SPUTNIK_WEIGHTS_OPERAND
+    elif td == torch.float32 and code in (None, SPUTNIK_WEIGHTS_F32):
+        got = SPUTNIK_WEIGHTS_F32
+    else:
+        want = (f"{logits.dtype} or torch.float32" if code is None else
+                "the dtype of the other weights / scores tensor")
+        raise TypeError(f"{what} is {td}, expected {want}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} has shape {tuple(t.shape)}, expected "
+                         f"{tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return got
+
+
+def RouterTopK(logits, top_experts, weights, normalize=False, scores=None,  # noqa: N802
+               stream=None):
+    """The router's choice from logits [tokens, E] (fp16, bf16 or fp32):
+    top_experts int32 [tokens, top_k] (the top_k largest logits, descending,
+    ties to the lower index, NaN below -inf), weights [tokens, top_k] (the
+    softmax probabilities of the picks, divided by their sum with
+    `normalize`) and, when given, scores [tokens, E] (the softmax). weights
+    and scores share one dtype, the logits' or fp32
+    (sputnik_router_topk; sputnik/block/router.h). Type and shape errors are
+    raised before the library is called."""
+    code, tokens, e = _router_logits(logits, "logits")
+    k = _router_picks(top_experts, tokens, e, "RouterTopK")
+    wcode = _router_values(weights, logits, (tokens, k), None, "weights")
+    if scores is not None:
+        _router_values(scores, logits, (tokens, e), wcode, "scores")
+    _check(lib().sputnik_router_topk(
+        _ptr(logits), _ptr(top_experts), _ptr(weights), _ptr(scores), tokens,
+        e, k, int(bool(normalize)), code, wcode, _stream(stream)),
+        "RouterTopK")
+
+
+def RouterTopKGrad(logits, top_experts, dweights, dlogits, normalize=False,  # noqa: N802
+                   dscores=None, stream=None):
+    """dlogits [tokens, E] (the logits' dtype): the gradient of RouterTopK's
+    weights (and scores, with `dscores`) with respect to the logits, the
+    softmax recomputed from `logits`. A top_experts entry outside [0, E)
+    contributes nothing, a duplicated one twice (sputnik_router_topk_grad).
+    Type and shape errors are raised before the library is called."""
+    code, tokens, e = _router_logits(logits, "logits")
+    k = _router_picks(top_experts, tokens, e, "RouterTopKGrad")
+    wcode = _router_values(dweights, logits, (tokens, k), None, "dweights")
+    if dscores is not None:
+        _router_values(dscores, logits, (tokens, e), wcode, "dscores")
+    _router_values(dlogits, logits, (tokens, e), SPUTNIK_WEIGHTS_OPERAND,
+                   "dlogits")
+    _check(lib().sputnik_router_topk_grad(
+        _ptr(logits), _ptr(top_experts), _ptr(dweights), _ptr(dscores),
+        _ptr(dlogits), tokens, e, k, int(bool(normalize)), code, wcode,
+        _stream(stream)), "RouterTopKGrad")
+
+
+def _moe_sort_sizes(n, num_experts, what: str):
+    n, e = int(n), int(num_experts)
+    if n < 0 or not 1 <= e <= ROUTER_MAX_EXPERTS:
+        raise ValueError(f"{what}: n = {n} must be >= 0 and num_experts = "
+                         f"{e} in [1, {ROUTER_MAX_EXPERTS}]")
+    if n + 127 * e > 2 ** 31 - 1:
+        raise ValueError(f"{what}: n + 127 * num_experts passes INT_MAX")
+    return n, e
+
+
+def moe_sort_workspace_bytes(n: int, num_experts: int) -> int:
+    """Bytes of workspace MoeSort needs for n assignments over num_experts:
+    ceil(n / 1024) * (num_experts + 1) * 4
+    (sputnik_moe_sort_workspace_bytes)."""
+    n, e = _moe_sort_sizes(n, num_experts, "moe_sort_workspace_bytes")
+    return int(lib().sputnik_moe_sort_workspace_bytes(n, e))
+
+
+def MoeSort(top_experts, num_experts, rows, indices, bin_ids, bins,  # noqa: N802
+            tokens_per_expert, padded_bins, row_of, workspace, stream=None):
+    """The routing tensors of moe.h from top_experts (int32, n elements of
+    any shape) in one call: a stable counting sort by expert into indices /
+    bin_ids (int32 [n]), the counts as bins / tokens_per_expert / padded_bins
+    (int32 [num_experts]) and row_of (int32 [n]) for a padded matrix of
+    `rows` rows. `workspace`: a contiguous tensor of at least
+    moe_sort_workspace_bytes(n, num_experts) bytes (None when that is 0); it
+    needs no initialisation (sputnik_moe_sort). Type and shape errors are
+    raised before the library is called."""
+    _moe_meta(top_experts, None, "top_experts")
+    n, e = _moe_sort_sizes(top_experts.numel(), num_experts, "MoeSort")
+    for name, t in (("indices", indices), ("bin_ids", bin_ids),
+                    ("row_of", row_of)):
+        _moe_meta(t, n, name)
+    for name, t in (("bins", bins), ("tokens_per_expert", tokens_per_expert),
+                    ("padded_bins", padded_bins)):
+        _moe_meta(t, e, name)
+    if isinstance(rows, bool) or not isinstance(rows, int) or rows < 0 \
+            or rows % 128:
+        raise ValueError(f"MoeSort: {rows!r} padded rows, not a multiple of "
+                         "128")
+    need = (n + MOE_SORT_CHUNK - 1) // MOE_SORT_CHUNK * (e + 1) * 4
+    have = 0
+    if workspace is not None:
+        if not workspace.is_contiguous():
+            raise ValueError("workspace must be contiguous")
+        have = int(workspace.numel()) * int(workspace.element_size())
+    if have < need:
+        raise ValueError(f"MoeSort: a workspace of {have} bytes, "
+                         f"{need} needed")
+    _check(lib().sputnik_moe_sort(
+        _ptr(top_experts), n, e, rows, _ptr(indices), _ptr(bin_ids),
+        _ptr(bins), _ptr(tokens_per_expert), _ptr(padded_bins), _ptr(row_of),
+        _ptr(workspace), have, _stream(stream)), "MoeSort")
+
+
 def Bitmask(m: BlockMatrix, stream=None):  # noqa: N802
     """reference sputnik/block/bitmask/bitmask.h:10 (on the device): the
     BitMatrix of m's topology, over the transposed order when m.offsets_t is
@@ -1122,6 +1301,9 @@ __all__ = [
     "MoeBins", "MoeRowMap", "PaddedGather", "PaddedScatter",
     "PaddedScatterWeightGrad", "SPUTNIK_WEIGHTS_OPERAND",
     "SPUTNIK_WEIGHTS_F32",
+    "RouterTopK", "RouterTopKGrad", "MoeSort", "moe_sort_workspace_bytes",
+    "SPUTNIK_ROUTER_F16", "SPUTNIK_ROUTER_BF16", "SPUTNIK_ROUTER_F32",
+    "MOE_SORT_CHUNK",
     "SputnikError", "Transpose", "can_implement", "lib", "version",
     "allgather_concat", "gather_row_panels", "gather_col_panels",
     "gather_block_runs",

@@ -11,6 +11,7 @@
 #include "sputnik/sputnik.h"
 #include "metadata.h"
 #include "moe_permute.h"
+#include "moe_router.h"
 #include "sputnik_amd.h"
 
 using sputnik::block::BlockMatrix;
@@ -537,6 +538,44 @@ int sputnik_padded_scatter_wgrad(const void *dout, const void *y,
   return sputnik_amd::RunPaddedScatterWgrad(
       dout, y, row_of, dw, tokens, hidden, top_k, rows, dtype, weights_dtype,
       static_cast<hipStream_t>(stream));
+}
+
+// MoE router and device sort (sputnik/block/router.h): moe_router.hip
+// validates.
+int sputnik_router_topk(const void *logits, int32_t *top_experts,
+                        void *weights, void *scores, int tokens,
+                        int num_experts, int top_k, int normalize,
+                        int logits_dtype, int weights_dtype, void *stream) {
+  return sputnik_amd::RunRouterTopK(logits, top_experts, weights, scores,
+                                    tokens, num_experts, top_k, normalize != 0,
+                                    logits_dtype, weights_dtype,
+                                    static_cast<hipStream_t>(stream));
+}
+
+int sputnik_router_topk_grad(const void *logits, const int32_t *top_experts,
+                             const void *dweights, const void *dscores,
+                             void *dlogits, int tokens, int num_experts,
+                             int top_k, int normalize, int logits_dtype,
+                             int weights_dtype, void *stream) {
+  return sputnik_amd::RunRouterTopKGrad(
+      logits, top_experts, dweights, dscores, dlogits, tokens, num_experts,
+      top_k, normalize != 0, logits_dtype, weights_dtype,
+      static_cast<hipStream_t>(stream));
+}
+
+size_t sputnik_moe_sort_workspace_bytes(int n, int num_experts) {
+  return sputnik_amd::MoeSortWorkspace(n, num_experts);
+}
+
+int sputnik_moe_sort(const int32_t *top_experts, int n, int num_experts,
+                     int rows, int32_t *indices, int32_t *bin_ids,
+                     int32_t *bins, int32_t *tokens_per_expert,
+                     int32_t *padded_bins, int32_t *row_of, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+  return sputnik_amd::RunMoeSort(top_experts, n, num_experts, rows, indices,
+                                 bin_ids, bins, tokens_per_expert, padded_bins,
+                                 row_of, workspace, workspace_bytes,
+                                 static_cast<hipStream_t>(stream));
 }
 
 int sputnik_can_implement(int op, const void *a, int transpose_a,

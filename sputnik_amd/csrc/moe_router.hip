@@ -1,0 +1,564 @@
+// sputnik-amd: the MoE router (sputnik/block/router.h): fused softmax / top-k
+// of the router logits, its gradient, and the stable counting sort that turns
+// top_experts into MegaBlocks' routing tensors.
+//
+// Router kernels: one wave per token, 4 waves per workgroup, a token's E
+// logits spread over the lanes as e = lane + 64 j with j < kPer = ceil(E / 64)
+// rounded up to a power of two (a template parameter, so the logits stay in
+// registers: every loop over j is unrolled, nothing is indexed dynamically).
+//
+//   top-k   k rounds of a wave arg-max over 64-bit keys: the order-preserving
+//           image of the fp32 value in the high word (NaN below -inf, -0 as
+//           +0), ~e in the low word, so that the larger key is the larger
+//           value and, among equal values, the lower index. A picked entry's
+//           key becomes 0, below every live key. The key carries the value,
+//           so the row maximum (pick 0) and every picked logit come out of
+//           the reduction itself. Lane r keeps pick r; the softmax sum is one
+//           more wave reduction.
+//   grad    recomputes p from the logits; lane r < k reads pick r's id and
+//           gradient (the id range-checked before it addresses the logits),
+//           the per-pick terms are reduced across the wave and added to the
+//           owning lane's dp by k broadcast rounds, so a duplicated id adds
+//           twice and nothing is written through an id.
+//
+// Sort: chunks of kMoeSortChunk = 1024 assignments, one per thread.
+//   histogram  per chunk: LDS integer adds into E + 1 counters (column E
+//              counts the ids outside [0, E)), stored to the workspace
+//              [chunks, E + 1]; every entry is written, so the workspace
+//              needs no initialisation.
+//   scan       one workgroup: column totals -> bins, tokens_per_expert,
+//              padded_bins; each workspace entry becomes the first sorted
+//              position of its (chunk, id): the exclusive scan over ids of
+//              the totals plus the counts of the earlier chunks.
+//   placement  per chunk: inside a wave an assignment's rank among equal ids
+//              is the popcount of the lower lanes of a ballot-built match
+//              mask; across the chunk's 16 waves a running counter per id in
+//              LDS is advanced wave by wave in wave order. Position = first
+//              position + earlier waves + rank: a function of the input
+//              alone, no global atomics.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdint>
+#include <initializer_list>
+#include <type_traits>
+
+#include "moe_router.h"
+#include "sputnik/block/router.h"
+
+namespace sputnik_amd {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxExperts = 1024;
+constexpr int kMaxTopK = 32;
+constexpr int kChunk = sputnik::block::kMoeSortChunk;
+constexpr int kSortThreads = 1024;
+static_assert(kChunk == kSortThreads, "one assignment per thread");
+
+__device__ __forceinline__ int wave_index() {
+  return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+
+// Order-preserving image of an fp32 value: a < b  <=>  image(a) < image(b),
+// -0 == +0, every NaN the image 1 (below -inf's 0x007fffff, above the 0 of a
+// dead key).
+__device__ __forceinline__ uint32_t order_image(float v) {
+  uint32_t b = __float_as_uint(v);
+  if (v != v) return 1u;
+  if (b == 0x80000000u) b = 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ float image_value(uint32_t u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+__device__ __forceinline__ float wave_sum(float s) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  return s;
+}
+
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(k, d, 64);
+    k = o > k ? o : k;
+  }
+  return k;
+}
+
+template <typename T, typename W, int kPer>
+__global__ void __launch_bounds__(kThreads)
+    router_topk_kernel(const T *__restrict__ logits,
+                       int *__restrict__ top_experts, W *__restrict__ weights,
+                       W *__restrict__ scores, int tokens, int num_experts,
+                       int top_k, int normalize) {
+  const int lane = threadIdx.x & 63;
+  const long long t = (long long)blockIdx.x * kWaves + wave_index();
+  if (t >= tokens) return;
+  const T *row = logits + t * num_experts;
+  float v[kPer];
+  unsigned long long key[kPer];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    const bool live = e < num_experts;
+    v[j] = live ? (float)row[e] : 0.0f;
+    key[j] = live ? ((unsigned long long)order_image(v[j]) << 32) |
+                        (uint32_t)~e
+                  : 0ull;
+  }
+  float m = 0.0f, my_val = 0.0f;
+  int my_id = 0;
+  for (int r = 0; r < top_k; ++r) {
+    unsigned long long best = key[0];
+#pragma unroll
+    for (int j = 1; j < kPer; ++j) best = key[j] > best ? key[j] : best;
+    best = wave_max(best);
+    // (top_k <= num_experts: a live key remains, so idx is in [0, E))
+    const int idx = (int)~(uint32_t)best;
+    const float val = image_value((uint32_t)(best >> 32));
+    if (r == 0) m = val;
+    if (lane == r) {
+      my_id = idx;
+      my_val = val;
+    }
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (idx == lane + 64 * j) key[j] = 0ull;
+  }
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (lane + 64 * j < num_experts) s += expf(v[j] - m);
+  s = wave_sum(s);
+  float p = lane < top_k ? expf(my_val - m) / s : 0.0f;
+  if (normalize) p = p / wave_sum(p);
+  if (lane < top_k) {
+    top_experts[t * top_k + lane] = my_id;
+    weights[t * top_k + lane] = (W)p;
+  }
+  if (scores != nullptr) {
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      const int e = lane + 64 * j;
+      if (e < num_experts)
+        scores[t * num_experts + e] = (W)(expf(v[j] - m) / s);
+    }
+  }
+}
+
+template <typename T, typename W, int kPer>
+__global__ void __launch_bounds__(kThreads)
+    router_topk_grad_kernel(const T *__restrict__ logits,
+                            const int *__restrict__ top_experts,
+                            const W *__restrict__ dweights,
+                            const W *__restrict__ dscores,
+                            T *__restrict__ dlogits, int tokens,
+                            int num_experts, int top_k, int normalize) {
+  const int lane = threadIdx.x & 63;
+  const long long t = (long long)blockIdx.x * kWaves + wave_index();
+  if (t >= tokens) return;
+  const T *row = logits + t * num_experts;
+  float v[kPer], dp[kPer];
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    const bool live = e < num_experts;
+    v[j] = live ? (float)row[e] : 0.0f;
+    dp[j] = live && dscores != nullptr
+                ? (float)dscores[t * num_experts + e] : 0.0f;
+    if (live) m = fmaxf(m, v[j]);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (lane + 64 * j < num_experts) s += expf(v[j] - m);
+  s = wave_sum(s);
+
+  // Lane r < top_k holds pick r: its id (-1 when out of range), its incoming
+  // gradient and, for normalize, its probability.
+  int id = -1;
+  float g = 0.0f;
+  if (lane < top_k) {
+    const int raw = top_experts[t * top_k + lane];
+    if (raw >= 0 && raw < num_experts) {
+      id = raw;
+      g = (float)dweights[t * top_k + lane];
+    }
+  }
+  if (normalize) {
+    const float psel = id >= 0 ? expf((float)row[id] - m) / s : 0.0f;
+    const float total = wave_sum(psel);             // S
+    const float c = wave_sum(g * psel) / total;     // sum_j dw_j w_j
+    g = id >= 0 ? (g - c) / total : 0.0f;
+  }
+  for (int r = 0; r < top_k; ++r) {
+    const int rid = __shfl(id, r, 64);
+    const float rg = __shfl(g, r, 64);
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (rid == lane + 64 * j) dp[j] += rg;
+  }
+  float p[kPer];
+  float dot = 0.0f;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const bool live = lane + 64 * j < num_experts;
+    p[j] = live ? expf(v[j] - m) / s : 0.0f;
+    if (live) dot += dp[j] * p[j];
+  }
+  dot = wave_sum(dot);
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    if (e < num_experts)
+      dlogits[t * num_experts + e] = (T)(p[j] * (dp[j] - dot));
+  }
+}
+
+// ---- sort -------------------------------------------------------------------
+
+// The counter column of an id: itself, or num_experts when out of range.
+__device__ __forceinline__ int sort_column(int id, int num_experts) {
+  return id >= 0 && id < num_experts ? id : num_experts;
+}
+
+__global__ void __launch_bounds__(kSortThreads)
+    moe_sort_histogram_kernel(const int *__restrict__ top_experts, int n,
+                              int num_experts, int *__restrict__ counts) {
+  __shared__ int hist[kMaxExperts + 1];
+  const int tid = threadIdx.x;
+  const int cols = num_experts + 1;
+  for (int e = tid; e < cols; e += kSortThreads) hist[e] = 0;
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * kChunk + tid;
+  if (i < n) atomicAdd(&hist[sort_column(top_experts[i], num_experts)], 1);
+  __syncthreads();
+  int *out = counts + (long long)blockIdx.x * cols;
+  for (int e = tid; e < cols; e += kSortThreads) out[e] = hist[e];
+}
+
+// One workgroup. With at most 1024 columns the threads split into `parts`
+// groups of `cols` threads, each group walking its share of the chunks.
+__global__ void __launch_bounds__(kSortThreads)
+    moe_sort_scan_kernel(int *__restrict__ counts, int chunks, int num_experts,
+                         int *__restrict__ bins,
+                         int *__restrict__ tokens_per_expert,
+                         int *__restrict__ padded_bins) {
+  __shared__ int part_sum[kMaxExperts + 1];  // [parts][cols]
+  __shared__ int first[kMaxExperts + 1];     // totals, then first positions
+  __shared__ int run[kSortThreads], padded_run[kSortThreads];
+  const int tid = threadIdx.x;
+  const int cols = num_experts + 1;
+  const int parts = cols <= kSortThreads ? kSortThreads / cols : 1;
+  const int per_part = (chunks + parts - 1) / parts;
+  for (int slot = tid; slot < parts * cols; slot += kSortThreads) {
+    const int e = slot % cols, part = slot / cols;
+    const int c0 = min(part * per_part, chunks);
+    const int c1 = min(c0 + per_part, chunks);
+    int sum = 0;
+    for (int c = c0; c < c1; ++c) sum += counts[(long long)c * cols + e];
+    part_sum[slot] = sum;
+  }
+  __syncthreads();
+  for (int e = tid; e < cols; e += kSortThreads) {
+    int sum = 0;
+    for (int part = 0; part < parts; ++part) sum += part_sum[part * cols + e];
+    first[e] = sum;
+  }
+  __syncthreads();
+  // Inclusive scans over the experts of the counts and of the counts rounded
+  // up to 128 (num_experts <= 1024 = one per thread).
+  const int count = tid < num_experts ? first[tid] : 0;
+  run[tid] = count;
+  padded_run[tid] = (count + 127) & ~127;
+  __syncthreads();
+  for (int stride = 1; stride < kSortThreads; stride <<= 1) {
+    const int a = tid >= stride ? run[tid - stride] : 0;
+    const int b = tid >= stride ? padded_run[tid - stride] : 0;
+    __syncthreads();
+    run[tid] += a;
+    padded_run[tid] += b;
+    __syncthreads();
+  }
+  if (tid < num_experts) {
+    bins[tid] = run[tid];
+    tokens_per_expert[tid] = count;
+    padded_bins[tid] = padded_run[tid];
+    first[tid] = run[tid] - count;
+  }
+  // (the ids out of range follow the last bin)
+  if (tid == 0) first[num_experts] = run[num_experts - 1];
+  __syncthreads();
+  for (int slot = tid; slot < parts * cols; slot += kSortThreads) {
+    const int e = slot % cols, part = slot / cols;
+    const int c0 = min(part * per_part, chunks);
+    const int c1 = min(c0 + per_part, chunks);
+    int pos = first[e];
+    for (int q = 0; q < part; ++q) pos += part_sum[q * cols + e];
+    for (int c = c0; c < c1; ++c) {
+      const long long at = (long long)c * cols + e;
+      const int here = counts[at];
+      counts[at] = pos;
+      pos += here;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kSortThreads)
+    moe_sort_place_kernel(const int *__restrict__ top_experts,
+                          const int *__restrict__ first_pos,
+                          const int *__restrict__ bins,
+                          const int *__restrict__ padded_bins, int n,
+                          int num_experts, int rows, int *__restrict__ indices,
+                          int *__restrict__ bin_ids, int *__restrict__ row_of) {
+  __shared__ int next[kMaxExperts + 1];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = wave_index();
+  const int cols = num_experts + 1;
+  const int *mine = first_pos + (long long)blockIdx.x * cols;
+  for (int e = tid; e < cols; e += kSortThreads) next[e] = mine[e];
+  const long long i = (long long)blockIdx.x * kChunk + tid;
+  const bool active = i < n;
+  const int col = active ? sort_column(top_experts[i], num_experts) : 0;
+  // Rank among the wave's equal columns, by lane.
+  int rank = 0, same = 0;
+  bool pending = active;
+  while (true) {
+    const unsigned long long todo = __ballot(pending);
+    if (todo == 0ull) break;
+    const int leader = __ffsll((long long)todo) - 1;
+    const int lead_col = __shfl(col, leader, 64);
+    const bool match = pending && col == lead_col;
+    const unsigned long long mask = __ballot(match);
+    if (match) {
+      rank = __popcll(mask & ((1ull << lane) - 1ull));
+      same = __popcll(mask);
+      pending = false;
+    }
+  }
+  __syncthreads();
+  // The waves take their turns in wave order; within a wave the reads of
+  // next[] precede the leaders' updates (program order, one wave).
+  int base = 0;
+  for (int w = 0; w < kSortThreads / 64; ++w) {
+    if (w == wave && active) {
+      base = next[col];
+      __builtin_amdgcn_wave_barrier();
+      if (rank == 0) next[col] = base + same;
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  const int pos = base + rank;
+  if (pos < 0 || pos >= n) return;  // (cannot happen for a consistent input)
+  int row = -1;
+  if (col < num_experts) {
+    const int bin0 = col ? bins[col - 1] : 0;
+    const int pad0 = col ? padded_bins[col - 1] : 0;
+    const long long r = (long long)pad0 + (pos - bin0);
+    if (pos >= bin0 && r >= 0 && r < rows) row = (int)r;
+  }
+  indices[pos] = (int)i;
+  bin_ids[pos] = col;
+  row_of[i] = row;
+}
+
+// ---- launchers ----------------------------------------------------------------
+
+bool RouterSizesOk(int tokens, int num_experts, int top_k, int logits_dtype,
+                   int weights_dtype) {
+  return tokens >= 0 && num_experts >= 1 && num_experts <= kMaxExperts &&
+         top_k >= 1 && top_k <= kMaxTopK && top_k <= num_experts &&
+         logits_dtype >= 0 && logits_dtype <= 2 &&
+         (weights_dtype == 0 || weights_dtype == 1);
+}
+
+bool Distinct(std::initializer_list<const void *> ptrs) {
+  for (auto a = ptrs.begin(); a != ptrs.end(); ++a)
+    for (auto b = a + 1; b != ptrs.end(); ++b)
+      if (*a != nullptr && *a == *b) return false;
+  return true;
+}
+
+// f(T, W, kPer) for the call's types and expert count.
+template <typename F>
+hipError_t WithRouterTypes(int logits_dtype, int weights_dtype,
+                           int num_experts, F f) {
+  auto with_per = [&](auto t, auto w) {
+    using T = decltype(t);
+    using W = decltype(w);
+    const int per = (num_experts + 63) / 64;
+    if (per <= 1) return f(T{}, W{}, std::integral_constant<int, 1>{});
+    if (per <= 2) return f(T{}, W{}, std::integral_constant<int, 2>{});
+    if (per <= 4) return f(T{}, W{}, std::integral_constant<int, 4>{});
+    if (per <= 8) return f(T{}, W{}, std::integral_constant<int, 8>{});
+    return f(T{}, W{}, std::integral_constant<int, 16>{});
+  };
+  const bool f32 = weights_dtype == 1;
+  if (logits_dtype == 2) return with_per(float{}, float{});
+  if (logits_dtype == 1)
+    return f32 ? with_per(__bf16{}, float{}) : with_per(__bf16{}, __bf16{});
+  return f32 ? with_per(_Float16{}, float{})
+             : with_per(_Float16{}, _Float16{});
+}
+
+unsigned TokenGrid(int tokens) {
+  return (unsigned)(((long long)tokens + kWaves - 1) / kWaves);
+}
+
+}  // namespace
+
+hipError_t RunRouterTopK(const void *logits, int *top_experts, void *weights,
+                         void *scores, int tokens, int num_experts, int top_k,
+                         bool normalize, int logits_dtype, int weights_dtype,
+                         hipStream_t stream) {
+  if (!RouterSizesOk(tokens, num_experts, top_k, logits_dtype, weights_dtype))
+    return hipErrorInvalidValue;
+  if (tokens == 0) return hipSuccess;
+  if (logits == nullptr || top_experts == nullptr || weights == nullptr)
+    return hipErrorInvalidValue;
+  if (!Distinct({logits, top_experts, weights, scores}))
+    return hipErrorInvalidValue;
+  return WithRouterTypes(logits_dtype, weights_dtype, num_experts,
+                         [&](auto t, auto w, auto per) {
+    using T = decltype(t);
+    using W = decltype(w);
+    hipLaunchKernelGGL((router_topk_kernel<T, W, decltype(per)::value>),
+                       dim3(TokenGrid(tokens)), dim3(kThreads), 0, stream,
+                       static_cast<const T *>(logits), top_experts,
+                       static_cast<W *>(weights), static_cast<W *>(scores),
+                       tokens, num_experts, top_k, normalize ? 1 : 0);
+    return hipGetLastError();
+  });
+}
+
+hipError_t RunRouterTopKGrad(const void *logits, const int *top_experts,
+                             const void *dweights, const void *dscores,
+                             void *dlogits, int tokens, int num_experts,
+                             int top_k, bool normalize, int logits_dtype,
+                             int weights_dtype, hipStream_t stream) {
+  if (!RouterSizesOk(tokens, num_experts, top_k, logits_dtype, weights_dtype))
+    return hipErrorInvalidValue;
+  if (tokens == 0) return hipSuccess;
+  if (logits == nullptr || top_experts == nullptr || dweights == nullptr ||
+      dlogits == nullptr)
+    return hipErrorInvalidValue;
+  if (dlogits == logits || dlogits == top_experts || dlogits == dweights ||
+      dlogits == dscores)
+    return hipErrorInvalidValue;
+  return WithRouterTypes(logits_dtype, weights_dtype, num_experts,
+                         [&](auto t, auto w, auto per) {
+    using T = decltype(t);
+    using W = decltype(w);
+    hipLaunchKernelGGL((router_topk_grad_kernel<T, W, decltype(per)::value>),
+                       dim3(TokenGrid(tokens)), dim3(kThreads), 0, stream,
+                       static_cast<const T *>(logits), top_experts,
+                       static_cast<const W *>(dweights),
+                       static_cast<const W *>(dscores),
+                       static_cast<T *>(dlogits), tokens, num_experts, top_k,
+                       normalize ? 1 : 0);
+    return hipGetLastError();
+  });
+}
+
+size_t MoeSortWorkspace(int n, int num_experts) {
+  if (n < 0 || num_experts < 1 || num_experts > kMaxExperts ||
+      (long long)n + 127LL * num_experts > INT_MAX)
+    return 0;
+  const size_t chunks = ((size_t)n + kChunk - 1) / kChunk;
+  return chunks * (size_t)(num_experts + 1) * sizeof(int);
+}
+
+hipError_t RunMoeSort(const int *top_experts, int n, int num_experts, int rows,
+                      int *indices, int *bin_ids, int *bins,
+                      int *tokens_per_expert, int *padded_bins, int *row_of,
+                      void *workspace, size_t workspace_bytes,
+                      hipStream_t stream) {
+  if (n < 0 || num_experts < 1 || num_experts > kMaxExperts || rows < 0 ||
+      rows % 128 != 0 || (long long)n + 127LL * num_experts > INT_MAX)
+    return hipErrorInvalidValue;
+  if (bins == nullptr || tokens_per_expert == nullptr ||
+      padded_bins == nullptr)
+    return hipErrorInvalidValue;
+  const size_t need = MoeSortWorkspace(n, num_experts);
+  if (n > 0 &&
+      (top_experts == nullptr || indices == nullptr || bin_ids == nullptr ||
+       row_of == nullptr || workspace == nullptr || workspace_bytes < need ||
+       reinterpret_cast<uintptr_t>(workspace) % alignof(int) != 0))
+    return hipErrorInvalidValue;
+  if (!Distinct({top_experts, indices, bin_ids, bins, tokens_per_expert,
+                 padded_bins, row_of, workspace}))
+    return hipErrorInvalidValue;
+  int *counts = static_cast<int *>(workspace);
+  const int chunks = (int)(((long long)n + kChunk - 1) / kChunk);
+  if (chunks > 0) {
+    hipLaunchKernelGGL(moe_sort_histogram_kernel, dim3(chunks),
+                       dim3(kSortThreads), 0, stream, top_experts, n,
+                       num_experts, counts);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(moe_sort_scan_kernel, dim3(1), dim3(kSortThreads), 0,
+                     stream, counts, chunks, num_experts, bins,
+                     tokens_per_expert, padded_bins);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (chunks > 0) {
+    hipLaunchKernelGGL(moe_sort_place_kernel, dim3(chunks),
+                       dim3(kSortThreads), 0, stream, top_experts, counts,
+                       bins, padded_bins, n, num_experts, rows, indices,
+                       bin_ids, row_of);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace sputnik_amd
+
+namespace sputnik {
+namespace block {
+
+hipError_t RouterTopK(const void *logits, int *top_experts, void *weights,
+                      void *scores, int tokens, int num_experts, int top_k,
+                      bool normalize, RouterType logits_type,
+                      WeightType weights_type, hipStream_t stream) {
+  return sputnik_amd::RunRouterTopK(logits, top_experts, weights, scores,
+                                    tokens, num_experts, top_k, normalize,
+                                    (int)logits_type, (int)weights_type,
+                                    stream);
+}
+
+hipError_t RouterTopKGrad(const void *logits, const int *top_experts,
+                          const void *dweights, const void *dscores,
+                          void *dlogits, int tokens, int num_experts,
+                          int top_k, bool normalize, RouterType logits_type,
+                          WeightType weights_type, hipStream_t stream) {
+  return sputnik_amd::RunRouterTopKGrad(logits, top_experts, dweights, dscores,
+                                        dlogits, tokens, num_experts, top_k,
+                                        normalize, (int)logits_type,
+                                        (int)weights_type, stream);
+}
+
+size_t MoeSortWorkspaceBytes(int n, int num_experts) {
+  return sputnik_amd::MoeSortWorkspace(n, num_experts);
+}
+
+hipError_t MoeSort(const int *top_experts, int n, int num_experts, int rows,
+                   int *indices, int *bin_ids, int *bins,
+                   int *tokens_per_expert, int *padded_bins, int *row_of,
+                   void *workspace, size_t workspace_bytes,
+                   hipStream_t stream) {
+  return sputnik_amd::RunMoeSort(top_experts, n, num_experts, rows, indices,
+                                 bin_ids, bins, tokens_per_expert, padded_bins,
+                                 row_of, workspace, workspace_bytes, stream);
+}
+
+}  // namespace block
+}  // namespace sputnik

@@ -25,7 +25,11 @@ dsd(act(sdd(x, w1, topo)) * sdd(x, v1, topo), w2) as one autograd function
 are the token permutation on either side of those MLPs (MegaBlocks'
 padded_gather / padded_scatter; sputnik/block/moe.h), and `moe_mlp` the whole
 layer behind a router: route, gather, expert topology, mlp / glu_mlp,
-weighted scatter. Every product runs on
+weighted scatter. `moe_router` is the router's fused softmax / top-k with its
+gradient (sputnik/block/router.h), `moe_device_route` builds a route with the
+library's counting sort instead of torch.sort, and `moe_layer` is the whole
+layer from activations to output: router GEMM (torch), moe_router, moe_mlp.
+Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
 
@@ -47,9 +51,10 @@ import torch
 from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                BlockMatrix, Matrix, Matmul, MatmulAccumulateEx,
                MatmulActivation, MatmulActivationGrad, MatmulEx, MatmulGated,
-               MatmulGatedGrad, MoeBins, MoeRowMap, PaddedGather,
-               PaddedScatter, PaddedScatterWeightGrad, RowIndices, Transpose,
-               _act_code,
+               MatmulGatedGrad, MoeBins, MoeRowMap, MoeSort, PaddedGather,
+               PaddedScatter, PaddedScatterWeightGrad, RouterTopK,
+               RouterTopKGrad, RowIndices, Transpose,
+               MOE_SORT_CHUNK, ROUTER_MAX_EXPERTS, ROUTER_MAX_TOP_K, _act_code,
                AllocateRowIndicesBuffer, AllocateTransposeBuffers,
                dsd_workspace_bytes, sdd_workspace_bytes)
 
@@ -893,6 +898,39 @@ def moe_route(top_experts: torch.Tensor, num_experts: int,
                     tokens, rows)
 
 
+def moe_device_route(top_experts: torch.Tensor, num_experts: int,
+                     rows: Optional[int] = None) -> MoeRoute:
+    """moe_route with the library's sort: the whole route is one MoeSort (a
+    stable counting sort in three launches, num_experts <= 1024;
+    sputnik/block/router.h) instead of torch.sort + MoeBins + MoeRowMap. For
+    ids in [0, num_experts) every tensor of the route is the same bit for
+    bit. The workspace is a per-call temporary from torch's caching
+    allocator. `rows` as in moe_route."""
+    tokens, top_k = _top_experts(top_experts, num_experts)
+    n = tokens * top_k
+    if rows is not None:
+        _route_rows(rows, n, num_experts, None)
+    if num_experts > ROUTER_MAX_EXPERTS:
+        raise ValueError(f"moe_device_route: num_experts = {num_experts} "
+                         f"passes {ROUTER_MAX_EXPERTS}")
+    dev = top_experts.device
+    flat = top_experts.reshape(-1).to(torch.int32).contiguous()
+    indices, bin_ids, row_of = (torch.empty(n, dtype=torch.int32, device=dev)
+                                for _ in range(3))
+    bins, tpe, padded_bins = (torch.empty(num_experts, dtype=torch.int32,
+                                          device=dev) for _ in range(3))
+    chunks = (n + MOE_SORT_CHUNK - 1) // MOE_SORT_CHUNK
+    ws = _bt_workspace(chunks * (num_experts + 1) * 4, dev)
+    # (rows None: the bound never cuts a row off; the exact size is read
+    # back below)
+    MoeSort(flat, num_experts,
+            moe_rows_bound(n, num_experts) if rows is None else rows,
+            indices, bin_ids, bins, tpe, padded_bins, row_of, ws)
+    rows = _route_rows(rows, n, num_experts, padded_bins)
+    return MoeRoute(indices, bin_ids, bins, padded_bins, tpe, row_of, top_k,
+                    tokens, rows)
+
+
 def _check_route(route, what: str):
     if not isinstance(route, MoeRoute):
         raise TypeError(f"{what}: route must be a MoeRoute")
@@ -992,21 +1030,20 @@ def padded_scatter(y: torch.Tensor, route: MoeRoute,
     return _PaddedScatter.apply(y, weights, route)
 
 
-def moe_mlp(x: torch.Tensor, top_experts: torch.Tensor,
-            expert_weights: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
-            num_experts: int, activation=None,
-            v1: Optional[torch.Tensor] = None,
-            rows: Optional[int] = None) -> torch.Tensor:
-    """A dropless MoE layer behind its router: moe_route(top_experts) ->
-    padded_gather(x) -> expert_topology -> mlp (glu_mlp when `v1` is given)
-    -> padded_scatter with `expert_weights`. x [tokens, d_model]; w1 (and
-    v1) [d_model, num_experts * ffn], w2 [num_experts * ffn, d_model], ffn a
-    multiple of 128, expert e owning columns / rows [e * ffn, (e + 1) * ffn).
-    `activation` None: the MLP's default ("gelu" for mlp, "silu" for
-    glu_mlp). `rows` as in moe_route (None: one host sync for the exact
-    padded size; moe_rows_bound(tokens * top_k, num_experts) or more: none).
-    Differentiable in x, expert_weights, w1, v1 and w2."""
-    tokens, top_k = _top_experts(top_experts, num_experts)
+def _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
+             activation, v1, rows):
+    """moe_mlp's checks and chain; returns the output and the route."""
+    route = top_experts if isinstance(top_experts, MoeRoute) else None
+    if route is None:
+        tokens, top_k = _top_experts(top_experts, num_experts)
+    else:
+        tokens, top_k = route.tokens, route.top_k
+        if route.num_experts != num_experts:
+            raise ValueError(f"moe_mlp: a route over {route.num_experts} "
+                             f"experts, num_experts = {num_experts}")
+        if rows is not None and rows != route.rows:
+            raise ValueError(f"moe_mlp: rows = {rows}, the route has "
+                             f"{route.rows}")
     _check_rows(x, tokens, "moe_mlp: x")
     ws = (w1, w2) if v1 is None else (w1, v1, w2)
     _check_dtypes(x, *ws)
@@ -1028,7 +1065,8 @@ def moe_mlp(x: torch.Tensor, top_experts: torch.Tensor,
     if int(expert_weights.numel()) != tokens * top_k:
         raise ValueError("moe_mlp: one expert weight per (token, k)")
     act = None if activation is None else _act_code(activation)
-    route = moe_route(top_experts, num_experts, rows)
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
     xp = padded_gather(x, route)
     topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
                            route.rows // BLOCK, dtype=x.dtype)
@@ -1036,11 +1074,151 @@ def moe_mlp(x: torch.Tensor, top_experts: torch.Tensor,
         y = mlp(xp, w1, w2, topo, "gelu" if act is None else act)
     else:
         y = glu_mlp(xp, w1, v1, w2, topo, "silu" if act is None else act)
-    return padded_scatter(y, route, expert_weights)
+    return padded_scatter(y, route, expert_weights), route
+
+
+def moe_mlp(x: torch.Tensor, top_experts: torch.Tensor,
+            expert_weights: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+            num_experts: int, activation=None,
+            v1: Optional[torch.Tensor] = None,
+            rows: Optional[int] = None) -> torch.Tensor:
+    """A dropless MoE layer behind its router: moe_route(top_experts) ->
+    padded_gather(x) -> expert_topology -> mlp (glu_mlp when `v1` is given)
+    -> padded_scatter with `expert_weights`. x [tokens, d_model]; w1 (and
+    v1) [d_model, num_experts * ffn], w2 [num_experts * ffn, d_model], ffn a
+    multiple of 128, expert e owning columns / rows [e * ffn, (e + 1) * ffn).
+    `activation` None: the MLP's default ("gelu" for mlp, "silu" for
+    glu_mlp). `rows` as in moe_route (None: one host sync for the exact
+    padded size; moe_rows_bound(tokens * top_k, num_experts) or more: none).
+    `top_experts` may also be a MoeRoute built beforehand (moe_route,
+    moe_device_route, MoeRoute.from_megablocks): the layer then uses it as
+    it is, and `rows`, when given, must be its row count. Differentiable in
+    x, expert_weights, w1, v1 and w2."""
+    return _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
+                    activation, v1, rows)[0]
+
+
+# ---- MoE router -------------------------------------------------------------
+
+class _Router(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, top_k, normalize, dtype, return_scores):
+        logits = logits.contiguous()
+        tokens, e = logits.shape
+        dev = logits.device
+        top = torch.empty(tokens, top_k, dtype=torch.int32, device=dev)
+        weights = torch.empty(tokens, top_k, dtype=dtype, device=dev)
+        scores = (torch.empty(tokens, e, dtype=dtype, device=dev)
+                  if return_scores else None)
+        RouterTopK(logits, top, weights, normalize, scores)
+        ctx.save_for_backward(logits, top)
+        ctx.normalize = normalize
+        ctx.dtype = dtype
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(top)
+        return (weights, top, scores) if return_scores else (weights, top)
+
+    @staticmethod
+    def backward(ctx, dweights, _dtop, dscores=None):
+        logits, top = ctx.saved_tensors
+        if dweights is None and dscores is None:
+            return None, None, None, None, None
+        if dweights is None:
+            dweights = torch.zeros(top.shape, dtype=ctx.dtype,
+                                   device=logits.device)
+        dlogits = torch.empty_like(logits)
+        RouterTopKGrad(logits, top, dweights.contiguous(), dlogits,
+                       ctx.normalize,
+                       None if dscores is None else dscores.contiguous())
+        return dlogits, None, None, None, None
+
+
+def moe_router(logits: torch.Tensor, top_k: int, normalize: bool = False,
+               weights_dtype=None, return_scores: bool = False):
+    """The router's choice from its logits [tokens, E] (fp16, bf16 or fp32):
+    (expert_weights [tokens, top_k], top_experts int32 [tokens, top_k]) and,
+    with `return_scores`, scores [tokens, E] (the softmax, for a
+    load-balancing loss). The picks are the top_k largest logits in
+    descending order, equal logits to the lower expert, NaN last; the
+    weights are their softmax probabilities, divided by their sum with
+    `normalize` (sputnik/block/router.h). `weights_dtype`: None (the logits'
+    dtype) or torch.float32, for weights and scores alike. One autograd
+    function: top_experts carries no gradient, backward is one
+    RouterTopKGrad over the gradients of the weights and of the scores."""
+    if (not isinstance(logits, torch.Tensor) or logits.dtype not in
+            (torch.float16, torch.bfloat16, torch.float32)):
+        raise TypeError("moe_router: logits must be an fp16, bf16 or fp32 "
+                        "tensor")
+    if logits.dim() != 2:
+        raise ValueError("moe_router: logits are [tokens, num_experts]")
+    e = int(logits.shape[1])
+    if not 1 <= e <= ROUTER_MAX_EXPERTS:
+        raise ValueError(f"moe_router: {e} experts, outside [1, "
+                         f"{ROUTER_MAX_EXPERTS}]")
+    if (isinstance(top_k, bool) or not isinstance(top_k, int)
+            or not 1 <= top_k <= min(e, ROUTER_MAX_TOP_K)):
+        raise ValueError(f"moe_router: top_k must be an int in [1, min({e}, "
+                         f"{ROUTER_MAX_TOP_K})], not {top_k!r}")
+    if weights_dtype is None:
+        weights_dtype = logits.dtype
+    elif weights_dtype not in (logits.dtype, torch.float32):
+        raise TypeError(f"moe_router: weights_dtype must be {logits.dtype} "
+                        "or torch.float32")
+    return _Router.apply(logits, top_k, bool(normalize), weights_dtype,
+                         bool(return_scores))
+
+
+def moe_layer(x: torch.Tensor, router_weight: torch.Tensor, w1: torch.Tensor,
+              w2: torch.Tensor, top_k: int, activation=None,
+              v1: Optional[torch.Tensor] = None, rows: Optional[int] = None,
+              normalize: bool = False, router_dtype=None,
+              device_sort: bool = True, return_scores: bool = False):
+    """A dropless MoE layer from activations to output: logits = x @
+    router_weight.t() (torch; router_weight [E, d_model], the weight of an
+    nn.Linear(d_model, E, bias=False)), moe_router(logits, top_k, normalize),
+    then moe_mlp with its choice, routed by moe_device_route (`device_sort`
+    False: by moe_route's torch.sort). `router_dtype` None: the logits in x's
+    dtype; torch.float32: x and router_weight are converted and the logits,
+    the softmax and the expert weights are fp32. With explicit `rows` the
+    whole layer makes no host sync. Differentiable in x, router_weight, w1,
+    v1 and w2. `return_scores`: returns (y, scores [tokens, E],
+    tokens_per_expert int32 [E]), what MegaBlocks' load-balancing loss is
+    formed from."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("moe_layer: x must be a 2-D tensor")
+    _check_dtypes(x)
+    if router_dtype is None:
+        router_dtype = x.dtype
+    elif router_dtype not in (x.dtype, torch.float32):
+        raise TypeError(f"moe_layer: router_dtype must be {x.dtype} or "
+                        "torch.float32")
+    if (not isinstance(router_weight, torch.Tensor)
+            or router_weight.dtype not in (x.dtype, torch.float32)):
+        raise TypeError(f"moe_layer: router_weight must be {x.dtype} or "
+                        "torch.float32")
+    if router_weight.dim() != 2 or router_weight.shape[1] != x.shape[1]:
+        raise ValueError("moe_layer: router_weight is [num_experts, d_model]")
+    num_experts = int(router_weight.shape[0])
+    if (isinstance(top_k, bool) or not isinstance(top_k, int)
+            or not 1 <= top_k <= min(num_experts, ROUTER_MAX_TOP_K)):
+        raise ValueError(f"moe_layer: top_k must be an int in [1, min("
+                         f"{num_experts}, {ROUTER_MAX_TOP_K})], not {top_k!r}")
+    logits = x.to(router_dtype) @ router_weight.to(router_dtype).t()
+    out = moe_router(logits, top_k, normalize, None, return_scores)
+    top = out[1]
+    if device_sort:
+        top = moe_device_route(top, num_experts, rows)
+    y, route = _moe_mlp(x, top, out[0], w1, w2, num_experts, activation, v1,
+                        rows)
+    if return_scores:
+        return y, out[2], route.tokens_per_expert
+    return y
 
 
 __all__ = ["MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
            "expert_topology", "from_dense_mask", "glu_mlp", "mlp",
-           "moe_mlp", "moe_route", "moe_rows_bound", "padded_gather",
+           "moe_device_route", "moe_layer", "moe_mlp", "moe_route",
+           "moe_router",
+           "moe_rows_bound", "padded_gather",
            "padded_scatter", "sdd", "sdd_act", "sdd_gated",
            "topology_from_mask"]
