@@ -21,7 +21,7 @@ using sputnik::block::BlockMatrix;
 using sputnik::block::Matrix;
 
 // Caller-owned device memory for the transposed copy of B (SDD NT / TT, DSD
-// NT; dispatch.cpp "caller-owned transposed-B workspaces"). Empty: none was
+// NT; workspaces.cpp "caller-owned transposed-B workspaces"). Empty: none was
 // supplied with the call.
 struct Workspace {
   void *ptr = nullptr;
@@ -67,9 +67,9 @@ hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
 // fused, the 8-wave kernel's epilogue (never the transposed-B path); two
 // kernels, RunSdd as it stands into the buffer that keeps x (or c.data) and
 // RunBlockEpilogue behind it. Auto: fused where the plain call would run the
-// 8-wave kernel alone (SddKernel 0 / 1), decided once from the prepared
-// params (dispatch.cpp SddActDecide); two kernels wherever the transposed-B
-// path applies to the problem.
+// 8-wave kernel alone (SddKernel 0 / 1), read off the call's SDD route
+// (dispatch.cpp RouteSdd, SddActRouteOf), whose params the fused launch then
+// uses; two kernels wherever the transposed-B path applies to the problem.
 hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
                           const BlockMatrix &c, int dtype, int act, int mode,
                           void *side0, void *side1, void *out1,
@@ -127,12 +127,15 @@ int StatusCode(Status st);
 bool CanImplement(int op, const void *a, bool ta, const void *b, bool tb,
                   const void *c);
 
-// SDD tile plan of a valid problem: 1 = grouped 128x512 tiles, 0 = one
-// k-split 128x128 block per workgroup, -1 = rejected. Reads the CU count of
-// the current device (no launch).
+// The queries below report the route a launch would take (dispatch.cpp
+// RouteSdd / RouteDds / RouteDsd, computed dry: no launch, nothing allocated).
+// SDD tile plan of a valid problem: 1 = grouped 128x512 tiles, 2 = grouped
+// tiles with each group's K split, 0 = one k-split 128x128 block per
+// workgroup, -1 = rejected. Reads the CU count of the current device.
 int SddPlan(const void *a, bool ta, const void *b, bool tb, const void *c);
 // SDD kernel (dispatch.cpp SddKernel): 0 8-wave k-split tile, 1 8-wave
-// grouped, 2 4-wave K-split, 3 4-wave grouped, -1 rejected.
+// grouped, 2 4-wave K-split, 3 4-wave grouped, 4 B transposed first (null
+// stream, no workspace known), -1 rejected.
 int SddKernel(const void *a, bool ta, const void *b, bool tb, const void *c);
 // DDS kernel plan (dispatch.cpp DdsPlan): 0 8-wave tile, 1 4-wave kernel,
 // 2 tall, 3 split (8-wave), -1 rejected.
@@ -143,7 +146,7 @@ int DdsPlan(const void *a, bool ta, const void *b, bool tb, const void *c,
 int DsdPlan(const void *a, bool ta, const void *b, bool tb, const void *c,
             hipStream_t stream);
 
-// Pair hand-offs that timed out (see dispatch.cpp), and the test knob that
+// Pair hand-offs that timed out (see workspaces.cpp), and the test knob that
 // makes every pair producer skip its publish.
 int PairErrors();
 void SetPairFault(int on);
@@ -156,7 +159,7 @@ bool Dsd4wEnabled();
 bool Dsd4wForced();
 int Dsd4wEpi();
 
-// Unsupported tuning knobs (dispatch.cpp kKnobs: name, environment
+// Unsupported tuning knobs (knobs.cpp kKnobs: name, environment
 // variable, default, range). Knob() reads one; TuningGet / TuningSet back
 // sputnik_tuning_get / sputnik_tuning_set (INT_MIN: unknown name or value
 // out of range).

@@ -1,0 +1,353 @@
+// sputnik-amd: the sputnik::block C++ overload set (drop-in for the
+// reference's), over the Run* entry points of dispatch.cpp.
+#include "api_internal.h"
+#include "dispatch_internal.h"
+#include "metadata.h"
+#include "sputnik/sputnik.h"
+
+namespace sputnik_amd {
+namespace {
+
+// C++ API convention: abort where the reference aborts.
+hipError_t OrAbort(Status st, const char *op) {
+  switch (st) {
+    case Status::kOk: return hipSuccess;
+    case Status::kNotSupported: return hipErrorNotSupported;
+    case Status::kNoKernel:
+      SPUTNIK_LOG(FATAL) << "No compatible kernel for " << op << " problem.";
+      break;
+    case Status::kMissingMetadata:
+      SPUTNIK_LOG(FATAL) << "Check failed: offsets_t && indices_t && "
+                            "block_offsets (" << op << ")";
+      break;
+    case Status::kMissingRowIndices:
+      SPUTNIK_LOG(FATAL) << "Check failed: c.row_indices (" << op << ")";
+      break;
+  }
+  return hipErrorUnknown;
+}
+
+}  // namespace
+}  // namespace sputnik_amd
+
+// ---- C++ API (drop-in for the reference's sputnik::block) ---------------
+
+namespace sputnik {
+namespace block {
+
+using sputnik_amd::Status;
+
+hipError_t Matmul(const BlockMatrix a, bool transpose_a, const Matrix b,
+                  bool transpose_b, Matrix c, DataType dtype,
+                  hipStream_t stream) {
+  Status st;
+  const hipError_t e =
+      sputnik_amd::RunDsd(a, transpose_a, b, transpose_b, c, (int)dtype,
+                          a.create_metadata, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dsd");
+}
+
+hipError_t MatmulEx(const BlockMatrix a, bool transpose_a, const Matrix b,
+                    bool transpose_b, Matrix c, DataType dtype,
+                    hipStream_t stream) {
+  BlockMatrix acp = a;
+  acp.create_metadata = false;
+  return Matmul(acp, transpose_a, b, transpose_b, c, dtype, stream);
+}
+
+hipError_t Matmul(const BlockMatrix a, bool transpose_a, const Matrix b,
+                  bool transpose_b, Matrix c, hipStream_t stream) {
+  return Matmul(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+hipError_t MatmulEx(const BlockMatrix a, bool transpose_a, const Matrix b,
+                    bool transpose_b, Matrix c, hipStream_t stream) {
+  return MatmulEx(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+hipError_t Matmul(const Matrix a, bool transpose_a, const BlockMatrix b,
+                  bool transpose_b, Matrix c, DataType dtype,
+                  hipStream_t stream) {
+  Status st;
+  const hipError_t e =
+      sputnik_amd::RunDds(a, transpose_a, b, transpose_b, c, (int)dtype,
+                          b.create_metadata, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dds");
+}
+
+hipError_t MatmulEx(const Matrix a, bool transpose_a, const BlockMatrix b,
+                    bool transpose_b, Matrix c, DataType dtype,
+                    hipStream_t stream) {
+  BlockMatrix bcp = b;
+  bcp.create_metadata = false;
+  return Matmul(a, transpose_a, bcp, transpose_b, c, dtype, stream);
+}
+
+hipError_t Matmul(const Matrix a, bool transpose_a, const BlockMatrix b,
+                  bool transpose_b, Matrix c, hipStream_t stream) {
+  return Matmul(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+hipError_t MatmulEx(const Matrix a, bool transpose_a, const BlockMatrix b,
+                    bool transpose_b, Matrix c, hipStream_t stream) {
+  return MatmulEx(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+// ---- accumulating DSD / DDS (sputnik/block/accumulate.h) ----
+
+static sputnik_amd::OutMode AccMode(OutputType c_type) {
+  return c_type == OutputType::kF32 ? sputnik_amd::OutMode::kAccF32
+                                    : sputnik_amd::OutMode::kAccT;
+}
+
+hipError_t MatmulAccumulate(const BlockMatrix a, bool transpose_a,
+                            const Matrix b, bool transpose_b, Matrix c,
+                            DataType dtype, OutputType c_type,
+                            hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunDsd(
+      a, transpose_a, b, transpose_b, c, (int)dtype, a.create_metadata, stream,
+      &st, sputnik_amd::Workspace{}, AccMode(c_type));
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dsd (accumulate)");
+}
+
+hipError_t MatmulAccumulateEx(const BlockMatrix a, bool transpose_a,
+                              const Matrix b, bool transpose_b, Matrix c,
+                              DataType dtype, OutputType c_type,
+                              hipStream_t stream) {
+  BlockMatrix acp = a;
+  acp.create_metadata = false;
+  return MatmulAccumulate(acp, transpose_a, b, transpose_b, c, dtype, c_type,
+                          stream);
+}
+
+hipError_t MatmulAccumulate(const Matrix a, bool transpose_a,
+                            const BlockMatrix b, bool transpose_b, Matrix c,
+                            DataType dtype, OutputType c_type,
+                            hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunDds(
+      a, transpose_a, b, transpose_b, c, (int)dtype, b.create_metadata, stream,
+      &st, AccMode(c_type));
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dds (accumulate)");
+}
+
+hipError_t MatmulAccumulateEx(const Matrix a, bool transpose_a,
+                              const BlockMatrix b, bool transpose_b, Matrix c,
+                              DataType dtype, OutputType c_type,
+                              hipStream_t stream) {
+  BlockMatrix bcp = b;
+  bcp.create_metadata = false;
+  return MatmulAccumulate(a, transpose_a, bcp, transpose_b, c, dtype, c_type,
+                          stream);
+}
+
+hipError_t Matmul(const Matrix a, bool transpose_a, const Matrix b,
+                  bool transpose_b, BlockMatrix c, DataType dtype,
+                  hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunSdd(a, transpose_a, b, transpose_b, c,
+                                           (int)dtype, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sdd");
+}
+
+hipError_t Matmul(const Matrix a, bool transpose_a, const Matrix b,
+                  bool transpose_b, BlockMatrix c, hipStream_t stream) {
+  return Matmul(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+// ---- SDD epilogue products (sputnik/block/activation.h, gated.h) ----
+
+static hipError_t MatmulEpilogue(const char *what, const Matrix &a, bool ta,
+                                 const Matrix &b, bool tb,
+                                 const BlockMatrix &c, Activation activation,
+                                 int mode, const void *side0,
+                                 const void *side1, void *out1, DataType dtype,
+                                 hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunSddEpilogue(
+      a, ta, b, tb, c, (int)dtype, (int)activation, mode,
+      const_cast<void *>(side0), const_cast<void *>(side1), out1, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, what);
+}
+
+hipError_t MatmulActivation(const Matrix a, bool transpose_a, const Matrix b,
+                            bool transpose_b, BlockMatrix c,
+                            Activation activation, void *pre_activation,
+                            DataType dtype, hipStream_t stream) {
+  return MatmulEpilogue("sdd (activation)", a, transpose_a, b, transpose_b, c,
+                        activation, sputnik_amd::kOutAct, pre_activation,
+                        nullptr, nullptr, dtype, stream);
+}
+
+hipError_t MatmulActivationGrad(const Matrix a, bool transpose_a,
+                                const Matrix b, bool transpose_b,
+                                BlockMatrix c, Activation activation,
+                                const void *pre_activation, DataType dtype,
+                                hipStream_t stream) {
+  return MatmulEpilogue("sdd (activation grad)", a, transpose_a, b,
+                        transpose_b, c, activation, sputnik_amd::kOutActGrad,
+                        pre_activation, nullptr, nullptr, dtype, stream);
+}
+
+hipError_t MatmulGated(const Matrix a, bool transpose_a, const Matrix b,
+                       bool transpose_b, BlockMatrix c, Activation activation,
+                       const void *gate, void *up, DataType dtype,
+                       hipStream_t stream) {
+  return MatmulEpilogue("sdd (gated)", a, transpose_a, b, transpose_b, c,
+                        activation, sputnik_amd::kOutGate, gate, up, nullptr,
+                        dtype, stream);
+}
+
+hipError_t MatmulGatedGrad(const Matrix a, bool transpose_a, const Matrix b,
+                           bool transpose_b, BlockMatrix c,
+                           Activation activation, const void *gate,
+                           const void *up, void *up_grad, DataType dtype,
+                           hipStream_t stream) {
+  return MatmulEpilogue("sdd (gated grad)", a, transpose_a, b, transpose_b, c,
+                        activation, sputnik_amd::kOutGateGrad, gate, up,
+                        up_grad, dtype, stream);
+}
+
+// SSD (reference sputnik/block/ssd/ssd.h:10-22) and SDS (sds.h:10-22).
+hipError_t Matmul(const BlockMatrix a, bool transpose_a, const Matrix b,
+                  bool transpose_b, BlockMatrix c, DataType dtype,
+                  hipStream_t stream) {
+  Status st;
+  const hipError_t e =
+      sputnik_amd::RunSsd(a, transpose_a, b, transpose_b, c, (int)dtype,
+                          a.create_metadata, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "ssd");
+}
+
+hipError_t MatmulEx(const BlockMatrix a, bool transpose_a, const Matrix b,
+                    bool transpose_b, BlockMatrix c, DataType dtype,
+                    hipStream_t stream) {
+  BlockMatrix acp = a;
+  acp.create_metadata = false;
+  return Matmul(acp, transpose_a, b, transpose_b, c, dtype, stream);
+}
+
+hipError_t Matmul(const BlockMatrix a, bool transpose_a, const Matrix b,
+                  bool transpose_b, BlockMatrix c, hipStream_t stream) {
+  return Matmul(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+hipError_t MatmulEx(const BlockMatrix a, bool transpose_a, const Matrix b,
+                    bool transpose_b, BlockMatrix c, hipStream_t stream) {
+  return MatmulEx(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+hipError_t Matmul(const Matrix a, bool transpose_a, const BlockMatrix b,
+                  bool transpose_b, BlockMatrix c, DataType dtype,
+                  hipStream_t stream) {
+  Status st;
+  const hipError_t e =
+      sputnik_amd::RunSds(a, transpose_a, b, transpose_b, c, (int)dtype,
+                          b.create_metadata, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sds");
+}
+
+hipError_t MatmulEx(const Matrix a, bool transpose_a, const BlockMatrix b,
+                    bool transpose_b, BlockMatrix c, DataType dtype,
+                    hipStream_t stream) {
+  BlockMatrix bcp = b;
+  bcp.create_metadata = false;
+  return Matmul(a, transpose_a, bcp, transpose_b, c, dtype, stream);
+}
+
+hipError_t Matmul(const Matrix a, bool transpose_a, const BlockMatrix b,
+                  bool transpose_b, BlockMatrix c, hipStream_t stream) {
+  return Matmul(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+hipError_t MatmulEx(const Matrix a, bool transpose_a, const BlockMatrix b,
+                    bool transpose_b, BlockMatrix c, hipStream_t stream) {
+  return MatmulEx(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+// DSS (reference sputnik/block/dss/dss.h:10-22).
+hipError_t Matmul(const BlockMatrix a, bool transpose_a, const BlockMatrix b,
+                  bool transpose_b, Matrix c, DataType dtype,
+                  hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunDss(
+      a, transpose_a, b, transpose_b, c, (int)dtype, a.create_metadata,
+      b.create_metadata, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dss");
+}
+
+hipError_t MatmulEx(const BlockMatrix a, bool transpose_a, const BlockMatrix b,
+                    bool transpose_b, Matrix c, DataType dtype,
+                    hipStream_t stream) {
+  BlockMatrix acp = a, bcp = b;
+  acp.create_metadata = false;
+  bcp.create_metadata = false;
+  return Matmul(acp, transpose_a, bcp, transpose_b, c, dtype, stream);
+}
+
+hipError_t Matmul(const BlockMatrix a, bool transpose_a, const BlockMatrix b,
+                  bool transpose_b, Matrix c, hipStream_t stream) {
+  return Matmul(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+hipError_t MatmulEx(const BlockMatrix a, bool transpose_a, const BlockMatrix b,
+                    bool transpose_b, Matrix c, hipStream_t stream) {
+  return MatmulEx(a, transpose_a, b, transpose_b, c, DataType::kF16, stream);
+}
+
+// Caller-owned workspaces (sputnik/block/workspace.h).
+hipError_t SetStreamWorkspace(hipStream_t stream, void *ptr, size_t bytes) {
+  return sputnik_amd::SetStreamWorkspace(stream, ptr, bytes);
+}
+
+size_t SddWorkspaceBytes(const Matrix a, bool transpose_a, const Matrix b,
+                         bool transpose_b, const BlockMatrix c) {
+  return sputnik_amd::SddWorkspaceBytes(a, transpose_a, b, transpose_b, c);
+}
+
+size_t DsdWorkspaceBytes(const BlockMatrix a, bool transpose_a, const Matrix b,
+                         bool transpose_b, const Matrix c) {
+  return sputnik_amd::DsdWorkspaceBytes(a, transpose_a, b, transpose_b, c);
+}
+
+size_t RetainedBytes() { return sputnik_amd::RetainedBytes(); }
+
+size_t ReleaseWorkspaces() { return sputnik_amd::ReleaseWorkspaces(); }
+
+hipError_t RowIndices(BlockMatrix a, short *row_indices, hipStream_t stream) {
+  if (AsInt(a.block_size) == 0) return hipErrorNotSupported;
+  return sputnik_amd::LaunchRowIndices(a.rows / AsInt(a.block_size),
+                                       static_cast<const int *>(a.offsets),
+                                       row_indices, stream);
+}
+
+hipError_t Bitmask(BlockMatrix m, hipStream_t stream) {
+  // bitmask.cu:8-16: the orientation follows offsets_t.
+  const bool trans = m.offsets_t != nullptr;
+  const int b = AsInt(m.block_size);
+  if (b == 0) return hipErrorNotSupported;
+  SPUTNIK_CHECK(m.bitmask);
+  const int block_rows = (trans ? m.cols : m.rows) / b;
+  const int block_cols = (trans ? m.rows : m.cols) / b;
+  return sputnik_amd::LaunchBitmask(
+      block_rows, block_cols,
+      static_cast<const int *>(trans ? m.offsets_t : m.offsets),
+      static_cast<const short *>(trans ? m.indices_t : m.indices),
+      static_cast<unsigned long long *>(m.bitmask), stream);
+}
+
+hipError_t Transpose(BlockMatrix a, hipStream_t stream) {
+  // transpose.cu:107-109 checks the three workspaces; with no nonzero block
+  // the two per-block ones are legitimately empty.
+  SPUTNIK_CHECK(a.offsets_t);
+  if (a.nonzeros > 0) {
+    SPUTNIK_CHECK(a.indices_t);
+    SPUTNIK_CHECK(a.block_offsets);
+  }
+  return sputnik_amd::BuildTransposed(a, stream);
+}
+
+}  // namespace block
+}  // namespace sputnik
+

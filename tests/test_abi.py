@@ -161,7 +161,7 @@ def test_dsd4w_asm_matches_generator():
 
 
 def test_tuning_knobs_host_only():
-    """The unsupported tuning knobs (sputnik_tuning_get / _set, dispatch.cpp
+    """The unsupported tuning knobs (sputnik_tuning_get / _set, knobs.cpp
     kKnobs): defaults, set returns the previous value, range and name checks
     change nothing, select_dsd_kernel is the "dsd4w" knob."""
     import os as _os

@@ -142,7 +142,7 @@ def test_kat_dsd_ex_tall(ta, tb, dtype, k):
 def test_kat_tall_persistent_repeated():
     """Tall DSD with many more tiles than workgroup slots runs persistent
     (tiles past the first grid fetched from a per-stream counter whose base
-    the host advances per launch, dispatch.cpp UseTall): repeated launches on
+    the host advances per launch, workspaces.cpp BindTileCounter): repeated launches on
     one stream, interleaved with launches on a second stream, all exact."""
     rng = np.random.default_rng(11)
     A = ISparse(65536, 256, 0.3, rng, "f16")
@@ -420,7 +420,7 @@ def test_kat_sdd_grouped_pow2_stride(ta, tb, m, order):
 
 @pytest.fixture
 def bt_small():
-    """The transposed-B SDD path (dispatch.cpp UseBtTranspose) from a 1-MiB
+    """The transposed-B SDD path (dispatch.cpp BtAppliesSdd) from a 1-MiB
     B on (default: 256 MiB, the MALL), so small problems take it."""
     prev = sp.tuning("sdd_bt_min_mib", 1)
     yield
@@ -502,7 +502,7 @@ def test_kat_sdd_tail_split(ta, tb, case):
 @pytest.mark.parametrize("ex", [False, True])
 def test_kat_dsd_nt_bt_transpose(dtype, ex, bt_small):
     """DSD NT over a dense A of >= 15000 rows (dispatch.cpp
-    UseBtTransposeDsd): B^T transposed into the library's buffer, then the
+    BtAppliesDsd): B^T transposed into the library's buffer, then the
     NN product; exact, Matmul and MatmulEx, and with the path off."""
     got, want, (A, Bd, C) = kat_dsd(16384, 256, 2048, 1.0, False, True, dtype, ex=ex,
                                     seed=51 + ex)
@@ -548,7 +548,7 @@ def test_graph_capture_sdd_tail_split():
 def test_sdd_bt_two_threads_one_stream(bt_small):
     """Two host threads issue SDD NT on one stream, one of them with a larger
     B (so the stream's transposed-B buffer grows while the other thread's
-    launches may be queued): every result exact (dispatch.cpp g_bt_mu)."""
+    launches may be queued): every result exact (workspaces.cpp g_bt_mu)."""
     import threading
     probs = []
     for n, seed in ((4096, 31), (6144, 32)):
@@ -1052,7 +1052,7 @@ def test_graph_capture_with_pairs():
 def test_graph_capture_workspace_freed_with_graph():
     """A capture's pair workspace (64 MiB) and persistent counter live as long
     as the captured graph: destroying the graph and its executable releases
-    them (a user object retained by the graph, dispatch.cpp
+    them (a user object retained by the graph, workspaces.cpp
     TieToCapturedGraph), so re-capturing per shape does not pin memory or
     fill the capture tables."""
     import time
