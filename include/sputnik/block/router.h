@@ -33,6 +33,33 @@
 //                   sum_i dp_i p_i). fp32, rounded once. A top_experts entry
 //                   outside [0, E) contributes nothing (neither to dp nor to
 //                   S); a duplicated entry adds twice.
+//   RouterTopKAux   RouterTopK (the same ids, weights and scores bit for bit)
+//                   plus the statistics the auxiliary losses are formed from,
+//                   fp32 whatever L and W are and taken from the unrounded
+//                   values: score_sums[e] = sum_t p_te (float [E], required)
+//                   and, when `z_sum` is not null, z_sum[0] = sum_t lse_t^2
+//                   with lse_t = m_t + log sum_j exp(l_tj - m_t) (float [1]).
+//                   MegaBlocks' load-balancing loss of one layer is
+//                   E / (tokens^2 k) sum_e tokens_per_expert_e score_sums_e,
+//                   the router z-loss z_sum / tokens.
+//                   A workgroup covers kRouterAuxTokens consecutive tokens, a
+//                   wave a quarter of them in order; the waves are added in
+//                   wave order and the workgroup stores its E + 1 partials to
+//                   the workspace; a second launch adds the workgroups in
+//                   ascending order. No atomics: the sums depend on the input
+//                   alone, bit for bit.
+//                   workspace: RouterAuxWorkspaceBytes(tokens, E) =
+//                   ceil(tokens / kRouterAuxTokens) * (E + 1) * 4 bytes, the
+//                   caller's, 4-byte aligned, no initialisation needed.
+//                   tokens = 0 needs none and still writes E zeros and 0.
+//                   A row holding NaN, +-inf or only -inf enters the sums
+//                   with what the formulas give.
+//   RouterTopKAuxGrad  RouterTopKGrad with the gradients of the statistics:
+//                   dscore_sums (float [E]) and dz_sum (float [1], read on
+//                   the device), either may be null. dp_j = dscores_j (or 0)
+//                   + the pick terms + dscore_sums_j (or 0); dlogits_j = p_j
+//                   (dp_j - sum_i dp_i p_i) + 2 dz_sum lse p_j, fp32, rounded
+//                   once. With both null: RouterTopKGrad bit for bit.
 //   MoeSort         top_experts.flatten() int32 [n] -> indices, bin_ids [n],
 //                   bins, tokens_per_expert, padded_bins [E] and row_of [n] as
 //                   moe.h defines them: a stable counting sort by expert. For
@@ -54,7 +81,8 @@
 //                   ceil(n / kMoeSortChunk) * (E + 1) * 4 bytes, the caller's,
 //                   4-byte aligned, no initialisation needed.
 //
-// Limits: 1 <= E <= 1024; RouterTopK / RouterTopKGrad 1 <= k <= min(E, 32).
+// Limits: 1 <= E <= 1024; RouterTopK / RouterTopKGrad and their Aux forms
+// 1 <= k <= min(E, 32).
 // Element offsets are long long (tokens * E may pass 2^31).
 //
 // Bounds: every id read from device memory (top_experts in RouterTopKGrad and
@@ -63,9 +91,10 @@
 // Stream-ordered; no call allocates or synchronises. They never abort:
 // hipErrorInvalidValue, with nothing launched, for a null required buffer, a
 // size outside the limits, an unknown type, rows % 128 != 0, n + 127 E past
-// INT_MAX, a workspace that is too small, or an output that is one of the
-// inputs or another output. Zero-sized work succeeds (MoeSort with n = 0
-// still writes the E zero counts).
+// INT_MAX, a workspace that is too small or not 4-byte aligned, or an output
+// that is one of the inputs, another output or the workspace. Zero-sized work
+// succeeds (MoeSort with n = 0 still writes the E zero counts, RouterTopKAux
+// with tokens = 0 the zero sums).
 #ifndef SPUTNIK_BLOCK_ROUTER_H_
 #define SPUTNIK_BLOCK_ROUTER_H_
 
@@ -92,6 +121,27 @@ hipError_t RouterTopKGrad(const void *logits, const int *top_experts,
                           void *dlogits, int tokens, int num_experts,
                           int top_k, bool normalize, RouterType logits_type,
                           WeightType weights_type, hipStream_t stream);
+
+// Tokens per workgroup of RouterTopKAux: four waves of 16 consecutive tokens.
+// It fixes the summation order of score_sums / z_sum and the workspace size.
+constexpr int kRouterAuxTokens = 64;
+
+// 0 for sizes RouterTopKAux rejects.
+size_t RouterAuxWorkspaceBytes(int tokens, int num_experts);
+
+hipError_t RouterTopKAux(const void *logits, int *top_experts, void *weights,
+                         void *scores, float *score_sums, float *z_sum,
+                         int tokens, int num_experts, int top_k,
+                         bool normalize, RouterType logits_type,
+                         WeightType weights_type, void *workspace,
+                         size_t workspace_bytes, hipStream_t stream);
+
+hipError_t RouterTopKAuxGrad(const void *logits, const int *top_experts,
+                             const void *dweights, const void *dscores,
+                             const float *dscore_sums, const float *dz_sum,
+                             void *dlogits, int tokens, int num_experts,
+                             int top_k, bool normalize, RouterType logits_type,
+                             WeightType weights_type, hipStream_t stream);
 
 // 0 for sizes MoeSort rejects.
 size_t MoeSortWorkspaceBytes(int n, int num_experts);

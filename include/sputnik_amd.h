@@ -464,6 +464,30 @@ int sputnik_router_topk_grad(const void *logits, const int32_t *top_experts,
                              void *dlogits, int tokens, int num_experts,
                              int top_k, int normalize, int logits_dtype,
                              int weights_dtype, void *stream);
+/* The router with the statistics of the auxiliary losses (RouterTopKAux /
+ * RouterTopKAuxGrad in sputnik/block/router.h): the ids, weights and scores
+ * of sputnik_router_topk bit for bit, plus score_sums float [E] (required) =
+ * sum_t p_te and z_sum float [1] (optional) = sum_t (log sum_j exp l_tj)^2,
+ * fp32 from the unrounded values, without atomics: a function of the input
+ * alone. workspace: sputnik_router_aux_workspace_bytes(tokens, E) =
+ * ceil(tokens / 64) * (E + 1) * 4 bytes, 4-byte aligned, no initialisation
+ * needed; tokens = 0 needs none and still writes the zeros. The gradient
+ * takes dscore_sums float [E] and dz_sum float [1] (a device pointer), either
+ * may be NULL; with both NULL it is sputnik_router_topk_grad bit for bit. */
+size_t sputnik_router_aux_workspace_bytes(int tokens, int num_experts);
+int sputnik_router_topk_aux(const void *logits, int32_t *top_experts,
+                            void *weights, void *scores, float *score_sums,
+                            float *z_sum, int tokens, int num_experts,
+                            int top_k, int normalize, int logits_dtype,
+                            int weights_dtype, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int sputnik_router_topk_aux_grad(const void *logits,
+                                 const int32_t *top_experts,
+                                 const void *dweights, const void *dscores,
+                                 const float *dscore_sums, const float *dz_sum,
+                                 void *dlogits, int tokens, int num_experts,
+                                 int top_k, int normalize, int logits_dtype,
+                                 int weights_dtype, void *stream);
 size_t sputnik_moe_sort_workspace_bytes(int n, int num_experts);
 int sputnik_moe_sort(const int32_t *top_experts, int n, int num_experts,
                      int rows, int32_t *indices, int32_t *bin_ids,

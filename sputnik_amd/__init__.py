@@ -167,6 +167,18 @@ _SIGNATURES = {
     "sputnik_router_topk_grad": [_P, _P, _P, _P, _P, ctypes.c_int,
                                  ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_int, ctypes.c_int, _P],
+    # the router with the loss statistics: (logits, top_experts, weights,
+    # scores, score_sums, z_sum, tokens, ..., weights_dtype, workspace, bytes,
+    # stream); (logits, top_experts, dweights, dscores, dscore_sums, dz_sum,
+    # dlogits, tokens, ..., stream)
+    "sputnik_router_aux_workspace_bytes": [ctypes.c_int, ctypes.c_int],
+    "sputnik_router_topk_aux": [_P, _P, _P, _P, _P, _P, ctypes.c_int,
+                                ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                ctypes.c_int, ctypes.c_int, _P,
+                                ctypes.c_size_t, _P],
+    "sputnik_router_topk_aux_grad": [_P, _P, _P, _P, _P, _P, _P, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, _P],
     "sputnik_moe_sort_workspace_bytes": [ctypes.c_int, ctypes.c_int],
     "sputnik_moe_sort": [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P,
                          _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
@@ -214,6 +226,7 @@ _RESTYPES = {
     "sputnik_sdd_workspace_bytes": ctypes.c_size_t,
     "sputnik_dsd_workspace_bytes": ctypes.c_size_t,
     "sputnik_moe_sort_workspace_bytes": ctypes.c_size_t,
+    "sputnik_router_aux_workspace_bytes": ctypes.c_size_t,
     "sputnik_retained_bytes": ctypes.c_size_t,
     "sputnik_release_workspaces": ctypes.c_size_t,
     "sputnik_incall_events": ctypes.c_ulonglong,
@@ -1064,6 +1077,104 @@ def RouterTopKGrad(logits, top_experts, dweights, dlogits, normalize=False,  # n
         _stream(stream)), "RouterTopKGrad")
 
 
+ROUTER_AUX_TOKENS = 64     # sputnik::block::kRouterAuxTokens
+
+
+def _router_stat(t, logits, numel: int, what: str) -> None:
+    """An fp32 statistic of the auxiliary losses or its gradient: `numel`
+    elements, 1-D, contiguous, on the logits' device."""
+    import torch
+
+    td = getattr(t, "dtype", None)
+    if td != torch.float32:
+        raise TypeError(f"{what} is {td}, expected torch.float32")
+    if tuple(t.shape) != (numel,):
+        raise ValueError(f"{what} has shape {tuple(t.shape)}, expected "
+                         f"({numel},)")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    if t.device != logits.device:
+        raise ValueError(f"{what} is on {t.device}, the logits on "
+                         f"{logits.device}")
+
+
+def router_aux_workspace_bytes(tokens: int, num_experts: int) -> int:
+    """Bytes of workspace RouterTopKAux needs: ceil(tokens / 64) *
+    (num_experts + 1) * 4 (sputnik_router_aux_workspace_bytes)."""
+    tokens, e = int(tokens), int(num_experts)
+    if tokens < 0 or not 1 <= e <= ROUTER_MAX_EXPERTS:
+        raise ValueError(f"router_aux_workspace_bytes: tokens = {tokens} "
+                         f"must be >= 0 and num_experts = {e} in [1, "
+                         f"{ROUTER_MAX_EXPERTS}]")
+    return int(lib().sputnik_router_aux_workspace_bytes(tokens, e))
+
+
+def RouterTopKAux(logits, top_experts, weights, score_sums, workspace,  # noqa: N802
+                  normalize=False, scores=None, z_sum=None, stream=None):
+    """RouterTopK (the same top_experts, weights and scores, bit for bit)
+    plus the statistics of the auxiliary losses in fp32, from the unrounded
+    probabilities: score_sums fp32 [E] = the column sums of the softmax and,
+    when given, z_sum fp32 [1] = the sum over tokens of logsumexp(logits)^2.
+    No atomics: the sums are a function of the logits alone. `workspace`: a
+    contiguous tensor of at least router_aux_workspace_bytes(tokens, E)
+    bytes (None when that is 0); it needs no initialisation
+    (sputnik_router_topk_aux; sputnik/block/router.h). Type, shape and device
+    errors are raised before the library is called."""
+    code, tokens, e = _router_logits(logits, "logits")
+    k = _router_picks(top_experts, tokens, e, "RouterTopKAux")
+    wcode = _router_values(weights, logits, (tokens, k), None, "weights")
+    if scores is not None:
+        _router_values(scores, logits, (tokens, e), wcode, "scores")
+    _router_stat(score_sums, logits, e, "score_sums")
+    if z_sum is not None:
+        _router_stat(z_sum, logits, 1, "z_sum")
+    need = ((tokens + ROUTER_AUX_TOKENS - 1) // ROUTER_AUX_TOKENS
+            * (e + 1) * 4)
+    have = 0
+    if workspace is not None:
+        if not workspace.is_contiguous():
+            raise ValueError("workspace must be contiguous")
+        if workspace.device != logits.device:
+            raise ValueError(f"workspace is on {workspace.device}, the "
+                             f"logits on {logits.device}")
+        have = int(workspace.numel()) * int(workspace.element_size())
+    if have < need:
+        raise ValueError(f"RouterTopKAux: a workspace of {have} bytes, "
+                         f"{need} needed")
+    _check(lib().sputnik_router_topk_aux(
+        _ptr(logits), _ptr(top_experts), _ptr(weights), _ptr(scores),
+        _ptr(score_sums), _ptr(z_sum), tokens, e, k, int(bool(normalize)),
+        code, wcode, _ptr(workspace), have, _stream(stream)),
+        "RouterTopKAux")
+
+
+def RouterTopKAuxGrad(logits, top_experts, dweights, dlogits,  # noqa: N802
+                      normalize=False, dscores=None, dscore_sums=None,
+                      dz_sum=None, stream=None):
+    """RouterTopKGrad with the gradients of RouterTopKAux's statistics:
+    dscore_sums fp32 [E] is added to every row of dp, and dz_sum fp32 [1]
+    (read on the device) adds 2 dz_sum logsumexp(logits_t) p_tj. Either may
+    be None; with both None the result is RouterTopKGrad's bit for bit
+    (sputnik_router_topk_aux_grad). Type, shape and device errors are raised
+    before the library is called."""
+    code, tokens, e = _router_logits(logits, "logits")
+    k = _router_picks(top_experts, tokens, e, "RouterTopKAuxGrad")
+    wcode = _router_values(dweights, logits, (tokens, k), None, "dweights")
+    if dscores is not None:
+        _router_values(dscores, logits, (tokens, e), wcode, "dscores")
+    if dscore_sums is not None:
+        _router_stat(dscore_sums, logits, e, "dscore_sums")
+    if dz_sum is not None:
+        _router_stat(dz_sum, logits, 1, "dz_sum")
+    _router_values(dlogits, logits, (tokens, e), SPUTNIK_WEIGHTS_OPERAND,
+                   "dlogits")
+    _check(lib().sputnik_router_topk_aux_grad(
+        _ptr(logits), _ptr(top_experts), _ptr(dweights), _ptr(dscores),
+        _ptr(dscore_sums), _ptr(dz_sum), _ptr(dlogits), tokens, e, k,
+        int(bool(normalize)), code, wcode, _stream(stream)),
+        "RouterTopKAuxGrad")
+
+
 def _moe_sort_sizes(n, num_experts, what: str):
     n, e = int(n), int(num_experts)
     if n < 0 or not 1 <= e <= ROUTER_MAX_EXPERTS:
@@ -1304,6 +1415,8 @@ __all__ = [
     "RouterTopK", "RouterTopKGrad", "MoeSort", "moe_sort_workspace_bytes",
     "SPUTNIK_ROUTER_F16", "SPUTNIK_ROUTER_BF16", "SPUTNIK_ROUTER_F32",
     "MOE_SORT_CHUNK",
+    "RouterTopKAux", "RouterTopKAuxGrad", "router_aux_workspace_bytes",
+    "ROUTER_AUX_TOKENS",
     "SputnikError", "Transpose", "can_implement", "lib", "version",
     "allgather_concat", "gather_row_panels", "gather_col_panels",
     "gather_block_runs",

@@ -563,6 +563,35 @@ int sputnik_router_topk_grad(const void *logits, const int32_t *top_experts,
       static_cast<hipStream_t>(stream));
 }
 
+size_t sputnik_router_aux_workspace_bytes(int tokens, int num_experts) {
+  return sputnik_amd::RouterAuxWorkspace(tokens, num_experts);
+}
+
+int sputnik_router_topk_aux(const void *logits, int32_t *top_experts,
+                            void *weights, void *scores, float *score_sums,
+                            float *z_sum, int tokens, int num_experts,
+                            int top_k, int normalize, int logits_dtype,
+                            int weights_dtype, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+  return sputnik_amd::RunRouterTopKAux(
+      logits, top_experts, weights, scores, score_sums, z_sum, tokens,
+      num_experts, top_k, normalize != 0, logits_dtype, weights_dtype,
+      workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int sputnik_router_topk_aux_grad(const void *logits,
+                                 const int32_t *top_experts,
+                                 const void *dweights, const void *dscores,
+                                 const float *dscore_sums, const float *dz_sum,
+                                 void *dlogits, int tokens, int num_experts,
+                                 int top_k, int normalize, int logits_dtype,
+                                 int weights_dtype, void *stream) {
+  return sputnik_amd::RunRouterTopKAuxGrad(
+      logits, top_experts, dweights, dscores, dscore_sums, dz_sum, dlogits,
+      tokens, num_experts, top_k, normalize != 0, logits_dtype, weights_dtype,
+      static_cast<hipStream_t>(stream));
+}
+
 size_t sputnik_moe_sort_workspace_bytes(int n, int num_experts) {
   return sputnik_amd::MoeSortWorkspace(n, num_experts);
 }

@@ -26,6 +26,22 @@ hipError_t RunRouterTopKGrad(const void *logits, const int *top_experts,
                              int top_k, bool normalize, int logits_dtype,
                              int weights_dtype, hipStream_t stream);
 
+size_t RouterAuxWorkspace(int tokens, int num_experts);
+
+hipError_t RunRouterTopKAux(const void *logits, int *top_experts,
+                            void *weights, void *scores, float *score_sums,
+                            float *z_sum, int tokens, int num_experts,
+                            int top_k, bool normalize, int logits_dtype,
+                            int weights_dtype, void *workspace,
+                            size_t workspace_bytes, hipStream_t stream);
+
+hipError_t RunRouterTopKAuxGrad(const void *logits, const int *top_experts,
+                                const void *dweights, const void *dscores,
+                                const float *dscore_sums, const float *dz_sum,
+                                void *dlogits, int tokens, int num_experts,
+                                int top_k, bool normalize, int logits_dtype,
+                                int weights_dtype, hipStream_t stream);
+
 size_t MoeSortWorkspace(int n, int num_experts);
 
 hipError_t RunMoeSort(const int *top_experts, int n, int num_experts, int rows,

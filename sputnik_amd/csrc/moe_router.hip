@@ -20,6 +20,15 @@
 //           the per-pick terms are reduced across the wave and added to the
 //           owning lane's dp by k broadcast rounds, so a duplicated id adds
 //           twice and nothing is written through an id.
+//   aux     the forward pass with the loss statistics: a workgroup covers
+//           kRouterAuxTokens = 64 consecutive tokens, 16 per wave in order;
+//           each lane adds its columns' unrounded probabilities into kPer
+//           registers (no cross-lane traffic) and the wave (m + log s)^2. The
+//           four waves meet in LDS and are added in wave order; the E + 1
+//           partials go to workspace[group]. A second launch adds the groups
+//           in ascending order, one thread per column. No atomics: the sums
+//           are a function of the input alone. The gradient kernel takes the
+//           sums' gradients as one [E] vector and one device scalar.
 //
 // Sort: chunks of kMoeSortChunk = 1024 assignments, one per thread.
 //   histogram  per chunk: LDS integer adds into E + 1 counters (column E
@@ -56,6 +65,9 @@ constexpr int kMaxTopK = 32;
 constexpr int kChunk = sputnik::block::kMoeSortChunk;
 constexpr int kSortThreads = 1024;
 static_assert(kChunk == kSortThreads, "one assignment per thread");
+constexpr int kAuxTokens = sputnik::block::kRouterAuxTokens;
+constexpr int kAuxPerWave = kAuxTokens / kWaves;
+static_assert(kAuxPerWave * kWaves == kAuxTokens, "whole tokens per wave");
 
 __device__ __forceinline__ int wave_index() {
   return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -88,6 +100,71 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
     k = o > k ? o : k;
   }
   return k;
+}
+
+// One token of router_topk_aux_kernel, by one wave: router_topk_kernel's body
+// (the same key order, the same fp32 expressions), with the token's unrounded
+// probabilities added to acc[j] (column lane + 64 j) and its (m + log s)^2 to
+// zacc, the same value in every lane.
+template <typename T, typename W, int kPer>
+__device__ __forceinline__ void router_topk_aux_token(
+    const T *__restrict__ logits, int *__restrict__ top_experts,
+    W *__restrict__ weights, W *__restrict__ scores, long long t,
+    int num_experts, int top_k, int normalize, int lane, float (&acc)[kPer],
+    float &zacc) {
+  const T *row = logits + t * num_experts;
+  float v[kPer];
+  unsigned long long key[kPer];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    const bool live = e < num_experts;
+    v[j] = live ? (float)row[e] : 0.0f;
+    key[j] = live ? ((unsigned long long)order_image(v[j]) << 32) |
+                        (uint32_t)~e
+                  : 0ull;
+  }
+  float m = 0.0f, my_val = 0.0f;
+  int my_id = 0;
+  for (int r = 0; r < top_k; ++r) {
+    unsigned long long best = key[0];
+#pragma unroll
+    for (int j = 1; j < kPer; ++j) best = key[j] > best ? key[j] : best;
+    best = wave_max(best);
+    // (top_k <= num_experts: a live key remains, so idx is in [0, E))
+    const int idx = (int)~(uint32_t)best;
+    const float val = image_value((uint32_t)(best >> 32));
+    if (r == 0) m = val;
+    if (lane == r) {
+      my_id = idx;
+      my_val = val;
+    }
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (idx == lane + 64 * j) key[j] = 0ull;
+  }
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (lane + 64 * j < num_experts) s += expf(v[j] - m);
+  s = wave_sum(s);
+  float p = lane < top_k ? expf(my_val - m) / s : 0.0f;
+  if (normalize) p = p / wave_sum(p);
+  if (lane < top_k) {
+    top_experts[t * top_k + lane] = my_id;
+    weights[t * top_k + lane] = (W)p;
+  }
+  const float lse = m + logf(s);
+  zacc += lse * lse;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    if (e < num_experts) {
+      const float pe = expf(v[j] - m) / s;
+      acc[j] += pe;
+      if (scores != nullptr) scores[t * num_experts + e] = (W)pe;
+    }
+  }
 }
 
 template <typename T, typename W, int kPer>
@@ -149,6 +226,62 @@ __global__ void __launch_bounds__(kThreads)
         scores[t * num_experts + e] = (W)(expf(v[j] - m) / s);
     }
   }
+}
+
+// RouterTopK plus the column sums of the probabilities and the sum of
+// (m + log s)^2: wave w of workgroup g walks tokens [g kAuxTokens + w
+// kAuxPerWave, + kAuxPerWave) in order, the four waves' registers meet in LDS
+// and are added in wave order, and the E + 1 partials go to partial[g] (column
+// E: the z partial; every entry written).
+template <typename T, typename W, int kPer>
+__global__ void __launch_bounds__(kThreads)
+    router_topk_aux_kernel(const T *__restrict__ logits,
+                           int *__restrict__ top_experts,
+                           W *__restrict__ weights, W *__restrict__ scores,
+                           float *__restrict__ partial, int tokens,
+                           int num_experts, int top_k, int normalize) {
+  __shared__ float cols[kWaves][kPer * 64];
+  __shared__ float zs[kWaves];
+  const int lane = threadIdx.x & 63;
+  const int wave = wave_index();
+  const long long t0 =
+      (long long)blockIdx.x * kAuxTokens + (long long)wave * kAuxPerWave;
+  float acc[kPer], zacc = 0.0f;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) acc[j] = 0.0f;
+  for (int i = 0; i < kAuxPerWave && t0 + i < tokens; ++i)
+    router_topk_aux_token<T, W, kPer>(logits, top_experts, weights, scores,
+                                      t0 + i, num_experts, top_k, normalize,
+                                      lane, acc, zacc);
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) cols[wave][lane + 64 * j] = acc[j];
+  if (lane == 0) zs[wave] = zacc;
+  __syncthreads();
+  float *out = partial + (long long)blockIdx.x * (num_experts + 1);
+  for (int e = threadIdx.x; e <= num_experts; e += kThreads) {
+    float sum = e < num_experts ? cols[0][e] : zs[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w)
+      sum += e < num_experts ? cols[w][e] : zs[w];
+    out[e] = sum;
+  }
+}
+
+// Column c of score_sums / z_sum: the groups' partials added in ascending
+// group order from +0, one thread per column.
+__global__ void __launch_bounds__(kThreads)
+    router_aux_reduce_kernel(const float *__restrict__ partial, int groups,
+                             int num_experts, float *__restrict__ score_sums,
+                             float *__restrict__ z_sum) {
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c > num_experts || (c == num_experts && z_sum == nullptr)) return;
+  float sum = 0.0f;
+  for (int g = 0; g < groups; ++g)
+    sum += partial[(long long)g * (num_experts + 1) + c];
+  if (c < num_experts)
+    score_sums[c] = sum;
+  else
+    z_sum[0] = sum;
 }
 
 template <typename T, typename W, int kPer>
@@ -220,6 +353,88 @@ __global__ void __launch_bounds__(kThreads)
     const int e = lane + 64 * j;
     if (e < num_experts)
       dlogits[t * num_experts + e] = (T)(p[j] * (dp[j] - dot));
+  }
+}
+
+// router_topk_grad_kernel with dscore_sums[e] (when not null) joining dp and
+// 2 dz (m + log s) p_j (when dz_sum is not null) the result.
+template <typename T, typename W, int kPer>
+__global__ void __launch_bounds__(kThreads)
+    router_topk_aux_grad_kernel(const T *__restrict__ logits,
+                                const int *__restrict__ top_experts,
+                                const W *__restrict__ dweights,
+                                const W *__restrict__ dscores,
+                                const float *__restrict__ dscore_sums,
+                                const float *__restrict__ dz_sum,
+                                T *__restrict__ dlogits, int tokens,
+                                int num_experts, int top_k, int normalize) {
+  const int lane = threadIdx.x & 63;
+  const long long t = (long long)blockIdx.x * kWaves + wave_index();
+  if (t >= tokens) return;
+  const T *row = logits + t * num_experts;
+  float v[kPer], dp[kPer];
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    const bool live = e < num_experts;
+    v[j] = live ? (float)row[e] : 0.0f;
+    dp[j] = live && dscores != nullptr
+                ? (float)dscores[t * num_experts + e] : 0.0f;
+    if (live && dscore_sums != nullptr) dp[j] += dscore_sums[e];
+    if (live) m = fmaxf(m, v[j]);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (lane + 64 * j < num_experts) s += expf(v[j] - m);
+  s = wave_sum(s);
+
+  // Lane r < top_k holds pick r: its id (-1 when out of range), its incoming
+  // gradient and, for normalize, its probability.
+  int id = -1;
+  float g = 0.0f;
+  if (lane < top_k) {
+    const int raw = top_experts[t * top_k + lane];
+    if (raw >= 0 && raw < num_experts) {
+      id = raw;
+      g = (float)dweights[t * top_k + lane];
+    }
+  }
+  if (normalize) {
+    const float psel = id >= 0 ? expf((float)row[id] - m) / s : 0.0f;
+    const float total = wave_sum(psel);             // S
+    const float c = wave_sum(g * psel) / total;     // sum_j dw_j w_j
+    g = id >= 0 ? (g - c) / total : 0.0f;
+  }
+  for (int r = 0; r < top_k; ++r) {
+    const int rid = __shfl(id, r, 64);
+    const float rg = __shfl(g, r, 64);
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (rid == lane + 64 * j) dp[j] += rg;
+  }
+  float p[kPer];
+  float dot = 0.0f;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const bool live = lane + 64 * j < num_experts;
+    p[j] = live ? expf(v[j] - m) / s : 0.0f;
+    if (live) dot += dp[j] * p[j];
+  }
+  dot = wave_sum(dot);
+  float zc = 0.0f;  // 2 dz lse
+  if (dz_sum != nullptr) zc = 2.0f * dz_sum[0] * (m + logf(s));
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    if (e < num_experts) {
+      float out = p[j] * (dp[j] - dot);
+      if (dz_sum != nullptr) out += zc * p[j];
+      dlogits[t * num_experts + e] = (T)out;
+    }
   }
 }
 
@@ -470,6 +685,94 @@ hipError_t RunRouterTopKGrad(const void *logits, const int *top_experts,
   });
 }
 
+size_t RouterAuxWorkspace(int tokens, int num_experts) {
+  if (tokens < 0 || num_experts < 1 || num_experts > kMaxExperts) return 0;
+  const size_t groups = ((size_t)tokens + kAuxTokens - 1) / kAuxTokens;
+  return groups * (size_t)(num_experts + 1) * sizeof(float);
+}
+
+hipError_t RunRouterTopKAux(const void *logits, int *top_experts,
+                            void *weights, void *scores, float *score_sums,
+                            float *z_sum, int tokens, int num_experts,
+                            int top_k, bool normalize, int logits_dtype,
+                            int weights_dtype, void *workspace,
+                            size_t workspace_bytes, hipStream_t stream) {
+  if (!RouterSizesOk(tokens, num_experts, top_k, logits_dtype, weights_dtype))
+    return hipErrorInvalidValue;
+  if (score_sums == nullptr) return hipErrorInvalidValue;
+  if (tokens > 0 &&
+      (logits == nullptr || top_experts == nullptr || weights == nullptr ||
+       workspace == nullptr ||
+       workspace_bytes < RouterAuxWorkspace(tokens, num_experts) ||
+       reinterpret_cast<uintptr_t>(workspace) % alignof(float) != 0))
+    return hipErrorInvalidValue;
+  if (!Distinct({logits, top_experts, weights, scores, score_sums, z_sum,
+                 workspace}))
+    return hipErrorInvalidValue;
+  float *partial = static_cast<float *>(workspace);
+  const unsigned groups =
+      (unsigned)(((long long)tokens + kAuxTokens - 1) / kAuxTokens);
+  if (groups > 0) {
+    const hipError_t e = WithRouterTypes(
+        logits_dtype, weights_dtype, num_experts,
+        [&](auto t, auto w, auto per) {
+          using T = decltype(t);
+          using W = decltype(w);
+          hipLaunchKernelGGL(
+              (router_topk_aux_kernel<T, W, decltype(per)::value>),
+              dim3(groups), dim3(kThreads), 0, stream,
+              static_cast<const T *>(logits), top_experts,
+              static_cast<W *>(weights), static_cast<W *>(scores), partial,
+              tokens, num_experts, top_k, normalize ? 1 : 0);
+          return hipGetLastError();
+        });
+    if (e != hipSuccess) return e;
+  }
+  // (no tokens: no groups, and the sums are written as zeros)
+  hipLaunchKernelGGL(router_aux_reduce_kernel,
+                     dim3((num_experts + 1 + kThreads - 1) / kThreads),
+                     dim3(kThreads), 0, stream, partial, (int)groups,
+                     num_experts, score_sums, z_sum);
+  return hipGetLastError();
+}
+
+hipError_t RunRouterTopKAuxGrad(const void *logits, const int *top_experts,
+                                const void *dweights, const void *dscores,
+                                const float *dscore_sums, const float *dz_sum,
+                                void *dlogits, int tokens, int num_experts,
+                                int top_k, bool normalize, int logits_dtype,
+                                int weights_dtype, hipStream_t stream) {
+  if (!RouterSizesOk(tokens, num_experts, top_k, logits_dtype, weights_dtype))
+    return hipErrorInvalidValue;
+  if (tokens == 0) return hipSuccess;
+  if (logits == nullptr || top_experts == nullptr || dweights == nullptr ||
+      dlogits == nullptr)
+    return hipErrorInvalidValue;
+  if (dlogits == logits || dlogits == top_experts || dlogits == dweights ||
+      dlogits == dscores || dlogits == dscore_sums || dlogits == dz_sum)
+    return hipErrorInvalidValue;
+  // Neither statistic's gradient: RouterTopKGrad's own kernel, so the result
+  // is its bit for bit by construction (the two kernels' code is scheduled
+  // and contracted separately by the compiler).
+  if (dscore_sums == nullptr && dz_sum == nullptr)
+    return RunRouterTopKGrad(logits, top_experts, dweights, dscores, dlogits,
+                             tokens, num_experts, top_k, normalize,
+                             logits_dtype, weights_dtype, stream);
+  return WithRouterTypes(logits_dtype, weights_dtype, num_experts,
+                         [&](auto t, auto w, auto per) {
+    using T = decltype(t);
+    using W = decltype(w);
+    hipLaunchKernelGGL(
+        (router_topk_aux_grad_kernel<T, W, decltype(per)::value>),
+        dim3(TokenGrid(tokens)), dim3(kThreads), 0, stream,
+        static_cast<const T *>(logits), top_experts,
+        static_cast<const W *>(dweights), static_cast<const W *>(dscores),
+        dscore_sums, dz_sum, static_cast<T *>(dlogits), tokens, num_experts,
+        top_k, normalize ? 1 : 0);
+    return hipGetLastError();
+  });
+}
+
 size_t MoeSortWorkspace(int n, int num_experts) {
   if (n < 0 || num_experts < 1 || num_experts > kMaxExperts ||
       (long long)n + 127LL * num_experts > INT_MAX)
@@ -544,6 +847,34 @@ hipError_t RouterTopKGrad(const void *logits, const int *top_experts,
                                         dlogits, tokens, num_experts, top_k,
                                         normalize, (int)logits_type,
                                         (int)weights_type, stream);
+}
+
+size_t RouterAuxWorkspaceBytes(int tokens, int num_experts) {
+  return sputnik_amd::RouterAuxWorkspace(tokens, num_experts);
+}
+
+hipError_t RouterTopKAux(const void *logits, int *top_experts, void *weights,
+                         void *scores, float *score_sums, float *z_sum,
+                         int tokens, int num_experts, int top_k,
+                         bool normalize, RouterType logits_type,
+                         WeightType weights_type, void *workspace,
+                         size_t workspace_bytes, hipStream_t stream) {
+  return sputnik_amd::RunRouterTopKAux(
+      logits, top_experts, weights, scores, score_sums, z_sum, tokens,
+      num_experts, top_k, normalize, (int)logits_type, (int)weights_type,
+      workspace, workspace_bytes, stream);
+}
+
+hipError_t RouterTopKAuxGrad(const void *logits, const int *top_experts,
+                             const void *dweights, const void *dscores,
+                             const float *dscore_sums, const float *dz_sum,
+                             void *dlogits, int tokens, int num_experts,
+                             int top_k, bool normalize, RouterType logits_type,
+                             WeightType weights_type, hipStream_t stream) {
+  return sputnik_amd::RunRouterTopKAuxGrad(
+      logits, top_experts, dweights, dscores, dscore_sums, dz_sum, dlogits,
+      tokens, num_experts, top_k, normalize, (int)logits_type,
+      (int)weights_type, stream);
 }
 
 size_t MoeSortWorkspaceBytes(int n, int num_experts) {

@@ -29,6 +29,10 @@ weighted scatter. `moe_router` is the router's fused softmax / top-k with its
 gradient (sputnik/block/router.h), `moe_device_route` builds a route with the
 library's counting sort instead of torch.sort, and `moe_layer` is the whole
 layer from activations to output: router GEMM (torch), moe_router, moe_mlp.
+`moe_router_aux` is moe_router with the fp32 statistics of the auxiliary
+losses (column sums of the softmax, sum of logsumexp^2) taken in the same
+pass, `load_balancing_loss` / `router_z_loss` the losses formed from them, and
+`moe_layer_aux` the layer that returns those statistics beside its output.
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -53,8 +57,9 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                MatmulActivation, MatmulActivationGrad, MatmulEx, MatmulGated,
                MatmulGatedGrad, MoeBins, MoeRowMap, MoeSort, PaddedGather,
                PaddedScatter, PaddedScatterWeightGrad, RouterTopK,
-               RouterTopKGrad, RowIndices, Transpose,
-               MOE_SORT_CHUNK, ROUTER_MAX_EXPERTS, ROUTER_MAX_TOP_K, _act_code,
+               RouterTopKAux, RouterTopKAuxGrad, RouterTopKGrad, RowIndices,
+               Transpose, MOE_SORT_CHUNK, ROUTER_AUX_TOKENS,
+               ROUTER_MAX_EXPERTS, ROUTER_MAX_TOP_K, _act_code,
                AllocateRowIndicesBuffer, AllocateTransposeBuffers,
                dsd_workspace_bytes, sdd_workspace_bytes)
 
@@ -1133,6 +1138,31 @@ class _Router(torch.autograd.Function):
         return dlogits, None, None, None, None
 
 
+def _router_args(logits, top_k, weights_dtype, what: str):
+    """The checks moe_router and moe_router_aux share; returns the dtype of
+    the weights."""
+    if (not isinstance(logits, torch.Tensor) or logits.dtype not in
+            (torch.float16, torch.bfloat16, torch.float32)):
+        raise TypeError(f"{what}: logits must be an fp16, bf16 or fp32 "
+                        "tensor")
+    if logits.dim() != 2:
+        raise ValueError(f"{what}: logits are [tokens, num_experts]")
+    e = int(logits.shape[1])
+    if not 1 <= e <= ROUTER_MAX_EXPERTS:
+        raise ValueError(f"{what}: {e} experts, outside [1, "
+                         f"{ROUTER_MAX_EXPERTS}]")
+    if (isinstance(top_k, bool) or not isinstance(top_k, int)
+            or not 1 <= top_k <= min(e, ROUTER_MAX_TOP_K)):
+        raise ValueError(f"{what}: top_k must be an int in [1, min({e}, "
+                         f"{ROUTER_MAX_TOP_K})], not {top_k!r}")
+    if weights_dtype is None:
+        weights_dtype = logits.dtype
+    elif weights_dtype not in (logits.dtype, torch.float32):
+        raise TypeError(f"{what}: weights_dtype must be {logits.dtype} "
+                        "or torch.float32")
+    return weights_dtype
+
+
 def moe_router(logits: torch.Tensor, top_k: int, normalize: bool = False,
                weights_dtype=None, return_scores: bool = False):
     """The router's choice from its logits [tokens, E] (fp16, bf16 or fp32):
@@ -1145,27 +1175,165 @@ def moe_router(logits: torch.Tensor, top_k: int, normalize: bool = False,
     dtype) or torch.float32, for weights and scores alike. One autograd
     function: top_experts carries no gradient, backward is one
     RouterTopKGrad over the gradients of the weights and of the scores."""
-    if (not isinstance(logits, torch.Tensor) or logits.dtype not in
-            (torch.float16, torch.bfloat16, torch.float32)):
-        raise TypeError("moe_router: logits must be an fp16, bf16 or fp32 "
-                        "tensor")
-    if logits.dim() != 2:
-        raise ValueError("moe_router: logits are [tokens, num_experts]")
-    e = int(logits.shape[1])
-    if not 1 <= e <= ROUTER_MAX_EXPERTS:
-        raise ValueError(f"moe_router: {e} experts, outside [1, "
-                         f"{ROUTER_MAX_EXPERTS}]")
-    if (isinstance(top_k, bool) or not isinstance(top_k, int)
-            or not 1 <= top_k <= min(e, ROUTER_MAX_TOP_K)):
-        raise ValueError(f"moe_router: top_k must be an int in [1, min({e}, "
-                         f"{ROUTER_MAX_TOP_K})], not {top_k!r}")
-    if weights_dtype is None:
-        weights_dtype = logits.dtype
-    elif weights_dtype not in (logits.dtype, torch.float32):
-        raise TypeError(f"moe_router: weights_dtype must be {logits.dtype} "
-                        "or torch.float32")
+    weights_dtype = _router_args(logits, top_k, weights_dtype, "moe_router")
     return _Router.apply(logits, top_k, bool(normalize), weights_dtype,
                          bool(return_scores))
+
+
+class _RouterAux(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, top_k, normalize, dtype):
+        logits = logits.contiguous()
+        tokens, e = logits.shape
+        dev = logits.device
+        top = torch.empty(tokens, top_k, dtype=torch.int32, device=dev)
+        weights = torch.empty(tokens, top_k, dtype=dtype, device=dev)
+        score_sums = torch.empty(e, dtype=torch.float32, device=dev)
+        z_sum = torch.empty(1, dtype=torch.float32, device=dev)
+        groups = (tokens + ROUTER_AUX_TOKENS - 1) // ROUTER_AUX_TOKENS
+        ws = _bt_workspace(groups * (e + 1) * 4, dev)
+        RouterTopKAux(logits, top, weights, score_sums, ws, normalize, None,
+                      z_sum)
+        ctx.save_for_backward(logits, top)
+        ctx.normalize = normalize
+        ctx.dtype = dtype
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(top)
+        return weights, top, score_sums, z_sum
+
+    @staticmethod
+    def backward(ctx, dweights, _dtop, dscore_sums, dz_sum):
+        logits, top = ctx.saved_tensors
+        if dweights is None and dscore_sums is None and dz_sum is None:
+            return None, None, None, None
+        if dweights is None:
+            dweights = torch.zeros(top.shape, dtype=ctx.dtype,
+                                   device=logits.device)
+        dlogits = torch.empty_like(logits)
+        RouterTopKAuxGrad(
+            logits, top, dweights.contiguous(), dlogits, ctx.normalize, None,
+            None if dscore_sums is None else dscore_sums.contiguous(),
+            None if dz_sum is None else dz_sum.contiguous())
+        return dlogits, None, None, None
+
+
+def moe_router_aux(logits: torch.Tensor, top_k: int, normalize: bool = False,
+                   weights_dtype=None):
+    """moe_router with the statistics of the auxiliary losses: (expert_weights
+    [tokens, top_k], top_experts int32 [tokens, top_k], score_sums fp32 [E],
+    z_sum fp32 [1]). Weights and ids are moe_router's bit for bit; score_sums
+    is the column sum over tokens of the softmax and z_sum the sum over
+    tokens of logsumexp(logits)^2, both accumulated in fp32 from the
+    unrounded values whatever the logits' dtype, without atomics (two calls
+    on one input agree bit for bit). No [tokens, E] tensor is written. One
+    autograd function that saves the logits and the ids: backward is one
+    RouterTopKAuxGrad, which takes the gradients of score_sums and z_sum as
+    an [E] vector and a device scalar (an absent one is not materialised).
+    Feed them to load_balancing_loss and router_z_loss."""
+    weights_dtype = _router_args(logits, top_k, weights_dtype,
+                                 "moe_router_aux")
+    return _RouterAux.apply(logits, top_k, bool(normalize), weights_dtype)
+
+
+def _loss_sizes(tokens, top_k, what: str):
+    for name, v in (("tokens", tokens), ("top_k", top_k)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{what}: {name} must be an int >= 1, not {v!r}")
+
+
+def load_balancing_loss(score_sums: torch.Tensor,
+                        tokens_per_expert: torch.Tensor, tokens: int,
+                        top_k: int, weight: float = 1.0) -> torch.Tensor:
+    """weight * E / (tokens^2 * top_k) * sum_e tokens_per_expert_e *
+    score_sums_e: MegaBlocks' batched_load_balancing_loss for one layer, from
+    moe_router_aux's score_sums (fp32 [E]) and the route's tokens_per_expert
+    ([E], any integer or float dtype; it carries no gradient). `weight` under
+    perfect balance. Plain torch on E elements, no host sync; a 0-d fp32
+    tensor."""
+    if (not isinstance(score_sums, torch.Tensor)
+            or score_sums.dtype != torch.float32):
+        raise TypeError("load_balancing_loss: score_sums must be an fp32 "
+                        "tensor")
+    if not isinstance(tokens_per_expert, torch.Tensor):
+        raise TypeError("load_balancing_loss: tokens_per_expert must be a "
+                        "tensor")
+    if score_sums.dim() != 1 or tokens_per_expert.shape != score_sums.shape:
+        raise ValueError("load_balancing_loss: score_sums and "
+                         "tokens_per_expert are [num_experts]")
+    _loss_sizes(tokens, top_k, "load_balancing_loss")
+    e = int(score_sums.numel())
+    scale = float(weight) * e / (float(tokens) * float(tokens) * top_k)
+    return scale * torch.dot(tokens_per_expert.detach().to(torch.float32),
+                             score_sums)
+
+
+def router_z_loss(z_sum: torch.Tensor, tokens: int,
+                  weight: float = 1.0) -> torch.Tensor:
+    """weight * z_sum / tokens: the router z-loss (the mean over tokens of
+    logsumexp(logits)^2) from moe_router_aux's z_sum (fp32 [1]). A 0-d fp32
+    tensor, no host sync."""
+    if (not isinstance(z_sum, torch.Tensor) or z_sum.dtype != torch.float32):
+        raise TypeError("router_z_loss: z_sum must be an fp32 tensor")
+    if z_sum.numel() != 1:
+        raise ValueError("router_z_loss: z_sum holds one element")
+    _loss_sizes(tokens, 1, "router_z_loss")
+    return (float(weight) / float(tokens)) * z_sum.reshape(())
+
+
+@dataclass
+class MoeAux:
+    """What moe_layer_aux returns beside its output, the
+    arguments of load_balancing_loss and router_z_loss: `score_sums` fp32 [E]
+    and `z_sum` fp32 [1] (differentiable), `tokens_per_expert` int32 [E],
+    and the layer's `tokens` and `top_k`."""
+
+    score_sums: torch.Tensor
+    z_sum: torch.Tensor
+    tokens_per_expert: torch.Tensor
+    tokens: int
+    top_k: int
+
+
+def _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
+               normalize, router_dtype, device_sort, returns: str, what: str):
+    """moe_layer's checks and chain. `returns`: "y", "scores" (moe_layer's
+    return_scores) or "aux" (moe_layer_aux: routing through
+    moe_router_aux)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"{what}: x must be a 2-D tensor")
+    _check_dtypes(x)
+    if router_dtype is None:
+        router_dtype = x.dtype
+    elif router_dtype not in (x.dtype, torch.float32):
+        raise TypeError(f"{what}: router_dtype must be {x.dtype} or "
+                        "torch.float32")
+    if (not isinstance(router_weight, torch.Tensor)
+            or router_weight.dtype not in (x.dtype, torch.float32)):
+        raise TypeError(f"{what}: router_weight must be {x.dtype} or "
+                        "torch.float32")
+    if router_weight.dim() != 2 or router_weight.shape[1] != x.shape[1]:
+        raise ValueError(f"{what}: router_weight is [num_experts, d_model]")
+    num_experts = int(router_weight.shape[0])
+    if (isinstance(top_k, bool) or not isinstance(top_k, int)
+            or not 1 <= top_k <= min(num_experts, ROUTER_MAX_TOP_K)):
+        raise ValueError(f"{what}: top_k must be an int in [1, min("
+                         f"{num_experts}, {ROUTER_MAX_TOP_K})], not {top_k!r}")
+    logits = x.to(router_dtype) @ router_weight.to(router_dtype).t()
+    if returns == "aux":
+        out = moe_router_aux(logits, top_k, normalize, None)
+    else:
+        out = moe_router(logits, top_k, normalize, None, returns == "scores")
+    top = out[1]
+    if device_sort:
+        top = moe_device_route(top, num_experts, rows)
+    y, route = _moe_mlp(x, top, out[0], w1, w2, num_experts, activation, v1,
+                        rows)
+    if returns == "aux":
+        return y, MoeAux(out[2], out[3], route.tokens_per_expert,
+                         int(x.shape[0]), top_k)
+    if returns == "scores":
+        return y, out[2], route.tokens_per_expert
+    return y
 
 
 def moe_layer(x: torch.Tensor, router_weight: torch.Tensor, w1: torch.Tensor,
@@ -1183,42 +1351,35 @@ def moe_layer(x: torch.Tensor, router_weight: torch.Tensor, w1: torch.Tensor,
     whole layer makes no host sync. Differentiable in x, router_weight, w1,
     v1 and w2. `return_scores`: returns (y, scores [tokens, E],
     tokens_per_expert int32 [E]), what MegaBlocks' load-balancing loss is
-    formed from."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 2:
-        raise ValueError("moe_layer: x must be a 2-D tensor")
-    _check_dtypes(x)
-    if router_dtype is None:
-        router_dtype = x.dtype
-    elif router_dtype not in (x.dtype, torch.float32):
-        raise TypeError(f"moe_layer: router_dtype must be {x.dtype} or "
-                        "torch.float32")
-    if (not isinstance(router_weight, torch.Tensor)
-            or router_weight.dtype not in (x.dtype, torch.float32)):
-        raise TypeError(f"moe_layer: router_weight must be {x.dtype} or "
-                        "torch.float32")
-    if router_weight.dim() != 2 or router_weight.shape[1] != x.shape[1]:
-        raise ValueError("moe_layer: router_weight is [num_experts, d_model]")
-    num_experts = int(router_weight.shape[0])
-    if (isinstance(top_k, bool) or not isinstance(top_k, int)
-            or not 1 <= top_k <= min(num_experts, ROUTER_MAX_TOP_K)):
-        raise ValueError(f"moe_layer: top_k must be an int in [1, min("
-                         f"{num_experts}, {ROUTER_MAX_TOP_K})], not {top_k!r}")
-    logits = x.to(router_dtype) @ router_weight.to(router_dtype).t()
-    out = moe_router(logits, top_k, normalize, None, return_scores)
-    top = out[1]
-    if device_sort:
-        top = moe_device_route(top, num_experts, rows)
-    y, route = _moe_mlp(x, top, out[0], w1, w2, num_experts, activation, v1,
-                        rows)
-    if return_scores:
-        return y, out[2], route.tokens_per_expert
-    return y
+    formed from (moe_layer_aux returns the loss statistics instead, without
+    the scores)."""
+    return _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
+                      normalize, router_dtype, device_sort,
+                      "scores" if return_scores else "y", "moe_layer")
 
 
-__all__ = ["MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
+def moe_layer_aux(x: torch.Tensor, router_weight: torch.Tensor,
+                  w1: torch.Tensor, w2: torch.Tensor, top_k: int,
+                  activation=None, v1: Optional[torch.Tensor] = None,
+                  rows: Optional[int] = None, normalize: bool = False,
+                  router_dtype=None, device_sort: bool = True):
+    """moe_layer for training with the auxiliary losses: the same layer, the
+    same arguments and the same output bit for bit, routed through
+    moe_router_aux; returns (y, MoeAux), the arguments of
+    load_balancing_loss and router_z_loss in fp32, without any [tokens, E]
+    tensor beside the logits. With explicit `rows` the layer, both losses
+    and the backward make no host sync."""
+    return _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
+                      normalize, router_dtype, device_sort, "aux",
+                      "moe_layer_aux")
+
+
+__all__ = ["MoeAux", "MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
            "expert_topology", "from_dense_mask", "glu_mlp", "mlp",
-           "moe_device_route", "moe_layer", "moe_mlp", "moe_route",
-           "moe_router",
+           "moe_device_route", "moe_layer", "moe_layer_aux", "moe_mlp",
+           "moe_route",
+           "moe_router", "moe_router_aux", "load_balancing_loss",
+           "router_z_loss",
            "moe_rows_bound", "padded_gather",
            "padded_scatter", "sdd", "sdd_act", "sdd_gated",
            "topology_from_mask"]
