@@ -40,11 +40,16 @@ def _ints(rng, shape):
     return rng.integers(-1, 2, size=shape).astype(np.float32)
 
 
+def _to_device(host, dtype):
+    return host.to(TD[dtype]).cuda()
+
+
 class ISparse:
     """BCSR operand with integer values: host dense copy + device matrix
     (tests/test_gpu_kat.py), with the transposed metadata built."""
 
-    def __init__(self, rows, cols, density, rng, dtype, topology=None):
+    def __init__(self, rows, cols, density, rng, dtype, topology=None,
+                 values=_ints, place=_to_device):
         self.rows, self.cols = rows, cols
         if topology is not None:
             self.offsets, self.indices = topology
@@ -53,10 +58,10 @@ class ISparse:
             nb = mu.nonzeros_for_density(rows, cols, density) // (B * B)
             self.offsets, self.indices = mu.random_topology(
                 rows // B, cols // B, nb, rng, unordered=True)
-        self.values = _ints(rng, (nb, B, B))
+        self.values = values(rng, (nb, B, B))
         self.dense = mu.to_dense(rows, cols, self.offsets, self.indices,
                                  self.values)
-        self.dev = torch.from_numpy(self.values).to(TD[dtype]).cuda()
+        self.dev = place(torch.from_numpy(self.values), dtype)
         self.m = sp.BlockMatrix(
             rows, cols, 128, nb * B * B, self.dev,
             torch.from_numpy(self.offsets.astype(np.int32)).cuda(),
@@ -66,13 +71,14 @@ class ISparse:
 
 
 class IDense:
-    def __init__(self, rows, cols, rng, dtype, zero_odd_axis=None):
-        self.values = _ints(rng, (rows, cols))
+    def __init__(self, rows, cols, rng, dtype, zero_odd_axis=None,
+                 values=_ints, place=_to_device):
+        self.values = values(rng, (rows, cols))
         if zero_odd_axis == 0:
             self.values[1::2, :] = 0
         elif zero_odd_axis == 1:
             self.values[:, 1::2] = 0
-        self.dev = torch.from_numpy(self.values).to(TD[dtype]).cuda()
+        self.dev = place(torch.from_numpy(self.values), dtype)
         self.m = sp.Matrix(rows, cols, self.dev)
 
 

@@ -41,11 +41,23 @@ def _ints(rng, shape):
     return rng.integers(-1, 2, size=shape).astype(np.float32)
 
 
+def _to_device(host, dtype):
+    return host.to(TD[dtype]).cuda()
+
+
+def _pair(values):
+    """values= of a product builder: one generator for both operands, or a
+    pair (first operand's, second operand's)."""
+    return values if isinstance(values, tuple) else (values, values)
+
+
 class ISparse:
-    """BCSR operand with integer values: host dense copy + device matrix."""
+    """BCSR operand with integer values: host dense copy + device matrix.
+    values(rng, shape) draws the block values (float32, exact in the operand
+    type); place(host tensor, dtype) puts them on the device."""
 
     def __init__(self, rows, cols, density, rng, dtype, unordered=True,
-                 nb=None, topology=None):
+                 nb=None, topology=None, values=_ints, place=_to_device):
         self.rows, self.cols = rows, cols
         if topology is not None:
             self.offsets, self.indices = topology
@@ -55,10 +67,10 @@ class ISparse:
                 nb = mu.nonzeros_for_density(rows, cols, density) // (B * B)
             self.offsets, self.indices = mu.random_topology(
                 rows // B, cols // B, nb, rng, unordered=unordered)
-        self.values = _ints(rng, (nb, B, B))
+        self.values = values(rng, (nb, B, B))
         self.dense = mu.to_dense(rows, cols, self.offsets, self.indices,
                                  self.values)
-        self.dev = torch.from_numpy(self.values).to(TD[dtype]).cuda()
+        self.dev = place(torch.from_numpy(self.values), dtype)
         self.m = sp.BlockMatrix(
             rows, cols, 128, nb * B * B, self.dev,
             torch.from_numpy(self.offsets.astype(np.int32)).cuda(),
@@ -74,9 +86,10 @@ class ISparse:
 
 
 class IDense:
-    def __init__(self, rows, cols, rng, dtype):
-        self.values = _ints(rng, (rows, cols))
-        self.dev = torch.from_numpy(self.values).to(TD[dtype]).cuda()
+    def __init__(self, rows, cols, rng, dtype, values=_ints,
+                 place=_to_device):
+        self.values = values(rng, (rows, cols))
+        self.dev = place(torch.from_numpy(self.values), dtype)
         self.m = sp.Matrix(rows, cols, self.dev)
 
 
@@ -107,12 +120,14 @@ def _nan_out(rows, cols, dtype):
 # ------------------------------------------------------------------ DSD --
 
 def kat_dsd(m, k, n, density, ta, tb, dtype, ex=False, seed=0,
-            topology=None):
+            topology=None, values=_ints, place=_to_device, out=_nan_out):
     rng = np.random.default_rng(seed)
+    va, vb = _pair(values)
     A = ISparse(*((k, m) if ta else (m, k)), density, rng, dtype,
-                topology=topology)
-    Bd = IDense(*((n, k) if tb else (k, n)), rng, dtype)
-    C, c_t = _nan_out(m, n, dtype)
+                topology=topology, values=va, place=place)
+    Bd = IDense(*((n, k) if tb else (k, n)), rng, dtype, values=vb,
+                place=place)
+    C, c_t = out(m, n, dtype)
     if ex:
         sp.Transpose(A.m)
         sp.MatmulEx(A.m, ta, Bd.m, tb, C)
@@ -323,12 +338,15 @@ def test_split_timeout_fails_loudly():
 # ------------------------------------------------------------------ DDS --
 
 def kat_dds(m, k, n, density, ta, tb, dtype, ex=False, seed=0,
-            topology=None, handles=False):
+            topology=None, handles=False, values=_ints, place=_to_device,
+            out=_nan_out):
     rng = np.random.default_rng(seed)
-    A = IDense(*((k, m) if ta else (m, k)), rng, dtype)
+    va, vb = _pair(values)
+    A = IDense(*((k, m) if ta else (m, k)), rng, dtype, values=va,
+               place=place)
     Bs = ISparse(*((n, k) if tb else (k, n)), density, rng, dtype,
-                 topology=topology)
-    C, c_t = _nan_out(m, n, dtype)
+                 topology=topology, values=vb, place=place)
+    C, c_t = out(m, n, dtype)
     if ex:
         sp.Transpose(Bs.m)
         sp.MatmulEx(A.m, ta, Bs.m, tb, C)
@@ -362,11 +380,16 @@ def test_kat_dds_4096_pairs():
 
 # ------------------------------------------------------------------ SDD --
 
-def kat_sdd(m, k, n, density, ta, tb, dtype, nb=None, seed=0):
+def kat_sdd(m, k, n, density, ta, tb, dtype, nb=None, seed=0,
+            topology=None, values=_ints, place=_to_device):
     rng = np.random.default_rng(seed)
-    A = IDense(*((k, m) if ta else (m, k)), rng, dtype)
-    Bd = IDense(*((n, k) if tb else (k, n)), rng, dtype)
-    Cs = ISparse(m, n, density, rng, dtype, nb=nb)
+    va, vb = _pair(values)
+    A = IDense(*((k, m) if ta else (m, k)), rng, dtype, values=va,
+               place=place)
+    Bd = IDense(*((n, k) if tb else (k, n)), rng, dtype, values=vb,
+                place=place)
+    Cs = ISparse(m, n, density, rng, dtype, nb=nb, topology=topology,
+                 place=place)
     Cs.dev.fill_(float("nan"))
     sp.AllocateRowIndicesBuffer(Cs.m)
     sp.RowIndices(Cs.m, Cs.m.row_indices)
@@ -872,26 +895,36 @@ def test_sdd_plan_threshold():
 
 # ------------------------------------------------------------ SSD / SDS --
 
-@pytest.mark.parametrize("ta,tb", TRANSPOSES)
-@pytest.mark.parametrize("op", ["ssd", "sds"])
-def test_kat_ss(op, ta, tb):
-    rng = np.random.default_rng(ta * 2 + tb)
-    m, k, n = 1024, 768, 1152
-    dtype = "f16"
+def kat_ss(op, m, k, n, ta, tb, dtype, seed=0, values=_ints,
+           place=_to_device):
+    """SSD (sparse first operand) or SDS (sparse second) into a sparse C."""
+    rng = np.random.default_rng(seed)
+    va, vb = _pair(values)
     if op == "ssd":
-        X = ISparse(*((k, m) if ta else (m, k)), 0.5, rng, dtype)
-        Y = IDense(*((n, k) if tb else (k, n)), rng, dtype)
+        X = ISparse(*((k, m) if ta else (m, k)), 0.5, rng, dtype, values=va,
+                    place=place)
+        Y = IDense(*((n, k) if tb else (k, n)), rng, dtype, values=vb,
+                   place=place)
         full = _op(X.dense, ta).astype(np.float64) @ _op(Y.values, tb)
     else:
-        X = IDense(*((k, m) if ta else (m, k)), rng, dtype)
-        Y = ISparse(*((n, k) if tb else (k, n)), 0.5, rng, dtype)
+        X = IDense(*((k, m) if ta else (m, k)), rng, dtype, values=va,
+                   place=place)
+        Y = ISparse(*((n, k) if tb else (k, n)), 0.5, rng, dtype, values=vb,
+                    place=place)
         full = _op(X.values, ta).astype(np.float64) @ _op(Y.dense, tb)
-    Cs = ISparse(m, n, 0.3, rng, dtype)
+    Cs = ISparse(m, n, 0.3, rng, dtype, place=place)
     Cs.dev.fill_(float("nan"))
     sp.AllocateRowIndicesBuffer(Cs.m)
     sp.RowIndices(Cs.m, Cs.m.row_indices)
     sp.Matmul(X.m, ta, Y.m, tb, Cs.m)
-    _equal(Cs.dev, _expect(Cs.blocks_of(full), dtype), f"{op} {ta}{tb}")
+    return Cs.dev, _expect(Cs.blocks_of(full), dtype)
+
+
+@pytest.mark.parametrize("ta,tb", TRANSPOSES)
+@pytest.mark.parametrize("op", ["ssd", "sds"])
+def test_kat_ss(op, ta, tb):
+    got, want = kat_ss(op, 1024, 768, 1152, ta, tb, "f16", seed=ta * 2 + tb)
+    _equal(got, want, f"{op} {ta}{tb}")
 
 
 # ------------------------------------------------------------------ DSS --
@@ -899,14 +932,22 @@ def test_kat_ss(op, ta, tb):
 @pytest.mark.parametrize("ta,tb", TRANSPOSES)
 @pytest.mark.parametrize("dtype,k", [("f16", 1024), ("bf16", 256)])
 def test_kat_dss(ta, tb, dtype, k):
-    rng = np.random.default_rng(10 + ta * 2 + tb)
-    m, n = 896, 1024
-    X = ISparse(*((k, m) if ta else (m, k)), 0.5, rng, dtype)
-    Y = ISparse(*((n, k) if tb else (k, n)), 0.5, rng, dtype)
-    C, c_t = _nan_out(m, n, dtype)
+    got, want = kat_dss(896, k, 1024, ta, tb, dtype, seed=10 + ta * 2 + tb)
+    _equal(got, want, f"dss {ta}{tb} {dtype}")
+
+
+def kat_dss(m, k, n, ta, tb, dtype, seed=0, values=_ints, place=_to_device,
+            out=_nan_out):
+    rng = np.random.default_rng(seed)
+    va, vb = _pair(values)
+    X = ISparse(*((k, m) if ta else (m, k)), 0.5, rng, dtype, values=va,
+                place=place)
+    Y = ISparse(*((n, k) if tb else (k, n)), 0.5, rng, dtype, values=vb,
+                place=place)
+    C, c_t = out(m, n, dtype)
     sp.Matmul(X.m, ta, Y.m, tb, C)
     want = _op(X.dense, ta).astype(np.float64) @ _op(Y.dense, tb)
-    _equal(c_t, _expect(want, dtype), f"dss {ta}{tb} {dtype}")
+    return c_t, _expect(want, dtype)
 
 
 # ------------------------------------------- pair hand-off robustness --
