@@ -1036,6 +1036,40 @@ def _router_values(t, logits, shape, code, what: str) -> int:
     return got
 
 
+def _router_head(logits, top_experts, weights, scores, what: str, d=""):
+    """(code, tokens, E, top_k, weights code) of a call's logits, picks,
+    weights [tokens, top_k] and optional scores [tokens, E]; with d = "d" the
+    last two are a gradient call's dweights and dscores."""
+    code, tokens, e = _router_logits(logits, "logits")
+    k = _router_picks(top_experts, tokens, e, what)
+    wcode = _router_values(weights, logits, (tokens, k), None, d + "weights")
+    if scores is not None:
+        _router_values(scores, logits, (tokens, e), wcode, d + "scores")
+    return code, tokens, e, k, wcode
+
+
+def _router_dlogits(dlogits, logits) -> None:
+    _router_values(dlogits, logits, tuple(logits.shape),
+                   SPUTNIK_WEIGHTS_OPERAND, "dlogits")
+
+
+def _workspace_bytes(workspace, need: int, what: str, device=None) -> int:
+    """Bytes of a caller's workspace tensor (None: 0), contiguous, on
+    `device` when given and at least `need`."""
+    have = 0
+    if workspace is not None:
+        if not workspace.is_contiguous():
+            raise ValueError("workspace must be contiguous")
+        if device is not None and workspace.device != device:
+            raise ValueError(f"workspace is on {workspace.device}, the "
+                             f"logits on {device}")
+        have = int(workspace.numel()) * int(workspace.element_size())
+    if have < need:
+        raise ValueError(f"{what}: a workspace of {have} bytes, "
+                         f"{need} needed")
+    return have
+
+
 def RouterTopK(logits, top_experts, weights, normalize=False, scores=None,  # noqa: N802
                stream=None):
     """The router's choice from logits [tokens, E] (fp16, bf16 or fp32):
@@ -1046,11 +1080,8 @@ def RouterTopK(logits, top_experts, weights, normalize=False, scores=None,  # no
     and scores share one dtype, the logits' or fp32
     (sputnik_router_topk; sputnik/block/router.h). Type and shape errors are
     raised before the library is called."""
-    code, tokens, e = _router_logits(logits, "logits")
-    k = _router_picks(top_experts, tokens, e, "RouterTopK")
-    wcode = _router_values(weights, logits, (tokens, k), None, "weights")
-    if scores is not None:
-        _router_values(scores, logits, (tokens, e), wcode, "scores")
+    code, tokens, e, k, wcode = _router_head(
+        logits, top_experts, weights, scores, "RouterTopK")
     _check(lib().sputnik_router_topk(
         _ptr(logits), _ptr(top_experts), _ptr(weights), _ptr(scores), tokens,
         e, k, int(bool(normalize)), code, wcode, _stream(stream)),
@@ -1064,13 +1095,9 @@ def RouterTopKGrad(logits, top_experts, dweights, dlogits, normalize=False,  # n
     softmax recomputed from `logits`. A top_experts entry outside [0, E)
     contributes nothing, a duplicated one twice (sputnik_router_topk_grad).
     Type and shape errors are raised before the library is called."""
-    code, tokens, e = _router_logits(logits, "logits")
-    k = _router_picks(top_experts, tokens, e, "RouterTopKGrad")
-    wcode = _router_values(dweights, logits, (tokens, k), None, "dweights")
-    if dscores is not None:
-        _router_values(dscores, logits, (tokens, e), wcode, "dscores")
-    _router_values(dlogits, logits, (tokens, e), SPUTNIK_WEIGHTS_OPERAND,
-                   "dlogits")
+    code, tokens, e, k, wcode = _router_head(
+        logits, top_experts, dweights, dscores, "RouterTopKGrad", "d")
+    _router_dlogits(dlogits, logits)
     _check(lib().sputnik_router_topk_grad(
         _ptr(logits), _ptr(top_experts), _ptr(dweights), _ptr(dscores),
         _ptr(dlogits), tokens, e, k, int(bool(normalize)), code, wcode,
@@ -1120,27 +1147,14 @@ def RouterTopKAux(logits, top_experts, weights, score_sums, workspace,  # noqa: 
     bytes (None when that is 0); it needs no initialisation
     (sputnik_router_topk_aux; sputnik/block/router.h). Type, shape and device
     errors are raised before the library is called."""
-    code, tokens, e = _router_logits(logits, "logits")
-    k = _router_picks(top_experts, tokens, e, "RouterTopKAux")
-    wcode = _router_values(weights, logits, (tokens, k), None, "weights")
-    if scores is not None:
-        _router_values(scores, logits, (tokens, e), wcode, "scores")
+    code, tokens, e, k, wcode = _router_head(
+        logits, top_experts, weights, scores, "RouterTopKAux")
     _router_stat(score_sums, logits, e, "score_sums")
     if z_sum is not None:
         _router_stat(z_sum, logits, 1, "z_sum")
     need = ((tokens + ROUTER_AUX_TOKENS - 1) // ROUTER_AUX_TOKENS
             * (e + 1) * 4)
-    have = 0
-    if workspace is not None:
-        if not workspace.is_contiguous():
-            raise ValueError("workspace must be contiguous")
-        if workspace.device != logits.device:
-            raise ValueError(f"workspace is on {workspace.device}, the "
-                             f"logits on {logits.device}")
-        have = int(workspace.numel()) * int(workspace.element_size())
-    if have < need:
-        raise ValueError(f"RouterTopKAux: a workspace of {have} bytes, "
-                         f"{need} needed")
+    have = _workspace_bytes(workspace, need, "RouterTopKAux", logits.device)
     _check(lib().sputnik_router_topk_aux(
         _ptr(logits), _ptr(top_experts), _ptr(weights), _ptr(scores),
         _ptr(score_sums), _ptr(z_sum), tokens, e, k, int(bool(normalize)),
@@ -1157,17 +1171,13 @@ def RouterTopKAuxGrad(logits, top_experts, dweights, dlogits,  # noqa: N802
     be None; with both None the result is RouterTopKGrad's bit for bit
     (sputnik_router_topk_aux_grad). Type, shape and device errors are raised
     before the library is called."""
-    code, tokens, e = _router_logits(logits, "logits")
-    k = _router_picks(top_experts, tokens, e, "RouterTopKAuxGrad")
-    wcode = _router_values(dweights, logits, (tokens, k), None, "dweights")
-    if dscores is not None:
-        _router_values(dscores, logits, (tokens, e), wcode, "dscores")
+    code, tokens, e, k, wcode = _router_head(
+        logits, top_experts, dweights, dscores, "RouterTopKAuxGrad", "d")
     if dscore_sums is not None:
         _router_stat(dscore_sums, logits, e, "dscore_sums")
     if dz_sum is not None:
         _router_stat(dz_sum, logits, 1, "dz_sum")
-    _router_values(dlogits, logits, (tokens, e), SPUTNIK_WEIGHTS_OPERAND,
-                   "dlogits")
+    _router_dlogits(dlogits, logits)
     _check(lib().sputnik_router_topk_aux_grad(
         _ptr(logits), _ptr(top_experts), _ptr(dweights), _ptr(dscores),
         _ptr(dscore_sums), _ptr(dz_sum), _ptr(dlogits), tokens, e, k,
@@ -1216,14 +1226,7 @@ def MoeSort(top_experts, num_experts, rows, indices, bin_ids, bins,  # noqa: N80
         raise ValueError(f"MoeSort: {rows!r} padded rows, not a multiple of "
                          "128")
     need = (n + MOE_SORT_CHUNK - 1) // MOE_SORT_CHUNK * (e + 1) * 4
-    have = 0
-    if workspace is not None:
-        if not workspace.is_contiguous():
-            raise ValueError("workspace must be contiguous")
-        have = int(workspace.numel()) * int(workspace.element_size())
-    if have < need:
-        raise ValueError(f"MoeSort: a workspace of {have} bytes, "
-                         f"{need} needed")
+    have = _workspace_bytes(workspace, need, "MoeSort")
     _check(lib().sputnik_moe_sort(
         _ptr(top_experts), n, e, rows, _ptr(indices), _ptr(bin_ids),
         _ptr(bins), _ptr(tokens_per_expert), _ptr(padded_bins), _ptr(row_of),

@@ -8,15 +8,17 @@
 
 #include "act_math.h"
 #include "api_internal.h"
+#include "sputnik/block/router.h"
 #include "sputnik/sputnik.h"
 #include "metadata.h"
 #include "moe_permute.h"
-#include "moe_router.h"
 #include "sputnik_amd.h"
 
 using sputnik::block::BlockMatrix;
 using sputnik::block::BlockSize;
 using sputnik::block::Matrix;
+using sputnik::block::RouterType;
+using sputnik::block::WeightType;
 
 static_assert(sizeof(BlockMatrix) == 88, "BlockMatrix ABI");
 static_assert(sizeof(sputnik_block_matrix_t) == 88, "C BlockMatrix ABI");
@@ -546,9 +548,10 @@ int sputnik_router_topk(const void *logits, int32_t *top_experts,
                         void *weights, void *scores, int tokens,
                         int num_experts, int top_k, int normalize,
                         int logits_dtype, int weights_dtype, void *stream) {
-  return sputnik_amd::RunRouterTopK(logits, top_experts, weights, scores,
+  return sputnik::block::RouterTopK(logits, top_experts, weights, scores,
                                     tokens, num_experts, top_k, normalize != 0,
-                                    logits_dtype, weights_dtype,
+                                    static_cast<RouterType>(logits_dtype),
+                                    static_cast<WeightType>(weights_dtype),
                                     static_cast<hipStream_t>(stream));
 }
 
@@ -557,14 +560,15 @@ int sputnik_router_topk_grad(const void *logits, const int32_t *top_experts,
                              void *dlogits, int tokens, int num_experts,
                              int top_k, int normalize, int logits_dtype,
                              int weights_dtype, void *stream) {
-  return sputnik_amd::RunRouterTopKGrad(
+  return sputnik::block::RouterTopKGrad(
       logits, top_experts, dweights, dscores, dlogits, tokens, num_experts,
-      top_k, normalize != 0, logits_dtype, weights_dtype,
+      top_k, normalize != 0, static_cast<RouterType>(logits_dtype),
+      static_cast<WeightType>(weights_dtype),
       static_cast<hipStream_t>(stream));
 }
 
 size_t sputnik_router_aux_workspace_bytes(int tokens, int num_experts) {
-  return sputnik_amd::RouterAuxWorkspace(tokens, num_experts);
+  return sputnik::block::RouterAuxWorkspaceBytes(tokens, num_experts);
 }
 
 int sputnik_router_topk_aux(const void *logits, int32_t *top_experts,
@@ -573,10 +577,12 @@ int sputnik_router_topk_aux(const void *logits, int32_t *top_experts,
                             int top_k, int normalize, int logits_dtype,
                             int weights_dtype, void *workspace,
                             size_t workspace_bytes, void *stream) {
-  return sputnik_amd::RunRouterTopKAux(
+  return sputnik::block::RouterTopKAux(
       logits, top_experts, weights, scores, score_sums, z_sum, tokens,
-      num_experts, top_k, normalize != 0, logits_dtype, weights_dtype,
-      workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+      num_experts, top_k, normalize != 0,
+      static_cast<RouterType>(logits_dtype),
+      static_cast<WeightType>(weights_dtype), workspace, workspace_bytes,
+      static_cast<hipStream_t>(stream));
 }
 
 int sputnik_router_topk_aux_grad(const void *logits,
@@ -586,14 +592,16 @@ int sputnik_router_topk_aux_grad(const void *logits,
                                  void *dlogits, int tokens, int num_experts,
                                  int top_k, int normalize, int logits_dtype,
                                  int weights_dtype, void *stream) {
-  return sputnik_amd::RunRouterTopKAuxGrad(
+  return sputnik::block::RouterTopKAuxGrad(
       logits, top_experts, dweights, dscores, dscore_sums, dz_sum, dlogits,
-      tokens, num_experts, top_k, normalize != 0, logits_dtype, weights_dtype,
+      tokens, num_experts, top_k, normalize != 0,
+      static_cast<RouterType>(logits_dtype),
+      static_cast<WeightType>(weights_dtype),
       static_cast<hipStream_t>(stream));
 }
 
 size_t sputnik_moe_sort_workspace_bytes(int n, int num_experts) {
-  return sputnik_amd::MoeSortWorkspace(n, num_experts);
+  return sputnik::block::MoeSortWorkspaceBytes(n, num_experts);
 }
 
 int sputnik_moe_sort(const int32_t *top_experts, int n, int num_experts,
@@ -601,7 +609,7 @@ int sputnik_moe_sort(const int32_t *top_experts, int n, int num_experts,
                      int32_t *bins, int32_t *tokens_per_expert,
                      int32_t *padded_bins, int32_t *row_of, void *workspace,
                      size_t workspace_bytes, void *stream) {
-  return sputnik_amd::RunMoeSort(top_experts, n, num_experts, rows, indices,
+  return sputnik::block::MoeSort(top_experts, n, num_experts, rows, indices,
                                  bin_ids, bins, tokens_per_expert, padded_bins,
                                  row_of, workspace, workspace_bytes,
                                  static_cast<hipStream_t>(stream));

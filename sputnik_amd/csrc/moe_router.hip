@@ -27,8 +27,19 @@
 //           four waves meet in LDS and are added in wave order; the E + 1
 //           partials go to workspace[group]. A second launch adds the groups
 //           in ascending order, one thread per column. No atomics: the sums
-//           are a function of the input alone. The gradient kernel takes the
-//           sums' gradients as one [E] vector and one device scalar.
+//           are a function of the input alone. The gradient takes the sums'
+//           gradients as one [E] vector and one device scalar.
+//
+// Each pass is written once and instantiated twice on `bool kStats`:
+// router_topk_token is one token of RouterTopK (false: no accumulators) and of
+// RouterTopKAux (true), and router_topk_grad_kernel is RouterTopKGrad (false)
+// and RouterTopKAuxGrad (true; false again when it is given neither
+// statistic's gradient). That the plain and the aux results agree bit for bit
+// is therefore a property of the source: what only the statistics need sits
+// under `if constexpr (kStats)`, every other statement is shared.
+//
+// The host functions at the end are sputnik/block/router.h's own; the C-ABI
+// (c_api.cpp) calls them.
 //
 // Sort: chunks of kMoeSortChunk = 1024 assignments, one per thread.
 //   histogram  per chunk: LDS integer adds into E + 1 counters (column E
@@ -52,7 +63,6 @@
 #include <initializer_list>
 #include <type_traits>
 
-#include "moe_router.h"
 #include "sputnik/block/router.h"
 
 namespace sputnik_amd {
@@ -102,16 +112,17 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
   return k;
 }
 
-// One token of router_topk_aux_kernel, by one wave: router_topk_kernel's body
-// (the same key order, the same fp32 expressions), with the token's unrounded
-// probabilities added to acc[j] (column lane + 64 j) and its (m + log s)^2 to
-// zacc, the same value in every lane.
-template <typename T, typename W, int kPer>
-__device__ __forceinline__ void router_topk_aux_token(
+// One token of the forward pass, by one wave: the body of router_topk_kernel
+// (kStats false; acc and zacc are not touched and may be null) and of
+// router_topk_aux_kernel (kStats true), which also adds the token's unrounded
+// probabilities to acc[j] (column lane + 64 j, kPer registers) and its
+// (m + log s)^2 to *zacc, the same value in every lane.
+template <typename T, typename W, int kPer, bool kStats>
+__device__ __forceinline__ void router_topk_token(
     const T *__restrict__ logits, int *__restrict__ top_experts,
     W *__restrict__ weights, W *__restrict__ scores, long long t,
-    int num_experts, int top_k, int normalize, int lane, float (&acc)[kPer],
-    float &zacc) {
+    int num_experts, int top_k, int normalize, int lane, float *acc,
+    float *zacc) {
   const T *row = logits + t * num_experts;
   float v[kPer];
   unsigned long long key[kPer];
@@ -154,15 +165,24 @@ __device__ __forceinline__ void router_topk_aux_token(
     top_experts[t * top_k + lane] = my_id;
     weights[t * top_k + lane] = (W)p;
   }
-  const float lse = m + logf(s);
-  zacc += lse * lse;
+  if constexpr (kStats) {
+    const float lse = m + logf(s);
+    *zacc += lse * lse;
 #pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const int e = lane + 64 * j;
-    if (e < num_experts) {
-      const float pe = expf(v[j] - m) / s;
-      acc[j] += pe;
-      if (scores != nullptr) scores[t * num_experts + e] = (W)pe;
+    for (int j = 0; j < kPer; ++j) {
+      const int e = lane + 64 * j;
+      if (e < num_experts) {
+        const float pe = expf(v[j] - m) / s;
+        acc[j] += pe;
+        if (scores != nullptr) scores[t * num_experts + e] = (W)pe;
+      }
+    }
+  } else if (scores != nullptr) {
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      const int e = lane + 64 * j;
+      if (e < num_experts)
+        scores[t * num_experts + e] = (W)(expf(v[j] - m) / s);
     }
   }
 }
@@ -173,59 +193,11 @@ __global__ void __launch_bounds__(kThreads)
                        int *__restrict__ top_experts, W *__restrict__ weights,
                        W *__restrict__ scores, int tokens, int num_experts,
                        int top_k, int normalize) {
-  const int lane = threadIdx.x & 63;
   const long long t = (long long)blockIdx.x * kWaves + wave_index();
   if (t >= tokens) return;
-  const T *row = logits + t * num_experts;
-  float v[kPer];
-  unsigned long long key[kPer];
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const int e = lane + 64 * j;
-    const bool live = e < num_experts;
-    v[j] = live ? (float)row[e] : 0.0f;
-    key[j] = live ? ((unsigned long long)order_image(v[j]) << 32) |
-                        (uint32_t)~e
-                  : 0ull;
-  }
-  float m = 0.0f, my_val = 0.0f;
-  int my_id = 0;
-  for (int r = 0; r < top_k; ++r) {
-    unsigned long long best = key[0];
-#pragma unroll
-    for (int j = 1; j < kPer; ++j) best = key[j] > best ? key[j] : best;
-    best = wave_max(best);
-    // (top_k <= num_experts: a live key remains, so idx is in [0, E))
-    const int idx = (int)~(uint32_t)best;
-    const float val = image_value((uint32_t)(best >> 32));
-    if (r == 0) m = val;
-    if (lane == r) {
-      my_id = idx;
-      my_val = val;
-    }
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-      if (idx == lane + 64 * j) key[j] = 0ull;
-  }
-  float s = 0.0f;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j)
-    if (lane + 64 * j < num_experts) s += expf(v[j] - m);
-  s = wave_sum(s);
-  float p = lane < top_k ? expf(my_val - m) / s : 0.0f;
-  if (normalize) p = p / wave_sum(p);
-  if (lane < top_k) {
-    top_experts[t * top_k + lane] = my_id;
-    weights[t * top_k + lane] = (W)p;
-  }
-  if (scores != nullptr) {
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      const int e = lane + 64 * j;
-      if (e < num_experts)
-        scores[t * num_experts + e] = (W)(expf(v[j] - m) / s);
-    }
-  }
+  router_topk_token<T, W, kPer, false>(logits, top_experts, weights, scores, t,
+                                       num_experts, top_k, normalize,
+                                       threadIdx.x & 63, nullptr, nullptr);
 }
 
 // RouterTopK plus the column sums of the probabilities and the sum of
@@ -250,9 +222,9 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
   for (int j = 0; j < kPer; ++j) acc[j] = 0.0f;
   for (int i = 0; i < kAuxPerWave && t0 + i < tokens; ++i)
-    router_topk_aux_token<T, W, kPer>(logits, top_experts, weights, scores,
-                                      t0 + i, num_experts, top_k, normalize,
-                                      lane, acc, zacc);
+    router_topk_token<T, W, kPer, true>(logits, top_experts, weights, scores,
+                                        t0 + i, num_experts, top_k, normalize,
+                                        lane, acc, &zacc);
 #pragma unroll
   for (int j = 0; j < kPer; ++j) cols[wave][lane + 64 * j] = acc[j];
   if (lane == 0) zs[wave] = zacc;
@@ -284,12 +256,18 @@ __global__ void __launch_bounds__(kThreads)
     z_sum[0] = sum;
 }
 
-template <typename T, typename W, int kPer>
+// The gradient of both forward passes. kStats false: RouterTopKGrad, and
+// RouterTopKAuxGrad given neither statistic's gradient (dscore_sums and dz_sum
+// are not looked at). kStats true: dscore_sums[e] (when not null) joins dp and
+// 2 dz (m + log s) p_j (when dz_sum is not null) the result.
+template <typename T, typename W, int kPer, bool kStats>
 __global__ void __launch_bounds__(kThreads)
     router_topk_grad_kernel(const T *__restrict__ logits,
                             const int *__restrict__ top_experts,
                             const W *__restrict__ dweights,
                             const W *__restrict__ dscores,
+                            const float *__restrict__ dscore_sums,
+                            const float *__restrict__ dz_sum,
                             T *__restrict__ dlogits, int tokens,
                             int num_experts, int top_k, int normalize) {
   const int lane = threadIdx.x & 63;
@@ -305,6 +283,8 @@ __global__ void __launch_bounds__(kThreads)
     v[j] = live ? (float)row[e] : 0.0f;
     dp[j] = live && dscores != nullptr
                 ? (float)dscores[t * num_experts + e] : 0.0f;
+    if constexpr (kStats)
+      if (live && dscore_sums != nullptr) dp[j] += dscore_sums[e];
     if (live) m = fmaxf(m, v[j]);
   }
 #pragma unroll
@@ -348,91 +328,16 @@ __global__ void __launch_bounds__(kThreads)
     if (live) dot += dp[j] * p[j];
   }
   dot = wave_sum(dot);
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const int e = lane + 64 * j;
-    if (e < num_experts)
-      dlogits[t * num_experts + e] = (T)(p[j] * (dp[j] - dot));
-  }
-}
-
-// router_topk_grad_kernel with dscore_sums[e] (when not null) joining dp and
-// 2 dz (m + log s) p_j (when dz_sum is not null) the result.
-template <typename T, typename W, int kPer>
-__global__ void __launch_bounds__(kThreads)
-    router_topk_aux_grad_kernel(const T *__restrict__ logits,
-                                const int *__restrict__ top_experts,
-                                const W *__restrict__ dweights,
-                                const W *__restrict__ dscores,
-                                const float *__restrict__ dscore_sums,
-                                const float *__restrict__ dz_sum,
-                                T *__restrict__ dlogits, int tokens,
-                                int num_experts, int top_k, int normalize) {
-  const int lane = threadIdx.x & 63;
-  const long long t = (long long)blockIdx.x * kWaves + wave_index();
-  if (t >= tokens) return;
-  const T *row = logits + t * num_experts;
-  float v[kPer], dp[kPer];
-  float m = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const int e = lane + 64 * j;
-    const bool live = e < num_experts;
-    v[j] = live ? (float)row[e] : 0.0f;
-    dp[j] = live && dscores != nullptr
-                ? (float)dscores[t * num_experts + e] : 0.0f;
-    if (live && dscore_sums != nullptr) dp[j] += dscore_sums[e];
-    if (live) m = fmaxf(m, v[j]);
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-  float s = 0.0f;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j)
-    if (lane + 64 * j < num_experts) s += expf(v[j] - m);
-  s = wave_sum(s);
-
-  // Lane r < top_k holds pick r: its id (-1 when out of range), its incoming
-  // gradient and, for normalize, its probability.
-  int id = -1;
-  float g = 0.0f;
-  if (lane < top_k) {
-    const int raw = top_experts[t * top_k + lane];
-    if (raw >= 0 && raw < num_experts) {
-      id = raw;
-      g = (float)dweights[t * top_k + lane];
-    }
-  }
-  if (normalize) {
-    const float psel = id >= 0 ? expf((float)row[id] - m) / s : 0.0f;
-    const float total = wave_sum(psel);             // S
-    const float c = wave_sum(g * psel) / total;     // sum_j dw_j w_j
-    g = id >= 0 ? (g - c) / total : 0.0f;
-  }
-  for (int r = 0; r < top_k; ++r) {
-    const int rid = __shfl(id, r, 64);
-    const float rg = __shfl(g, r, 64);
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-      if (rid == lane + 64 * j) dp[j] += rg;
-  }
-  float p[kPer];
-  float dot = 0.0f;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const bool live = lane + 64 * j < num_experts;
-    p[j] = live ? expf(v[j] - m) / s : 0.0f;
-    if (live) dot += dp[j] * p[j];
-  }
-  dot = wave_sum(dot);
-  float zc = 0.0f;  // 2 dz lse
-  if (dz_sum != nullptr) zc = 2.0f * dz_sum[0] * (m + logf(s));
+  [[maybe_unused]] float zc = 0.0f;  // 2 dz lse
+  if constexpr (kStats)
+    if (dz_sum != nullptr) zc = 2.0f * dz_sum[0] * (m + logf(s));
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
     const int e = lane + 64 * j;
     if (e < num_experts) {
       float out = p[j] * (dp[j] - dot);
-      if (dz_sum != nullptr) out += zc * p[j];
+      if constexpr (kStats)
+        if (dz_sum != nullptr) out += zc * p[j];
       dlogits[t * num_experts + e] = (T)out;
     }
   }
@@ -587,43 +492,79 @@ __global__ void __launch_bounds__(kSortThreads)
   row_of[i] = row;
 }
 
-// ---- launchers ----------------------------------------------------------------
+// ---- host: sputnik/block/router.h ---------------------------------------------
 
-bool RouterSizesOk(int tokens, int num_experts, int top_k, int logits_dtype,
-                   int weights_dtype) {
-  return tokens >= 0 && num_experts >= 1 && num_experts <= kMaxExperts &&
-         top_k >= 1 && top_k <= kMaxTopK && top_k <= num_experts &&
-         logits_dtype >= 0 && logits_dtype <= 2 &&
-         (weights_dtype == 0 || weights_dtype == 1);
-}
+using Buffers = std::initializer_list<const void *>;
 
-bool Distinct(std::initializer_list<const void *> ptrs) {
-  for (auto a = ptrs.begin(); a != ptrs.end(); ++a)
-    for (auto b = a + 1; b != ptrs.end(); ++b)
-      if (*a != nullptr && *a == *b) return false;
+// No output is one of the inputs or another output (null: absent).
+bool Distinct(Buffers outs, Buffers ins) {
+  for (auto a = outs.begin(); a != outs.end(); ++a) {
+    if (*a == nullptr) continue;
+    for (auto b = a + 1; b != outs.end(); ++b)
+      if (*a == *b) return false;
+    for (const void *in : ins)
+      if (*a == in) return false;
+  }
   return true;
 }
 
-// f(T, W, kPer) for the call's types and expert count.
-template <typename F>
-hipError_t WithRouterTypes(int logits_dtype, int weights_dtype,
-                           int num_experts, F f) {
+// What the four router calls check first: the sizes and types and, unless
+// there are no tokens, that every required buffer is there.
+bool RouterArgsOk(int tokens, int num_experts, int top_k,
+                  sputnik::block::RouterType logits_type,
+                  sputnik::block::WeightType weights_type, Buffers required) {
+  const int l = (int)logits_type, w = (int)weights_type;
+  if (tokens < 0 || num_experts < 1 || num_experts > kMaxExperts ||
+      top_k < 1 || top_k > kMaxTopK || top_k > num_experts || l < 0 ||
+      l > 2 || (w != 0 && w != 1))
+    return false;
+  for (const void *p : required)
+    if (tokens > 0 && p == nullptr) return false;
+  return true;
+}
+
+// The arguments converted to the kernel's parameter types (void pointers to
+// its T and W pointers).
+template <typename... P, typename... A>
+void Enqueue(void (*kernel)(P...), unsigned grid, hipStream_t stream,
+             A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, stream,
+                     (P)args...);
+}
+
+// Enqueues pick(T{}, W{}, kPer), the call's kernel for its types and expert
+// count, over `grid` workgroups.
+template <typename Pick, typename... A>
+hipError_t LaunchRouter(sputnik::block::RouterType logits_type,
+                        sputnik::block::WeightType weights_type,
+                        int num_experts, unsigned grid, hipStream_t stream,
+                        Pick pick, A... args) {
   auto with_per = [&](auto t, auto w) {
-    using T = decltype(t);
-    using W = decltype(w);
     const int per = (num_experts + 63) / 64;
-    if (per <= 1) return f(T{}, W{}, std::integral_constant<int, 1>{});
-    if (per <= 2) return f(T{}, W{}, std::integral_constant<int, 2>{});
-    if (per <= 4) return f(T{}, W{}, std::integral_constant<int, 4>{});
-    if (per <= 8) return f(T{}, W{}, std::integral_constant<int, 8>{});
-    return f(T{}, W{}, std::integral_constant<int, 16>{});
+    if (per <= 1)
+      Enqueue(pick(t, w, std::integral_constant<int, 1>{}), grid, stream,
+              args...);
+    else if (per <= 2)
+      Enqueue(pick(t, w, std::integral_constant<int, 2>{}), grid, stream,
+              args...);
+    else if (per <= 4)
+      Enqueue(pick(t, w, std::integral_constant<int, 4>{}), grid, stream,
+              args...);
+    else if (per <= 8)
+      Enqueue(pick(t, w, std::integral_constant<int, 8>{}), grid, stream,
+              args...);
+    else
+      Enqueue(pick(t, w, std::integral_constant<int, 16>{}), grid, stream,
+              args...);
   };
-  const bool f32 = weights_dtype == 1;
-  if (logits_dtype == 2) return with_per(float{}, float{});
-  if (logits_dtype == 1)
-    return f32 ? with_per(__bf16{}, float{}) : with_per(__bf16{}, __bf16{});
-  return f32 ? with_per(_Float16{}, float{})
-             : with_per(_Float16{}, _Float16{});
+  const bool f32 = weights_type == sputnik::block::WeightType::kF32;
+  if (logits_type == sputnik::block::RouterType::kF32)
+    with_per(float{}, float{});
+  else if (logits_type == sputnik::block::RouterType::kBF16)
+    f32 ? with_per(__bf16{}, float{}) : with_per(__bf16{}, __bf16{});
+  else
+    f32 ? with_per(_Float16{}, float{}) : with_per(_Float16{}, _Float16{});
+  return hipGetLastError();
 }
 
 unsigned TokenGrid(int tokens) {
@@ -631,101 +572,69 @@ unsigned TokenGrid(int tokens) {
 }
 
 }  // namespace
+}  // namespace sputnik_amd
 
-hipError_t RunRouterTopK(const void *logits, int *top_experts, void *weights,
-                         void *scores, int tokens, int num_experts, int top_k,
-                         bool normalize, int logits_dtype, int weights_dtype,
-                         hipStream_t stream) {
-  if (!RouterSizesOk(tokens, num_experts, top_k, logits_dtype, weights_dtype))
+namespace sputnik {
+namespace block {
+
+using namespace sputnik_amd;  // NOLINT: the kernels and helpers above
+
+hipError_t RouterTopK(const void *logits, int *top_experts, void *weights,
+                      void *scores, int tokens, int num_experts, int top_k,
+                      bool normalize, RouterType logits_type,
+                      WeightType weights_type, hipStream_t stream) {
+  if (!RouterArgsOk(tokens, num_experts, top_k, logits_type, weights_type,
+                    {logits, top_experts, weights}))
     return hipErrorInvalidValue;
   if (tokens == 0) return hipSuccess;
-  if (logits == nullptr || top_experts == nullptr || weights == nullptr)
+  if (!Distinct({top_experts, weights, scores}, {logits}))
     return hipErrorInvalidValue;
-  if (!Distinct({logits, top_experts, weights, scores}))
-    return hipErrorInvalidValue;
-  return WithRouterTypes(logits_dtype, weights_dtype, num_experts,
-                         [&](auto t, auto w, auto per) {
-    using T = decltype(t);
-    using W = decltype(w);
-    hipLaunchKernelGGL((router_topk_kernel<T, W, decltype(per)::value>),
-                       dim3(TokenGrid(tokens)), dim3(kThreads), 0, stream,
-                       static_cast<const T *>(logits), top_experts,
-                       static_cast<W *>(weights), static_cast<W *>(scores),
-                       tokens, num_experts, top_k, normalize ? 1 : 0);
-    return hipGetLastError();
-  });
+  return LaunchRouter(
+      logits_type, weights_type, num_experts, TokenGrid(tokens), stream,
+      [](auto t, auto w, auto per) {
+        return router_topk_kernel<decltype(t), decltype(w),
+                                  decltype(per)::value>;
+      },
+      logits, top_experts, weights, scores, tokens, num_experts, top_k,
+      normalize ? 1 : 0);
 }
 
-hipError_t RunRouterTopKGrad(const void *logits, const int *top_experts,
-                             const void *dweights, const void *dscores,
-                             void *dlogits, int tokens, int num_experts,
-                             int top_k, bool normalize, int logits_dtype,
-                             int weights_dtype, hipStream_t stream) {
-  if (!RouterSizesOk(tokens, num_experts, top_k, logits_dtype, weights_dtype))
-    return hipErrorInvalidValue;
-  if (tokens == 0) return hipSuccess;
-  if (logits == nullptr || top_experts == nullptr || dweights == nullptr ||
-      dlogits == nullptr)
-    return hipErrorInvalidValue;
-  if (dlogits == logits || dlogits == top_experts || dlogits == dweights ||
-      dlogits == dscores)
-    return hipErrorInvalidValue;
-  return WithRouterTypes(logits_dtype, weights_dtype, num_experts,
-                         [&](auto t, auto w, auto per) {
-    using T = decltype(t);
-    using W = decltype(w);
-    hipLaunchKernelGGL((router_topk_grad_kernel<T, W, decltype(per)::value>),
-                       dim3(TokenGrid(tokens)), dim3(kThreads), 0, stream,
-                       static_cast<const T *>(logits), top_experts,
-                       static_cast<const W *>(dweights),
-                       static_cast<const W *>(dscores),
-                       static_cast<T *>(dlogits), tokens, num_experts, top_k,
-                       normalize ? 1 : 0);
-    return hipGetLastError();
-  });
-}
-
-size_t RouterAuxWorkspace(int tokens, int num_experts) {
+size_t RouterAuxWorkspaceBytes(int tokens, int num_experts) {
   if (tokens < 0 || num_experts < 1 || num_experts > kMaxExperts) return 0;
   const size_t groups = ((size_t)tokens + kAuxTokens - 1) / kAuxTokens;
   return groups * (size_t)(num_experts + 1) * sizeof(float);
 }
 
-hipError_t RunRouterTopKAux(const void *logits, int *top_experts,
-                            void *weights, void *scores, float *score_sums,
-                            float *z_sum, int tokens, int num_experts,
-                            int top_k, bool normalize, int logits_dtype,
-                            int weights_dtype, void *workspace,
-                            size_t workspace_bytes, hipStream_t stream) {
-  if (!RouterSizesOk(tokens, num_experts, top_k, logits_dtype, weights_dtype))
+hipError_t RouterTopKAux(const void *logits, int *top_experts, void *weights,
+                         void *scores, float *score_sums, float *z_sum,
+                         int tokens, int num_experts, int top_k,
+                         bool normalize, RouterType logits_type,
+                         WeightType weights_type, void *workspace,
+                         size_t workspace_bytes, hipStream_t stream) {
+  if (!RouterArgsOk(tokens, num_experts, top_k, logits_type, weights_type,
+                    {logits, top_experts, weights, workspace}))
     return hipErrorInvalidValue;
-  if (score_sums == nullptr) return hipErrorInvalidValue;
+  // (the sums are written even for no tokens)
+  if (score_sums == nullptr ||
+      !Distinct({top_experts, weights, scores, score_sums, z_sum, workspace},
+                {logits}))
+    return hipErrorInvalidValue;
   if (tokens > 0 &&
-      (logits == nullptr || top_experts == nullptr || weights == nullptr ||
-       workspace == nullptr ||
-       workspace_bytes < RouterAuxWorkspace(tokens, num_experts) ||
+      (workspace_bytes < RouterAuxWorkspaceBytes(tokens, num_experts) ||
        reinterpret_cast<uintptr_t>(workspace) % alignof(float) != 0))
-    return hipErrorInvalidValue;
-  if (!Distinct({logits, top_experts, weights, scores, score_sums, z_sum,
-                 workspace}))
     return hipErrorInvalidValue;
   float *partial = static_cast<float *>(workspace);
   const unsigned groups =
       (unsigned)(((long long)tokens + kAuxTokens - 1) / kAuxTokens);
   if (groups > 0) {
-    const hipError_t e = WithRouterTypes(
-        logits_dtype, weights_dtype, num_experts,
-        [&](auto t, auto w, auto per) {
-          using T = decltype(t);
-          using W = decltype(w);
-          hipLaunchKernelGGL(
-              (router_topk_aux_kernel<T, W, decltype(per)::value>),
-              dim3(groups), dim3(kThreads), 0, stream,
-              static_cast<const T *>(logits), top_experts,
-              static_cast<W *>(weights), static_cast<W *>(scores), partial,
-              tokens, num_experts, top_k, normalize ? 1 : 0);
-          return hipGetLastError();
-        });
+    const hipError_t e = LaunchRouter(
+        logits_type, weights_type, num_experts, groups, stream,
+        [](auto t, auto w, auto per) {
+          return router_topk_aux_kernel<decltype(t), decltype(w),
+                                        decltype(per)::value>;
+        },
+        logits, top_experts, weights, scores, partial, tokens, num_experts,
+        top_k, normalize ? 1 : 0);
     if (e != hipSuccess) return e;
   }
   // (no tokens: no groups, and the sums are written as zeros)
@@ -736,44 +645,46 @@ hipError_t RunRouterTopKAux(const void *logits, int *top_experts,
   return hipGetLastError();
 }
 
-hipError_t RunRouterTopKAuxGrad(const void *logits, const int *top_experts,
-                                const void *dweights, const void *dscores,
-                                const float *dscore_sums, const float *dz_sum,
-                                void *dlogits, int tokens, int num_experts,
-                                int top_k, bool normalize, int logits_dtype,
-                                int weights_dtype, hipStream_t stream) {
-  if (!RouterSizesOk(tokens, num_experts, top_k, logits_dtype, weights_dtype))
+// Neither statistic's gradient: the kStats = false instantiation, which is
+// RouterTopKGrad's, so the result is its bit for bit by construction.
+hipError_t RouterTopKAuxGrad(const void *logits, const int *top_experts,
+                             const void *dweights, const void *dscores,
+                             const float *dscore_sums, const float *dz_sum,
+                             void *dlogits, int tokens, int num_experts,
+                             int top_k, bool normalize, RouterType logits_type,
+                             WeightType weights_type, hipStream_t stream) {
+  if (!RouterArgsOk(tokens, num_experts, top_k, logits_type, weights_type,
+                    {logits, top_experts, dweights, dlogits}))
     return hipErrorInvalidValue;
   if (tokens == 0) return hipSuccess;
-  if (logits == nullptr || top_experts == nullptr || dweights == nullptr ||
-      dlogits == nullptr)
+  if (!Distinct({dlogits}, {logits, top_experts, dweights, dscores,
+                            dscore_sums, dz_sum}))
     return hipErrorInvalidValue;
-  if (dlogits == logits || dlogits == top_experts || dlogits == dweights ||
-      dlogits == dscores || dlogits == dscore_sums || dlogits == dz_sum)
-    return hipErrorInvalidValue;
-  // Neither statistic's gradient: RouterTopKGrad's own kernel, so the result
-  // is its bit for bit by construction (the two kernels' code is scheduled
-  // and contracted separately by the compiler).
-  if (dscore_sums == nullptr && dz_sum == nullptr)
-    return RunRouterTopKGrad(logits, top_experts, dweights, dscores, dlogits,
-                             tokens, num_experts, top_k, normalize,
-                             logits_dtype, weights_dtype, stream);
-  return WithRouterTypes(logits_dtype, weights_dtype, num_experts,
-                         [&](auto t, auto w, auto per) {
-    using T = decltype(t);
-    using W = decltype(w);
-    hipLaunchKernelGGL(
-        (router_topk_aux_grad_kernel<T, W, decltype(per)::value>),
-        dim3(TokenGrid(tokens)), dim3(kThreads), 0, stream,
-        static_cast<const T *>(logits), top_experts,
-        static_cast<const W *>(dweights), static_cast<const W *>(dscores),
-        dscore_sums, dz_sum, static_cast<T *>(dlogits), tokens, num_experts,
-        top_k, normalize ? 1 : 0);
-    return hipGetLastError();
-  });
+  const bool stats = dscore_sums != nullptr || dz_sum != nullptr;
+  return LaunchRouter(
+      logits_type, weights_type, num_experts, TokenGrid(tokens), stream,
+      [stats](auto t, auto w, auto per) {
+        using T = decltype(t);
+        using W = decltype(w);
+        constexpr int kPer = decltype(per)::value;
+        return stats ? router_topk_grad_kernel<T, W, kPer, true>
+                     : router_topk_grad_kernel<T, W, kPer, false>;
+      },
+      logits, top_experts, dweights, dscores, dscore_sums, dz_sum, dlogits,
+      tokens, num_experts, top_k, normalize ? 1 : 0);
 }
 
-size_t MoeSortWorkspace(int n, int num_experts) {
+hipError_t RouterTopKGrad(const void *logits, const int *top_experts,
+                          const void *dweights, const void *dscores,
+                          void *dlogits, int tokens, int num_experts,
+                          int top_k, bool normalize, RouterType logits_type,
+                          WeightType weights_type, hipStream_t stream) {
+  return RouterTopKAuxGrad(logits, top_experts, dweights, dscores, nullptr,
+                           nullptr, dlogits, tokens, num_experts, top_k,
+                           normalize, logits_type, weights_type, stream);
+}
+
+size_t MoeSortWorkspaceBytes(int n, int num_experts) {
   if (n < 0 || num_experts < 1 || num_experts > kMaxExperts ||
       (long long)n + 127LL * num_experts > INT_MAX)
     return 0;
@@ -781,25 +692,25 @@ size_t MoeSortWorkspace(int n, int num_experts) {
   return chunks * (size_t)(num_experts + 1) * sizeof(int);
 }
 
-hipError_t RunMoeSort(const int *top_experts, int n, int num_experts, int rows,
-                      int *indices, int *bin_ids, int *bins,
-                      int *tokens_per_expert, int *padded_bins, int *row_of,
-                      void *workspace, size_t workspace_bytes,
-                      hipStream_t stream) {
+hipError_t MoeSort(const int *top_experts, int n, int num_experts, int rows,
+                   int *indices, int *bin_ids, int *bins,
+                   int *tokens_per_expert, int *padded_bins, int *row_of,
+                   void *workspace, size_t workspace_bytes,
+                   hipStream_t stream) {
   if (n < 0 || num_experts < 1 || num_experts > kMaxExperts || rows < 0 ||
       rows % 128 != 0 || (long long)n + 127LL * num_experts > INT_MAX)
     return hipErrorInvalidValue;
   if (bins == nullptr || tokens_per_expert == nullptr ||
       padded_bins == nullptr)
     return hipErrorInvalidValue;
-  const size_t need = MoeSortWorkspace(n, num_experts);
+  const size_t need = MoeSortWorkspaceBytes(n, num_experts);
   if (n > 0 &&
       (top_experts == nullptr || indices == nullptr || bin_ids == nullptr ||
        row_of == nullptr || workspace == nullptr || workspace_bytes < need ||
        reinterpret_cast<uintptr_t>(workspace) % alignof(int) != 0))
     return hipErrorInvalidValue;
-  if (!Distinct({top_experts, indices, bin_ids, bins, tokens_per_expert,
-                 padded_bins, row_of, workspace}))
+  if (!Distinct({indices, bin_ids, bins, tokens_per_expert, padded_bins,
+                 row_of, workspace}, {top_experts}))
     return hipErrorInvalidValue;
   int *counts = static_cast<int *>(workspace);
   const int chunks = (int)(((long long)n + kChunk - 1) / kChunk);
@@ -821,74 +732,6 @@ hipError_t RunMoeSort(const int *top_experts, int n, int num_experts, int rows,
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
   return hipSuccess;
-}
-
-}  // namespace sputnik_amd
-
-namespace sputnik {
-namespace block {
-
-hipError_t RouterTopK(const void *logits, int *top_experts, void *weights,
-                      void *scores, int tokens, int num_experts, int top_k,
-                      bool normalize, RouterType logits_type,
-                      WeightType weights_type, hipStream_t stream) {
-  return sputnik_amd::RunRouterTopK(logits, top_experts, weights, scores,
-                                    tokens, num_experts, top_k, normalize,
-                                    (int)logits_type, (int)weights_type,
-                                    stream);
-}
-
-hipError_t RouterTopKGrad(const void *logits, const int *top_experts,
-                          const void *dweights, const void *dscores,
-                          void *dlogits, int tokens, int num_experts,
-                          int top_k, bool normalize, RouterType logits_type,
-                          WeightType weights_type, hipStream_t stream) {
-  return sputnik_amd::RunRouterTopKGrad(logits, top_experts, dweights, dscores,
-                                        dlogits, tokens, num_experts, top_k,
-                                        normalize, (int)logits_type,
-                                        (int)weights_type, stream);
-}
-
-size_t RouterAuxWorkspaceBytes(int tokens, int num_experts) {
-  return sputnik_amd::RouterAuxWorkspace(tokens, num_experts);
-}
-
-hipError_t RouterTopKAux(const void *logits, int *top_experts, void *weights,
-                         void *scores, float *score_sums, float *z_sum,
-                         int tokens, int num_experts, int top_k,
-                         bool normalize, RouterType logits_type,
-                         WeightType weights_type, void *workspace,
-                         size_t workspace_bytes, hipStream_t stream) {
-  return sputnik_amd::RunRouterTopKAux(
-      logits, top_experts, weights, scores, score_sums, z_sum, tokens,
-      num_experts, top_k, normalize, (int)logits_type, (int)weights_type,
-      workspace, workspace_bytes, stream);
-}
-
-hipError_t RouterTopKAuxGrad(const void *logits, const int *top_experts,
-                             const void *dweights, const void *dscores,
-                             const float *dscore_sums, const float *dz_sum,
-                             void *dlogits, int tokens, int num_experts,
-                             int top_k, bool normalize, RouterType logits_type,
-                             WeightType weights_type, hipStream_t stream) {
-  return sputnik_amd::RunRouterTopKAuxGrad(
-      logits, top_experts, dweights, dscores, dscore_sums, dz_sum, dlogits,
-      tokens, num_experts, top_k, normalize, (int)logits_type,
-      (int)weights_type, stream);
-}
-
-size_t MoeSortWorkspaceBytes(int n, int num_experts) {
-  return sputnik_amd::MoeSortWorkspace(n, num_experts);
-}
-
-hipError_t MoeSort(const int *top_experts, int n, int num_experts, int rows,
-                   int *indices, int *bin_ids, int *bins,
-                   int *tokens_per_expert, int *padded_bins, int *row_of,
-                   void *workspace, size_t workspace_bytes,
-                   hipStream_t stream) {
-  return sputnik_amd::RunMoeSort(top_experts, n, num_experts, rows, indices,
-                                 bin_ids, bins, tokens_per_expert, padded_bins,
-                                 row_of, workspace, workspace_bytes, stream);
 }
 
 }  // namespace block

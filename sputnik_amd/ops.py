@@ -1105,36 +1105,56 @@ def moe_mlp(x: torch.Tensor, top_experts: torch.Tensor,
 
 # ---- MoE router -------------------------------------------------------------
 
+def _router_forward(ctx, logits, top_k, normalize, dtype):
+    """What _Router and _RouterAux begin with: (contiguous logits, top,
+    weights), the outputs allocated, and the context set up for
+    _router_backward (top carries no gradient, absent gradients stay None)."""
+    logits = logits.contiguous()
+    tokens = logits.shape[0]
+    top = torch.empty(tokens, top_k, dtype=torch.int32, device=logits.device)
+    weights = torch.empty(tokens, top_k, dtype=dtype, device=logits.device)
+    ctx.save_for_backward(logits, top)
+    ctx.normalize = normalize
+    ctx.dtype = dtype
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(top)
+    return logits, top, weights
+
+
+def _router_backward(ctx, dweights, *others):
+    """(logits, top, dweights, dlogits) for the gradient call, an absent
+    dweights as zeros; None when every incoming gradient is absent."""
+    if dweights is None and all(g is None for g in others):
+        return None
+    logits, top = ctx.saved_tensors
+    if dweights is None:
+        dweights = torch.zeros(top.shape, dtype=ctx.dtype,
+                               device=logits.device)
+    return logits, top, dweights.contiguous(), torch.empty_like(logits)
+
+
+def _contiguous(g):
+    return None if g is None else g.contiguous()
+
+
 class _Router(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, top_k, normalize, dtype, return_scores):
-        logits = logits.contiguous()
-        tokens, e = logits.shape
-        dev = logits.device
-        top = torch.empty(tokens, top_k, dtype=torch.int32, device=dev)
-        weights = torch.empty(tokens, top_k, dtype=dtype, device=dev)
-        scores = (torch.empty(tokens, e, dtype=dtype, device=dev)
+        logits, top, weights = _router_forward(ctx, logits, top_k, normalize,
+                                               dtype)
+        scores = (torch.empty(logits.shape, dtype=dtype, device=logits.device)
                   if return_scores else None)
         RouterTopK(logits, top, weights, normalize, scores)
-        ctx.save_for_backward(logits, top)
-        ctx.normalize = normalize
-        ctx.dtype = dtype
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(top)
         return (weights, top, scores) if return_scores else (weights, top)
 
     @staticmethod
     def backward(ctx, dweights, _dtop, dscores=None):
-        logits, top = ctx.saved_tensors
-        if dweights is None and dscores is None:
+        args = _router_backward(ctx, dweights, dscores)
+        if args is None:
             return None, None, None, None, None
-        if dweights is None:
-            dweights = torch.zeros(top.shape, dtype=ctx.dtype,
-                                   device=logits.device)
-        dlogits = torch.empty_like(logits)
-        RouterTopKGrad(logits, top, dweights.contiguous(), dlogits,
-                       ctx.normalize,
-                       None if dscores is None else dscores.contiguous())
+        logits, top, dweights, dlogits = args
+        RouterTopKGrad(logits, top, dweights, dlogits, ctx.normalize,
+                       _contiguous(dscores))
         return dlogits, None, None, None, None
 
 
@@ -1183,37 +1203,26 @@ def moe_router(logits: torch.Tensor, top_k: int, normalize: bool = False,
 class _RouterAux(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, top_k, normalize, dtype):
-        logits = logits.contiguous()
+        logits, top, weights = _router_forward(ctx, logits, top_k, normalize,
+                                               dtype)
         tokens, e = logits.shape
         dev = logits.device
-        top = torch.empty(tokens, top_k, dtype=torch.int32, device=dev)
-        weights = torch.empty(tokens, top_k, dtype=dtype, device=dev)
         score_sums = torch.empty(e, dtype=torch.float32, device=dev)
         z_sum = torch.empty(1, dtype=torch.float32, device=dev)
         groups = (tokens + ROUTER_AUX_TOKENS - 1) // ROUTER_AUX_TOKENS
         ws = _bt_workspace(groups * (e + 1) * 4, dev)
         RouterTopKAux(logits, top, weights, score_sums, ws, normalize, None,
                       z_sum)
-        ctx.save_for_backward(logits, top)
-        ctx.normalize = normalize
-        ctx.dtype = dtype
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(top)
         return weights, top, score_sums, z_sum
 
     @staticmethod
     def backward(ctx, dweights, _dtop, dscore_sums, dz_sum):
-        logits, top = ctx.saved_tensors
-        if dweights is None and dscore_sums is None and dz_sum is None:
+        args = _router_backward(ctx, dweights, dscore_sums, dz_sum)
+        if args is None:
             return None, None, None, None
-        if dweights is None:
-            dweights = torch.zeros(top.shape, dtype=ctx.dtype,
-                                   device=logits.device)
-        dlogits = torch.empty_like(logits)
-        RouterTopKAuxGrad(
-            logits, top, dweights.contiguous(), dlogits, ctx.normalize, None,
-            None if dscore_sums is None else dscore_sums.contiguous(),
-            None if dz_sum is None else dz_sum.contiguous())
+        logits, top, dweights, dlogits = args
+        RouterTopKAuxGrad(logits, top, dweights, dlogits, ctx.normalize, None,
+                          _contiguous(dscore_sums), _contiguous(dz_sum))
         return dlogits, None, None, None
 
 
