@@ -60,6 +60,43 @@
 //                   + the pick terms + dscore_sums_j (or 0); dlogits_j = p_j
 //                   (dp_j - sum_i dp_i p_i) + 2 dz_sum lse p_j, fp32, rounded
 //                   once. With both null: RouterTopKGrad bit for bit.
+//   RouterScoreTopK  the router of DeepSeek-V3 and its successors: sigmoid
+//                   scores, a per-expert selection bias, a group-limited
+//                   choice. logits [tokens, E], bias float [E] (null: 0) ->
+//                   top_experts int32 [tokens, k], weights W [tokens, k] and,
+//                   when `scores` is not null, scores W [tokens, E]. fp32
+//                   throughout, each output rounded once.
+//                   Scores: s_e = 1 / (1 + expf(-l_e)).
+//                   Selection value: c_e = s_e + bias_e, as computed in fp32.
+//                   Two different logits whose c rounds to the same float are
+//                   a tie (saturated sigmoids, for instance) and go to the
+//                   lower index.
+//                   Order, here and below: the larger value first, equal
+//                   values to the lower index (-0 equals +0), NaN below -inf
+//                   (NaNs among themselves by index).
+//                   Groups: G = num_groups, gs = E / G, group g owns the
+//                   experts [g gs, (g + 1) gs). Its score is a + b in fp32
+//                   with a, b the first two of its c values in that order (a
+//                   alone when gs = 1). The topk_groups groups first in that
+//                   order on the group scores are eligible (ties to the lower
+//                   group, NaN last). G = 1: no group step.
+//                   Picks: the k first eligible experts in that order on c:
+//                   every row yields k distinct ids in [0, E) whatever the
+//                   logits and the bias hold.
+//                   Weights: w_k = s_{sel k} (without the bias); with
+//                   `normalize` divided by sum_k' s_{sel k'} (no epsilon: a
+//                   zero sum gives what the formula gives); then multiplied by
+//                   `scale`. scores = s.
+//   RouterScoreTopKGrad  dlogits L [tokens, E] from the logits, top_experts,
+//                   dweights W [tokens, k] and an optional dscores W
+//                   [tokens, E]; s is recomputed. g_k = scale dw_k, or with
+//                   `normalize` g_k = scale (dw_k - sum_j dw_j s_j / S) / S
+//                   with S = sum_k s_{sel k}; ds_e = dscores_e (or 0) +
+//                   sum_{k: sel k = e} g_k; dlogits_e = ds_e s_e (1 - s_e).
+//                   fp32, rounded once. A top_experts entry outside [0, E)
+//                   contributes nothing (neither to ds nor to S); a
+//                   duplicated entry adds twice. Bias and groups do not enter
+//                   the gradient; the bias has none.
 //   MoeSort         top_experts.flatten() int32 [n] -> indices, bin_ids [n],
 //                   bins, tokens_per_expert, padded_bins [E] and row_of [n] as
 //                   moe.h defines them: a stable counting sort by expert. For
@@ -82,11 +119,13 @@
 //                   4-byte aligned, no initialisation needed.
 //
 // Limits: 1 <= E <= 1024; RouterTopK / RouterTopKGrad and their Aux forms
-// 1 <= k <= min(E, 32).
+// 1 <= k <= min(E, 32). RouterScoreTopK: 1 <= topk_groups <= num_groups <= 64,
+// E % num_groups == 0, 1 <= k <= min(32, topk_groups * E / num_groups);
+// RouterScoreTopKGrad: 1 <= k <= min(E, 32); for both, `scale` is finite.
 // Element offsets are long long (tokens * E may pass 2^31).
 //
-// Bounds: every id read from device memory (top_experts in RouterTopKGrad and
-// MoeSort) is range-checked before it forms an address.
+// Bounds: every id read from device memory (top_experts in RouterTopKGrad,
+// RouterScoreTopKGrad and MoeSort) is range-checked before it forms an address.
 //
 // Stream-ordered; no call allocates or synchronises. They never abort:
 // hipErrorInvalidValue, with nothing launched, for a null required buffer, a
@@ -142,6 +181,23 @@ hipError_t RouterTopKAuxGrad(const void *logits, const int *top_experts,
                              void *dlogits, int tokens, int num_experts,
                              int top_k, bool normalize, RouterType logits_type,
                              WeightType weights_type, hipStream_t stream);
+
+// Most groups RouterScoreTopK takes (one lane per group).
+constexpr int kRouterMaxGroups = 64;
+
+hipError_t RouterScoreTopK(const void *logits, const float *bias,
+                           int *top_experts, void *weights, void *scores,
+                           int tokens, int num_experts, int top_k,
+                           int num_groups, int topk_groups, bool normalize,
+                           float scale, RouterType logits_type,
+                           WeightType weights_type, hipStream_t stream);
+
+hipError_t RouterScoreTopKGrad(const void *logits, const int *top_experts,
+                               const void *dweights, const void *dscores,
+                               void *dlogits, int tokens, int num_experts,
+                               int top_k, bool normalize, float scale,
+                               RouterType logits_type,
+                               WeightType weights_type, hipStream_t stream);
 
 // 0 for sizes MoeSort rejects.
 size_t MoeSortWorkspaceBytes(int n, int num_experts);

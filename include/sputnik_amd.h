@@ -488,6 +488,29 @@ int sputnik_router_topk_aux_grad(const void *logits,
                                  void *dlogits, int tokens, int num_experts,
                                  int top_k, int normalize, int logits_dtype,
                                  int weights_dtype, void *stream);
+/* The router with sigmoid scores, a selection bias and a group-limited
+ * choice (RouterScoreTopK / RouterScoreTopKGrad in sputnik/block/router.h):
+ * s = 1 / (1 + exp(-logit)); the picks are the top_k largest s + bias (bias
+ * float [E], NULL: 0) among the experts of the topk_groups best of num_groups
+ * groups, a group's score being the sum of its two largest s + bias; weights
+ * = s at the picks, divided by their sum with normalize, times scale; scores
+ * (optional) = s. Ties to the lower index, NaN last: always top_k distinct
+ * ids in [0, E). 1 <= topk_groups <= num_groups <= 64, E % num_groups == 0,
+ * top_k <= min(32, topk_groups * E / num_groups), scale finite. The gradient
+ * recomputes s and takes neither bias nor groups. */
+int sputnik_router_score_topk(const void *logits, const float *bias,
+                              int32_t *top_experts, void *weights,
+                              void *scores, int tokens, int num_experts,
+                              int top_k, int num_groups, int topk_groups,
+                              int normalize, float scale, int logits_dtype,
+                              int weights_dtype, void *stream);
+int sputnik_router_score_topk_grad(const void *logits,
+                                   const int32_t *top_experts,
+                                   const void *dweights, const void *dscores,
+                                   void *dlogits, int tokens, int num_experts,
+                                   int top_k, int normalize, float scale,
+                                   int logits_dtype, int weights_dtype,
+                                   void *stream);
 size_t sputnik_moe_sort_workspace_bytes(int n, int num_experts);
 int sputnik_moe_sort(const int32_t *top_experts, int n, int num_experts,
                      int rows, int32_t *indices, int32_t *bin_ids,

@@ -179,6 +179,18 @@ _SIGNATURES = {
     "sputnik_router_topk_aux_grad": [_P, _P, _P, _P, _P, _P, _P, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, _P],
+    # the sigmoid-score router: (logits, bias, top_experts, weights, scores,
+    # tokens, experts, top_k, num_groups, topk_groups, normalize, scale,
+    # logits_dtype, weights_dtype, stream); (logits, top_experts, dweights,
+    # dscores, dlogits, tokens, experts, top_k, normalize, scale, ..., stream)
+    "sputnik_router_score_topk": [_P, _P, _P, _P, _P, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                  ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_router_score_topk_grad": [_P, _P, _P, _P, _P, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_float,
+                                       ctypes.c_int, ctypes.c_int, _P],
     "sputnik_moe_sort_workspace_bytes": [ctypes.c_int, ctypes.c_int],
     "sputnik_moe_sort": [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P,
                          _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
@@ -1185,6 +1197,105 @@ def RouterTopKAuxGrad(logits, top_experts, dweights, dlogits,  # noqa: N802
         "RouterTopKAuxGrad")
 
 
+ROUTER_MAX_GROUPS = 64     # sputnik::block::kRouterMaxGroups
+
+
+def _router_scale(scale, what: str) -> float:
+    import math
+
+    if (isinstance(scale, bool) or not isinstance(scale, (int, float))
+            or not math.isfinite(scale)
+            or not math.isfinite(ctypes.c_float(scale).value)):
+        raise ValueError(f"{what}: scale must be a finite number (in fp32), "
+                         f"not {scale!r}")
+    return float(scale)
+
+
+def _router_groups(e: int, k: int, num_groups, topk_groups, what: str) -> None:
+    """RouterScoreTopK's limits on the groups: 1 <= topk_groups <= num_groups
+    <= 64, E % num_groups == 0, top_k <= topk_groups * E / num_groups."""
+    for name, v in (("num_groups", num_groups), ("topk_groups", topk_groups)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{what}: {name} must be an int, not {v!r}")
+    if not 1 <= topk_groups <= num_groups <= ROUTER_MAX_GROUPS:
+        raise ValueError(f"{what}: 1 <= topk_groups <= num_groups <= "
+                         f"{ROUTER_MAX_GROUPS} does not hold for topk_groups "
+                         f"= {topk_groups}, num_groups = {num_groups}")
+    if e % num_groups != 0:
+        raise ValueError(f"{what}: {e} experts do not divide into "
+                         f"{num_groups} groups")
+    if k > topk_groups * (e // num_groups):
+        raise ValueError(f"{what}: top_k = {k}, but {topk_groups} groups of "
+                         f"{e // num_groups} experts are eligible")
+
+
+def _router_distinct(outs, ins, what: str) -> None:
+    """No output (name, tensor) shares its address with an input or another
+    output; absent and empty tensors are left out."""
+    seen = {t.data_ptr(): name for name, t in ins
+            if t is not None and int(t.numel()) > 0}
+    for name, t in outs:
+        if t is None or int(t.numel()) == 0:
+            continue
+        if t.data_ptr() in seen:
+            raise ValueError(f"{what}: {name} aliases {seen[t.data_ptr()]}")
+        seen[t.data_ptr()] = name
+
+
+def RouterScoreTopK(logits, top_experts, weights, bias=None, num_groups=1,  # noqa: N802
+                    topk_groups=1, normalize=False, scale=1.0, scores=None,
+                    stream=None):
+    """The choice of a router with sigmoid scores (DeepSeek-V3's) from logits
+    [tokens, E] (fp16, bf16 or fp32): s = sigmoid(logits); top_experts int32
+    [tokens, top_k] = the top_k largest s + bias (bias fp32 [E], None: 0)
+    among the experts of the `topk_groups` best of `num_groups` groups of
+    E / num_groups consecutive experts, a group's score being the sum of its
+    two largest s + bias; ties to the lower index, NaN last. weights
+    [tokens, top_k] = s at the picks, divided by their sum with `normalize`,
+    times `scale`; scores [tokens, E], when given, = s. weights and scores
+    share one dtype, the logits' or fp32 (sputnik_router_score_topk;
+    sputnik/block/router.h). Type, shape, limit and aliasing errors are raised
+    before the library is called."""
+    what = "RouterScoreTopK"
+    code, tokens, e, k, wcode = _router_head(
+        logits, top_experts, weights, scores, what)
+    if bias is not None:
+        _router_stat(bias, logits, e, "bias")
+    _router_groups(e, k, num_groups, topk_groups, what)
+    scale = _router_scale(scale, what)
+    _router_distinct([("top_experts", top_experts), ("weights", weights),
+                      ("scores", scores)],
+                     [("logits", logits), ("bias", bias)], what)
+    _check(lib().sputnik_router_score_topk(
+        _ptr(logits), _ptr(bias), _ptr(top_experts), _ptr(weights),
+        _ptr(scores), tokens, e, k, num_groups, topk_groups,
+        int(bool(normalize)), scale, code, wcode, _stream(stream)), what)
+
+
+def RouterScoreTopKGrad(logits, top_experts, dweights, dlogits,  # noqa: N802
+                        normalize=False, scale=1.0, dscores=None,
+                        stream=None):
+    """dlogits [tokens, E] (the logits' dtype): the gradient of
+    RouterScoreTopK's weights (and scores, with `dscores`) with respect to
+    the logits, the sigmoid recomputed from `logits`; `normalize` and `scale`
+    as in the forward call. Bias and groups do not enter. A top_experts entry
+    outside [0, E) contributes nothing, a duplicated one twice
+    (sputnik_router_score_topk_grad). Errors are raised before the library is
+    called."""
+    what = "RouterScoreTopKGrad"
+    code, tokens, e, k, wcode = _router_head(
+        logits, top_experts, dweights, dscores, what, "d")
+    _router_dlogits(dlogits, logits)
+    scale = _router_scale(scale, what)
+    _router_distinct([("dlogits", dlogits)],
+                     [("logits", logits), ("top_experts", top_experts),
+                      ("dweights", dweights), ("dscores", dscores)], what)
+    _check(lib().sputnik_router_score_topk_grad(
+        _ptr(logits), _ptr(top_experts), _ptr(dweights), _ptr(dscores),
+        _ptr(dlogits), tokens, e, k, int(bool(normalize)), scale, code, wcode,
+        _stream(stream)), what)
+
+
 def _moe_sort_sizes(n, num_experts, what: str):
     n, e = int(n), int(num_experts)
     if n < 0 or not 1 <= e <= ROUTER_MAX_EXPERTS:
@@ -1420,6 +1531,7 @@ __all__ = [
     "MOE_SORT_CHUNK",
     "RouterTopKAux", "RouterTopKAuxGrad", "router_aux_workspace_bytes",
     "ROUTER_AUX_TOKENS",
+    "RouterScoreTopK", "RouterScoreTopKGrad", "ROUTER_MAX_GROUPS",
     "SputnikError", "Transpose", "can_implement", "lib", "version",
     "allgather_concat", "gather_row_panels", "gather_col_panels",
     "gather_block_runs",

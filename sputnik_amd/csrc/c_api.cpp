@@ -600,6 +600,34 @@ int sputnik_router_topk_aux_grad(const void *logits,
       static_cast<hipStream_t>(stream));
 }
 
+int sputnik_router_score_topk(const void *logits, const float *bias,
+                              int32_t *top_experts, void *weights,
+                              void *scores, int tokens, int num_experts,
+                              int top_k, int num_groups, int topk_groups,
+                              int normalize, float scale, int logits_dtype,
+                              int weights_dtype, void *stream) {
+  return sputnik::block::RouterScoreTopK(
+      logits, bias, top_experts, weights, scores, tokens, num_experts, top_k,
+      num_groups, topk_groups, normalize != 0, scale,
+      static_cast<RouterType>(logits_dtype),
+      static_cast<WeightType>(weights_dtype),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_router_score_topk_grad(const void *logits,
+                                   const int32_t *top_experts,
+                                   const void *dweights, const void *dscores,
+                                   void *dlogits, int tokens, int num_experts,
+                                   int top_k, int normalize, float scale,
+                                   int logits_dtype, int weights_dtype,
+                                   void *stream) {
+  return sputnik::block::RouterScoreTopKGrad(
+      logits, top_experts, dweights, dscores, dlogits, tokens, num_experts,
+      top_k, normalize != 0, scale, static_cast<RouterType>(logits_dtype),
+      static_cast<WeightType>(weights_dtype),
+      static_cast<hipStream_t>(stream));
+}
+
 size_t sputnik_moe_sort_workspace_bytes(int n, int num_experts) {
   return sputnik::block::MoeSortWorkspaceBytes(n, num_experts);
 }

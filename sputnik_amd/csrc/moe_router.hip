@@ -1,6 +1,7 @@
 // sputnik-amd: the MoE router (sputnik/block/router.h): fused softmax / top-k
-// of the router logits, its gradient, and the stable counting sort that turns
-// top_experts into MegaBlocks' routing tensors.
+// of the router logits, its gradient, the same for sigmoid scores with a
+// selection bias and a group-limited choice, and the stable counting sort that
+// turns top_experts into MegaBlocks' routing tensors.
 //
 // Router kernels: one wave per token, 4 waves per workgroup, a token's E
 // logits spread over the lanes as e = lane + 64 j with j < kPer = ceil(E / 64)
@@ -30,6 +31,15 @@
 //           are a function of the input alone. The gradient takes the sums'
 //           gradients as one [E] vector and one device scalar.
 //
+//   score   RouterScoreTopK / RouterScoreTopKGrad, the same layout and the
+//           same keys on c = sigmoid(l) + bias, with a body of their own
+//           (router_score_token, router_score_grad_kernel; the softmax bodies
+//           know nothing of them). Before the pick rounds the group step
+//           kills the keys of the experts outside the topk_groups best
+//           groups: the wave stages the keys' high words in LDS, 64 / G lanes
+//           per group scan for the group's two largest, a few shuffle steps
+//           merge them, and topk_groups arg-max rounds rank the group keys.
+//
 // Each pass is written once and instantiated twice on `bool kStats`:
 // router_topk_token is one token of RouterTopK (false: no accumulators) and of
 // RouterTopKAux (true), and router_topk_grad_kernel is RouterTopKGrad (false)
@@ -58,7 +68,9 @@
 //              alone, no global atomics.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <initializer_list>
 #include <type_traits>
@@ -72,6 +84,7 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxExperts = 1024;
 constexpr int kMaxTopK = 32;
+constexpr int kMaxGroups = sputnik::block::kRouterMaxGroups;
 constexpr int kChunk = sputnik::block::kMoeSortChunk;
 constexpr int kSortThreads = 1024;
 static_assert(kChunk == kSortThreads, "one assignment per thread");
@@ -340,6 +353,201 @@ __global__ void __launch_bounds__(kThreads)
         if (dz_sum != nullptr) out += zc * p[j];
       dlogits[t * num_experts + e] = (T)out;
     }
+  }
+}
+
+// ---- sigmoid scores, selection bias, group-limited top-k ----------------------
+
+__device__ __forceinline__ float sigmoid(float l) {
+  return 1.0f / (1.0f + expf(-l));
+}
+
+// One token of RouterScoreTopK, by one wave. The keys are built on c = s +
+// bias. The group step works on their high words alone (a group's score needs
+// its two largest values, not where they sit): the wave stages the images in
+// LDS (`stage`, kPer * 64 words of its own), group g gets the 2^shift = 64 / G
+// (rounded down to a power of two) lanes from g << shift on, each lane scans
+// its share of the group for a local (a, b), the two largest, `shift` shuffle
+// steps merge the pairs, and lane g << shift keeps the group's key. Then
+// topk_groups arg-max rounds over the group keys mark the eligible groups'
+// experts, the other keys die, and the pick rounds follow. A pick's unbiased
+// score comes from the lane that owns it.
+template <typename T, typename W, int kPer>
+__device__ __forceinline__ void router_score_token(
+    const T *__restrict__ logits, const float *__restrict__ bias,
+    int *__restrict__ top_experts, W *__restrict__ weights,
+    W *__restrict__ scores, long long t, int num_experts, int top_k,
+    int num_groups, int topk_groups, int normalize, float scale, int lane,
+    uint32_t *stage) {
+  const T *row = logits + t * num_experts;
+  float s[kPer];
+  unsigned long long key[kPer];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    const bool live = e < num_experts;
+    s[j] = live ? sigmoid((float)row[e]) : 0.0f;
+    const float c = live && bias != nullptr ? s[j] + bias[e] : s[j];
+    key[j] = live ? ((unsigned long long)order_image(c) << 32) | (uint32_t)~e
+                  : 0ull;
+  }
+  if (num_groups > 1) {
+    const int gs = num_experts / num_groups;
+    unsigned long long gkey = 0ull;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      stage[lane + 64 * j] = (uint32_t)(key[j] >> 32);
+    // (one wave writes and reads: its LDS operations complete in order)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int shift = 31 - __clz(64 / num_groups);
+    const int g = lane >> shift, per = 1 << shift;
+    uint32_t a = 0u, b = 0u;  // the two largest images seen, a >= b
+    if (g < num_groups)
+      for (int i = lane & (per - 1); i < gs; i += per) {
+        const uint32_t img = stage[g * gs + i];
+        b = img > a ? a : (img > b ? img : b);
+        a = img > a ? img : a;
+      }
+    for (int d = 1; d < per; d <<= 1) {
+      const uint32_t oa = __shfl_xor(a, d, 64), ob = __shfl_xor(b, d, 64);
+      const uint32_t low = oa < a ? oa : a, high = ob > b ? ob : b;
+      a = oa > a ? oa : a;
+      b = low > high ? low : high;
+    }
+    if (g < num_groups && lane == g << shift) {
+      const float score =
+          gs > 1 ? image_value(a) + image_value(b) : image_value(a);
+      gkey = ((unsigned long long)order_image(score) << 32) | (uint32_t)~g;
+    }
+    unsigned keep = 0u;  // bit j: expert lane + 64 j is eligible
+    for (int r = 0; r < topk_groups; ++r) {
+      // (topk_groups <= num_groups: a live group key remains)
+      const int best = (int)~(uint32_t)wave_max(gkey);
+      if (lane == best << shift) gkey = 0ull;
+#pragma unroll
+      for (int j = 0; j < kPer; ++j)
+        if ((unsigned)(lane + 64 * j - best * gs) < (unsigned)gs)
+          keep |= 1u << j;
+    }
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (!((keep >> j) & 1u)) key[j] = 0ull;
+  }
+  float my_s = 0.0f;
+  int my_id = 0;
+  for (int r = 0; r < top_k; ++r) {
+    unsigned long long best = key[0];
+#pragma unroll
+    for (int j = 1; j < kPer; ++j) best = key[j] > best ? key[j] : best;
+    best = wave_max(best);
+    // (top_k <= topk_groups * gs: a live key remains, so idx is in [0, E))
+    const int idx = (int)~(uint32_t)best;
+    float mine = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (idx == lane + 64 * j) {
+        mine = s[j];
+        key[j] = 0ull;
+      }
+    const float sel = __shfl(mine, idx & 63, 64);
+    if (lane == r) {
+      my_id = idx;
+      my_s = sel;
+    }
+  }
+  float p = my_s;  // (0 in the lanes from top_k on)
+  if (normalize) p = p / wave_sum(p);
+  p *= scale;
+  if (lane < top_k) {
+    top_experts[t * top_k + lane] = my_id;
+    weights[t * top_k + lane] = (W)p;
+  }
+  if (scores != nullptr) {
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      const int e = lane + 64 * j;
+      if (e < num_experts) scores[t * num_experts + e] = (W)s[j];
+    }
+  }
+}
+
+template <typename T, typename W, int kPer>
+__global__ void __launch_bounds__(kThreads)
+    router_score_topk_kernel(const T *__restrict__ logits,
+                             const float *__restrict__ bias,
+                             int *__restrict__ top_experts,
+                             W *__restrict__ weights, W *__restrict__ scores,
+                             int tokens, int num_experts, int top_k,
+                             int num_groups, int topk_groups, int normalize,
+                             float scale) {
+  __shared__ uint32_t stage[kWaves][kPer * 64];
+  const int wave = wave_index();
+  const long long t = (long long)blockIdx.x * kWaves + wave;
+  if (t >= tokens) return;
+  router_score_token<T, W, kPer>(logits, bias, top_experts, weights, scores, t,
+                                 num_experts, top_k, num_groups, topk_groups,
+                                 normalize, scale, threadIdx.x & 63,
+                                 stage[wave]);
+}
+
+// RouterScoreTopKGrad: the layout of router_topk_grad_kernel, without a
+// softmax (no row maximum, no dot product): ds = dscores (or 0) plus the
+// picks' terms, dlogits = ds s (1 - s).
+template <typename T, typename W, int kPer>
+__global__ void __launch_bounds__(kThreads)
+    router_score_grad_kernel(const T *__restrict__ logits,
+                             const int *__restrict__ top_experts,
+                             const W *__restrict__ dweights,
+                             const W *__restrict__ dscores,
+                             T *__restrict__ dlogits, int tokens,
+                             int num_experts, int top_k, int normalize,
+                             float scale) {
+  const int lane = threadIdx.x & 63;
+  const long long t = (long long)blockIdx.x * kWaves + wave_index();
+  if (t >= tokens) return;
+  const T *row = logits + t * num_experts;
+  float s[kPer], ds[kPer];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    const bool live = e < num_experts;
+    s[j] = live ? sigmoid((float)row[e]) : 0.0f;
+    ds[j] = live && dscores != nullptr
+                ? (float)dscores[t * num_experts + e] : 0.0f;
+  }
+  // Lane r < top_k holds pick r: its id (-1 when out of range) and its
+  // incoming gradient.
+  int id = -1;
+  float g = 0.0f;
+  if (lane < top_k) {
+    const int raw = top_experts[t * top_k + lane];
+    if (raw >= 0 && raw < num_experts) {
+      id = raw;
+      g = (float)dweights[t * top_k + lane];
+    }
+  }
+  if (normalize) {
+    const float ssel = id >= 0 ? sigmoid((float)row[id]) : 0.0f;
+    const float total = wave_sum(ssel);             // S
+    const float c = wave_sum(g * ssel) / total;     // sum_j dw_j s_j / S
+    g = id >= 0 ? scale * (g - c) / total : 0.0f;
+  } else {
+    g *= scale;
+  }
+  for (int r = 0; r < top_k; ++r) {
+    const int rid = __shfl(id, r, 64);
+    const float rg = __shfl(g, r, 64);
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (rid == lane + 64 * j) ds[j] += rg;
+  }
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int e = lane + 64 * j;
+    if (e < num_experts)
+      dlogits[t * num_experts + e] = (T)(ds[j] * s[j] * (1.0f - s[j]));
   }
 }
 
@@ -682,6 +890,56 @@ hipError_t RouterTopKGrad(const void *logits, const int *top_experts,
   return RouterTopKAuxGrad(logits, top_experts, dweights, dscores, nullptr,
                            nullptr, dlogits, tokens, num_experts, top_k,
                            normalize, logits_type, weights_type, stream);
+}
+
+hipError_t RouterScoreTopK(const void *logits, const float *bias,
+                           int *top_experts, void *weights, void *scores,
+                           int tokens, int num_experts, int top_k,
+                           int num_groups, int topk_groups, bool normalize,
+                           float scale, RouterType logits_type,
+                           WeightType weights_type, hipStream_t stream) {
+  if (!RouterArgsOk(tokens, num_experts, top_k, logits_type, weights_type,
+                    {logits, top_experts, weights}))
+    return hipErrorInvalidValue;
+  if (num_groups < 1 || num_groups > kMaxGroups || topk_groups < 1 ||
+      topk_groups > num_groups || num_experts % num_groups != 0 ||
+      top_k > topk_groups * (num_experts / num_groups) ||
+      !(fabsf(scale) <= FLT_MAX))
+    return hipErrorInvalidValue;
+  if (tokens == 0) return hipSuccess;
+  if (!Distinct({top_experts, weights, scores}, {logits, bias}))
+    return hipErrorInvalidValue;
+  return LaunchRouter(
+      logits_type, weights_type, num_experts, TokenGrid(tokens), stream,
+      [](auto t, auto w, auto per) {
+        return router_score_topk_kernel<decltype(t), decltype(w),
+                                        decltype(per)::value>;
+      },
+      logits, bias, top_experts, weights, scores, tokens, num_experts, top_k,
+      num_groups, topk_groups, normalize ? 1 : 0, scale);
+}
+
+hipError_t RouterScoreTopKGrad(const void *logits, const int *top_experts,
+                               const void *dweights, const void *dscores,
+                               void *dlogits, int tokens, int num_experts,
+                               int top_k, bool normalize, float scale,
+                               RouterType logits_type,
+                               WeightType weights_type, hipStream_t stream) {
+  if (!RouterArgsOk(tokens, num_experts, top_k, logits_type, weights_type,
+                    {logits, top_experts, dweights, dlogits}) ||
+      !(fabsf(scale) <= FLT_MAX))
+    return hipErrorInvalidValue;
+  if (tokens == 0) return hipSuccess;
+  if (!Distinct({dlogits}, {logits, top_experts, dweights, dscores}))
+    return hipErrorInvalidValue;
+  return LaunchRouter(
+      logits_type, weights_type, num_experts, TokenGrid(tokens), stream,
+      [](auto t, auto w, auto per) {
+        return router_score_grad_kernel<decltype(t), decltype(w),
+                                        decltype(per)::value>;
+      },
+      logits, top_experts, dweights, dscores, dlogits, tokens, num_experts,
+      top_k, normalize ? 1 : 0, scale);
 }
 
 size_t MoeSortWorkspaceBytes(int n, int num_experts) {

@@ -33,6 +33,10 @@ layer from activations to output: router GEMM (torch), moe_router, moe_mlp.
 losses (column sums of the softmax, sum of logsumexp^2) taken in the same
 pass, `load_balancing_loss` / `router_z_loss` the losses formed from them, and
 `moe_layer_aux` the layer that returns those statistics beside its output.
+`moe_score_router` is the router of models that score with a sigmoid, select
+on score + bias and limit the choice to the best groups of experts
+(RouterScoreTopK), `moe_score_layer` the layer routed by it and
+`router_bias_update` the auxiliary-loss-free correction of that bias.
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -47,6 +51,7 @@ columns; `offsets_t` / `indices_t` / `block_offsets` are what
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -57,9 +62,10 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                MatmulActivation, MatmulActivationGrad, MatmulEx, MatmulGated,
                MatmulGatedGrad, MoeBins, MoeRowMap, MoeSort, PaddedGather,
                PaddedScatter, PaddedScatterWeightGrad, RouterTopK,
-               RouterTopKAux, RouterTopKAuxGrad, RouterTopKGrad, RowIndices,
-               Transpose, MOE_SORT_CHUNK, ROUTER_AUX_TOKENS,
-               ROUTER_MAX_EXPERTS, ROUTER_MAX_TOP_K, _act_code,
+               RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
+               RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
+               MOE_SORT_CHUNK, ROUTER_AUX_TOKENS, ROUTER_MAX_EXPERTS,
+               ROUTER_MAX_GROUPS, ROUTER_MAX_TOP_K, _act_code,
                AllocateRowIndicesBuffer, AllocateTransposeBuffers,
                dsd_workspace_bytes, sdd_workspace_bytes)
 
@@ -1244,6 +1250,108 @@ def moe_router_aux(logits: torch.Tensor, top_k: int, normalize: bool = False,
     return _RouterAux.apply(logits, top_k, bool(normalize), weights_dtype)
 
 
+class _ScoreRouter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, bias, top_k, num_groups, topk_groups, normalize,
+                scale, dtype, return_scores):
+        logits, top, weights = _router_forward(ctx, logits, top_k, normalize,
+                                               dtype)
+        ctx.scale = scale
+        scores = (torch.empty(logits.shape, dtype=dtype, device=logits.device)
+                  if return_scores else None)
+        RouterScoreTopK(logits, top, weights, bias, num_groups, topk_groups,
+                        normalize, scale, scores)
+        return (weights, top, scores) if return_scores else (weights, top)
+
+    @staticmethod
+    def backward(ctx, dweights, _dtop, dscores=None):
+        args = _router_backward(ctx, dweights, dscores)
+        if args is None:
+            return (None,) * 9
+        logits, top, dweights, dlogits = args
+        RouterScoreTopKGrad(logits, top, dweights, dlogits, ctx.normalize,
+                            ctx.scale, _contiguous(dscores))
+        return (dlogits,) + (None,) * 8
+
+
+def _score_args(logits, top_k, bias, num_groups, topk_groups, scale,
+                what: str):
+    """moe_score_router's checks beyond _router_args': the bias (detached,
+    contiguous), the groups and the scale."""
+    e = int(logits.shape[1])
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError(f"{what}: bias must be an fp32 tensor")
+        if tuple(bias.shape) != (e,):
+            raise ValueError(f"{what}: bias is [num_experts]")
+        bias = bias.detach().contiguous()
+    for name, v in (("num_groups", num_groups), ("topk_groups", topk_groups)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{what}: {name} must be an int, not {v!r}")
+    if (not 1 <= topk_groups <= num_groups <= ROUTER_MAX_GROUPS
+            or e % num_groups != 0):
+        raise ValueError(f"{what}: needs 1 <= topk_groups <= num_groups <= "
+                         f"{ROUTER_MAX_GROUPS} and num_groups dividing {e} "
+                         f"experts, not topk_groups = {topk_groups}, "
+                         f"num_groups = {num_groups}")
+    if top_k > topk_groups * (e // num_groups):
+        raise ValueError(f"{what}: top_k = {top_k}, but {topk_groups} groups "
+                         f"of {e // num_groups} experts are eligible")
+    if (isinstance(scale, bool) or not isinstance(scale, (int, float))
+            or not math.isfinite(scale)):
+        raise ValueError(f"{what}: scale must be a finite number, not "
+                         f"{scale!r}")
+    return bias, float(scale)
+
+
+def moe_score_router(logits: torch.Tensor, top_k: int,
+                     bias: Optional[torch.Tensor] = None, num_groups: int = 1,
+                     topk_groups: int = 1, normalize: bool = False,
+                     scale: float = 1.0, weights_dtype=None,
+                     return_scores: bool = False):
+    """The choice of a router with sigmoid scores, a selection bias and a
+    group limit (DeepSeek-V3's gate) from its logits [tokens, E]: the same
+    returns as moe_router, (expert_weights [tokens, top_k], top_experts int32
+    [tokens, top_k]) and, with `return_scores`, scores [tokens, E] (the
+    sigmoid). The picks are the top_k largest sigmoid(logits) + bias (`bias`
+    fp32 [E], None: 0) among the experts of the `topk_groups` best of
+    `num_groups` groups, a group scoring the sum of its two largest; equal
+    values to the lower expert, NaN last. The weights are the picks' scores
+    without the bias, divided by their sum with `normalize`, times `scale`
+    (sputnik/block/router.h, RouterScoreTopK). One autograd function,
+    differentiable in the logits through weights and scores; the bias takes
+    no gradient (router_bias_update moves it)."""
+    what = "moe_score_router"
+    weights_dtype = _router_args(logits, top_k, weights_dtype, what)
+    bias, scale = _score_args(logits, top_k, bias, num_groups, topk_groups,
+                              scale, what)
+    return _ScoreRouter.apply(logits, bias, top_k, num_groups, topk_groups,
+                              bool(normalize), scale, weights_dtype,
+                              bool(return_scores))
+
+
+def router_bias_update(bias: torch.Tensor, tokens_per_expert: torch.Tensor,
+                       rate: float) -> torch.Tensor:
+    """The auxiliary-loss-free balancing step on moe_score_router's bias, in
+    place: bias += rate * sign(mean(tokens_per_expert) - tokens_per_expert),
+    so an overloaded expert's bias falls and an underloaded one's rises.
+    `tokens_per_expert` [E] (any integer or float dtype) is a route's
+    (MoeRoute.tokens_per_expert). Plain torch on E elements, no host sync;
+    returns `bias`."""
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+        raise TypeError("router_bias_update: bias must be an fp32 tensor")
+    if not isinstance(tokens_per_expert, torch.Tensor):
+        raise TypeError("router_bias_update: tokens_per_expert must be a "
+                        "tensor")
+    if bias.dim() != 1 or tokens_per_expert.shape != bias.shape:
+        raise ValueError("router_bias_update: bias and tokens_per_expert are "
+                         "[num_experts]")
+    with torch.no_grad():
+        load = tokens_per_expert.detach().to(torch.float32)
+        bias.add_(torch.sign(load.mean() - load), alpha=float(rate))
+    return bias
+
+
 def _loss_sizes(tokens, top_k, what: str):
     for name, v in (("tokens", tokens), ("top_k", top_k)):
         if isinstance(v, bool) or not isinstance(v, int) or v < 1:
@@ -1304,10 +1412,13 @@ class MoeAux:
 
 
 def _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
-               normalize, router_dtype, device_sort, returns: str, what: str):
+               normalize, router_dtype, device_sort, returns: str, what: str,
+               score=None):
     """moe_layer's checks and chain. `returns`: "y", "scores" (moe_layer's
     return_scores) or "aux" (moe_layer_aux: routing through
-    moe_router_aux)."""
+    moe_router_aux). `score`: None, or moe_score_layer's (router_bias,
+    num_groups, topk_groups, routed_scale): routing through
+    moe_score_router."""
     if not isinstance(x, torch.Tensor) or x.dim() != 2:
         raise ValueError(f"{what}: x must be a 2-D tensor")
     _check_dtypes(x)
@@ -1328,7 +1439,11 @@ def _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
         raise ValueError(f"{what}: top_k must be an int in [1, min("
                          f"{num_experts}, {ROUTER_MAX_TOP_K})], not {top_k!r}")
     logits = x.to(router_dtype) @ router_weight.to(router_dtype).t()
-    if returns == "aux":
+    if score is not None:
+        bias, num_groups, topk_groups, scale = score
+        out = moe_score_router(logits, top_k, bias, num_groups, topk_groups,
+                               normalize, scale, None, returns == "scores")
+    elif returns == "aux":
         out = moe_router_aux(logits, top_k, normalize, None)
     else:
         out = moe_router(logits, top_k, normalize, None, returns == "scores")
@@ -1383,11 +1498,34 @@ def moe_layer_aux(x: torch.Tensor, router_weight: torch.Tensor,
                       "moe_layer_aux")
 
 
+def moe_score_layer(x: torch.Tensor, router_weight: torch.Tensor,
+                    w1: torch.Tensor, w2: torch.Tensor, top_k: int,
+                    activation=None, v1: Optional[torch.Tensor] = None,
+                    rows: Optional[int] = None, normalize: bool = False,
+                    router_dtype=None, device_sort: bool = True,
+                    return_scores: bool = False,
+                    router_bias: Optional[torch.Tensor] = None,
+                    num_groups: int = 1, topk_groups: int = 1,
+                    routed_scale: float = 1.0):
+    """moe_layer with a sigmoid-score router: the same layer and the same
+    leading arguments, routed through moe_score_router(logits, top_k,
+    router_bias, num_groups, topk_groups, normalize, routed_scale) instead of
+    moe_router. `return_scores` returns the sigmoid scores. With explicit
+    `rows` the layer makes no host sync. `router_bias` takes no gradient:
+    feed the route's tokens_per_expert (returned with `return_scores`) to
+    router_bias_update."""
+    return _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
+                      normalize, router_dtype, device_sort,
+                      "scores" if return_scores else "y", "moe_score_layer",
+                      (router_bias, num_groups, topk_groups, routed_scale))
+
+
 __all__ = ["MoeAux", "MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
            "expert_topology", "from_dense_mask", "glu_mlp", "mlp",
            "moe_device_route", "moe_layer", "moe_layer_aux", "moe_mlp",
            "moe_route",
            "moe_router", "moe_router_aux", "load_balancing_loss",
+           "moe_score_router", "moe_score_layer", "router_bias_update",
            "router_z_loss",
            "moe_rows_bound", "padded_gather",
            "padded_scatter", "sdd", "sdd_act", "sdd_gated",
