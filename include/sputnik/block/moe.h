@@ -40,9 +40,34 @@
 //                               float(y[row_of[a], h]), accumulated in fp32
 //                 (free order), stored in the weights' type.
 //
+//   PaddedScatterBias
+//                 PaddedScatter with an output bias b2 [E, hidden] of T:
+//                   out[t] = round_T(sum_k float(w_k) * (float(y[row_k]) +
+//                                                        float(b2[e_k])))
+//                 one fp32 add, one fp32 multiply (omitted without weights)
+//                 and one fp32 accumulate per k, ascending k from 0, no
+//                 contraction. e_k is read off the row: the number of experts
+//                 with padded_bins[e] <= row_k. An assignment whose row is
+//                 outside [0, rows), or at or past padded_bins[E-1],
+//                 contributes zero, bias included.
+//   PaddedScatterBiasWeightGrad
+//                 dw[a] = sum_h float(dout[a / top_k, h]) *
+//                         (float(y[row_of[a], h]) + float(b2[e, h])), as
+//                 PaddedScatterWeightGrad.
+//   PaddedScatterBiasGrad
+//                 bias_grad[e, h] = sum over e's sorted positions i in
+//                 [bins[e-1], bins[e]) of float(w[indices[i]]) *
+//                 float(dout[indices[i] / top_k, h]): fp32 [E, hidden] from
+//                 the unrounded products (without weights a plain sum). No
+//                 atomics and no workspace; the order of the sum depends on
+//                 the bins alone, so two runs give the same bits. An expert
+//                 without tokens gives +0.
+//
 // The gradients are these same calls: d PaddedGather / dx is the unweighted
 // PaddedScatter, d PaddedScatter / dy is PaddedGather of dout with the
 // weights, d PaddedScatter / dw is PaddedScatterWeightGrad.
+//
+// With the bias, dy is unchanged and dw / db2 are the two calls above.
 //
 // weights: n elements of T (WeightType::kOperand) or of float
 // (WeightType::kF32), indexed by assignment; null means unweighted.
@@ -93,6 +118,28 @@ hipError_t PaddedScatterWeightGrad(const void *dout, const void *y,
                                    int hidden, int top_k, int rows,
                                    DataType dtype, WeightType weights_type,
                                    hipStream_t stream);
+
+hipError_t PaddedScatterBias(const void *y, const int *row_of,
+                             const int *padded_bins, const void *bias,
+                             const void *weights, void *out, int tokens,
+                             int hidden, int top_k, int num_experts, int rows,
+                             DataType dtype, WeightType weights_type,
+                             hipStream_t stream);
+
+hipError_t PaddedScatterBiasWeightGrad(const void *dout, const void *y,
+                                       const int *row_of,
+                                       const int *padded_bins,
+                                       const void *bias, void *dw, int tokens,
+                                       int hidden, int top_k, int num_experts,
+                                       int rows, DataType dtype,
+                                       WeightType weights_type,
+                                       hipStream_t stream);
+
+hipError_t PaddedScatterBiasGrad(const void *dout, const int *indices,
+                                 const int *bins, const void *weights,
+                                 float *bias_grad, int tokens, int hidden,
+                                 int top_k, int num_experts, DataType dtype,
+                                 WeightType weights_type, hipStream_t stream);
 
 }  // namespace block
 }  // namespace sputnik

@@ -7,6 +7,7 @@
 #include "sputnik/block/accumulate.h"
 #include "sputnik/block/activation.h"
 #include "sputnik/block/arguments.h"
+#include "sputnik/block/bias.h"
 #include "sputnik/block/bitmask/bitmask.h"
 #include "sputnik/block/dsd/dsd.h"
 #include "sputnik/block/gated.h"

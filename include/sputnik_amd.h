@@ -201,6 +201,41 @@ int sputnik_block_gate_grad(const void *d, const void *g, const void *u,
                             void *dg, void *du, long long n, int act,
                             int dtype, void *stream);
 
+/* ---- SDD with a column bias, column sums (sputnik/block/bias.h,
+ * INTEGRATION.md 3i). bias: c->cols elements of T indexed by C's logical
+ * column, any 2-byte alignment. With x = round_T(acc),
+ *   xb = round_T((float(x) + float(bias[col])) + 0.0f)
+ * and the product sees xb where the bias-free one sees x:
+ *   sputnik_sdd_bias        c->data = xb
+ *   sputnik_sdd_bias_act    as sputnik_sdd_act on xb; z (may be NULL)
+ *                           receives xb
+ *   sputnik_sdd_bias_gated  as sputnik_sdd_gated on xb; up (may be NULL)
+ *                           receives xb
+ * The gradient products read the kept z / up as they stand. A bias that is
+ * NULL or equals c->data, z / gate / up, A or B: hipErrorInvalidValue, nothing
+ * launched. Routes, workspace arguments and acceptance as sputnik_sdd_act.
+ *   sputnik_block_column_sum  out[c] = sum_r float(s[r, c]) over the stored
+ *                           blocks, fp32 [s->cols]; +0 for a column block
+ *                           without blocks; no atomics, no workspace, same
+ *                           bits on every run. Needs s->offsets_t and
+ *                           s->block_offsets (NULL: hipErrorInvalidValue). */
+int sputnik_sdd_bias(const sputnik_matrix_t *a, int transpose_a,
+                     const sputnik_matrix_t *b, int transpose_b,
+                     const sputnik_block_matrix_t *c, const void *bias,
+                     int dtype, void *ws, size_t ws_bytes, void *stream);
+int sputnik_sdd_bias_act(const sputnik_matrix_t *a, int transpose_a,
+                         const sputnik_matrix_t *b, int transpose_b,
+                         const sputnik_block_matrix_t *c, const void *bias,
+                         int act, void *z, int dtype, void *ws,
+                         size_t ws_bytes, void *stream);
+int sputnik_sdd_bias_gated(const sputnik_matrix_t *a, int transpose_a,
+                           const sputnik_matrix_t *b, int transpose_b,
+                           const sputnik_block_matrix_t *c, const void *bias,
+                           int act, const void *gate, void *up, int dtype,
+                           void *ws, size_t ws_bytes, void *stream);
+int sputnik_block_column_sum(const sputnik_block_matrix_t *s, int dtype,
+                             float *out, void *stream);
+
 /* ---- Caller-owned workspaces for the transposed-B path
  * SDD NT / TT, and DSD NT over a nearly dense A, transpose B once into a
  * scratch buffer when B is at least "sdd_bt_min_mib" MiB and the product is
@@ -413,6 +448,33 @@ int sputnik_padded_scatter_wgrad(const void *dout, const void *y,
                                  const int32_t *row_of, void *dw, int tokens,
                                  int hidden, int top_k, int rows, int dtype,
                                  int weights_dtype, void *stream);
+
+/* The scatter with an output bias [num_experts, hidden] of T (moe.h
+ * PaddedScatterBias*): out[t] = round_T(sum_k w_k * (float(y[row_k]) +
+ * float(bias[e_k]))), one fp32 add, multiply and accumulate per k, e_k read
+ * off the row through padded_bins; a row outside [0, rows) or past the last
+ * padded bin contributes zero, bias included. _wgrad: dw[a] = sum_h dout *
+ * (y + bias). _grad: bias_grad[e, h] = sum over e's sorted positions of
+ * w * dout, fp32 [num_experts, hidden], no atomics, no workspace, same bits
+ * on every run, +0 for an expert without tokens. Argument rules as above. */
+int sputnik_padded_scatter_bias(const void *y, const int32_t *row_of,
+                                const int32_t *padded_bins, const void *bias,
+                                const void *weights, void *out, int tokens,
+                                int hidden, int top_k, int num_experts,
+                                int rows, int dtype, int weights_dtype,
+                                void *stream);
+int sputnik_padded_scatter_bias_wgrad(const void *dout, const void *y,
+                                      const int32_t *row_of,
+                                      const int32_t *padded_bins,
+                                      const void *bias, void *dw, int tokens,
+                                      int hidden, int top_k, int num_experts,
+                                      int rows, int dtype, int weights_dtype,
+                                      void *stream);
+int sputnik_padded_scatter_bias_grad(const void *dout, const int32_t *indices,
+                                     const int32_t *bins, const void *weights,
+                                     float *bias_grad, int tokens, int hidden,
+                                     int top_k, int num_experts, int dtype,
+                                     int weights_dtype, void *stream);
 
 /* ---- MoE router and device sort (sputnik/block/router.h, INTEGRATION.md
  * 3h): what stands in front of the permutation above. L is the logits' type

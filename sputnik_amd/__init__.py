@@ -127,6 +127,17 @@ _SIGNATURES = {
                            ctypes.c_int, _P],
     "sputnik_block_gate_grad": [_P, _P, _P, _P, _P, ctypes.c_longlong,
                                 ctypes.c_int, ctypes.c_int, _P],
+    # SDD with a column bias: (a, ta, b, tb, c, bias, [act, side buffers,]
+    # dtype, ws, ws_bytes, stream); column sums: (s, dtype, out, stream)
+    "sputnik_sdd_bias": [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P,
+                         ctypes.c_int, _P, ctypes.c_size_t, _P],
+    "sputnik_sdd_bias_act": [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P,
+                             ctypes.c_int, _P, ctypes.c_int, _P,
+                             ctypes.c_size_t, _P],
+    "sputnik_sdd_bias_gated": [_P, ctypes.c_int, _P, ctypes.c_int, _P, _P,
+                               ctypes.c_int, _P, _P, ctypes.c_int, _P,
+                               ctypes.c_size_t, _P],
+    "sputnik_block_column_sum": [_P, ctypes.c_int, _P, _P],
     "sputnik_ssd": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_ssd_ex": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_sds": [_P, ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
@@ -156,6 +167,24 @@ _SIGNATURES = {
     "sputnik_padded_scatter_wgrad": [_P, _P, _P, _P, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, _P],
+    # the scatter with an output bias: (y, row_of, padded_bins, bias, weights,
+    # out, tokens, hidden, top_k, experts, rows, dtype, weights_dtype,
+    # stream); (dout, y, row_of, padded_bins, bias, dw, tokens, ..., stream);
+    # (dout, indices, bins, weights, bias_grad, tokens, hidden, top_k,
+    # experts, dtype, weights_dtype, stream)
+    "sputnik_padded_scatter_bias": [_P, _P, _P, _P, _P, _P, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    _P],
+    "sputnik_padded_scatter_bias_wgrad": [_P, _P, _P, _P, _P, _P,
+                                          ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, _P],
+    "sputnik_padded_scatter_bias_grad": [_P, _P, _P, _P, _P, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, _P],
     # MoE router and device sort: (logits, top_experts, weights, scores,
     # tokens, experts, top_k, normalize, logits_dtype, weights_dtype, stream);
     # (logits, top_experts, dweights, dscores, dlogits, tokens, ..., stream);
@@ -718,6 +747,92 @@ def BlockGateGrad(d, g, u, activation, dg=None, du=None, stream=None):  # noqa: 
     return dg, du
 
 
+def _column_bias(bias, c, dtype, what: str) -> None:
+    """A column bias of an SDD: 1-D, c.cols elements of `dtype`, contiguous
+    (any 2-byte alignment: a slice of a longer tensor will do). Raises before
+    any library call."""
+    if bias is None:
+        raise TypeError(f"{what} needs a bias; without one call the "
+                        "bias-free product")
+    _act_buffer(bias, dtype, int(c.cols), "bias")
+    if bias.dim() != 1:
+        raise ValueError(f"bias has shape {tuple(bias.shape)}, expected "
+                         f"[{int(c.cols)}]")
+
+
+def _call_sdd_bias(fn: str, label: str, a, transpose_a, b, transpose_b, c,
+                   bias, tail, stream, workspace):
+    """One bias product; `tail`: the arguments between bias and dtype."""
+    dtype = _sdd_act_operands(a, b, c, label)
+    _column_bias(bias, c, a.data.dtype, label)
+    ws = _workspace(workspace) if workspace is not None else (None, 0)
+    ca, cb, cc = a._c(), b._c(), c._c()
+    _check(getattr(lib(), fn)(
+        ctypes.byref(ca), int(bool(transpose_a)), ctypes.byref(cb),
+        int(bool(transpose_b)), ctypes.byref(cc), _ptr(bias), *tail, dtype,
+        ws[0], ws[1], _stream(stream)), label)
+
+
+def MatmulBias(a, transpose_a, b, transpose_b, c, bias, stream=None,  # noqa: N802
+               workspace=None):
+    """SDD with a column bias: c.data = round(Z + bias[col]) at c's blocks,
+    Z = op(a) op(b) rounded to the operand type, `bias` a 1-D tensor of
+    c.cols elements of the operands' dtype indexed by c's logical column, at
+    any 2-byte alignment (sputnik/block/bias.h). The result is the plain
+    product followed by the add, bit for bit, whichever kernel runs."""
+    _call_sdd_bias("sputnik_sdd_bias", "sdd (bias)", a, transpose_a, b,
+                   transpose_b, c, bias, (), stream, workspace)
+
+
+def MatmulBiasActivation(a, transpose_a, b, transpose_b, c, bias,  # noqa: N802
+                         activation, pre_activation=None, stream=None,
+                         workspace=None):
+    """MatmulActivation on the biased product: Z = round(op(a) op(b)) +
+    bias[col], rounded, c.data = act(Z); `pre_activation` (optional) receives
+    that biased Z, which is what MatmulActivationGrad reads."""
+    act = _act_code(activation)
+    if pre_activation is not None:
+        _act_buffer(pre_activation, a.data.dtype, int(c.nonzeros),
+                    "pre_activation")
+    _call_sdd_bias("sputnik_sdd_bias_act", "sdd (bias, activation)", a,
+                   transpose_a, b, transpose_b, c, bias,
+                   (act, _ptr(pre_activation)), stream, workspace)
+
+
+def MatmulBiasGated(a, transpose_a, b, transpose_b, c, bias, activation,  # noqa: N802
+                    gate, up=None, stream=None, workspace=None):
+    """MatmulGated on the biased product: U = round(op(a) op(b)) +
+    bias[col], rounded, c.data = U * act(G); `up` (optional) receives that
+    biased U, which is what MatmulGatedGrad reads. G = `gate` (required)
+    would itself come from MatmulBias with the gate's bias."""
+    act = _act_code(activation)
+    if gate is None:
+        raise TypeError("MatmulBiasGated needs the gate")
+    for name, t in (("gate", gate), ("up", up)):
+        if t is not None:
+            _act_buffer(t, a.data.dtype, int(c.nonzeros), name)
+    _call_sdd_bias("sputnik_sdd_bias_gated", "sdd (bias, gated)", a,
+                   transpose_a, b, transpose_b, c, bias,
+                   (act, _ptr(gate), _ptr(up)), stream, workspace)
+
+
+def BlockColumnSum(s, out, stream=None):  # noqa: N802
+    """out[c] = the fp32 sum of column c over s's stored blocks, `out` a
+    contiguous fp32 tensor of s.cols elements: the bias gradient of a sparse
+    matrix (sputnik_block_column_sum). No atomics: two runs give the same
+    bits. s needs its transposed metadata (AllocateTransposeBuffers +
+    Transpose); without it the library returns hipErrorInvalidValue."""
+    import torch
+
+    if not isinstance(s, BlockMatrix):
+        raise TypeError("BlockColumnSum takes a BlockMatrix")
+    dtype = _dtype_code(s.data)
+    _act_buffer(out, torch.float32, int(s.cols), "out")
+    cs = s._c()
+    _check(lib().sputnik_block_column_sum(ctypes.byref(cs), dtype, _ptr(out),
+                                          _stream(stream)), "BlockColumnSum")
+
+
 def sdd_act_route(a, transpose_a, b, transpose_b, c) -> int:
     """Route MatmulActivation[Grad] would take for this problem now: 1 the
     fused epilogue of the 8-wave kernel, 2 plain SDD plus the elementwise
@@ -978,6 +1093,82 @@ def PaddedScatterWeightGrad(dout, y, row_of, dw, top_k, stream=None):  # noqa: N
     _check(lib().sputnik_padded_scatter_wgrad(
         _ptr(dout), _ptr(y), _ptr(row_of), _ptr(dw), tokens, hidden, top_k,
         rows, dtype, wcode, _stream(stream)), "PaddedScatterWeightGrad")
+
+
+def _expert_bias(bias, dtype, hidden: int, what: str) -> int:
+    """The number of experts of an output bias [E, hidden] of `dtype`."""
+    _moe_matrix(bias, dtype, hidden, what)
+    return int(bias.shape[0])
+
+
+def PaddedScatterBias(y, row_of, padded_bins, bias, out, top_k,  # noqa: N802
+                      weights=None, stream=None):
+    """PaddedScatter with an output bias [E, hidden] of y's dtype: out[t] =
+    sum_k w_k * (y[row_k] + bias[e_k]) in fp32 (one add, one multiply, one
+    accumulate per k, ascending k), rounded once. The expert e_k is read off
+    the row through padded_bins (int32 [E]); an assignment whose row is out
+    of range contributes zero, bias included
+    (sputnik_padded_scatter_bias)."""
+    _moe_matrix(y, None, None, "y")
+    dtype = _dtype_code(y)
+    rows, hidden = int(y.shape[0]), int(y.shape[1])
+    _moe_matrix(out, y.dtype, hidden, "out")
+    tokens = int(out.shape[0])
+    n = _moe_sizes(tokens, top_k, rows, "PaddedScatterBias")
+    _moe_meta(row_of, n, "row_of")
+    e = _expert_bias(bias, y.dtype, hidden, "bias")
+    _moe_meta(padded_bins, e, "padded_bins")
+    wcode = (SPUTNIK_WEIGHTS_OPERAND if weights is None
+             else _moe_weights(weights, y.dtype, n, "weights"))
+    _check(lib().sputnik_padded_scatter_bias(
+        _ptr(y), _ptr(row_of), _ptr(padded_bins), _ptr(bias), _ptr(weights),
+        _ptr(out), tokens, hidden, top_k, e, rows, dtype, wcode,
+        _stream(stream)), "PaddedScatterBias")
+
+
+def PaddedScatterBiasWeightGrad(dout, y, row_of, padded_bins, bias, dw,  # noqa: N802
+                                top_k, stream=None):
+    """dw[a] = dot(dout[a // top_k], y[row_of[a]] + bias[e]) in fp32, stored
+    in dw's dtype: the gradient of PaddedScatterBias with respect to its
+    weights (sputnik_padded_scatter_bias_wgrad)."""
+    _moe_matrix(dout, None, None, "dout")
+    dtype = _dtype_code(dout)
+    tokens, hidden = int(dout.shape[0]), int(dout.shape[1])
+    _moe_matrix(y, dout.dtype, hidden, "y")
+    rows = int(y.shape[0])
+    n = _moe_sizes(tokens, top_k, rows, "PaddedScatterBiasWeightGrad")
+    _moe_meta(row_of, n, "row_of")
+    e = _expert_bias(bias, dout.dtype, hidden, "bias")
+    _moe_meta(padded_bins, e, "padded_bins")
+    wcode = _moe_weights(dw, dout.dtype, n, "dw")
+    _check(lib().sputnik_padded_scatter_bias_wgrad(
+        _ptr(dout), _ptr(y), _ptr(row_of), _ptr(padded_bins), _ptr(bias),
+        _ptr(dw), tokens, hidden, top_k, e, rows, dtype, wcode,
+        _stream(stream)), "PaddedScatterBiasWeightGrad")
+
+
+def PaddedScatterBiasGrad(dout, indices, bins, bias_grad, top_k,  # noqa: N802
+                          weights=None, stream=None):
+    """bias_grad [E, hidden] (fp32) = for every expert the sum over its
+    sorted positions i of weights[indices[i]] * dout[indices[i] // top_k]:
+    the gradient of PaddedScatterBias with respect to its bias, from the
+    unrounded fp32 products. No atomics: two runs give the same bits; an
+    expert without tokens gives +0 (sputnik_padded_scatter_bias_grad)."""
+    import torch
+
+    _moe_matrix(dout, None, None, "dout")
+    dtype = _dtype_code(dout)
+    tokens, hidden = int(dout.shape[0]), int(dout.shape[1])
+    n = _moe_sizes(tokens, top_k, 0, "PaddedScatterBiasGrad")
+    e = _expert_bias(bias_grad, torch.float32, hidden, "bias_grad")
+    _moe_meta(indices, n, "indices")
+    _moe_meta(bins, e, "bins")
+    wcode = (SPUTNIK_WEIGHTS_OPERAND if weights is None
+             else _moe_weights(weights, dout.dtype, n, "weights"))
+    _check(lib().sputnik_padded_scatter_bias_grad(
+        _ptr(dout), _ptr(indices), _ptr(bins), _ptr(weights),
+        _ptr(bias_grad), tokens, hidden, top_k, e, dtype, wcode,
+        _stream(stream)), "PaddedScatterBiasGrad")
 
 
 SPUTNIK_ROUTER_F16 = 0
@@ -1523,6 +1714,9 @@ __all__ = [
     "BlockActivationGrad", "SPUTNIK_ACT_RELU", "SPUTNIK_ACT_GELU",
     "SPUTNIK_ACT_SILU", "sdd_act_route",
     "MatmulGated", "MatmulGatedGrad", "BlockGate", "BlockGateGrad",
+    "MatmulBias", "MatmulBiasActivation", "MatmulBiasGated", "BlockColumnSum",
+    "PaddedScatterBias", "PaddedScatterBiasWeightGrad",
+    "PaddedScatterBiasGrad",
     "MoeBins", "MoeRowMap", "PaddedGather", "PaddedScatter",
     "PaddedScatterWeightGrad", "SPUTNIK_WEIGHTS_OPERAND",
     "SPUTNIK_WEIGHTS_F32",

@@ -245,14 +245,53 @@ __device__ __forceinline__ void gate_grad8(int act, act_t8<T> d, act_t8<T> g,
 //   kOutGateGrad  D   G    U    dG   dU          o0 = x s1 act'(s0),
 //                                                o1 = x act(s0)
 //
+//   kOutBias      C             C                o0 = x
+//
 // kKeepsX: the fused route also stores x itself, on request, to the first
 // side slot the op does not read (GemmParams z_data for kOutAct, u_data for
 // kOutGate); the two-kernel route has the plain SDD write x there instead.
+//
+// kTakesBias (sputnik/block/bias.h): with a bias b of C's columns set, the
+// forward ops see xb = round_T((float(x) + float(b[col])) + 0.0f) wherever
+// the table says x, the kept x included (bias_add below). kOutBias is that
+// stage alone; without a bias it is the plain product.
 constexpr int kOutAct = 3, kOutActGrad = 4;
 constexpr int kOutGate = 5, kOutGateGrad = 6;
+constexpr int kOutBias = 7;
 constexpr bool OutModeIsSddEpilogue(int m) {
   return m == kOutAct || m == kOutActGrad || m == kOutGate ||
-         m == kOutGateGrad;
+         m == kOutGateGrad || m == kOutBias;
+}
+
+// The bias stage on one value and on a chunk of 8 (as 4 pairs).
+template <typename T>
+__device__ __forceinline__ T bias_add(T x, T b) {
+#pragma clang fp contract(off)
+  return (T)(((float)x + (float)b) + 0.0f);
+}
+template <typename T>
+__device__ __forceinline__ act_t8<T> bias_add8(act_t8<T> x, act_t8<T> b) {
+#pragma clang fp contract(off)
+  act_t8<T> r;
+#pragma unroll
+  for (int i = 0; i < 8; i += 2) {
+    const act_f2 s = (act_f2{(float)x[i], (float)x[i + 1]} +
+                      act_f2{(float)b[i], (float)b[i + 1]}) + 0.0f;
+    r[i] = (T)s.x;
+    r[i + 1] = (T)s.y;
+  }
+  return r;
+}
+// 8 bias elements from b + col (col % 8 == 0): one 16-byte load when b is
+// 16-byte aligned, 8 element loads otherwise.
+template <typename T>
+__device__ __forceinline__ act_t8<T> bias_load8(const T *b, long long col,
+                                                bool aligned) {
+  if (aligned) return *reinterpret_cast<const act_t8<T> *>(b + col);
+  act_t8<T> r;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r[i] = b[col + i];
+  return r;
 }
 
 template <int kMode>
@@ -261,6 +300,7 @@ struct SddEpilogue;
 template <>
 struct SddEpilogue<kOutAct> {
   static constexpr int kMode = kOutAct;
+  static constexpr bool kTakesBias = true;
   static constexpr int kSideInputs = 0;
   static constexpr bool kKeepsX = true, kSecondOutput = false;
   template <typename T>
@@ -279,6 +319,7 @@ struct SddEpilogue<kOutAct> {
 template <>
 struct SddEpilogue<kOutActGrad> {
   static constexpr int kMode = kOutActGrad;
+  static constexpr bool kTakesBias = false;
   static constexpr int kSideInputs = 1;
   static constexpr bool kKeepsX = false, kSecondOutput = false;
   template <typename T>
@@ -297,6 +338,7 @@ struct SddEpilogue<kOutActGrad> {
 template <>
 struct SddEpilogue<kOutGate> {
   static constexpr int kMode = kOutGate;
+  static constexpr bool kTakesBias = true;
   static constexpr int kSideInputs = 1;
   static constexpr bool kKeepsX = true, kSecondOutput = false;
   template <typename T>
@@ -315,6 +357,7 @@ struct SddEpilogue<kOutGate> {
 template <>
 struct SddEpilogue<kOutGateGrad> {
   static constexpr int kMode = kOutGateGrad;
+  static constexpr bool kTakesBias = false;
   static constexpr int kSideInputs = 2;
   static constexpr bool kKeepsX = false, kSecondOutput = true;
   template <typename T>
@@ -330,6 +373,24 @@ struct SddEpilogue<kOutGateGrad> {
   }
 };
 
+template <>
+struct SddEpilogue<kOutBias> {
+  static constexpr int kMode = kOutBias;
+  static constexpr bool kTakesBias = true;
+  static constexpr int kSideInputs = 0;
+  static constexpr bool kKeepsX = false, kSecondOutput = false;
+  template <typename T>
+  __device__ __forceinline__ static void apply8(int, act_t8<T> x, act_t8<T>,
+                                                act_t8<T>, act_t8<T> *o0,
+                                                act_t8<T> *) {
+    *o0 = x;
+  }
+  template <typename T>
+  __device__ __forceinline__ static void apply(int, T x, T, T, T *o0, T *) {
+    *o0 = x;
+  }
+};
+
 // f(SddEpilogue<mode>{}) for a mode known at run time: the one place that
 // lists the ops for the host code (launchers, dispatch). Not an epilogue
 // mode: `otherwise`.
@@ -340,6 +401,7 @@ R WithSddEpilogue(int mode, R otherwise, F &&f) {
     case kOutActGrad: return f(SddEpilogue<kOutActGrad>{});
     case kOutGate: return f(SddEpilogue<kOutGate>{});
     case kOutGateGrad: return f(SddEpilogue<kOutGateGrad>{});
+    case kOutBias: return f(SddEpilogue<kOutBias>{});
   }
   return otherwise;
 }

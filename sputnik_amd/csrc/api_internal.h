@@ -75,6 +75,23 @@ hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
                           void *side0, void *side1, void *out1,
                           hipStream_t stream, Status *status,
                           Workspace ws = Workspace{});
+// The same with a column bias (sputnik/block/bias.h): `mode` kOutBias,
+// kOutAct or kOutGate, bias c.columns elements of the operand type at any
+// 2-byte alignment. The op sees xb = round(x + bias[col]) for x, and the kept
+// Z / U is xb. A bias that is null or equals c.data, a side buffer, A or B is
+// hipErrorInvalidValue with nothing launched. Same routes: fused, the column
+// from the tile's block; two kernels, the elementwise stage reads
+// c.indices and writes xb back over the kept x in place.
+hipError_t RunSddEpilogueBias(const Matrix &a, bool ta, const Matrix &b,
+                              bool tb, const BlockMatrix &c, int dtype,
+                              int act, int mode, void *side0, void *side1,
+                              const void *bias, hipStream_t stream,
+                              Status *status, Workspace ws = Workspace{});
+// out[c] = sum over the stored blocks of column c of float(s[r, c]), fp32
+// [s.columns] (block_reduce.hip). Walks s's transposed metadata; null there:
+// hipErrorInvalidValue.
+hipError_t RunBlockColumnSum(const BlockMatrix &s, int dtype, float *out,
+                             hipStream_t stream);
 // The route RunSddEpilogue would take now: 1 fused, 2 two kernels, -1
 // rejected.
 int SddActRoute(const Matrix &a, bool ta, const Matrix &b, bool tb,
@@ -90,7 +107,9 @@ hipError_t RunBlockEpilogue(int dtype, int act, int mode, const void *x,
 hipError_t LaunchBlockEpilogue(int dtype, int mode, int act, const void *x,
                                const void *s0, const void *s1, void *o0,
                                void *o1, long long n, int cus,
-                               hipStream_t stream);
+                               hipStream_t stream, const void *bias = nullptr,
+                               const short *column_indices = nullptr,
+                               int col_blocks = 0);
 
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.

@@ -209,6 +209,54 @@ hipError_t MatmulGatedGrad(const Matrix a, bool transpose_a, const Matrix b,
                         up_grad, dtype, stream);
 }
 
+// ---- SDD with a column bias, column sums (sputnik/block/bias.h) ----
+
+static hipError_t MatmulBiasEpilogue(const char *what, const Matrix &a,
+                                     bool ta, const Matrix &b, bool tb,
+                                     const BlockMatrix &c, const void *bias,
+                                     int act, int mode, const void *side0,
+                                     void *side1, DataType dtype,
+                                     hipStream_t stream) {
+  Status st;
+  const hipError_t e = sputnik_amd::RunSddEpilogueBias(
+      a, ta, b, tb, c, (int)dtype, act, mode, const_cast<void *>(side0),
+      side1, bias, stream, &st);
+  return st == Status::kOk ? e : sputnik_amd::OrAbort(st, what);
+}
+
+hipError_t MatmulBias(const Matrix a, bool transpose_a, const Matrix b,
+                      bool transpose_b, BlockMatrix c, const void *bias,
+                      DataType dtype, hipStream_t stream) {
+  return MatmulBiasEpilogue("sdd (bias)", a, transpose_a, b, transpose_b, c,
+                            bias, 0, sputnik_amd::kOutBias, nullptr, nullptr,
+                            dtype, stream);
+}
+
+hipError_t MatmulBiasActivation(const Matrix a, bool transpose_a,
+                                const Matrix b, bool transpose_b,
+                                BlockMatrix c, const void *bias,
+                                Activation activation, void *pre_activation,
+                                DataType dtype, hipStream_t stream) {
+  return MatmulBiasEpilogue("sdd (bias, activation)", a, transpose_a, b,
+                            transpose_b, c, bias, (int)activation,
+                            sputnik_amd::kOutAct, pre_activation, nullptr,
+                            dtype, stream);
+}
+
+hipError_t MatmulBiasGated(const Matrix a, bool transpose_a, const Matrix b,
+                           bool transpose_b, BlockMatrix c, const void *bias,
+                           Activation activation, const void *gate, void *up,
+                           DataType dtype, hipStream_t stream) {
+  return MatmulBiasEpilogue("sdd (bias, gated)", a, transpose_a, b,
+                            transpose_b, c, bias, (int)activation,
+                            sputnik_amd::kOutGate, gate, up, dtype, stream);
+}
+
+hipError_t BlockColumnSum(const BlockMatrix s, DataType dtype, float *out,
+                          hipStream_t stream) {
+  return sputnik_amd::RunBlockColumnSum(s, (int)dtype, out, stream);
+}
+
 // SSD (reference sputnik/block/ssd/ssd.h:10-22) and SDS (sds.h:10-22).
 hipError_t Matmul(const BlockMatrix a, bool transpose_a, const Matrix b,
                   bool transpose_b, BlockMatrix c, DataType dtype,

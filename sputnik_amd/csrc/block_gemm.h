@@ -250,10 +250,14 @@ struct GemmParams {
   int act;
   char *u_data;
   char *du_data;
+  // Column bias of the forward epilogue ops (act_math.h kTakesBias): C's
+  // columns elements of T, any 2-byte alignment, nullptr: none. Last, so
+  // every other field keeps its offset.
+  const char *bias;
 };
 // The kernels read these fields at fixed offsets of the kernel argument:
 // growing or reordering the struct changes the code of every instantiation.
-static_assert(sizeof(GemmParams) == 320, "GemmParams changed");
+static_assert(sizeof(GemmParams) == 328, "GemmParams changed");
 
 // XOR key of the m/n-contiguous image: spreads the 8 k-rows one
 // ds_read_b64_tr_b16 half-wave touches over 8 distinct 32-byte bank sectors.
@@ -601,7 +605,8 @@ constexpr int kOutStore = 0, kOutAccT = 1, kOutAccF32 = 2;
 // kOutGateGrad, with D = round_T(acc), stores dG = round_T((float(D) *
 // float(U)) * act'(float(G))) to C and dU = round_T(float(D) * act(float(G)))
 // to p.du_data, G read from p.z_data and U from p.u_data. (These four are
-// the SDD epilogue ops: constants and traits in act_math.h.)
+// the SDD epilogue ops: constants and traits in act_math.h, where kOutBias
+// and the column bias p.bias of the forward ops are described too.)
 template <typename T, bool kSparseOut, bool kSKC, bool kDKC, bool kOutT,
           class Cfg, bool kSparseIn = false, bool kSparseD = false,
           int kOutMode = kOutStore>
@@ -1670,7 +1675,21 @@ __global__ void __launch_bounds__(64 * Cfg::kWaves,
           const long long off = dst - p.c_data;
           const int act = p.act;
           char *const side[2] = {p.z_data, p.u_data};
-          const t8 x = __builtin_bit_cast(t8, v);
+          t8 x = __builtin_bit_cast(t8, v);
+          if constexpr (E::kTakesBias) {
+            // (the chunk's logical columns: the block's column index, read
+            // back through the offset of its destination in C)
+            if (p.bias != nullptr) {
+              const long long col =
+                  (long long)p.c_indices[off / (kBlock * kBlock * 2)] * kBlock +
+                  (off / 2) % kBlock;
+              const T *b = reinterpret_cast<const T *>(p.bias);
+              x = bias_add8<T>(
+                  x, bias_load8<T>(b, col,
+                                   (reinterpret_cast<uintptr_t>(b) & 15) == 0));
+              v = __builtin_bit_cast(uint4, x);
+            }
+          }
           t8 s0 = x, s1 = x, o0, o1;
           if constexpr (E::kSideInputs >= 1)
             s0 = *reinterpret_cast<const t8 *>(side[0] + off);

@@ -2,10 +2,11 @@
 // 8-wave kernel: the activation products H = act(A B) (Z = A B stored on
 // request) and C = (A B) * act'(Z), and the gated products H = (A B) * act(G)
 // (U = A B stored on request) and the pair dU = (A B) * act(G), dG =
-// (A B) * U * act'(G) (block_gemm.h kOutMode). Their own translation unit,
+// (A B) * U * act'(G), and the column bias of the forward ops and on its own
+// (sputnik/block/bias.h; block_gemm.h kOutMode). Their own translation unit,
 // so the plain products' instantiations in block_gemm.hip are compiled
 // exactly as before. Which activation runs is a runtime field
-// (GemmParams::act), so there are four modes x the plain SDD's
+// (GemmParams::act), so there are five modes x the plain SDD's
 // instantiations: CfgSdd (one k-split block per workgroup) and
 // CfgSddGrouped, four transposes, two types.
 #include "block_gemm.h"

@@ -276,6 +276,63 @@ int sputnik_sdd_gated_grad(const sputnik_matrix_t *a, int transpose_a,
                          ws, ws_bytes, stream);
 }
 
+// SDD with a column bias (sputnik/block/bias.h).
+static int SddBiasCall(const sputnik_matrix_t *a, int transpose_a,
+                       const sputnik_matrix_t *b, int transpose_b,
+                       const sputnik_block_matrix_t *c, const void *bias,
+                       int act, int mode, const void *side0, void *side1,
+                       int dtype, void *ws, size_t ws_bytes, void *stream) {
+  if (!a || !b || !c) return hipErrorInvalidValue;
+  if (act != SPUTNIK_ACT_RELU && act != SPUTNIK_ACT_GELU &&
+      act != SPUTNIK_ACT_SILU)
+    return hipErrorInvalidValue;
+  if (mode == sputnik_amd::kOutGate && side0 == nullptr)
+    return hipErrorInvalidValue;
+  sputnik_amd::Status st;
+  const hipError_t e = sputnik_amd::RunSddEpilogueBias(
+      ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
+      act, mode, const_cast<void *>(side0), side1, bias,
+      static_cast<hipStream_t>(stream), &st,
+      sputnik_amd::Workspace{ws, ws_bytes});
+  return Code(e, sputnik_amd::StatusCode(st));
+}
+
+int sputnik_sdd_bias(const sputnik_matrix_t *a, int transpose_a,
+                     const sputnik_matrix_t *b, int transpose_b,
+                     const sputnik_block_matrix_t *c, const void *bias,
+                     int dtype, void *ws, size_t ws_bytes, void *stream) {
+  return SddBiasCall(a, transpose_a, b, transpose_b, c, bias,
+                     SPUTNIK_ACT_RELU, sputnik_amd::kOutBias, nullptr, nullptr,
+                     dtype, ws, ws_bytes, stream);
+}
+
+int sputnik_sdd_bias_act(const sputnik_matrix_t *a, int transpose_a,
+                         const sputnik_matrix_t *b, int transpose_b,
+                         const sputnik_block_matrix_t *c, const void *bias,
+                         int act, void *z, int dtype, void *ws,
+                         size_t ws_bytes, void *stream) {
+  return SddBiasCall(a, transpose_a, b, transpose_b, c, bias, act,
+                     sputnik_amd::kOutAct, z, nullptr, dtype, ws, ws_bytes,
+                     stream);
+}
+
+int sputnik_sdd_bias_gated(const sputnik_matrix_t *a, int transpose_a,
+                           const sputnik_matrix_t *b, int transpose_b,
+                           const sputnik_block_matrix_t *c, const void *bias,
+                           int act, const void *gate, void *up, int dtype,
+                           void *ws, size_t ws_bytes, void *stream) {
+  return SddBiasCall(a, transpose_a, b, transpose_b, c, bias, act,
+                     sputnik_amd::kOutGate, gate, up, dtype, ws, ws_bytes,
+                     stream);
+}
+
+int sputnik_block_column_sum(const sputnik_block_matrix_t *s, int dtype,
+                             float *out, void *stream) {
+  if (!s) return hipErrorInvalidValue;
+  return sputnik_amd::RunBlockColumnSum(ToCpp(s), dtype, out,
+                                        static_cast<hipStream_t>(stream));
+}
+
 // The elementwise stages alone, in the trait's argument order (x, s0, s1;
 // o0, o1).
 int sputnik_block_activation(const void *z, void *h, long long n, int act,
@@ -540,6 +597,41 @@ int sputnik_padded_scatter_wgrad(const void *dout, const void *y,
   return sputnik_amd::RunPaddedScatterWgrad(
       dout, y, row_of, dw, tokens, hidden, top_k, rows, dtype, weights_dtype,
       static_cast<hipStream_t>(stream));
+}
+
+int sputnik_padded_scatter_bias(const void *y, const int32_t *row_of,
+                                const int32_t *padded_bins, const void *bias,
+                                const void *weights, void *out, int tokens,
+                                int hidden, int top_k, int num_experts,
+                                int rows, int dtype, int weights_dtype,
+                                void *stream) {
+  return sputnik_amd::RunPaddedScatterBias(
+      y, row_of, padded_bins, bias, weights, out, tokens, hidden, top_k,
+      num_experts, rows, dtype, weights_dtype,
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_padded_scatter_bias_wgrad(const void *dout, const void *y,
+                                      const int32_t *row_of,
+                                      const int32_t *padded_bins,
+                                      const void *bias, void *dw, int tokens,
+                                      int hidden, int top_k, int num_experts,
+                                      int rows, int dtype, int weights_dtype,
+                                      void *stream) {
+  return sputnik_amd::RunPaddedScatterBiasWgrad(
+      dout, y, row_of, padded_bins, bias, dw, tokens, hidden, top_k,
+      num_experts, rows, dtype, weights_dtype,
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_padded_scatter_bias_grad(const void *dout, const int32_t *indices,
+                                     const int32_t *bins, const void *weights,
+                                     float *bias_grad, int tokens, int hidden,
+                                     int top_k, int num_experts, int dtype,
+                                     int weights_dtype, void *stream) {
+  return sputnik_amd::RunPaddedScatterBiasGrad(
+      dout, indices, bins, weights, bias_grad, tokens, hidden, top_k,
+      num_experts, dtype, weights_dtype, static_cast<hipStream_t>(stream));
 }
 
 // MoE router and device sort (sputnik/block/router.h): moe_router.hip

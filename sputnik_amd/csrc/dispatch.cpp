@@ -959,10 +959,14 @@ static bool GatedBuffersOk(const Matrix &a, const Matrix &b,
   return true;
 }
 
-hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
-                          const BlockMatrix &c, int dtype, int act, int mode,
-                          void *side0, void *side1, void *out1,
-                          hipStream_t stream, Status *st_out, Workspace ws) {
+// Both entry points: bias null, no bias stage (the caller has checked the
+// bias's own rules).
+static hipError_t SddEpilogueRun(const Matrix &a, bool ta, const Matrix &b,
+                                 bool tb, const BlockMatrix &c, int dtype,
+                                 int act, int mode, void *side0, void *side1,
+                                 void *out1, const void *bias,
+                                 hipStream_t stream, Status *st_out,
+                                 Workspace ws) {
   SddRoute r;
   const int route = SddActRouteOf(a, ta, b, tb, c, stream, &r);
   *st_out = r.status;
@@ -974,7 +978,7 @@ hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
       mode == kOutGate || mode == kOutGateGrad
           ? GatedBuffersOk(a, b, c, side0, side1, out1, mode == kOutGateGrad)
           : !(mode == kOutActGrad && side0 == nullptr) &&
-                !(side0 != nullptr && side0 == c.data);
+                !(side0 != nullptr && side0 == c.data);  // (kOutBias: no side)
   if (!buffers_ok) return hipErrorInvalidValue;
   void *const side[2] = {side0, side1};
   if (route == 2) {
@@ -987,11 +991,23 @@ hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
     const hipError_t err =
         RunSdd(a, ta, b, tb, prod, dtype, stream, st_out, ws);
     if (err != hipSuccess || *st_out != Status::kOk) return err;
-    return RunBlockEpilogue(dtype, act, mode, prod.data,
-                            e.side_inputs >= 1 ? side0 : nullptr,
-                            e.side_inputs >= 2 ? side1 : nullptr, c.data,
-                            e.second_output ? out1 : nullptr, c.nonzeros,
-                            stream);
+    if (bias == nullptr)
+      return RunBlockEpilogue(dtype, act, mode, prod.data,
+                              e.side_inputs >= 1 ? side0 : nullptr,
+                              e.side_inputs >= 2 ? side1 : nullptr, c.data,
+                              e.second_output ? out1 : nullptr, c.nonzeros,
+                              stream);
+    // (the forward ops: at most one side input, no second output)
+    if (c.nonzeros <= 0) return hipSuccess;
+    if (c.indices == nullptr || (dtype != 0 && dtype != 1))
+      return hipErrorInvalidValue;
+    int dev = 0;
+    const int cus = hipGetDevice(&dev) == hipSuccess ? DeviceCUs(dev) : 0;
+    return LaunchBlockEpilogue(dtype, mode, act, prod.data,
+                               e.side_inputs >= 1 ? side0 : nullptr, nullptr,
+                               c.data, nullptr, c.nonzeros, cus, stream, bias,
+                               static_cast<const short *>(c.indices),
+                               c.cols / kBlock);
   }
   // Fused: the 8-wave kernel with the route's own params and tile plan.
   const InProduct in_product;
@@ -1001,8 +1017,39 @@ hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
   p.z_data = static_cast<char *>(side0);
   p.u_data = static_cast<char *>(side1);
   p.du_data = static_cast<char *>(out1);
+  p.bias = static_cast<const char *>(bias);
   return LaunchBlockGemmEpilogue(dtype, /*s_kc=*/!ta, /*d_kc=*/tb, r.grouped,
                                  mode, p, stream);
+}
+
+hipError_t RunSddEpilogue(const Matrix &a, bool ta, const Matrix &b, bool tb,
+                          const BlockMatrix &c, int dtype, int act, int mode,
+                          void *side0, void *side1, void *out1,
+                          hipStream_t stream, Status *st_out, Workspace ws) {
+  // (kOutBias is the bias entry point's alone)
+  if (mode == kOutBias) {
+    *st_out = Status::kOk;
+    return hipErrorInvalidValue;
+  }
+  return SddEpilogueRun(a, ta, b, tb, c, dtype, act, mode, side0, side1, out1,
+                        nullptr, stream, st_out, ws);
+}
+
+hipError_t RunSddEpilogueBias(const Matrix &a, bool ta, const Matrix &b,
+                              bool tb, const BlockMatrix &c, int dtype,
+                              int act, int mode, void *side0, void *side1,
+                              const void *bias, hipStream_t stream,
+                              Status *st_out, Workspace ws) {
+  *st_out = Status::kOk;
+  if (mode != kOutBias && mode != kOutAct && mode != kOutGate)
+    return hipErrorInvalidValue;
+  if (bias == nullptr || bias == c.data || bias == a.data || bias == b.data ||
+      bias == side0 || bias == side1)
+    return hipErrorInvalidValue;
+  // (kOutBias has no activation: any valid code)
+  return SddEpilogueRun(a, ta, b, tb, c, dtype,
+                        mode == kOutBias ? kActRelu : act, mode, side0, side1,
+                        nullptr, bias, stream, st_out, ws);
 }
 
 hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,

@@ -37,6 +37,29 @@ hipError_t RunPaddedScatterWgrad(const void *dout, const void *y,
                                  int hidden, int top_k, int rows, int dtype,
                                  int weights_dtype, hipStream_t stream);
 
+// The scatter with an output bias [num_experts, hidden] of the operand type
+// and its gradients (moe.h PaddedScatterBias*): the expert of an assignment
+// is read off its row through padded_bins.
+hipError_t RunPaddedScatterBias(const void *y, const int *row_of,
+                                const int *padded_bins, const void *bias,
+                                const void *weights, void *out, int tokens,
+                                int hidden, int top_k, int num_experts,
+                                int rows, int dtype, int weights_dtype,
+                                hipStream_t stream);
+
+hipError_t RunPaddedScatterBiasWgrad(const void *dout, const void *y,
+                                     const int *row_of, const int *padded_bins,
+                                     const void *bias, void *dw, int tokens,
+                                     int hidden, int top_k, int num_experts,
+                                     int rows, int dtype, int weights_dtype,
+                                     hipStream_t stream);
+
+hipError_t RunPaddedScatterBiasGrad(const void *dout, const int *indices,
+                                    const int *bins, const void *weights,
+                                    float *db, int tokens, int hidden,
+                                    int top_k, int num_experts, int dtype,
+                                    int weights_dtype, hipStream_t stream);
+
 }  // namespace sputnik_amd
 
 #endif  // SPUTNIK_AMD_MOE_PERMUTE_H_

@@ -259,6 +259,223 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// ---- the scatter with an output bias (moe.h PaddedScatterBias) ---------------
+// The expert of an assignment is read off its row: #{e : padded_bins[e] <=
+// row}. A row outside [0, rows), or at or past padded_bins[E-1] (no expert
+// owns it), contributes zero, bias included. Contraction is off: one add, one
+// multiply (with weights) and one accumulate per k, as moe.h states them.
+
+// The expert that owns padded row `row`, or -1.
+__device__ __forceinline__ int row_expert(int row, int rows,
+                                          const int *__restrict__ padded_bins,
+                                          int num_experts) {
+  if (row < 0 || row >= rows) return -1;
+  const int e = upper_bound(padded_bins, num_experts, row);
+  return e < num_experts ? e : -1;
+}
+
+constexpr int kHoist = 4;  // picks looked up in front of the piece loop
+
+template <typename T, typename W, bool kVec>
+__global__ void __launch_bounds__(kThreads)
+    padded_scatter_bias_kernel(const T *__restrict__ y,
+                               const int *__restrict__ row_of,
+                               const int *__restrict__ padded_bins,
+                               const T *__restrict__ bias,
+                               const W *__restrict__ weights,
+                               T *__restrict__ out, int tokens, int hidden,
+                               int top_k, int num_experts, int rows) {
+#pragma clang fp contract(off)
+  using P = typename Piece<T, kVec>::type;
+  constexpr int kElems = Piece<T, kVec>::kElems;
+  const int lane = threadIdx.x & 63;
+  const int pieces = hidden / kElems;
+  const int tasks =
+      tokens / kRowsInFlight + (tokens % kRowsInFlight != 0);
+  const int stride = gridDim.x * kWaves;
+  for (int task = blockIdx.x * kWaves + wave_index(); task < tasks;
+       task += stride) {
+    const int t0 = task * kRowsInFlight;
+    // The row, expert and weight of pick k of the task's tokens (e < 0:
+    // contributes zero). Wave-uniform; the first kHoist picks are looked up
+    // once per task, in front of the piece loop, so that the searches are
+    // not on every piece's path to its loads.
+    struct Pick { int row, e; float wt; };
+    auto pick = [&](int u, int k) {
+      const int t = t0 + u;
+      const int a = t < tokens ? t * top_k + k : 0;  // < n <= INT_MAX
+      const int row = t < tokens ? row_of[a] : -1;
+      const int e = row_expert(row, rows, padded_bins, num_experts);
+      return Pick{row, e,
+                  e >= 0 && weights != nullptr ? (float)weights[a] : 1.0f};
+    };
+    Pick first[kHoist][kRowsInFlight];
+#pragma unroll
+    for (int k = 0; k < kHoist; ++k)
+#pragma unroll
+      for (int u = 0; u < kRowsInFlight; ++u)
+        first[k][u] = k < top_k ? pick(u, k) : Pick{-1, -1, 1.0f};
+    for (int c = lane; c < pieces; c += 64) {
+      float acc[kRowsInFlight][kElems];
+#pragma unroll
+      for (int u = 0; u < kRowsInFlight; ++u)
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) acc[u][j] = 0.0f;
+      // One pick of every token: the loads, then add, multiply, accumulate.
+      auto step = [&](const Pick (&q)[kRowsInFlight]) {
+        P v[kRowsInFlight], b[kRowsInFlight];
+#pragma unroll
+        for (int u = 0; u < kRowsInFlight; ++u) {
+          const bool ok = q[u].e >= 0;
+          v[u] = ok ? reinterpret_cast<const P *>(
+                          y + (long long)q[u].row * hidden)[c]
+                    : piece_zero<T, kVec>();
+          b[u] = ok ? reinterpret_cast<const P *>(
+                          bias + (long long)q[u].e * hidden)[c]
+                    : piece_zero<T, kVec>();
+        }
+#pragma unroll
+        for (int u = 0; u < kRowsInFlight; ++u)
+#pragma unroll
+          for (int j = 0; j < kElems; ++j) {
+            float s = piece_get<T, kVec>(v[u], j) + piece_get<T, kVec>(b[u], j);
+            if (weights != nullptr) s = q[u].wt * s;
+            acc[u][j] = acc[u][j] + s;
+          }
+      };
+#pragma unroll
+      for (int k = 0; k < kHoist; ++k)
+        if (k < top_k) step(first[k]);
+      for (int k = kHoist; k < top_k; ++k) {
+        Pick q[kRowsInFlight];
+#pragma unroll
+        for (int u = 0; u < kRowsInFlight; ++u) q[u] = pick(u, k);
+        step(q);
+      }
+#pragma unroll
+      for (int u = 0; u < kRowsInFlight; ++u) {
+        const int t = t0 + u;
+        if (t >= tokens) continue;
+        P r;
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) piece_set<T, kVec>(&r, j, acc[u][j]);
+        reinterpret_cast<P *>(out + (long long)t * hidden)[c] = r;
+      }
+    }
+  }
+}
+
+template <typename T, typename W, bool kVec>
+__global__ void __launch_bounds__(kThreads)
+    padded_scatter_bias_wgrad_kernel(const T *__restrict__ dout,
+                                     const T *__restrict__ y,
+                                     const int *__restrict__ row_of,
+                                     const int *__restrict__ padded_bins,
+                                     const T *__restrict__ bias,
+                                     W *__restrict__ dw, int n, int hidden,
+                                     int top_k, int num_experts, int rows) {
+  using P = typename Piece<T, kVec>::type;
+  constexpr int kElems = Piece<T, kVec>::kElems;
+  const int lane = threadIdx.x & 63;
+  const int pieces = hidden / kElems;
+  const int stride = gridDim.x * kWaves;
+  for (long long a = blockIdx.x * kWaves + wave_index(); a < n;
+       a += stride) {
+    const int row = row_of[a];
+    const int e = row_expert(row, rows, padded_bins, num_experts);
+    float s = 0.0f;
+    if (e >= 0) {
+      const P *d = reinterpret_cast<const P *>(
+          dout + (long long)(a / top_k) * hidden);
+      const P *r = reinterpret_cast<const P *>(y + (long long)row * hidden);
+      const P *b = reinterpret_cast<const P *>(bias + (long long)e * hidden);
+      for (int c0 = lane; c0 < pieces; c0 += 64 * kRowsInFlight) {
+        P dv[kRowsInFlight], rv[kRowsInFlight], bv[kRowsInFlight];
+#pragma unroll
+        for (int u = 0; u < kRowsInFlight; ++u) {
+          const int c = c0 + 64 * u;
+          dv[u] = c < pieces ? d[c] : piece_zero<T, kVec>();
+          rv[u] = c < pieces ? r[c] : piece_zero<T, kVec>();
+          bv[u] = c < pieces ? b[c] : piece_zero<T, kVec>();
+        }
+#pragma unroll
+        for (int u = 0; u < kRowsInFlight; ++u)
+#pragma unroll
+          for (int j = 0; j < kElems; ++j)
+            s += piece_get<T, kVec>(dv[u], j) *
+                 (piece_get<T, kVec>(rv[u], j) + piece_get<T, kVec>(bv[u], j));
+      }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    if (lane == 0) dw[a] = (W)s;
+  }
+}
+
+// db2[e, h] = sum over expert e's sorted positions i of w[indices[i]] *
+// dout[indices[i] / top_k, h]. One workgroup per (expert, slice of 16 pieces
+// of a row: 256 bytes on the vector path). Thread (g, l), g = 0..63, takes
+// piece l of positions b0 + g, b0 + g + 64, ..., kRowsInFlight of them in
+// flight, and adds them in that order; the 64 partial sums of a column are
+// then added through LDS in g order by one thread. No atomics, no workspace;
+// the order depends on the bins alone.
+constexpr int kReduceThreads = 1024;
+constexpr int kReduceGroups = kReduceThreads / 16;
+
+template <typename T, typename W, bool kVec>
+__global__ void __launch_bounds__(kReduceThreads)
+    padded_scatter_bias_grad_kernel(const T *__restrict__ dout,
+                                    const int *__restrict__ indices,
+                                    const int *__restrict__ bins,
+                                    const W *__restrict__ weights,
+                                    float *__restrict__ db, int n, int hidden,
+                                    int top_k, int slices) {
+#pragma clang fp contract(off)
+  using P = typename Piece<T, kVec>::type;
+  constexpr int kElems = Piece<T, kVec>::kElems;
+  __shared__ float part[kReduceGroups][16 * kElems];
+  const int l = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const int e = blockIdx.x / slices, slice = blockIdx.x % slices;
+  const int c = slice * 16 + l;  // this thread's piece
+  const int pieces = hidden / kElems;
+  int b0 = e ? bins[e - 1] : 0, b1 = bins[e];
+  // (bins out of range: the part of them that is in range)
+  b0 = min(max(b0, 0), n);
+  b1 = min(max(b1, b0), n);
+  float acc[kElems];
+#pragma unroll
+  for (int j = 0; j < kElems; ++j) acc[j] = 0.0f;
+  for (int i0 = b0 + g; i0 < b1; i0 += kReduceGroups * kRowsInFlight) {
+    P v[kRowsInFlight];
+    float wt[kRowsInFlight];
+#pragma unroll
+    for (int u = 0; u < kRowsInFlight; ++u) {
+      const int i = i0 + u * kReduceGroups;
+      const int a = i < b1 ? indices[i] : -1;
+      const bool ok = a >= 0 && a < n && c < pieces;
+      v[u] = ok ? reinterpret_cast<const P *>(
+                      dout + (long long)(a / top_k) * hidden)[c]
+                : piece_zero<T, kVec>();
+      wt[u] = ok && weights != nullptr ? (float)weights[a] : 1.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < kRowsInFlight; ++u)
+#pragma unroll
+      for (int j = 0; j < kElems; ++j)
+        acc[j] = acc[j] + wt[u] * piece_get<T, kVec>(v[u], j);
+  }
+#pragma unroll
+  for (int j = 0; j < kElems; ++j) part[g][l * kElems + j] = acc[j];
+  __syncthreads();
+  if (threadIdx.x < 16 * kElems) {
+    float s = 0.0f;
+#pragma unroll 8
+    for (int r = 0; r < kReduceGroups; ++r) s = s + part[r][threadIdx.x];
+    const long long h = (long long)slice * 16 * kElems + threadIdx.x;
+    if (h < hidden) db[(long long)e * hidden + h] = s + 0.0f;
+  }
+}
+
 // ---- metadata ---------------------------------------------------------------
 // One workgroup. bins[e] = #{i : bin_ids[i] <= e}, a binary search of the
 // sorted ids per expert; then tokens_per_expert (the differences) and
@@ -501,10 +718,147 @@ hipError_t RunPaddedScatterWgrad(const void *dout, const void *y,
   });
 }
 
+hipError_t RunPaddedScatterBias(const void *y, const int *row_of,
+                                const int *padded_bins, const void *bias,
+                                const void *weights, void *out, int tokens,
+                                int hidden, int top_k, int num_experts,
+                                int rows, int dtype, int weights_dtype,
+                                hipStream_t stream) {
+  if (!SizesOk(tokens, hidden, top_k, rows, dtype) || num_experts < 0 ||
+      (weights != nullptr && weights_dtype != 0 && weights_dtype != 1))
+    return hipErrorInvalidValue;
+  if (tokens == 0 || hidden == 0) return hipSuccess;
+  // (without experts or rows every assignment contributes zero)
+  const bool routed = rows > 0 && num_experts > 0;
+  if (out == nullptr || row_of == nullptr ||
+      (routed && (y == nullptr || bias == nullptr || padded_bins == nullptr)))
+    return hipErrorInvalidValue;
+  if (out == y || out == weights || out == row_of || out == bias ||
+      out == padded_bins)
+    return hipErrorInvalidValue;
+  const bool vec = hidden % 8 == 0 && Aligned16({y, out, bias});
+  const unsigned grid =
+      GridFor(((long long)tokens + kRowsInFlight - 1) / kRowsInFlight);
+  return WithTypes(dtype, weights != nullptr ? weights_dtype : 0, vec,
+                   [&](auto t, auto w, auto v) {
+    using T = decltype(t);
+    using W = decltype(w);
+    hipLaunchKernelGGL((padded_scatter_bias_kernel<T, W, decltype(v)::value>),
+                       dim3(grid), dim3(kThreads), 0, stream,
+                       static_cast<const T *>(y), row_of, padded_bins,
+                       static_cast<const T *>(bias),
+                       static_cast<const W *>(weights), static_cast<T *>(out),
+                       tokens, hidden, top_k, routed ? num_experts : 0,
+                       routed ? rows : 0);
+    return hipGetLastError();
+  });
+}
+
+hipError_t RunPaddedScatterBiasWgrad(const void *dout, const void *y,
+                                     const int *row_of, const int *padded_bins,
+                                     const void *bias, void *dw, int tokens,
+                                     int hidden, int top_k, int num_experts,
+                                     int rows, int dtype, int weights_dtype,
+                                     hipStream_t stream) {
+  if (!SizesOk(tokens, hidden, top_k, rows, dtype) || num_experts < 0 ||
+      (weights_dtype != 0 && weights_dtype != 1))
+    return hipErrorInvalidValue;
+  if (tokens == 0) return hipSuccess;
+  const bool routed = rows > 0 && num_experts > 0 && hidden > 0;
+  if (dw == nullptr || row_of == nullptr ||
+      (routed && (dout == nullptr || y == nullptr || bias == nullptr ||
+                  padded_bins == nullptr)))
+    return hipErrorInvalidValue;
+  if (dw == dout || dw == y || dw == row_of || dw == bias ||
+      dw == padded_bins)
+    return hipErrorInvalidValue;
+  const int n = tokens * top_k;
+  const bool vec = hidden % 8 == 0 && Aligned16({dout, y, bias});
+  const unsigned grid = GridFor(n);
+  return WithTypes(dtype, weights_dtype, vec, [&](auto t, auto w, auto v) {
+    using T = decltype(t);
+    using W = decltype(w);
+    hipLaunchKernelGGL(
+        (padded_scatter_bias_wgrad_kernel<T, W, decltype(v)::value>),
+        dim3(grid), dim3(kThreads), 0, stream, static_cast<const T *>(dout),
+        static_cast<const T *>(y), row_of, padded_bins,
+        static_cast<const T *>(bias), static_cast<W *>(dw), n, hidden, top_k,
+        routed ? num_experts : 0, routed ? rows : 0);
+    return hipGetLastError();
+  });
+}
+
+hipError_t RunPaddedScatterBiasGrad(const void *dout, const int *indices,
+                                    const int *bins, const void *weights,
+                                    float *db, int tokens, int hidden,
+                                    int top_k, int num_experts, int dtype,
+                                    int weights_dtype, hipStream_t stream) {
+  if (!SizesOk(tokens, hidden, top_k, 0, dtype) || num_experts < 0 ||
+      (weights != nullptr && weights_dtype != 0 && weights_dtype != 1))
+    return hipErrorInvalidValue;
+  if (num_experts == 0 || hidden == 0) return hipSuccess;
+  const int n = tokens * top_k;
+  if (db == nullptr || bins == nullptr ||
+      (n > 0 && (dout == nullptr || indices == nullptr)))
+    return hipErrorInvalidValue;
+  if (db == dout || db == weights || db == (const void *)indices ||
+      db == (const void *)bins)
+    return hipErrorInvalidValue;
+  const bool vec = hidden % 8 == 0 && Aligned16({dout});
+  const int per_slice = 16 * (vec ? 8 : 1);
+  const long long slices = ((long long)hidden + per_slice - 1) / per_slice;
+  if (slices * num_experts > INT_MAX) return hipErrorInvalidValue;
+  return WithTypes(dtype, weights != nullptr ? weights_dtype : 0, vec,
+                   [&](auto t, auto w, auto v) {
+    using T = decltype(t);
+    using W = decltype(w);
+    hipLaunchKernelGGL(
+        (padded_scatter_bias_grad_kernel<T, W, decltype(v)::value>),
+        dim3((unsigned)(slices * num_experts)), dim3(kReduceThreads), 0,
+        stream, static_cast<const T *>(dout), indices, bins,
+        static_cast<const W *>(weights), db, n, hidden, top_k, (int)slices);
+    return hipGetLastError();
+  });
+}
+
 }  // namespace sputnik_amd
 
 namespace sputnik {
 namespace block {
+
+hipError_t PaddedScatterBias(const void *y, const int *row_of,
+                             const int *padded_bins, const void *bias,
+                             const void *weights, void *out, int tokens,
+                             int hidden, int top_k, int num_experts, int rows,
+                             DataType dtype, WeightType weights_type,
+                             hipStream_t stream) {
+  return sputnik_amd::RunPaddedScatterBias(
+      y, row_of, padded_bins, bias, weights, out, tokens, hidden, top_k,
+      num_experts, rows, (int)dtype, (int)weights_type, stream);
+}
+
+hipError_t PaddedScatterBiasWeightGrad(const void *dout, const void *y,
+                                       const int *row_of,
+                                       const int *padded_bins,
+                                       const void *bias, void *dw, int tokens,
+                                       int hidden, int top_k, int num_experts,
+                                       int rows, DataType dtype,
+                                       WeightType weights_type,
+                                       hipStream_t stream) {
+  return sputnik_amd::RunPaddedScatterBiasWgrad(
+      dout, y, row_of, padded_bins, bias, dw, tokens, hidden, top_k,
+      num_experts, rows, (int)dtype, (int)weights_type, stream);
+}
+
+hipError_t PaddedScatterBiasGrad(const void *dout, const int *indices,
+                                 const int *bins, const void *weights,
+                                 float *bias_grad, int tokens, int hidden,
+                                 int top_k, int num_experts, DataType dtype,
+                                 WeightType weights_type, hipStream_t stream) {
+  return sputnik_amd::RunPaddedScatterBiasGrad(
+      dout, indices, bins, weights, bias_grad, tokens, hidden, top_k,
+      num_experts, (int)dtype, (int)weights_type, stream);
+}
 
 hipError_t MoeBins(const int *bin_ids, int n, int num_experts, int *bins,
                    int *tokens_per_expert, int *padded_bins,

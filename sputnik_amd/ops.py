@@ -37,6 +37,14 @@ pass, `load_balancing_loss` / `router_z_loss` the losses formed from them, and
 on score + bias and limit the choice to the best groups of experts
 (RouterScoreTopK), `moe_score_layer` the layer routed by it and
 `router_bias_update` the auxiliary-loss-free correction of that bias.
+Expert biases (sputnik/block/bias.h) come as entry points of their own, each
+named after the bias-free one and equal to it without a bias: `sdd_bias(a, b,
+topo, bias)`, `sdd_act_bias` and `sdd_gated_bias` add a column bias in the
+product's epilogue, `column_sum(sparse)` is its gradient, `mlp_bias(..., b1=)`
+/ `glu_mlp_bias(..., b1=, bv1=)`, `padded_scatter_bias(..., bias=)` and
+`moe_mlp_bias` / `moe_layer_bias` / `moe_layer_aux_bias` /
+`moe_score_layer_bias(..., b1=, bv1=, b2=)` carry them through the expert
+MLP and the scatter.
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -62,6 +70,9 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                MatmulActivation, MatmulActivationGrad, MatmulEx, MatmulGated,
                MatmulGatedGrad, MoeBins, MoeRowMap, MoeSort, PaddedGather,
                PaddedScatter, PaddedScatterWeightGrad, RouterTopK,
+               BlockColumnSum, MatmulBias, MatmulBiasActivation,
+               MatmulBiasGated, PaddedScatterBias, PaddedScatterBiasGrad,
+               PaddedScatterBiasWeightGrad,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
                RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
                MOE_SORT_CHUNK, ROUTER_AUX_TOKENS, ROUTER_MAX_EXPERTS,
@@ -279,41 +290,90 @@ def _sdd_setup(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix):
     return am, ta, bm, tb, cd, ws, data
 
 
-def _sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix) -> torch.Tensor:
+def _sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
+         bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Block values of (a @ b) at topo's nonzero blocks, in topo's storage
-    order."""
+    order; with `bias`, of round(a @ b) + bias[col] (MatmulBias)."""
     am, ta, bm, tb, cd, ws, data = _sdd_setup(a, b, topo)
-    Matmul(am, ta, bm, tb, cd, workspace=ws)
+    if bias is None:
+        Matmul(am, ta, bm, tb, cd, workspace=ws)
+    else:
+        MatmulBias(am, ta, bm, tb, cd, bias, workspace=ws)
     return data
+
+
+def _check_bias(bias, ref: torch.Tensor, shape: tuple, what: str):
+    """An expert bias: a tensor of `shape`, of ref's dtype and device."""
+    if not isinstance(bias, torch.Tensor):
+        raise TypeError(f"{what} must be a tensor")
+    if bias.dtype != ref.dtype:
+        raise TypeError(f"{what} is {bias.dtype}, expected {ref.dtype}")
+    if bias.device != ref.device:
+        raise ValueError(f"{what} is on {bias.device}, expected {ref.device}")
+    if tuple(bias.shape) != tuple(shape):
+        raise ValueError(f"{what} has shape {tuple(bias.shape)}, expected "
+                         f"{tuple(shape)}")
+
+
+def _column_bias(bias, ref: torch.Tensor, topo: SparseMatrix, what: str):
+    """A column bias of an SDD into topo (None passes): [topo's columns] of
+    ref's dtype and device, made contiguous. The bias is indexed by the
+    stored matrix's columns, so a transposed topo view takes none."""
+    if bias is None:
+        return None
+    if topo.is_transposed():
+        raise ValueError(f"{what}: a bias needs a topo that is not a .t() "
+                         "view")
+    _check_bias(bias, ref, (topo.shape[1],), what)
+    return bias.contiguous()
+
+
+def _column_sum(data: torch.Tensor, topo: SparseMatrix) -> torch.Tensor:
+    """fp32 [columns]: the column sums of topo's blocks with values `data`
+    (BlockColumnSum)."""
+    topo._meta.ensure_transposed(data)
+    out = torch.empty(topo._meta.cols, dtype=torch.float32,
+                      device=data.device)
+    BlockColumnSum(topo._meta.descriptor(data), out)
+    return out
 
 
 def _sdd_act(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix, act: int,
              z: Optional[torch.Tensor] = None, grad: bool = False,
-             keep_z: bool = False):
+             keep_z: bool = False, bias: Optional[torch.Tensor] = None):
     """_sdd with the activation epilogue (MatmulActivation[Grad]). Forward
-    (grad False): returns (H, Z), Z None unless keep_z. Gradient: returns
-    round(a @ b) * act'(z) at topo's blocks."""
+    (grad False): returns (H, Z), Z None unless keep_z; with `bias`, Z is the
+    biased product (MatmulBiasActivation). Gradient: returns round(a @ b) *
+    act'(z) at topo's blocks."""
     am, ta, bm, tb, cd, ws, data = _sdd_setup(a, b, topo)
     if grad:
         MatmulActivationGrad(am, ta, bm, tb, cd, act, z, workspace=ws)
         return data
     z = torch.empty_like(data) if keep_z else None
-    MatmulActivation(am, ta, bm, tb, cd, act, z, workspace=ws)
+    if bias is None:
+        MatmulActivation(am, ta, bm, tb, cd, act, z, workspace=ws)
+    else:
+        MatmulBiasActivation(am, ta, bm, tb, cd, bias, act, z, workspace=ws)
     return data, z
 
 
 def _sdd_gated(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix, act: int,
                gate: torch.Tensor, up: Optional[torch.Tensor] = None,
-               grad: bool = False, keep_up: bool = False):
+               grad: bool = False, keep_up: bool = False,
+               bias: Optional[torch.Tensor] = None):
     """_sdd with the gated epilogue (MatmulGated[Grad]); `gate` is G's block
-    data. Forward (grad False): returns (H, U), U None unless keep_up.
-    Gradient: returns (dG, dU) of D = a @ b, dU written over `up`."""
+    data. Forward (grad False): returns (H, U), U None unless keep_up; with
+    `bias`, U is the biased product (MatmulBiasGated). Gradient: returns
+    (dG, dU) of D = a @ b, dU written over `up`."""
     am, ta, bm, tb, cd, ws, data = _sdd_setup(a, b, topo)
     if grad:
         MatmulGatedGrad(am, ta, bm, tb, cd, act, gate, up, up, workspace=ws)
         return data, up
     up = torch.empty_like(data) if keep_up else None
-    MatmulGated(am, ta, bm, tb, cd, act, gate, up, workspace=ws)
+    if bias is None:
+        MatmulGated(am, ta, bm, tb, cd, act, gate, up, workspace=ws)
+    else:
+        MatmulBiasGated(am, ta, bm, tb, cd, bias, act, gate, up, workspace=ws)
     return data, up
 
 
@@ -453,11 +513,12 @@ class _DDS(torch.autograd.Function):
 
 class _SDD(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, topo, a_sink, b_sink):
+    def forward(ctx, a, b, topo, a_sink, b_sink, bias=None):
         ctx.topo = topo
         ctx.a_sink, ctx.b_sink = a_sink, b_sink
         ctx.save_for_backward(a, b)
-        return _sdd(a, b, topo)
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return _sdd(a, b, topo, bias)
 
     @staticmethod
     def backward(ctx, dc_data):
@@ -472,18 +533,23 @@ class _SDD(torch.autograd.Function):
             ctx.b_sink.add_dds(a.t(), dc)              # sink += A^T dC
         elif ctx.needs_input_grad[1]:
             db = _dds(a.t(), dc)                       # A^T dC
-        return da, db, None, None, None
+        dbias = None
+        if ctx.bias_dtype is not None and ctx.needs_input_grad[5]:
+            dbias = _column_sum(dc.data, ctx.topo).to(ctx.bias_dtype)
+        return da, db, None, None, None, dbias
 
 
 class _SDDAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, topo, act, a_sink, b_sink):
+    def forward(ctx, a, b, topo, act, a_sink, b_sink, bias=None):
         ctx.topo, ctx.act = topo, act
         ctx.a_sink, ctx.b_sink = a_sink, b_sink
+        ctx.bias_dtype = None if bias is None else bias.dtype
         # (Z is stored only when a backward pass can follow)
         keep = (any(ctx.needs_input_grad[:2]) or a_sink is not None
-                or b_sink is not None)
-        h, z = _sdd_act(a, b, topo, act, keep_z=keep)
+                or b_sink is not None
+                or (bias is not None and ctx.needs_input_grad[6]))
+        h, z = _sdd_act(a, b, topo, act, keep_z=keep, bias=bias)
         if keep:
             ctx.save_for_backward(a, b, z)
         return h
@@ -503,7 +569,10 @@ class _SDDAct(torch.autograd.Function):
             ctx.b_sink.add_dds(a.t(), dc)              # sink += A^T dZ
         elif ctx.needs_input_grad[1]:
             db = _dds(a.t(), dc)                       # A^T dZ
-        return da, db, None, None, None, None
+        dbias = None
+        if ctx.bias_dtype is not None and ctx.needs_input_grad[6]:
+            dbias = _column_sum(dz, ctx.topo).to(ctx.bias_dtype)
+        return da, db, None, None, None, None, dbias
 
 
 class _MLP(torch.autograd.Function):
@@ -511,12 +580,14 @@ class _MLP(torch.autograd.Function):
     recomputed in backward, bit for bit what forward multiplied by w2."""
 
     @staticmethod
-    def forward(ctx, x, w1, w2, topo, act, w1_sink, w2_sink):
+    def forward(ctx, x, w1, w2, topo, act, w1_sink, w2_sink, b1=None):
         ctx.topo, ctx.act = topo, act
         ctx.w1_sink, ctx.w2_sink = w1_sink, w2_sink
+        # (the bias is not kept: backward needs its dtype alone)
+        ctx.b1 = b1 is not None and ctx.needs_input_grad[7] and b1.dtype
         keep = (any(ctx.needs_input_grad[:3]) or w1_sink is not None
-                or w2_sink is not None)
-        h, z = _sdd_act(x, w1, topo, act, keep_z=keep)
+                or w2_sink is not None or bool(ctx.b1))
+        h, z = _sdd_act(x, w1, topo, act, keep_z=keep, bias=b1)
         if keep:
             ctx.save_for_backward(x, w1, w2, z)
         return _dsd(topo.with_data(h), w2)
@@ -525,7 +596,7 @@ class _MLP(torch.autograd.Function):
     def backward(ctx, dy):
         x, w1, w2, z = ctx.saved_tensors
         topo = ctx.topo
-        dx = dw1 = dw2 = None
+        dx = dw1 = dw2 = db1 = None
         if ctx.w2_sink is not None or ctx.needs_input_grad[2]:
             h = topo.with_data(BlockActivation(z, ctx.act))
             if ctx.w2_sink is not None:
@@ -534,7 +605,7 @@ class _MLP(torch.autograd.Function):
                 dw2 = _dsd(h.t(), dy)                  # H^T dY
             del h
         if (ctx.w1_sink is not None or ctx.needs_input_grad[0]
-                or ctx.needs_input_grad[1]):
+                or ctx.needs_input_grad[1] or ctx.b1):
             # dZ = (dY W2^T) * act'(Z), one product
             dz = topo.with_data(_sdd_act(dy, w2.t(), topo, ctx.act, z=z,
                                          grad=True))
@@ -544,19 +615,23 @@ class _MLP(torch.autograd.Function):
                 ctx.w1_sink.add_dds(x.t(), dz)         # sink += X^T dZ
             elif ctx.needs_input_grad[1]:
                 dw1 = _dds(x.t(), dz)                  # X^T dZ
-        return dx, dw1, dw2, None, None, None, None
+            if ctx.b1:
+                db1 = _column_sum(dz.data, topo).to(ctx.b1)
+        return dx, dw1, dw2, None, None, None, None, db1
 
 
 class _SDDGated(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, gate_data, topo, act, a_sink, b_sink):
+    def forward(ctx, a, b, gate_data, topo, act, a_sink, b_sink, bias=None):
         ctx.topo, ctx.act = topo, act
         ctx.a_sink, ctx.b_sink = a_sink, b_sink
+        ctx.bias_dtype = None if bias is None else bias.dtype
         # (U is stored only when a backward pass can follow)
         keep = (any(ctx.needs_input_grad[:3]) or a_sink is not None
-                or b_sink is not None)
+                or b_sink is not None
+                or (bias is not None and ctx.needs_input_grad[7]))
         g = gate_data.contiguous()
-        h, u = _sdd_gated(a, b, topo, act, g, keep_up=keep)
+        h, u = _sdd_gated(a, b, topo, act, g, keep_up=keep, bias=bias)
         if keep:
             ctx.save_for_backward(a, b, g, u)
         return h
@@ -578,7 +653,10 @@ class _SDDGated(torch.autograd.Function):
             db = _dds(a.t(), dc)                       # A^T dU
         if not ctx.needs_input_grad[2]:
             dg = None
-        return da, db, dg, None, None, None, None
+        dbias = None
+        if ctx.bias_dtype is not None and ctx.needs_input_grad[7]:
+            dbias = _column_sum(du, ctx.topo).to(ctx.bias_dtype)
+        return da, db, dg, None, None, None, None, dbias
 
 
 class _GLUMLP(torch.autograd.Function):
@@ -587,13 +665,18 @@ class _GLUMLP(torch.autograd.Function):
     forward multiplied by w2, and dZ2 is written over Z2."""
 
     @staticmethod
-    def forward(ctx, x, w1, v1, w2, topo, act, w1_sink, v1_sink, w2_sink):
+    def forward(ctx, x, w1, v1, w2, topo, act, w1_sink, v1_sink, w2_sink,
+                b1=None, bv1=None):
         ctx.topo, ctx.act = topo, act
         ctx.w1_sink, ctx.v1_sink, ctx.w2_sink = w1_sink, v1_sink, w2_sink
+        # (the biases are not kept: backward needs their dtypes alone)
+        ctx.b1 = b1 is not None and ctx.needs_input_grad[9] and b1.dtype
+        ctx.bv1 = bv1 is not None and ctx.needs_input_grad[10] and bv1.dtype
         keep = (any(ctx.needs_input_grad[:4]) or w1_sink is not None
-                or v1_sink is not None or w2_sink is not None)
-        z1 = _sdd(x, w1, topo)
-        h, z2 = _sdd_gated(x, v1, topo, act, z1, keep_up=keep)
+                or v1_sink is not None or w2_sink is not None
+                or bool(ctx.b1) or bool(ctx.bv1))
+        z1 = _sdd(x, w1, topo, b1)
+        h, z2 = _sdd_gated(x, v1, topo, act, z1, keep_up=keep, bias=bv1)
         if keep:
             ctx.save_for_backward(x, w1, v1, w2, z1, z2)
         return _dsd(topo.with_data(h), w2)
@@ -602,7 +685,7 @@ class _GLUMLP(torch.autograd.Function):
     def backward(ctx, dy):
         x, w1, v1, w2, z1, z2 = ctx.saved_tensors
         topo = ctx.topo
-        dx = dw1 = dv1 = dw2 = None
+        dx = dw1 = dv1 = dw2 = db1 = dbv1 = None
         if ctx.w2_sink is not None or ctx.needs_input_grad[3]:
             h = topo.with_data(BlockGate(z2, z1, ctx.act))
             if ctx.w2_sink is not None:
@@ -611,7 +694,7 @@ class _GLUMLP(torch.autograd.Function):
                 dw2 = _dsd(h.t(), dy)                  # H^T dY
             del h
         if (ctx.w1_sink is not None or ctx.v1_sink is not None
-                or any(ctx.needs_input_grad[:3])):
+                or any(ctx.needs_input_grad[:3]) or ctx.b1 or ctx.bv1):
             # D = dY W2^T: dZ1 = D Z2 act'(Z1), dZ2 = D act(Z1) over Z2, one
             # product. Z2 is gone after it, so this node runs backward once.
             if getattr(ctx, "z2_consumed", False):
@@ -632,7 +715,11 @@ class _GLUMLP(torch.autograd.Function):
                 ctx.v1_sink.add_dds(x.t(), dz2)        # sink += X^T dZ2
             elif ctx.needs_input_grad[2]:
                 dv1 = _dds(x.t(), dz2)                 # X^T dZ2
-        return dx, dw1, dv1, dw2, None, None, None, None, None
+            if ctx.b1:
+                db1 = _column_sum(dz1.data, topo).to(ctx.b1)
+            if ctx.bv1:
+                dbv1 = _column_sum(dz2.data, topo).to(ctx.bv1)
+        return (dx, dw1, dv1, dw2, None, None, None, None, None, db1, dbv1)
 
 
 # Gradient sinks (`*_grad_out`): a contiguous tensor of the dense operand's
@@ -661,7 +748,35 @@ def sdd(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
     """Sparse (topo's blocks) = dense @ dense (reference sdd.h:10-15)."""
     return topo.with_data(_SDD.apply(
         a, b, topo, _sink(a_grad_out, a, "sdd a_grad_out"),
-        _sink(b_grad_out, b, "sdd b_grad_out")))
+        _sink(b_grad_out, b, "sdd b_grad_out"), None))
+
+
+def sdd_bias(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
+             bias: torch.Tensor,
+             a_grad_out: Optional[torch.Tensor] = None,
+             b_grad_out: Optional[torch.Tensor] = None) -> SparseMatrix:
+    """Sparse (topo's blocks) = dense @ dense + bias[column], the bias added
+    in the product's epilogue (MatmulBias): `bias` is [topo's columns] of the
+    operands' dtype, and the result is round(a @ b) + bias rounded once more.
+    Differentiable in a, b and bias (column_sum of the incoming gradient)."""
+    if bias is None:
+        raise TypeError("sdd_bias needs a bias; sdd is the bias-free product")
+    return topo.with_data(_SDD.apply(
+        a, b, topo, _sink(a_grad_out, a, "sdd_bias a_grad_out"),
+        _sink(b_grad_out, b, "sdd_bias b_grad_out"),
+        _column_bias(bias, a, topo, "sdd_bias: bias")))
+
+
+def column_sum(sparse: SparseMatrix) -> torch.Tensor:
+    """fp32 [columns]: the sum of every column of `sparse` over its stored
+    blocks (BlockColumnSum), the bias gradient of a sparse matrix. No
+    atomics: two calls give the same bits. Not differentiable."""
+    if not isinstance(sparse, SparseMatrix):
+        raise TypeError("column_sum takes a SparseMatrix")
+    if sparse.is_transposed():
+        raise ValueError("column_sum: not a .t() view")
+    _check_dtypes(sparse.data)
+    return _column_sum(sparse.data.detach().contiguous(), sparse)
 
 
 def sdd_act(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
@@ -671,10 +786,22 @@ def sdd_act(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
     the product (MatmulActivation; "relu", "gelu": the tanh form, "silu").
     The pre-activation is kept for backward, which gates the incoming
     gradient with act' and proceeds as sdd's. Sinks as in sdd."""
+    return sdd_act_bias(a, b, topo, activation, a_grad_out, b_grad_out)
+
+
+def sdd_act_bias(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
+                 activation, a_grad_out: Optional[torch.Tensor] = None,
+                 b_grad_out: Optional[torch.Tensor] = None, *,
+                 bias: Optional[torch.Tensor] = None) -> SparseMatrix:
+    """sdd_act with a column bias: act(dense @ dense + bias), `bias` [topo's
+    columns] added as sdd_bias adds it (MatmulBiasActivation); the kept
+    pre-activation is the biased one. Differentiable in bias too. Without
+    `bias` it is sdd_act."""
     return topo.with_data(_SDDAct.apply(
         a, b, topo, _act_code(activation),
         _sink(a_grad_out, a, "sdd_act a_grad_out"),
-        _sink(b_grad_out, b, "sdd_act b_grad_out")))
+        _sink(b_grad_out, b, "sdd_act b_grad_out"),
+        _column_bias(bias, a, topo, "sdd_act_bias: bias")))
 
 
 def mlp(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
@@ -686,9 +813,22 @@ def mlp(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
     dZ = (dy @ w2^T) * act'(Z) with one MatmulActivationGrad, then dw2 =
     H^T dy, dx = dZ w1^T and dw1 = x^T dZ. Only Z is kept between the passes.
     `w1_grad_out` / `w2_grad_out`: gradient sinks as in sdd / dsd."""
+    return mlp_bias(x, w1, w2, topo, activation, w1_grad_out, w2_grad_out)
+
+
+def mlp_bias(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+             topo: SparseMatrix, activation="gelu",
+             w1_grad_out: Optional[torch.Tensor] = None,
+             w2_grad_out: Optional[torch.Tensor] = None, *,
+             b1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mlp with a bias on the hidden matrix: `b1` ([topo's columns], x's
+    dtype), Z = x w1 + b1 added in the product's epilogue; db1 =
+    column_sum(dZ), cast to b1's dtype. Z is still the only tensor kept
+    between the passes besides the operands. Without `b1` it is mlp."""
     return _MLP.apply(x, w1, w2, topo, _act_code(activation),
                       _sink(w1_grad_out, w1, "mlp w1_grad_out"),
-                      _sink(w2_grad_out, w2, "mlp w2_grad_out"))
+                      _sink(w2_grad_out, w2, "mlp w2_grad_out"),
+                      _column_bias(b1, x, topo, "mlp_bias: b1"))
 
 
 def sdd_gated(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
@@ -700,6 +840,18 @@ def sdd_gated(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
     topo's topology and storage order. Differentiable in a, b and gate.data:
     the product U is kept, backward is one BlockGateGrad giving (dG, dU) and
     then sdd's backward on dU. Sinks as in sdd."""
+    return sdd_gated_bias(a, b, topo, gate, activation, a_grad_out, b_grad_out)
+
+
+def sdd_gated_bias(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
+                   gate: SparseMatrix, activation,
+                   a_grad_out: Optional[torch.Tensor] = None,
+                   b_grad_out: Optional[torch.Tensor] = None, *,
+                   bias: Optional[torch.Tensor] = None) -> SparseMatrix:
+    """sdd_gated with a column bias: (dense @ dense + bias) * act(gate),
+    `bias` [topo's columns] added as sdd_bias adds it (MatmulBiasGated); the
+    kept U is the biased one. Differentiable in bias too. Without `bias` it
+    is sdd_gated."""
     if not isinstance(gate, SparseMatrix):
         raise TypeError("sdd_gated: gate must be a SparseMatrix")
     if (gate.shape != topo.shape or gate.is_transposed() != topo.is_transposed()
@@ -708,7 +860,8 @@ def sdd_gated(a: torch.Tensor, b: torch.Tensor, topo: SparseMatrix,
     return topo.with_data(_SDDGated.apply(
         a, b, gate.data, topo, _act_code(activation),
         _sink(a_grad_out, a, "sdd_gated a_grad_out"),
-        _sink(b_grad_out, b, "sdd_gated b_grad_out")))
+        _sink(b_grad_out, b, "sdd_gated b_grad_out"),
+        _column_bias(bias, a, topo, "sdd_gated_bias: bias")))
 
 
 def glu_mlp(x: torch.Tensor, w1: torch.Tensor, v1: torch.Tensor,
@@ -723,10 +876,28 @@ def glu_mlp(x: torch.Tensor, w1: torch.Tensor, v1: torch.Tensor,
     over Z2), then dw1 = x^T dZ1, dv1 = x^T dZ2 and dx = dZ1 w1^T with
     dZ2 v1^T accumulated into it. Only Z1 and Z2 are kept between the passes.
     `*_grad_out`: gradient sinks as in sdd / dsd."""
+    return glu_mlp_bias(x, w1, v1, w2, topo, activation, w1_grad_out,
+                        v1_grad_out, w2_grad_out)
+
+
+def glu_mlp_bias(x: torch.Tensor, w1: torch.Tensor, v1: torch.Tensor,
+                 w2: torch.Tensor, topo: SparseMatrix, activation="silu",
+                 w1_grad_out: Optional[torch.Tensor] = None,
+                 v1_grad_out: Optional[torch.Tensor] = None,
+                 w2_grad_out: Optional[torch.Tensor] = None, *,
+                 b1: Optional[torch.Tensor] = None,
+                 bv1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """glu_mlp with biases on its two hidden matrices ([topo's columns], x's
+    dtype): `b1` the gate's, Z1 = x w1 + b1, `bv1` the up projection's, Z2 =
+    x v1 + bv1, each added in its product's epilogue; db1 = column_sum(dZ1),
+    dbv1 = column_sum(dZ2), cast to the bias's dtype. Z1 and Z2 are still the
+    only tensors kept besides the operands. Without biases it is glu_mlp."""
     return _GLUMLP.apply(x, w1, v1, w2, topo, _act_code(activation),
                          _sink(w1_grad_out, w1, "glu_mlp w1_grad_out"),
                          _sink(v1_grad_out, v1, "glu_mlp v1_grad_out"),
-                         _sink(w2_grad_out, w2, "glu_mlp w2_grad_out"))
+                         _sink(w2_grad_out, w2, "glu_mlp w2_grad_out"),
+                         _column_bias(b1, x, topo, "glu_mlp_bias: b1"),
+                         _column_bias(bv1, x, topo, "glu_mlp_bias: bv1"))
 
 
 def from_dense_mask(x: torch.Tensor, mask) -> SparseMatrix:
@@ -976,10 +1147,15 @@ def _gather(x: torch.Tensor, route: MoeRoute, weights) -> torch.Tensor:
     return out
 
 
-def _scatter(y: torch.Tensor, route: MoeRoute, weights) -> torch.Tensor:
+def _scatter(y: torch.Tensor, route: MoeRoute, weights,
+             bias=None) -> torch.Tensor:
     out = torch.empty(route.tokens, y.shape[1], dtype=y.dtype, device=y.device)
-    PaddedScatter(y.contiguous(), route.row_of, out, route.top_k,
-                  None if weights is None else weights.contiguous())
+    w = None if weights is None else weights.contiguous()
+    if bias is None:
+        PaddedScatter(y.contiguous(), route.row_of, out, route.top_k, w)
+    else:
+        PaddedScatterBias(y.contiguous(), route.row_of, route.padded_bins,
+                          bias, out, route.top_k, w)
     return out
 
 
@@ -996,25 +1172,37 @@ class _PaddedGather(torch.autograd.Function):
 
 class _PaddedScatter(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y, weights, route):
+    def forward(ctx, y, weights, route, bias=None):
         ctx.route = route
-        ctx.save_for_backward(y, weights)
-        return _scatter(y, route, weights)
+        ctx.save_for_backward(y, weights, bias)
+        return _scatter(y, route, weights, bias)
 
     @staticmethod
     def backward(ctx, dout):
-        y, weights = ctx.saved_tensors
+        y, weights, bias = ctx.saved_tensors
         route = ctx.route
-        dy = dw = None
+        dy = dw = db = None
         dout = dout.contiguous()
         if ctx.needs_input_grad[0]:
             dy = _gather(dout, route, weights)         # w[a] dout[a / top_k]
         if weights is not None and ctx.needs_input_grad[1]:
             dw = torch.empty_like(weights,
                                   memory_format=torch.contiguous_format)
-            PaddedScatterWeightGrad(dout, y.contiguous(), route.row_of, dw,
-                                    route.top_k)
-        return dy, dw, None
+            if bias is None:
+                PaddedScatterWeightGrad(dout, y.contiguous(), route.row_of,
+                                        dw, route.top_k)
+            else:
+                PaddedScatterBiasWeightGrad(dout, y.contiguous(),
+                                            route.row_of, route.padded_bins,
+                                            bias, dw, route.top_k)
+        if bias is not None and ctx.needs_input_grad[3]:
+            db32 = torch.empty(bias.shape, dtype=torch.float32,
+                               device=bias.device)
+            PaddedScatterBiasGrad(
+                dout, route.indices, route.bins, db32, route.top_k,
+                None if weights is None else weights.contiguous())
+            db = db32.to(bias.dtype)
+        return dy, dw, None, db
 
 
 def padded_gather(x: torch.Tensor, route: MoeRoute) -> torch.Tensor:
@@ -1034,15 +1222,43 @@ def padded_scatter(y: torch.Tensor, route: MoeRoute,
     `weights` ([tokens, top_k] or flat, y's dtype or fp32). Differentiable
     in y (a padded_gather of the incoming gradient with the weights) and in
     weights (PaddedScatterWeightGrad)."""
+    return padded_scatter_bias(y, route, weights)
+
+
+def padded_scatter_bias(y: torch.Tensor, route: MoeRoute,
+                        weights: Optional[torch.Tensor] = None, *,
+                        bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """padded_scatter with an output bias: `bias` ([num_experts, hidden],
+    y's dtype), out[t] = sum_k weights[t, k] * (y[row] + bias[expert of the
+    row]), the add in fp32 before the multiply (PaddedScatterBias).
+    Differentiable in bias too (PaddedScatterBiasGrad, no atomics, cast to
+    its dtype). Without `bias` it is padded_scatter."""
     _check_route(route, "padded_scatter")
     _check_rows(y, route.rows, "padded_scatter: y")
     if weights is not None:
         _check_weights(weights, y, route, "padded_scatter")
-    return _PaddedScatter.apply(y, weights, route)
+    if bias is not None:
+        _check_bias(bias, y, (route.num_experts, int(y.shape[1])),
+                    "padded_scatter_bias: bias")
+        bias = bias.contiguous()
+    return _PaddedScatter.apply(y, weights, route, bias)
+
+
+def _check_moe_biases(x, w1, v1, num_experts: int, biases, what: str):
+    """The expert biases (b1, bv1, b2) of a MoE layer, each None or of x's
+    dtype and device: b1 / bv1 [w1's columns], b2 [num_experts, d_model]."""
+    b1, bv1, b2 = biases
+    if bv1 is not None and v1 is None:
+        raise ValueError(f"{what}: bv1 is the bias of v1, which is missing")
+    for name, t in (("b1", b1), ("bv1", bv1)):
+        if t is not None:
+            _check_bias(t, x, (int(w1.shape[-1]),), f"{what}: {name}")
+    if b2 is not None:
+        _check_bias(b2, x, (num_experts, int(x.shape[-1])), f"{what}: b2")
 
 
 def _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
-             activation, v1, rows):
+             activation, v1, rows, b1=None, bv1=None, b2=None):
     """moe_mlp's checks and chain; returns the output and the route."""
     route = top_experts if isinstance(top_experts, MoeRoute) else None
     if route is None:
@@ -1075,6 +1291,7 @@ def _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
                         "torch.float32")
     if int(expert_weights.numel()) != tokens * top_k:
         raise ValueError("moe_mlp: one expert weight per (token, k)")
+    _check_moe_biases(x, w1, v1, num_experts, (b1, bv1, b2), "moe_mlp")
     act = None if activation is None else _act_code(activation)
     if route is None:
         route = moe_route(top_experts, num_experts, rows)
@@ -1082,10 +1299,11 @@ def _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
     topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
                            route.rows // BLOCK, dtype=x.dtype)
     if v1 is None:
-        y = mlp(xp, w1, w2, topo, "gelu" if act is None else act)
+        y = mlp_bias(xp, w1, w2, topo, "gelu" if act is None else act, b1=b1)
     else:
-        y = glu_mlp(xp, w1, v1, w2, topo, "silu" if act is None else act)
-    return padded_scatter(y, route, expert_weights), route
+        y = glu_mlp_bias(xp, w1, v1, w2, topo,
+                         "silu" if act is None else act, b1=b1, bv1=bv1)
+    return padded_scatter_bias(y, route, expert_weights, bias=b2), route
 
 
 def moe_mlp(x: torch.Tensor, top_experts: torch.Tensor,
@@ -1107,6 +1325,23 @@ def moe_mlp(x: torch.Tensor, top_experts: torch.Tensor,
     x, expert_weights, w1, v1 and w2."""
     return _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
                     activation, v1, rows)[0]
+
+
+def moe_mlp_bias(x: torch.Tensor, top_experts: torch.Tensor,
+                 expert_weights: torch.Tensor, w1: torch.Tensor,
+                 w2: torch.Tensor, num_experts: int, activation=None,
+                 v1: Optional[torch.Tensor] = None,
+                 rows: Optional[int] = None, *,
+                 b1: Optional[torch.Tensor] = None,
+                 bv1: Optional[torch.Tensor] = None,
+                 b2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_mlp with expert biases, all of x's dtype: `b1` [num_experts * ffn]
+    on x w1 (the gate of a GLU), `bv1` the same on x v1, `b2` [num_experts,
+    d_model] on the expert's output, added before the router weight
+    multiplies it (mlp_bias / glu_mlp_bias, padded_scatter_bias).
+    Differentiable in each. Without biases it is moe_mlp."""
+    return _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
+                    activation, v1, rows, b1, bv1, b2)[0]
 
 
 # ---- MoE router -------------------------------------------------------------
@@ -1413,7 +1648,7 @@ class MoeAux:
 
 def _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
                normalize, router_dtype, device_sort, returns: str, what: str,
-               score=None):
+               score=None, biases=(None, None, None)):
     """moe_layer's checks and chain. `returns`: "y", "scores" (moe_layer's
     return_scores) or "aux" (moe_layer_aux: routing through
     moe_router_aux). `score`: None, or moe_score_layer's (router_bias,
@@ -1438,6 +1673,8 @@ def _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
             or not 1 <= top_k <= min(num_experts, ROUTER_MAX_TOP_K)):
         raise ValueError(f"{what}: top_k must be an int in [1, min("
                          f"{num_experts}, {ROUTER_MAX_TOP_K})], not {top_k!r}")
+    if any(b is not None for b in biases):
+        _check_moe_biases(x, w1, v1, num_experts, biases, what)
     logits = x.to(router_dtype) @ router_weight.to(router_dtype).t()
     if score is not None:
         bias, num_groups, topk_groups, scale = score
@@ -1451,7 +1688,7 @@ def _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
     if device_sort:
         top = moe_device_route(top, num_experts, rows)
     y, route = _moe_mlp(x, top, out[0], w1, w2, num_experts, activation, v1,
-                        rows)
+                        rows, *biases)
     if returns == "aux":
         return y, MoeAux(out[2], out[3], route.tokens_per_expert,
                          int(x.shape[0]), top_k)
@@ -1482,6 +1719,24 @@ def moe_layer(x: torch.Tensor, router_weight: torch.Tensor, w1: torch.Tensor,
                       "scores" if return_scores else "y", "moe_layer")
 
 
+def moe_layer_bias(x: torch.Tensor, router_weight: torch.Tensor,
+                   w1: torch.Tensor, w2: torch.Tensor, top_k: int,
+                   activation=None, v1: Optional[torch.Tensor] = None,
+                   rows: Optional[int] = None, normalize: bool = False,
+                   router_dtype=None, device_sort: bool = True,
+                   return_scores: bool = False, *,
+                   b1: Optional[torch.Tensor] = None,
+                   bv1: Optional[torch.Tensor] = None,
+                   b2: Optional[torch.Tensor] = None):
+    """moe_layer with the expert biases of moe_mlp_bias (`b1`, `bv1`, `b2`):
+    the same layer and the same leading arguments; with explicit `rows` it
+    still makes no host sync. Without biases it is moe_layer, bit for bit."""
+    return _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
+                      normalize, router_dtype, device_sort,
+                      "scores" if return_scores else "y", "moe_layer_bias",
+                      biases=(b1, bv1, b2))
+
+
 def moe_layer_aux(x: torch.Tensor, router_weight: torch.Tensor,
                   w1: torch.Tensor, w2: torch.Tensor, top_k: int,
                   activation=None, v1: Optional[torch.Tensor] = None,
@@ -1496,6 +1751,20 @@ def moe_layer_aux(x: torch.Tensor, router_weight: torch.Tensor,
     return _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
                       normalize, router_dtype, device_sort, "aux",
                       "moe_layer_aux")
+
+
+def moe_layer_aux_bias(x: torch.Tensor, router_weight: torch.Tensor,
+                       w1: torch.Tensor, w2: torch.Tensor, top_k: int,
+                       activation=None, v1: Optional[torch.Tensor] = None,
+                       rows: Optional[int] = None, normalize: bool = False,
+                       router_dtype=None, device_sort: bool = True, *,
+                       b1: Optional[torch.Tensor] = None,
+                       bv1: Optional[torch.Tensor] = None,
+                       b2: Optional[torch.Tensor] = None):
+    """moe_layer_aux with the expert biases of moe_mlp_bias."""
+    return _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
+                      normalize, router_dtype, device_sort, "aux",
+                      "moe_layer_aux_bias", biases=(b1, bv1, b2))
 
 
 def moe_score_layer(x: torch.Tensor, router_weight: torch.Tensor,
@@ -1520,6 +1789,28 @@ def moe_score_layer(x: torch.Tensor, router_weight: torch.Tensor,
                       (router_bias, num_groups, topk_groups, routed_scale))
 
 
+def moe_score_layer_bias(x: torch.Tensor, router_weight: torch.Tensor,
+                         w1: torch.Tensor, w2: torch.Tensor, top_k: int,
+                         activation=None, v1: Optional[torch.Tensor] = None,
+                         rows: Optional[int] = None, normalize: bool = False,
+                         router_dtype=None, device_sort: bool = True,
+                         return_scores: bool = False,
+                         router_bias: Optional[torch.Tensor] = None,
+                         num_groups: int = 1, topk_groups: int = 1,
+                         routed_scale: float = 1.0, *,
+                         b1: Optional[torch.Tensor] = None,
+                         bv1: Optional[torch.Tensor] = None,
+                         b2: Optional[torch.Tensor] = None):
+    """moe_score_layer with the expert biases of moe_mlp_bias (the router's
+    selection bias stays `router_bias`)."""
+    return _moe_layer(x, router_weight, w1, w2, top_k, activation, v1, rows,
+                      normalize, router_dtype, device_sort,
+                      "scores" if return_scores else "y",
+                      "moe_score_layer_bias",
+                      (router_bias, num_groups, topk_groups, routed_scale),
+                      biases=(b1, bv1, b2))
+
+
 __all__ = ["MoeAux", "MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_acc",
            "expert_topology", "from_dense_mask", "glu_mlp", "mlp",
            "moe_device_route", "moe_layer", "moe_layer_aux", "moe_mlp",
@@ -1527,6 +1818,9 @@ __all__ = ["MoeAux", "MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_a
            "moe_router", "moe_router_aux", "load_balancing_loss",
            "moe_score_router", "moe_score_layer", "router_bias_update",
            "router_z_loss",
-           "moe_rows_bound", "padded_gather",
+           "moe_rows_bound", "padded_gather", "column_sum", "sdd_bias",
+           "sdd_act_bias", "sdd_gated_bias", "mlp_bias", "glu_mlp_bias",
+           "padded_scatter_bias", "moe_mlp_bias", "moe_layer_bias",
+           "moe_layer_aux_bias", "moe_score_layer_bias",
            "padded_scatter", "sdd", "sdd_act", "sdd_gated",
            "topology_from_mask"]
