@@ -1057,24 +1057,76 @@ def PaddedGather(x, indices, bins, padded_bins, out, top_k, weights=None,  # noq
         wcode, _stream(stream)), "PaddedGather")
 
 
+def _expert_bias(bias, dtype, hidden: int, what: str) -> int:
+    """The number of experts of an output bias [E, hidden] of `dtype`."""
+    _moe_matrix(bias, dtype, hidden, what)
+    return int(bias.shape[0])
+
+
+def _padded_scatter(what: str, y, row_of, out, top_k, weights, stream,
+                    expert_bias=None) -> None:
+    """PaddedScatter, or with expert_bias = (padded_bins, bias)
+    PaddedScatterBias: the checks of both, then each one's own C symbol."""
+    _moe_matrix(y, None, None, "y")
+    dtype = _dtype_code(y)
+    rows, hidden = int(y.shape[0]), int(y.shape[1])
+    _moe_matrix(out, y.dtype, hidden, "out")
+    tokens = int(out.shape[0])
+    n = _moe_sizes(tokens, top_k, rows, what)
+    _moe_meta(row_of, n, "row_of")
+    if expert_bias is not None:
+        padded_bins, bias = expert_bias
+        e = _expert_bias(bias, y.dtype, hidden, "bias")
+        _moe_meta(padded_bins, e, "padded_bins")
+    wcode = (SPUTNIK_WEIGHTS_OPERAND if weights is None
+             else _moe_weights(weights, y.dtype, n, "weights"))
+    if expert_bias is None:
+        code = lib().sputnik_padded_scatter(
+            _ptr(y), _ptr(row_of), _ptr(weights), _ptr(out), tokens, hidden,
+            top_k, rows, dtype, wcode, _stream(stream))
+    else:
+        code = lib().sputnik_padded_scatter_bias(
+            _ptr(y), _ptr(row_of), _ptr(padded_bins), _ptr(bias),
+            _ptr(weights), _ptr(out), tokens, hidden, top_k, e, rows, dtype,
+            wcode, _stream(stream))
+    _check(code, what)
+
+
+def _padded_scatter_wgrad(what: str, dout, y, row_of, dw, top_k, stream,
+                          expert_bias=None) -> None:
+    """PaddedScatterWeightGrad, or with expert_bias = (padded_bins, bias)
+    PaddedScatterBiasWeightGrad, as _padded_scatter."""
+    _moe_matrix(dout, None, None, "dout")
+    dtype = _dtype_code(dout)
+    tokens, hidden = int(dout.shape[0]), int(dout.shape[1])
+    _moe_matrix(y, dout.dtype, hidden, "y")
+    rows = int(y.shape[0])
+    n = _moe_sizes(tokens, top_k, rows, what)
+    _moe_meta(row_of, n, "row_of")
+    if expert_bias is not None:
+        padded_bins, bias = expert_bias
+        e = _expert_bias(bias, dout.dtype, hidden, "bias")
+        _moe_meta(padded_bins, e, "padded_bins")
+    wcode = _moe_weights(dw, dout.dtype, n, "dw")
+    if expert_bias is None:
+        code = lib().sputnik_padded_scatter_wgrad(
+            _ptr(dout), _ptr(y), _ptr(row_of), _ptr(dw), tokens, hidden,
+            top_k, rows, dtype, wcode, _stream(stream))
+    else:
+        code = lib().sputnik_padded_scatter_bias_wgrad(
+            _ptr(dout), _ptr(y), _ptr(row_of), _ptr(padded_bins), _ptr(bias),
+            _ptr(dw), tokens, hidden, top_k, e, rows, dtype, wcode,
+            _stream(stream))
+    _check(code, what)
+
+
 def PaddedScatter(y, row_of, out, top_k, weights=None, stream=None):  # noqa: N802
     """out [tokens, hidden] = for every token the sum over its top_k padded
     rows of y [rows, hidden], read through row_of (int32 [tokens * top_k])
     and multiplied by `weights` when given; fp32 sum in ascending k, rounded
     once, no atomics (sputnik_padded_scatter). Type and shape errors are
     raised before the library is called."""
-    _moe_matrix(y, None, None, "y")
-    dtype = _dtype_code(y)
-    rows, hidden = int(y.shape[0]), int(y.shape[1])
-    _moe_matrix(out, y.dtype, hidden, "out")
-    tokens = int(out.shape[0])
-    n = _moe_sizes(tokens, top_k, rows, "PaddedScatter")
-    _moe_meta(row_of, n, "row_of")
-    wcode = (SPUTNIK_WEIGHTS_OPERAND if weights is None
-             else _moe_weights(weights, y.dtype, n, "weights"))
-    _check(lib().sputnik_padded_scatter(
-        _ptr(y), _ptr(row_of), _ptr(weights), _ptr(out), tokens, hidden,
-        top_k, rows, dtype, wcode, _stream(stream)), "PaddedScatter")
+    _padded_scatter("PaddedScatter", y, row_of, out, top_k, weights, stream)
 
 
 def PaddedScatterWeightGrad(dout, y, row_of, dw, top_k, stream=None):  # noqa: N802
@@ -1082,23 +1134,8 @@ def PaddedScatterWeightGrad(dout, y, row_of, dw, top_k, stream=None):  # noqa: N
     dtype (the operands' or fp32): the gradient of PaddedScatter with respect
     to its weights (sputnik_padded_scatter_wgrad). Type and shape errors are
     raised before the library is called."""
-    _moe_matrix(dout, None, None, "dout")
-    dtype = _dtype_code(dout)
-    tokens, hidden = int(dout.shape[0]), int(dout.shape[1])
-    _moe_matrix(y, dout.dtype, hidden, "y")
-    rows = int(y.shape[0])
-    n = _moe_sizes(tokens, top_k, rows, "PaddedScatterWeightGrad")
-    _moe_meta(row_of, n, "row_of")
-    wcode = _moe_weights(dw, dout.dtype, n, "dw")
-    _check(lib().sputnik_padded_scatter_wgrad(
-        _ptr(dout), _ptr(y), _ptr(row_of), _ptr(dw), tokens, hidden, top_k,
-        rows, dtype, wcode, _stream(stream)), "PaddedScatterWeightGrad")
-
-
-def _expert_bias(bias, dtype, hidden: int, what: str) -> int:
-    """The number of experts of an output bias [E, hidden] of `dtype`."""
-    _moe_matrix(bias, dtype, hidden, what)
-    return int(bias.shape[0])
+    _padded_scatter_wgrad("PaddedScatterWeightGrad", dout, y, row_of, dw,
+                          top_k, stream)
 
 
 def PaddedScatterBias(y, row_of, padded_bins, bias, out, top_k,  # noqa: N802
@@ -1109,21 +1146,8 @@ def PaddedScatterBias(y, row_of, padded_bins, bias, out, top_k,  # noqa: N802
     the row through padded_bins (int32 [E]); an assignment whose row is out
     of range contributes zero, bias included
     (sputnik_padded_scatter_bias)."""
-    _moe_matrix(y, None, None, "y")
-    dtype = _dtype_code(y)
-    rows, hidden = int(y.shape[0]), int(y.shape[1])
-    _moe_matrix(out, y.dtype, hidden, "out")
-    tokens = int(out.shape[0])
-    n = _moe_sizes(tokens, top_k, rows, "PaddedScatterBias")
-    _moe_meta(row_of, n, "row_of")
-    e = _expert_bias(bias, y.dtype, hidden, "bias")
-    _moe_meta(padded_bins, e, "padded_bins")
-    wcode = (SPUTNIK_WEIGHTS_OPERAND if weights is None
-             else _moe_weights(weights, y.dtype, n, "weights"))
-    _check(lib().sputnik_padded_scatter_bias(
-        _ptr(y), _ptr(row_of), _ptr(padded_bins), _ptr(bias), _ptr(weights),
-        _ptr(out), tokens, hidden, top_k, e, rows, dtype, wcode,
-        _stream(stream)), "PaddedScatterBias")
+    _padded_scatter("PaddedScatterBias", y, row_of, out, top_k, weights,
+                    stream, (padded_bins, bias))
 
 
 def PaddedScatterBiasWeightGrad(dout, y, row_of, padded_bins, bias, dw,  # noqa: N802
@@ -1131,20 +1155,8 @@ def PaddedScatterBiasWeightGrad(dout, y, row_of, padded_bins, bias, dw,  # noqa:
     """dw[a] = dot(dout[a // top_k], y[row_of[a]] + bias[e]) in fp32, stored
     in dw's dtype: the gradient of PaddedScatterBias with respect to its
     weights (sputnik_padded_scatter_bias_wgrad)."""
-    _moe_matrix(dout, None, None, "dout")
-    dtype = _dtype_code(dout)
-    tokens, hidden = int(dout.shape[0]), int(dout.shape[1])
-    _moe_matrix(y, dout.dtype, hidden, "y")
-    rows = int(y.shape[0])
-    n = _moe_sizes(tokens, top_k, rows, "PaddedScatterBiasWeightGrad")
-    _moe_meta(row_of, n, "row_of")
-    e = _expert_bias(bias, dout.dtype, hidden, "bias")
-    _moe_meta(padded_bins, e, "padded_bins")
-    wcode = _moe_weights(dw, dout.dtype, n, "dw")
-    _check(lib().sputnik_padded_scatter_bias_wgrad(
-        _ptr(dout), _ptr(y), _ptr(row_of), _ptr(padded_bins), _ptr(bias),
-        _ptr(dw), tokens, hidden, top_k, e, rows, dtype, wcode,
-        _stream(stream)), "PaddedScatterBiasWeightGrad")
+    _padded_scatter_wgrad("PaddedScatterBiasWeightGrad", dout, y, row_of, dw,
+                          top_k, stream, (padded_bins, bias))
 
 
 def PaddedScatterBiasGrad(dout, indices, bins, bias_grad, top_k,  # noqa: N802

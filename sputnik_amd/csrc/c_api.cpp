@@ -11,11 +11,11 @@
 #include "sputnik/block/router.h"
 #include "sputnik/sputnik.h"
 #include "metadata.h"
-#include "moe_permute.h"
 #include "sputnik_amd.h"
 
 using sputnik::block::BlockMatrix;
 using sputnik::block::BlockSize;
+using sputnik::block::DataType;
 using sputnik::block::Matrix;
 using sputnik::block::RouterType;
 using sputnik::block::WeightType;
@@ -556,7 +556,7 @@ int sputnik_expert_topology(const int32_t *padded_bins, int num_experts,
 int sputnik_moe_bins(const int32_t *bin_ids, int n, int num_experts,
                      int32_t *bins, int32_t *tokens_per_expert,
                      int32_t *padded_bins, void *stream) {
-  return sputnik_amd::RunMoeBins(bin_ids, n, num_experts, bins,
+  return sputnik::block::MoeBins(bin_ids, n, num_experts, bins,
                                  tokens_per_expert, padded_bins,
                                  static_cast<hipStream_t>(stream));
 }
@@ -565,7 +565,7 @@ int sputnik_moe_row_map(const int32_t *indices, const int32_t *bin_ids,
                         const int32_t *bins, const int32_t *padded_bins,
                         int n, int num_experts, int rows, int32_t *row_of,
                         void *stream) {
-  return sputnik_amd::RunMoeRowMap(indices, bin_ids, bins, padded_bins, n,
+  return sputnik::block::MoeRowMap(indices, bin_ids, bins, padded_bins, n,
                                    num_experts, rows, row_of,
                                    static_cast<hipStream_t>(stream));
 }
@@ -575,9 +575,10 @@ int sputnik_padded_gather(const void *x, const int32_t *indices,
                           const void *weights, void *out, int tokens,
                           int hidden, int top_k, int num_experts, int rows,
                           int dtype, int weights_dtype, void *stream) {
-  return sputnik_amd::RunPaddedGather(
+  return sputnik::block::PaddedGather(
       x, indices, bins, padded_bins, weights, out, tokens, hidden, top_k,
-      num_experts, rows, dtype, weights_dtype,
+      num_experts, rows, static_cast<DataType>(dtype),
+      static_cast<WeightType>(weights_dtype),
       static_cast<hipStream_t>(stream));
 }
 
@@ -585,17 +586,19 @@ int sputnik_padded_scatter(const void *y, const int32_t *row_of,
                            const void *weights, void *out, int tokens,
                            int hidden, int top_k, int rows, int dtype,
                            int weights_dtype, void *stream) {
-  return sputnik_amd::RunPaddedScatter(y, row_of, weights, out, tokens, hidden,
-                                       top_k, rows, dtype, weights_dtype,
-                                       static_cast<hipStream_t>(stream));
+  return sputnik::block::PaddedScatter(
+      y, row_of, weights, out, tokens, hidden, top_k, rows,
+      static_cast<DataType>(dtype), static_cast<WeightType>(weights_dtype),
+      static_cast<hipStream_t>(stream));
 }
 
 int sputnik_padded_scatter_wgrad(const void *dout, const void *y,
                                  const int32_t *row_of, void *dw, int tokens,
                                  int hidden, int top_k, int rows, int dtype,
                                  int weights_dtype, void *stream) {
-  return sputnik_amd::RunPaddedScatterWgrad(
-      dout, y, row_of, dw, tokens, hidden, top_k, rows, dtype, weights_dtype,
+  return sputnik::block::PaddedScatterWeightGrad(
+      dout, y, row_of, dw, tokens, hidden, top_k, rows,
+      static_cast<DataType>(dtype), static_cast<WeightType>(weights_dtype),
       static_cast<hipStream_t>(stream));
 }
 
@@ -605,9 +608,10 @@ int sputnik_padded_scatter_bias(const void *y, const int32_t *row_of,
                                 int hidden, int top_k, int num_experts,
                                 int rows, int dtype, int weights_dtype,
                                 void *stream) {
-  return sputnik_amd::RunPaddedScatterBias(
+  return sputnik::block::PaddedScatterBias(
       y, row_of, padded_bins, bias, weights, out, tokens, hidden, top_k,
-      num_experts, rows, dtype, weights_dtype,
+      num_experts, rows, static_cast<DataType>(dtype),
+      static_cast<WeightType>(weights_dtype),
       static_cast<hipStream_t>(stream));
 }
 
@@ -618,9 +622,10 @@ int sputnik_padded_scatter_bias_wgrad(const void *dout, const void *y,
                                       int hidden, int top_k, int num_experts,
                                       int rows, int dtype, int weights_dtype,
                                       void *stream) {
-  return sputnik_amd::RunPaddedScatterBiasWgrad(
+  return sputnik::block::PaddedScatterBiasWeightGrad(
       dout, y, row_of, padded_bins, bias, dw, tokens, hidden, top_k,
-      num_experts, rows, dtype, weights_dtype,
+      num_experts, rows, static_cast<DataType>(dtype),
+      static_cast<WeightType>(weights_dtype),
       static_cast<hipStream_t>(stream));
 }
 
@@ -629,9 +634,11 @@ int sputnik_padded_scatter_bias_grad(const void *dout, const int32_t *indices,
                                      float *bias_grad, int tokens, int hidden,
                                      int top_k, int num_experts, int dtype,
                                      int weights_dtype, void *stream) {
-  return sputnik_amd::RunPaddedScatterBiasGrad(
+  return sputnik::block::PaddedScatterBiasGrad(
       dout, indices, bins, weights, bias_grad, tokens, hidden, top_k,
-      num_experts, dtype, weights_dtype, static_cast<hipStream_t>(stream));
+      num_experts, static_cast<DataType>(dtype),
+      static_cast<WeightType>(weights_dtype),
+      static_cast<hipStream_t>(stream));
 }
 
 // MoE router and device sort (sputnik/block/router.h): moe_router.hip

@@ -24,9 +24,19 @@
 //   wgrad    one wave per assignment: a dot product of two rows, reduced by
 //            shuffles.
 //
+// The scatter and the weight gradient are each one kernel body and one
+// launcher, instantiated on `bool kBias` for the calls with an output bias
+// (PaddedScatterBias, PaddedScatterBiasWeightGrad): kBias adds the expert
+// read off the row, the load of its bias piece and the bias arithmetic, and
+// nothing to the plain instantiation. The bias gradient is a column
+// reduction of its own shape.
+//
 // Every index read from device memory (indices[i], bins / padded_bins
 // entries, row_of[a]) is range-checked before it forms an address; an entry
 // out of range stands for a row of zeros.
+//
+// The sputnik::block functions at the end are the host entry points, of the
+// C++ API and (through c_api.cpp) of the C-ABI: they validate and launch.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -34,7 +44,6 @@
 #include <initializer_list>
 #include <type_traits>
 
-#include "moe_permute.h"
 #include "sputnik/block/moe.h"
 
 namespace sputnik_amd {
@@ -162,110 +171,8 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-template <typename T, typename W, bool kVec>
-__global__ void __launch_bounds__(kThreads)
-    padded_scatter_kernel(const T *__restrict__ y,
-                          const int *__restrict__ row_of,
-                          const W *__restrict__ weights, T *__restrict__ out,
-                          int tokens, int hidden, int top_k, int rows) {
-  using P = typename Piece<T, kVec>::type;
-  constexpr int kElems = Piece<T, kVec>::kElems;
-  const int lane = threadIdx.x & 63;
-  const int pieces = hidden / kElems;
-  const int tasks =
-      tokens / kRowsInFlight + (tokens % kRowsInFlight != 0);
-  const int stride = gridDim.x * kWaves;
-  for (int task = blockIdx.x * kWaves + wave_index(); task < tasks;
-       task += stride) {
-    const int t0 = task * kRowsInFlight;
-    for (int c = lane; c < pieces; c += 64) {
-      float acc[kRowsInFlight][kElems];
-#pragma unroll
-      for (int u = 0; u < kRowsInFlight; ++u)
-#pragma unroll
-        for (int j = 0; j < kElems; ++j) acc[u][j] = 0.0f;
-      for (int k = 0; k < top_k; ++k) {
-        P v[kRowsInFlight];
-        float wt[kRowsInFlight];
-#pragma unroll
-        for (int u = 0; u < kRowsInFlight; ++u) {
-          const int t = t0 + u;
-          const int a = t < tokens ? t * top_k + k : 0;  // < n <= INT_MAX
-          const int row = t < tokens ? row_of[a] : -1;
-          const bool ok = row >= 0 && row < rows;
-          v[u] = ok ? reinterpret_cast<const P *>(
-                          y + (long long)row * hidden)[c]
-                    : piece_zero<T, kVec>();
-          wt[u] = ok && weights != nullptr ? (float)weights[a] : 1.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < kRowsInFlight; ++u)
-#pragma unroll
-          for (int j = 0; j < kElems; ++j)
-            acc[u][j] += wt[u] * piece_get<T, kVec>(v[u], j);
-      }
-#pragma unroll
-      for (int u = 0; u < kRowsInFlight; ++u) {
-        const int t = t0 + u;
-        if (t >= tokens) continue;
-        P r;
-#pragma unroll
-        for (int j = 0; j < kElems; ++j) piece_set<T, kVec>(&r, j, acc[u][j]);
-        reinterpret_cast<P *>(out + (long long)t * hidden)[c] = r;
-      }
-    }
-  }
-}
-
-template <typename T, typename W, bool kVec>
-__global__ void __launch_bounds__(kThreads)
-    padded_scatter_wgrad_kernel(const T *__restrict__ dout,
-                                const T *__restrict__ y,
-                                const int *__restrict__ row_of,
-                                W *__restrict__ dw, int n, int hidden,
-                                int top_k, int rows) {
-  using P = typename Piece<T, kVec>::type;
-  constexpr int kElems = Piece<T, kVec>::kElems;
-  const int lane = threadIdx.x & 63;
-  const int pieces = hidden / kElems;
-  const int stride = gridDim.x * kWaves;
-  for (long long a = blockIdx.x * kWaves + wave_index(); a < n;
-       a += stride) {
-    const int row = row_of[a];
-    float s = 0.0f;
-    if (row >= 0 && row < rows) {
-      const P *d = reinterpret_cast<const P *>(
-          dout + (long long)(a / top_k) * hidden);
-      const P *r = reinterpret_cast<const P *>(y + (long long)row * hidden);
-      // kRowsInFlight pieces of each of the two rows in flight per lane.
-      for (int c0 = lane; c0 < pieces; c0 += 64 * kRowsInFlight) {
-        P dv[kRowsInFlight], rv[kRowsInFlight];
-#pragma unroll
-        for (int u = 0; u < kRowsInFlight; ++u) {
-          const int c = c0 + 64 * u;
-          dv[u] = c < pieces ? d[c] : piece_zero<T, kVec>();
-          rv[u] = c < pieces ? r[c] : piece_zero<T, kVec>();
-        }
-#pragma unroll
-        for (int u = 0; u < kRowsInFlight; ++u)
-#pragma unroll
-          for (int j = 0; j < kElems; ++j)
-            s += piece_get<T, kVec>(dv[u], j) * piece_get<T, kVec>(rv[u], j);
-      }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    if (lane == 0) dw[a] = (W)s;
-  }
-}
-
-// ---- the scatter with an output bias (moe.h PaddedScatterBias) ---------------
-// The expert of an assignment is read off its row: #{e : padded_bins[e] <=
-// row}. A row outside [0, rows), or at or past padded_bins[E-1] (no expert
-// owns it), contributes zero, bias included. Contraction is off: one add, one
-// multiply (with weights) and one accumulate per k, as moe.h states them.
-
-// The expert that owns padded row `row`, or -1.
+// The expert that owns padded row `row`, or -1: #{e : padded_bins[e] <= row}
+// for a row in [0, rows) that lies in front of padded_bins[E-1].
 __device__ __forceinline__ int row_expert(int row, int rows,
                                           const int *__restrict__ padded_bins,
                                           int num_experts) {
@@ -274,18 +181,29 @@ __device__ __forceinline__ int row_expert(int row, int rows,
   return e < num_experts ? e : -1;
 }
 
-constexpr int kHoist = 4;  // picks looked up in front of the piece loop
-
-template <typename T, typename W, bool kVec>
+// The scatter, with kBias the scatter with an output bias (moe.h
+// PaddedScatterBias). kBias adds the expert of every pick, read off its row
+// through padded_bins (a row that no expert owns contributes zero, bias
+// included), one more load per pick (the piece of bias[e]) and the arithmetic
+// as moe.h states it: one add, one multiply (with weights) and one accumulate
+// per k, contraction off. Without it the sum is acc += wt * y under the
+// compiler's default contraction, and padded_bins and bias are not read.
+//
+// kHoist picks are looked up in front of the piece loop: 4 with a bias, whose
+// lookup is a search of padded_bins, and 1 without, where it is a range check
+// and a weight load. Measured (profiles/moe_permute_refactor/README.md):
+// holding 4 plain picks across the loop is 3% slower with fp32 weights at
+// top_k 2, holding none 3% slower with weights of T at top_k 1.
+template <typename T, typename W, bool kVec, bool kBias>
 __global__ void __launch_bounds__(kThreads)
-    padded_scatter_bias_kernel(const T *__restrict__ y,
-                               const int *__restrict__ row_of,
-                               const int *__restrict__ padded_bins,
-                               const T *__restrict__ bias,
-                               const W *__restrict__ weights,
-                               T *__restrict__ out, int tokens, int hidden,
-                               int top_k, int num_experts, int rows) {
-#pragma clang fp contract(off)
+    padded_scatter_kernel(const T *__restrict__ y,
+                          const int *__restrict__ row_of,
+                          const int *__restrict__ padded_bins,
+                          const T *__restrict__ bias,
+                          const W *__restrict__ weights, T *__restrict__ out,
+                          int tokens, int hidden, int top_k, int num_experts,
+                          int rows) {
+  constexpr int kHoist = kBias ? 4 : 1;
   using P = typename Piece<T, kVec>::type;
   constexpr int kElems = Piece<T, kVec>::kElems;
   const int lane = threadIdx.x & 63;
@@ -296,16 +214,20 @@ __global__ void __launch_bounds__(kThreads)
   for (int task = blockIdx.x * kWaves + wave_index(); task < tasks;
        task += stride) {
     const int t0 = task * kRowsInFlight;
-    // The row, expert and weight of pick k of the task's tokens (e < 0:
-    // contributes zero). Wave-uniform; the first kHoist picks are looked up
-    // once per task, in front of the piece loop, so that the searches are
-    // not on every piece's path to its loads.
+    // The row, expert (0 without a bias) and weight of pick k of the task's
+    // tokens (e < 0: contributes zero). Wave-uniform; the first kHoist picks
+    // are looked up once per task, so that the searches are not on every
+    // piece's path to its loads.
     struct Pick { int row, e; float wt; };
     auto pick = [&](int u, int k) {
       const int t = t0 + u;
       const int a = t < tokens ? t * top_k + k : 0;  // < n <= INT_MAX
       const int row = t < tokens ? row_of[a] : -1;
-      const int e = row_expert(row, rows, padded_bins, num_experts);
+      int e;
+      if constexpr (kBias)
+        e = row_expert(row, rows, padded_bins, num_experts);
+      else
+        e = row >= 0 && row < rows ? 0 : -1;
       return Pick{row, e,
                   e >= 0 && weights != nullptr ? (float)weights[a] : 1.0f};
     };
@@ -321,7 +243,7 @@ __global__ void __launch_bounds__(kThreads)
       for (int u = 0; u < kRowsInFlight; ++u)
 #pragma unroll
         for (int j = 0; j < kElems; ++j) acc[u][j] = 0.0f;
-      // One pick of every token: the loads, then add, multiply, accumulate.
+      // One pick of every token: the loads, then the sum.
       auto step = [&](const Pick (&q)[kRowsInFlight]) {
         P v[kRowsInFlight], b[kRowsInFlight];
 #pragma unroll
@@ -330,17 +252,24 @@ __global__ void __launch_bounds__(kThreads)
           v[u] = ok ? reinterpret_cast<const P *>(
                           y + (long long)q[u].row * hidden)[c]
                     : piece_zero<T, kVec>();
-          b[u] = ok ? reinterpret_cast<const P *>(
-                          bias + (long long)q[u].e * hidden)[c]
-                    : piece_zero<T, kVec>();
+          if constexpr (kBias)
+            b[u] = ok ? reinterpret_cast<const P *>(
+                            bias + (long long)q[u].e * hidden)[c]
+                      : piece_zero<T, kVec>();
         }
 #pragma unroll
         for (int u = 0; u < kRowsInFlight; ++u)
 #pragma unroll
           for (int j = 0; j < kElems; ++j) {
-            float s = piece_get<T, kVec>(v[u], j) + piece_get<T, kVec>(b[u], j);
-            if (weights != nullptr) s = q[u].wt * s;
-            acc[u][j] = acc[u][j] + s;
+            if constexpr (kBias) {
+#pragma clang fp contract(off)
+              float s =
+                  piece_get<T, kVec>(v[u], j) + piece_get<T, kVec>(b[u], j);
+              if (weights != nullptr) s = q[u].wt * s;
+              acc[u][j] = acc[u][j] + s;
+            } else {
+              acc[u][j] += q[u].wt * piece_get<T, kVec>(v[u], j);
+            }
           }
       };
 #pragma unroll
@@ -365,15 +294,17 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-template <typename T, typename W, bool kVec>
+// The router-weight gradient; with kBias of the scatter with a bias:
+// dot(dout, y + bias[e]), e read off the row as above.
+template <typename T, typename W, bool kVec, bool kBias>
 __global__ void __launch_bounds__(kThreads)
-    padded_scatter_bias_wgrad_kernel(const T *__restrict__ dout,
-                                     const T *__restrict__ y,
-                                     const int *__restrict__ row_of,
-                                     const int *__restrict__ padded_bins,
-                                     const T *__restrict__ bias,
-                                     W *__restrict__ dw, int n, int hidden,
-                                     int top_k, int num_experts, int rows) {
+    padded_scatter_wgrad_kernel(const T *__restrict__ dout,
+                                const T *__restrict__ y,
+                                const int *__restrict__ row_of,
+                                W *__restrict__ dw, int n, int hidden,
+                                int top_k, int rows,
+                                const int *__restrict__ padded_bins,
+                                const T *__restrict__ bias, int num_experts) {
   using P = typename Piece<T, kVec>::type;
   constexpr int kElems = Piece<T, kVec>::kElems;
   const int lane = threadIdx.x & 63;
@@ -382,13 +313,17 @@ __global__ void __launch_bounds__(kThreads)
   for (long long a = blockIdx.x * kWaves + wave_index(); a < n;
        a += stride) {
     const int row = row_of[a];
-    const int e = row_expert(row, rows, padded_bins, num_experts);
+    int e = 0;
+    if constexpr (kBias) e = row_expert(row, rows, padded_bins, num_experts);
     float s = 0.0f;
-    if (e >= 0) {
+    if (kBias ? e >= 0 : row >= 0 && row < rows) {
       const P *d = reinterpret_cast<const P *>(
           dout + (long long)(a / top_k) * hidden);
       const P *r = reinterpret_cast<const P *>(y + (long long)row * hidden);
-      const P *b = reinterpret_cast<const P *>(bias + (long long)e * hidden);
+      const P *b = nullptr;
+      if constexpr (kBias)
+        b = reinterpret_cast<const P *>(bias + (long long)e * hidden);
+      // kRowsInFlight pieces of each of the rows in flight per lane.
       for (int c0 = lane; c0 < pieces; c0 += 64 * kRowsInFlight) {
         P dv[kRowsInFlight], rv[kRowsInFlight], bv[kRowsInFlight];
 #pragma unroll
@@ -396,14 +331,20 @@ __global__ void __launch_bounds__(kThreads)
           const int c = c0 + 64 * u;
           dv[u] = c < pieces ? d[c] : piece_zero<T, kVec>();
           rv[u] = c < pieces ? r[c] : piece_zero<T, kVec>();
-          bv[u] = c < pieces ? b[c] : piece_zero<T, kVec>();
+          if constexpr (kBias)
+            bv[u] = c < pieces ? b[c] : piece_zero<T, kVec>();
         }
 #pragma unroll
         for (int u = 0; u < kRowsInFlight; ++u)
 #pragma unroll
-          for (int j = 0; j < kElems; ++j)
-            s += piece_get<T, kVec>(dv[u], j) *
-                 (piece_get<T, kVec>(rv[u], j) + piece_get<T, kVec>(bv[u], j));
+          for (int j = 0; j < kElems; ++j) {
+            if constexpr (kBias)
+              s += piece_get<T, kVec>(dv[u], j) *
+                   (piece_get<T, kVec>(rv[u], j) +
+                    piece_get<T, kVec>(bv[u], j));
+            else
+              s += piece_get<T, kVec>(dv[u], j) * piece_get<T, kVec>(rv[u], j);
+          }
       }
     }
 #pragma unroll
@@ -586,11 +527,111 @@ hipError_t WithTypes(int dtype, int weights_dtype, bool vec, F f) {
                             : with_vec(_Float16{}, _Float16{});
 }
 
-}  // namespace
+// PaddedScatter (`biased` false: bias and padded_bins null, num_experts 0)
+// and PaddedScatterBias. The plain entry reads y whenever there are rows and
+// passes `rows` through; the bias entry reads y, bias and padded_bins only
+// with both rows and experts, and otherwise runs with num_experts = rows = 0
+// (every assignment contributes zero). The kernel takes its bias form when
+// there is a bias.
+hipError_t LaunchScatter(const void *y, const int *row_of,
+                         const int *padded_bins, const void *bias,
+                         const void *weights, void *out, int tokens,
+                         int hidden, int top_k, int num_experts, int rows,
+                         int dtype, int weights_dtype, bool biased,
+                         hipStream_t stream) {
+  if (!SizesOk(tokens, hidden, top_k, rows, dtype) || num_experts < 0 ||
+      (weights != nullptr && weights_dtype != 0 && weights_dtype != 1))
+    return hipErrorInvalidValue;
+  if (tokens == 0 || hidden == 0) return hipSuccess;
+  const bool routed = rows > 0 && (!biased || num_experts > 0);
+  if (out == nullptr || row_of == nullptr ||
+      (routed && (y == nullptr ||
+                  (biased && (bias == nullptr || padded_bins == nullptr)))))
+    return hipErrorInvalidValue;
+  if (out == y || out == weights || out == row_of ||
+      (biased && (out == bias || out == padded_bins)))
+    return hipErrorInvalidValue;
+  const bool vec = hidden % 8 == 0 && Aligned16({y, out, bias});
+  const unsigned grid =
+      GridFor(((long long)tokens + kRowsInFlight - 1) / kRowsInFlight);
+  return WithTypes(dtype, weights != nullptr ? weights_dtype : 0, vec,
+                   [&](auto t, auto w, auto v) {
+    using T = decltype(t);
+    using W = decltype(w);
+    auto launch = [&](auto b) {
+      hipLaunchKernelGGL(
+          (padded_scatter_kernel<T, W, decltype(v)::value, decltype(b)::value>),
+          dim3(grid), dim3(kThreads), 0, stream, static_cast<const T *>(y),
+          row_of, padded_bins, static_cast<const T *>(bias),
+          static_cast<const W *>(weights), static_cast<T *>(out), tokens,
+          hidden, top_k, routed ? num_experts : 0, routed ? rows : 0);
+      return hipGetLastError();
+    };
+    return bias != nullptr ? launch(std::true_type{})
+                           : launch(std::false_type{});
+  });
+}
 
-hipError_t RunMoeBins(const int *bin_ids, int n, int num_experts, int *bins,
-                      int *tokens_per_expert, int *padded_bins,
-                      hipStream_t stream) {
+// PaddedScatterWeightGrad and PaddedScatterBiasWeightGrad, as above. The
+// plain entry reads dout whenever hidden > 0 and y with rows; the bias entry
+// reads its operands only with rows, experts and hidden all there.
+hipError_t LaunchScatterWgrad(const void *dout, const void *y,
+                              const int *row_of, const int *padded_bins,
+                              const void *bias, void *dw, int tokens,
+                              int hidden, int top_k, int num_experts,
+                              int rows, int dtype, int weights_dtype,
+                              bool biased, hipStream_t stream) {
+  if (!SizesOk(tokens, hidden, top_k, rows, dtype) || num_experts < 0 ||
+      (weights_dtype != 0 && weights_dtype != 1))
+    return hipErrorInvalidValue;
+  if (tokens == 0) return hipSuccess;
+  const bool routed = !biased || (rows > 0 && num_experts > 0 && hidden > 0);
+  const bool reads_dout = biased ? routed : hidden > 0;
+  const bool reads_y = biased ? routed : hidden > 0 && rows > 0;
+  if (dw == nullptr || row_of == nullptr || (reads_dout && dout == nullptr) ||
+      (reads_y && y == nullptr) ||
+      (biased && routed && (bias == nullptr || padded_bins == nullptr)))
+    return hipErrorInvalidValue;
+  if (dw == dout || dw == y || dw == row_of ||
+      (biased && (dw == bias || dw == padded_bins)))
+    return hipErrorInvalidValue;
+  const int n = tokens * top_k;
+  const bool vec = hidden % 8 == 0 && Aligned16({dout, y, bias});
+  const unsigned grid = GridFor(n);
+  return WithTypes(dtype, weights_dtype, vec, [&](auto t, auto w, auto v) {
+    using T = decltype(t);
+    using W = decltype(w);
+    auto launch = [&](auto b) {
+      hipLaunchKernelGGL(
+          (padded_scatter_wgrad_kernel<T, W, decltype(v)::value,
+                                       decltype(b)::value>),
+          dim3(grid), dim3(kThreads), 0, stream, static_cast<const T *>(dout),
+          static_cast<const T *>(y), row_of, static_cast<W *>(dw), n, hidden,
+          top_k, routed ? rows : 0, padded_bins, static_cast<const T *>(bias),
+          routed ? num_experts : 0);
+      return hipGetLastError();
+    };
+    return bias != nullptr ? launch(std::true_type{})
+                           : launch(std::false_type{});
+  });
+}
+
+}  // namespace
+}  // namespace sputnik_amd
+
+// The host entry points (sputnik/block/moe.h), also behind the C-ABI: each
+// validates its arguments (hipErrorInvalidValue, nothing launched; the enums
+// by their integer value, 0 or 1), returns hipSuccess for zero-sized work,
+// and otherwise enqueues its kernel on `stream`. None allocates or
+// synchronises.
+namespace sputnik {
+namespace block {
+
+using namespace sputnik_amd;  // NOLINT: the kernels and launchers above
+
+hipError_t MoeBins(const int *bin_ids, int n, int num_experts, int *bins,
+                   int *tokens_per_expert, int *padded_bins,
+                   hipStream_t stream) {
   if (n < 0 || num_experts < 0 ||
       (long long)n + 127LL * num_experts > INT_MAX)
     return hipErrorInvalidValue;
@@ -608,10 +649,9 @@ hipError_t RunMoeBins(const int *bin_ids, int n, int num_experts, int *bins,
   return hipGetLastError();
 }
 
-hipError_t RunMoeRowMap(const int *indices, const int *bin_ids,
-                        const int *bins, const int *padded_bins, int n,
-                        int num_experts, int rows, int *row_of,
-                        hipStream_t stream) {
+hipError_t MoeRowMap(const int *indices, const int *bin_ids, const int *bins,
+                     const int *padded_bins, int n, int num_experts, int rows,
+                     int *row_of, hipStream_t stream) {
   if (n < 0 || num_experts < 0 || rows < 0 || rows % 128 != 0)
     return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
@@ -627,12 +667,13 @@ hipError_t RunMoeRowMap(const int *indices, const int *bin_ids,
   return hipGetLastError();
 }
 
-hipError_t RunPaddedGather(const void *x, const int *indices, const int *bins,
-                           const int *padded_bins, const void *weights,
-                           void *out, int tokens, int hidden, int top_k,
-                           int num_experts, int rows, int dtype,
-                           int weights_dtype, hipStream_t stream) {
-  if (!SizesOk(tokens, hidden, top_k, rows, dtype) || num_experts < 0 ||
+hipError_t PaddedGather(const void *x, const int *indices, const int *bins,
+                        const int *padded_bins, const void *weights,
+                        void *out, int tokens, int hidden, int top_k,
+                        int num_experts, int rows, DataType dtype,
+                        WeightType weights_type, hipStream_t stream) {
+  const int weights_dtype = (int)weights_type;
+  if (!SizesOk(tokens, hidden, top_k, rows, (int)dtype) || num_experts < 0 ||
       (weights != nullptr && weights_dtype != 0 && weights_dtype != 1))
     return hipErrorInvalidValue;
   if (rows == 0 || hidden == 0) return hipSuccess;
@@ -649,7 +690,7 @@ hipError_t RunPaddedGather(const void *x, const int *indices, const int *bins,
   const bool vec = hidden % 8 == 0 && Aligned16({x, out});
   const unsigned grid =
       GridFor(((long long)rows + kRowsInFlight - 1) / kRowsInFlight);
-  return WithTypes(dtype, weights != nullptr ? weights_dtype : 0, vec,
+  return WithTypes((int)dtype, weights != nullptr ? weights_dtype : 0, vec,
                    [&](auto t, auto w, auto v) {
     using T = decltype(t);
     using W = decltype(w);
@@ -663,168 +704,24 @@ hipError_t RunPaddedGather(const void *x, const int *indices, const int *bins,
   });
 }
 
-hipError_t RunPaddedScatter(const void *y, const int *row_of,
-                            const void *weights, void *out, int tokens,
-                            int hidden, int top_k, int rows, int dtype,
-                            int weights_dtype, hipStream_t stream) {
-  if (!SizesOk(tokens, hidden, top_k, rows, dtype) ||
-      (weights != nullptr && weights_dtype != 0 && weights_dtype != 1))
-    return hipErrorInvalidValue;
-  if (tokens == 0 || hidden == 0) return hipSuccess;
-  if (out == nullptr || row_of == nullptr || (rows > 0 && y == nullptr))
-    return hipErrorInvalidValue;
-  if (out == y || out == weights || out == row_of)
-    return hipErrorInvalidValue;
-  const bool vec = hidden % 8 == 0 && Aligned16({y, out});
-  const unsigned grid =
-      GridFor(((long long)tokens + kRowsInFlight - 1) / kRowsInFlight);
-  return WithTypes(dtype, weights != nullptr ? weights_dtype : 0, vec,
-                   [&](auto t, auto w, auto v) {
-    using T = decltype(t);
-    using W = decltype(w);
-    hipLaunchKernelGGL((padded_scatter_kernel<T, W, decltype(v)::value>),
-                       dim3(grid), dim3(kThreads), 0, stream,
-                       static_cast<const T *>(y), row_of,
-                       static_cast<const W *>(weights), static_cast<T *>(out),
-                       tokens, hidden, top_k, rows);
-    return hipGetLastError();
-  });
+hipError_t PaddedScatter(const void *y, const int *row_of,
+                         const void *weights, void *out, int tokens,
+                         int hidden, int top_k, int rows, DataType dtype,
+                         WeightType weights_type, hipStream_t stream) {
+  return LaunchScatter(y, row_of, nullptr, nullptr, weights, out, tokens,
+                       hidden, top_k, 0, rows, (int)dtype, (int)weights_type,
+                       false, stream);
 }
 
-hipError_t RunPaddedScatterWgrad(const void *dout, const void *y,
-                                 const int *row_of, void *dw, int tokens,
-                                 int hidden, int top_k, int rows, int dtype,
-                                 int weights_dtype, hipStream_t stream) {
-  if (!SizesOk(tokens, hidden, top_k, rows, dtype) ||
-      (weights_dtype != 0 && weights_dtype != 1))
-    return hipErrorInvalidValue;
-  if (tokens == 0) return hipSuccess;
-  if (dw == nullptr || row_of == nullptr ||
-      (hidden > 0 && (dout == nullptr || (rows > 0 && y == nullptr))))
-    return hipErrorInvalidValue;
-  if (dw == dout || dw == y || dw == row_of) return hipErrorInvalidValue;
-  const int n = tokens * top_k;
-  const bool vec = hidden % 8 == 0 && Aligned16({dout, y});
-  const unsigned grid = GridFor(n);
-  return WithTypes(dtype, weights_dtype, vec, [&](auto t, auto w, auto v) {
-    using T = decltype(t);
-    using W = decltype(w);
-    hipLaunchKernelGGL(
-        (padded_scatter_wgrad_kernel<T, W, decltype(v)::value>), dim3(grid),
-        dim3(kThreads), 0, stream, static_cast<const T *>(dout),
-        static_cast<const T *>(y), row_of, static_cast<W *>(dw), n, hidden,
-        top_k, rows);
-    return hipGetLastError();
-  });
+hipError_t PaddedScatterWeightGrad(const void *dout, const void *y,
+                                   const int *row_of, void *dw, int tokens,
+                                   int hidden, int top_k, int rows,
+                                   DataType dtype, WeightType weights_type,
+                                   hipStream_t stream) {
+  return LaunchScatterWgrad(dout, y, row_of, nullptr, nullptr, dw, tokens,
+                            hidden, top_k, 0, rows, (int)dtype,
+                            (int)weights_type, false, stream);
 }
-
-hipError_t RunPaddedScatterBias(const void *y, const int *row_of,
-                                const int *padded_bins, const void *bias,
-                                const void *weights, void *out, int tokens,
-                                int hidden, int top_k, int num_experts,
-                                int rows, int dtype, int weights_dtype,
-                                hipStream_t stream) {
-  if (!SizesOk(tokens, hidden, top_k, rows, dtype) || num_experts < 0 ||
-      (weights != nullptr && weights_dtype != 0 && weights_dtype != 1))
-    return hipErrorInvalidValue;
-  if (tokens == 0 || hidden == 0) return hipSuccess;
-  // (without experts or rows every assignment contributes zero)
-  const bool routed = rows > 0 && num_experts > 0;
-  if (out == nullptr || row_of == nullptr ||
-      (routed && (y == nullptr || bias == nullptr || padded_bins == nullptr)))
-    return hipErrorInvalidValue;
-  if (out == y || out == weights || out == row_of || out == bias ||
-      out == padded_bins)
-    return hipErrorInvalidValue;
-  const bool vec = hidden % 8 == 0 && Aligned16({y, out, bias});
-  const unsigned grid =
-      GridFor(((long long)tokens + kRowsInFlight - 1) / kRowsInFlight);
-  return WithTypes(dtype, weights != nullptr ? weights_dtype : 0, vec,
-                   [&](auto t, auto w, auto v) {
-    using T = decltype(t);
-    using W = decltype(w);
-    hipLaunchKernelGGL((padded_scatter_bias_kernel<T, W, decltype(v)::value>),
-                       dim3(grid), dim3(kThreads), 0, stream,
-                       static_cast<const T *>(y), row_of, padded_bins,
-                       static_cast<const T *>(bias),
-                       static_cast<const W *>(weights), static_cast<T *>(out),
-                       tokens, hidden, top_k, routed ? num_experts : 0,
-                       routed ? rows : 0);
-    return hipGetLastError();
-  });
-}
-
-hipError_t RunPaddedScatterBiasWgrad(const void *dout, const void *y,
-                                     const int *row_of, const int *padded_bins,
-                                     const void *bias, void *dw, int tokens,
-                                     int hidden, int top_k, int num_experts,
-                                     int rows, int dtype, int weights_dtype,
-                                     hipStream_t stream) {
-  if (!SizesOk(tokens, hidden, top_k, rows, dtype) || num_experts < 0 ||
-      (weights_dtype != 0 && weights_dtype != 1))
-    return hipErrorInvalidValue;
-  if (tokens == 0) return hipSuccess;
-  const bool routed = rows > 0 && num_experts > 0 && hidden > 0;
-  if (dw == nullptr || row_of == nullptr ||
-      (routed && (dout == nullptr || y == nullptr || bias == nullptr ||
-                  padded_bins == nullptr)))
-    return hipErrorInvalidValue;
-  if (dw == dout || dw == y || dw == row_of || dw == bias ||
-      dw == padded_bins)
-    return hipErrorInvalidValue;
-  const int n = tokens * top_k;
-  const bool vec = hidden % 8 == 0 && Aligned16({dout, y, bias});
-  const unsigned grid = GridFor(n);
-  return WithTypes(dtype, weights_dtype, vec, [&](auto t, auto w, auto v) {
-    using T = decltype(t);
-    using W = decltype(w);
-    hipLaunchKernelGGL(
-        (padded_scatter_bias_wgrad_kernel<T, W, decltype(v)::value>),
-        dim3(grid), dim3(kThreads), 0, stream, static_cast<const T *>(dout),
-        static_cast<const T *>(y), row_of, padded_bins,
-        static_cast<const T *>(bias), static_cast<W *>(dw), n, hidden, top_k,
-        routed ? num_experts : 0, routed ? rows : 0);
-    return hipGetLastError();
-  });
-}
-
-hipError_t RunPaddedScatterBiasGrad(const void *dout, const int *indices,
-                                    const int *bins, const void *weights,
-                                    float *db, int tokens, int hidden,
-                                    int top_k, int num_experts, int dtype,
-                                    int weights_dtype, hipStream_t stream) {
-  if (!SizesOk(tokens, hidden, top_k, 0, dtype) || num_experts < 0 ||
-      (weights != nullptr && weights_dtype != 0 && weights_dtype != 1))
-    return hipErrorInvalidValue;
-  if (num_experts == 0 || hidden == 0) return hipSuccess;
-  const int n = tokens * top_k;
-  if (db == nullptr || bins == nullptr ||
-      (n > 0 && (dout == nullptr || indices == nullptr)))
-    return hipErrorInvalidValue;
-  if (db == dout || db == weights || db == (const void *)indices ||
-      db == (const void *)bins)
-    return hipErrorInvalidValue;
-  const bool vec = hidden % 8 == 0 && Aligned16({dout});
-  const int per_slice = 16 * (vec ? 8 : 1);
-  const long long slices = ((long long)hidden + per_slice - 1) / per_slice;
-  if (slices * num_experts > INT_MAX) return hipErrorInvalidValue;
-  return WithTypes(dtype, weights != nullptr ? weights_dtype : 0, vec,
-                   [&](auto t, auto w, auto v) {
-    using T = decltype(t);
-    using W = decltype(w);
-    hipLaunchKernelGGL(
-        (padded_scatter_bias_grad_kernel<T, W, decltype(v)::value>),
-        dim3((unsigned)(slices * num_experts)), dim3(kReduceThreads), 0,
-        stream, static_cast<const T *>(dout), indices, bins,
-        static_cast<const W *>(weights), db, n, hidden, top_k, (int)slices);
-    return hipGetLastError();
-  });
-}
-
-}  // namespace sputnik_amd
-
-namespace sputnik {
-namespace block {
 
 hipError_t PaddedScatterBias(const void *y, const int *row_of,
                              const int *padded_bins, const void *bias,
@@ -832,9 +729,9 @@ hipError_t PaddedScatterBias(const void *y, const int *row_of,
                              int hidden, int top_k, int num_experts, int rows,
                              DataType dtype, WeightType weights_type,
                              hipStream_t stream) {
-  return sputnik_amd::RunPaddedScatterBias(
-      y, row_of, padded_bins, bias, weights, out, tokens, hidden, top_k,
-      num_experts, rows, (int)dtype, (int)weights_type, stream);
+  return LaunchScatter(y, row_of, padded_bins, bias, weights, out, tokens,
+                       hidden, top_k, num_experts, rows, (int)dtype,
+                       (int)weights_type, true, stream);
 }
 
 hipError_t PaddedScatterBiasWeightGrad(const void *dout, const void *y,
@@ -845,9 +742,9 @@ hipError_t PaddedScatterBiasWeightGrad(const void *dout, const void *y,
                                        int rows, DataType dtype,
                                        WeightType weights_type,
                                        hipStream_t stream) {
-  return sputnik_amd::RunPaddedScatterBiasWgrad(
-      dout, y, row_of, padded_bins, bias, dw, tokens, hidden, top_k,
-      num_experts, rows, (int)dtype, (int)weights_type, stream);
+  return LaunchScatterWgrad(dout, y, row_of, padded_bins, bias, dw, tokens,
+                            hidden, top_k, num_experts, rows, (int)dtype,
+                            (int)weights_type, true, stream);
 }
 
 hipError_t PaddedScatterBiasGrad(const void *dout, const int *indices,
@@ -855,54 +752,36 @@ hipError_t PaddedScatterBiasGrad(const void *dout, const int *indices,
                                  float *bias_grad, int tokens, int hidden,
                                  int top_k, int num_experts, DataType dtype,
                                  WeightType weights_type, hipStream_t stream) {
-  return sputnik_amd::RunPaddedScatterBiasGrad(
-      dout, indices, bins, weights, bias_grad, tokens, hidden, top_k,
-      num_experts, (int)dtype, (int)weights_type, stream);
-}
-
-hipError_t MoeBins(const int *bin_ids, int n, int num_experts, int *bins,
-                   int *tokens_per_expert, int *padded_bins,
-                   hipStream_t stream) {
-  return sputnik_amd::RunMoeBins(bin_ids, n, num_experts, bins,
-                                 tokens_per_expert, padded_bins, stream);
-}
-
-hipError_t MoeRowMap(const int *indices, const int *bin_ids, const int *bins,
-                     const int *padded_bins, int n, int num_experts, int rows,
-                     int *row_of, hipStream_t stream) {
-  return sputnik_amd::RunMoeRowMap(indices, bin_ids, bins, padded_bins, n,
-                                   num_experts, rows, row_of, stream);
-}
-
-hipError_t PaddedGather(const void *x, const int *indices, const int *bins,
-                        const int *padded_bins, const void *weights,
-                        void *out, int tokens, int hidden, int top_k,
-                        int num_experts, int rows, DataType dtype,
-                        WeightType weights_type, hipStream_t stream) {
-  return sputnik_amd::RunPaddedGather(x, indices, bins, padded_bins, weights,
-                                      out, tokens, hidden, top_k, num_experts,
-                                      rows, (int)dtype, (int)weights_type,
-                                      stream);
-}
-
-hipError_t PaddedScatter(const void *y, const int *row_of,
-                         const void *weights, void *out, int tokens,
-                         int hidden, int top_k, int rows, DataType dtype,
-                         WeightType weights_type, hipStream_t stream) {
-  return sputnik_amd::RunPaddedScatter(y, row_of, weights, out, tokens, hidden,
-                                       top_k, rows, (int)dtype,
-                                       (int)weights_type, stream);
-}
-
-hipError_t PaddedScatterWeightGrad(const void *dout, const void *y,
-                                   const int *row_of, void *dw, int tokens,
-                                   int hidden, int top_k, int rows,
-                                   DataType dtype, WeightType weights_type,
-                                   hipStream_t stream) {
-  return sputnik_amd::RunPaddedScatterWgrad(dout, y, row_of, dw, tokens,
-                                            hidden, top_k, rows, (int)dtype,
-                                            (int)weights_type, stream);
+  const int weights_dtype = (int)weights_type;
+  if (!SizesOk(tokens, hidden, top_k, 0, (int)dtype) || num_experts < 0 ||
+      (weights != nullptr && weights_dtype != 0 && weights_dtype != 1))
+    return hipErrorInvalidValue;
+  if (num_experts == 0 || hidden == 0) return hipSuccess;
+  const int n = tokens * top_k;
+  if (bias_grad == nullptr || bins == nullptr ||
+      (n > 0 && (dout == nullptr || indices == nullptr)))
+    return hipErrorInvalidValue;
+  if (bias_grad == dout || bias_grad == weights ||
+      bias_grad == (const void *)indices || bias_grad == (const void *)bins)
+    return hipErrorInvalidValue;
+  const bool vec = hidden % 8 == 0 && Aligned16({dout});
+  const int per_slice = 16 * (vec ? 8 : 1);
+  const long long slices = ((long long)hidden + per_slice - 1) / per_slice;
+  if (slices * num_experts > INT_MAX) return hipErrorInvalidValue;
+  return WithTypes((int)dtype, weights != nullptr ? weights_dtype : 0, vec,
+                   [&](auto t, auto w, auto v) {
+    using T = decltype(t);
+    using W = decltype(w);
+    hipLaunchKernelGGL(
+        (padded_scatter_bias_grad_kernel<T, W, decltype(v)::value>),
+        dim3((unsigned)(slices * num_experts)), dim3(kReduceThreads), 0,
+        stream, static_cast<const T *>(dout), indices, bins,
+        static_cast<const W *>(weights), bias_grad, n, hidden, top_k,
+        (int)slices);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace block
 }  // namespace sputnik
+

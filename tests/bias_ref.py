@@ -35,8 +35,7 @@ P_BITS = M.P_BITS
 # scatter tests run.
 HIDDEN = [8, 264, 100]
 LONG_CASE = ((129, 2, 4, "empty"), 4096)
-# top_k past the picks the scatter kernel looks up in front of its piece loop
-DEEP_CASE = ((37, 6, 8, "random"), 264)
+DEEP_CASE = M.DEEP_CASE
 
 
 # ---- the bias stage ---------------------------------------------------------

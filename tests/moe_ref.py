@@ -50,6 +50,20 @@ CASES = [
 ]
 HIDDEN = [8, 264, 100, 4096]
 DTYPES = ["f16", "bf16"]
+# (case, hidden) with top_k past the 4 picks the scatter kernel looks up in
+# front of its piece loop: 37 tokens leave one live row in the last 4-row
+# task, and 264 is a partial last step on the 16-byte path.
+DEEP_CASE = ((37, 6, 8, "random"), 264)
+
+
+def scatter_cases():
+    """(case, hidden) pairs of the scatter and weight-gradient tests."""
+    return [(c, h) for c in CASES for h in HIDDEN] + [DEEP_CASE]
+
+
+def scatter_hiddens(case):
+    """The row lengths at which scatter_cases() runs `case`."""
+    return [h for c, h in scatter_cases() if c == case]
 
 
 def rows_bound(n: int, num_experts: int) -> int:

@@ -402,6 +402,43 @@ def test_scatter_bias_row_out_of_range(dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case,hidden", [R.DEEP_CASE,
+                                         ((129, 2, 4, "empty"), 264)],
+                         ids=["deep", "empty"])
+def test_wgrad_with_a_zero_bias_is_the_plain_wgrad(case, hidden, dtype):
+    """PaddedScatterBiasWeightGrad with an all +0 bias equals
+    PaddedScatterWeightGrad bit for bit, dw of T and of fp32, on the 16-byte
+    path and (buffers offset by 4 elements) the element path: the two are
+    one kernel body, the sum order is the same, and y + 0 changes no term
+    in a way that can change the sum."""
+    c = M.case_inputs(case, hidden, dtype)
+    r, td = c.route, H.torch_dtype(dtype)
+    rows, n = M.exact_rows(r), r.tokens * r.top_k
+    row_of, padded_bins = _i32(r.row_of), _i32(r.padded_bins)
+
+    def put(values, offset):
+        flat = torch.zeros(values.size + offset, dtype=td, device="cuda")
+        assert flat.data_ptr() % 16 == 0
+        t = flat[offset:].view(*values.shape)
+        t.copy_(_dev(values, dtype))
+        return t
+    for offset in (0, 4):
+        dout, y = put(c.dout, offset), put(c.y[:rows], offset)
+        zero = put(np.zeros((case[2], hidden), dtype=np.float32), offset)
+        for wd in (td, torch.float32):
+            plain = torch.full((n,), float("nan"), dtype=wd, device="cuda")
+            biased = torch.full_like(plain, float("nan"))
+            sp.PaddedScatterWeightGrad(dout, y, row_of, plain, r.top_k)
+            sp.PaddedScatterBiasWeightGrad(dout, y, row_of, padded_bins, zero,
+                                           biased, r.top_k)
+            torch.cuda.synchronize()
+            assert not torch.isnan(plain.float()).any()
+            assert torch.equal(plain.view(torch.uint8),
+                               biased.view(torch.uint8)), \
+                f"offset {offset}, dw {wd}"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_scatter_bias_integers_are_exact(dtype):
     """Integer y, b2 and dout with unit weights: every order is exact."""
     hidden = 264

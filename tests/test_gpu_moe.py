@@ -2,7 +2,8 @@
 ctypes bindings of the C entry points, against tests/moe_ref.py (numpy; it
 never calls the library).
 
-Every case of moe_ref.CASES x HIDDEN x fp16 / bf16 runs in four layouts: the
+Every case of moe_ref.CASES x HIDDEN x fp16 / bf16 (the scatter and the
+weight gradient: DEEP_CASE too) runs in four layouts: the
 buffers 256-byte aligned (the 16-byte path wherever hidden % 8 == 0) and
 offset by 4 elements (8 bytes: the element path), each with the padded matrix
 sized exactly (padded_bins[-1]) and by rows_bound (trailing zero rows).
@@ -39,6 +40,13 @@ CASE_IDS = ["%dx%d-E%d-%s" % c for c in R.CASES]
 cases = pytest.mark.parametrize("case", R.CASES, ids=CASE_IDS)
 hiddens = pytest.mark.parametrize("hidden", R.HIDDEN)
 dtypes = pytest.mark.parametrize("dtype", R.DTYPES)
+# moe_ref.scatter_cases(): cases x hiddens x dtypes under the ids of the three
+# marks above, plus DEEP_CASE (the scatter's picks past the hoisted ones).
+scatter_cases = pytest.mark.parametrize(
+    "case,hidden,dtype",
+    [(c, h, d) for c, h in R.scatter_cases() for d in R.DTYPES],
+    ids=["%s-%d-%dx%d-E%d-%s" % (d, h, *c)
+         for c, h in R.scatter_cases() for d in R.DTYPES])
 
 
 def _i32(a):
@@ -120,9 +128,7 @@ def test_gather_bit_exact(case, hidden, dtype):
                            f"weights {wref is not None}")
 
 
-@cases
-@hiddens
-@dtypes
+@scatter_cases
 def test_scatter_bit_exact(case, hidden, dtype):
     c = R.case_inputs(case, hidden, dtype)
     r, td = c.route, H.torch_dtype(dtype)
@@ -142,9 +148,7 @@ def test_scatter_bit_exact(case, hidden, dtype):
                            f"weights {weighted}")
 
 
-@cases
-@hiddens
-@dtypes
+@scatter_cases
 def test_scatter_fp32_weights(case, hidden, dtype):
     c = R.case_inputs(case, hidden, dtype)
     r, td = c.route, H.torch_dtype(dtype)
@@ -163,9 +167,7 @@ def test_scatter_fp32_weights(case, hidden, dtype):
             assert (err <= bound).all()
 
 
-@cases
-@hiddens
-@dtypes
+@scatter_cases
 def test_wgrad(case, hidden, dtype):
     c = R.case_inputs(case, hidden, dtype)
     r, td = c.route, H.torch_dtype(dtype)

@@ -79,9 +79,9 @@ def test_rows_bound_covers_every_routing():
 # ---- the emulation meets the GPU tests' bounds ------------------------------
 
 @pytest.mark.parametrize("dtype", R.DTYPES)
-@pytest.mark.parametrize("case", R.CASES)
+@pytest.mark.parametrize("case", R.CASES + [R.DEEP_CASE[0]])
 def test_emulation_meets_the_fp32_weight_scatter_bound(case, dtype):
-    for hidden in R.HIDDEN:
+    for hidden in R.scatter_hiddens(case):
         c = R.case_inputs(case, hidden, dtype)
         r = c.route
         got = R.scatter32(c.y_cols, r, c.w32, dtype).astype(np.float64)
@@ -91,9 +91,9 @@ def test_emulation_meets_the_fp32_weight_scatter_bound(case, dtype):
 
 
 @pytest.mark.parametrize("dtype", R.DTYPES)
-@pytest.mark.parametrize("case", R.CASES)
+@pytest.mark.parametrize("case", R.CASES + [R.DEEP_CASE[0]])
 def test_emulation_meets_the_wgrad_bound(case, dtype):
-    for hidden in R.HIDDEN:
+    for hidden in R.scatter_hiddens(case):
         c = R.case_inputs(case, hidden, dtype)
         acc = R.wgrad32(c.dout_abs, c.y_rows, c.route)
         ref, absum = R.wgrad64(c.dout_abs, c.y_rows, c.route)
