@@ -10,6 +10,7 @@
 #include "sputnik/block/bias.h"
 #include "sputnik/block/bitmask/bitmask.h"
 #include "sputnik/block/dsd/dsd.h"
+#include "sputnik/block/fp8.h"
 #include "sputnik/block/gated.h"
 #include "sputnik/block/moe.h"
 #include "sputnik/block/router.h"

@@ -580,6 +580,57 @@ int sputnik_moe_sort(const int32_t *top_experts, int n, int num_experts,
                      int32_t *padded_bins, int32_t *row_of, void *workspace,
                      size_t workspace_bytes, void *stream);
 
+/* ---- FP8 (e4m3) expert products with block scales, forward
+ * (sputnik/block/fp8.h has the contract, INTEGRATION.md 3j the recipe).
+ * Elements are OCP e4m3fn bytes (torch.float8_e4m3fn), scales fp32 with
+ * value = float(q) * scale: one per 1 x 128 row tile of an activation or of
+ * a sparse operand's stored blocks, one per 128 x 128 weight block.
+ * scale = max(amax / 448, 2^-126), or with `pow2` the smallest power of two
+ * >= 2^-126 with amax / scale <= 448; q = rne_e4m3(x / scale), both IEEE
+ * fp32 divisions; NaN / +-Inf become 0x7F / 0xFF.
+ *
+ *   sputnik_quantize_rows        x [rows, cols] of T -> q [rows, cols],
+ *                                scales [rows, cols / 128]
+ *   sputnik_quantize_rows_act    the same of round_T(act(x)), as
+ *                                sputnik_block_activation computes it
+ *   sputnik_quantize_rows_gated  the same of round_T(x * act(gate)), as
+ *                                sputnik_block_gate computes it
+ *   sputnik_quantize_weight      w [k, n] of T (transpose: the buffer is
+ *                                [n, k]) -> q [n, k], scales [k / 128, n / 128]
+ *   sputnik_sdd_fp8   C (BCSR, T) = Aq [c.rows, k] . Bq at C's stored blocks
+ *                     (c.indices and c.row_indices); a_scales [c.rows,
+ *                     k / 128], Bq [c.cols, k], b_scales [k / 128,
+ *                     c.cols / 128]
+ *   sputnik_dsd_fp8   C [s.rows, c.cols] (T) = Sq (BCSR, e4m3 bytes in
+ *                     s.data, s_scales [blocks * 128]) . Bq [c.cols, s.cols]
+ *
+ * Per k-block in ascending (SDD) or storage (DSD) order, acc = fma(sa * sb, P,
+ * acc) in fp32 with P the MFMA sum of the block's 128 products, held to fp32
+ * precision; C = round_T(acc).
+ * No split-K, no atomics: bitwise reproducible. `dtype` is T (0 fp16,
+ * 1 bf16), act 0 relu / 1 gelu / 2 silu. Stream-ordered; nothing is
+ * allocated or synchronised. hipErrorInvalidValue with nothing launched for
+ * a null required buffer, a negative size, a dimension that is not a multiple
+ * of 128, an output that is one of the inputs, or (the two products) a
+ * 16-byte misaligned Aq / Sq / Bq / C. Zero-sized work succeeds. */
+int sputnik_quantize_rows(const void *x, int rows, int cols, void *q,
+                          float *scales, int pow2, int dtype, void *stream);
+int sputnik_quantize_rows_act(const void *x, int rows, int cols, int act,
+                              void *q, float *scales, int pow2, int dtype,
+                              void *stream);
+int sputnik_quantize_rows_gated(const void *x, const void *gate, int rows,
+                                int cols, int act, void *q, float *scales,
+                                int pow2, int dtype, void *stream);
+int sputnik_quantize_weight(const void *w, int k, int n, int transpose,
+                            void *q, float *scales, int pow2, int dtype,
+                            void *stream);
+int sputnik_sdd_fp8(const void *aq, const float *a_scales, int k,
+                    const void *bq, const float *b_scales,
+                    const sputnik_block_matrix_t *c, int dtype, void *stream);
+int sputnik_dsd_fp8(const sputnik_block_matrix_t *s, const float *s_scales,
+                    const void *bq, const float *b_scales,
+                    const sputnik_matrix_t *c, int dtype, void *stream);
+
 /* ---- Host-only queries (no GPU work; safe without a device) */
 /* 1 when the reference would accept the problem (same rules as
  * can_launch_* + ValidMatmul), 0 otherwise. op: 0=DSD 1=DDS 2=SDD. */

@@ -1,0 +1,142 @@
+"""Same-process timing of the fp8 forward path (sputnik/block/fp8.h) against
+the 16-bit SDD and DSD it stands beside: sdd_fp8, dsd_fp8 and the two hot
+quantisers (quantize_rows of the gathered activations, quantize_sparse with
+gelu of the SDD output) next to ops' raw bf16 sdd and dsd on the same
+topology. Recorded, not gated (DESIGN "FP8 forward path").
+
+Protocol: one process, HIP events, every arm warmed for at
+least --warm-ms of device time, then --rounds interleaved rounds, each window
+long enough to hold at least --load-ms of back-to-back calls; medians and
+ranges over the rounds.
+
+Shapes (bf16 outputs, 8 experts, d_model 4096, d_ff 14336, every expert with
+the same number of rows, the dMoE topology of ops.expert_topology):
+    c4      BASELINE config 4: 8192 rows (1024 per expert), 7168 blocks
+    decode  128 rows per expert (1024 rows, 896 blocks): the weights, 0.94 GB
+            each in bf16, dominate the traffic
+
+Per arm: microseconds, TFLOP/s from 2 * blocks * 128 * 128 * K for the
+products, and for the quantisers the achieved bytes per second (2 bytes read,
+1 written per element, 4 per scale) as a share of the 6.3 TB/s achievable HBM
+rate. One JSON line per shape.
+
+python scripts/bench_fp8.py [--shapes c4,decode] [--out profiles/fp8/bench_fp8.jsonl]
+"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+EXPERTS, D_MODEL, D_FF = 8, 4096, 14336
+SHAPES = {"c4": 1024, "decode": 128}  # rows per expert
+HBM_TBS = 6.3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="c4,decode")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warm-ms", type=float, default=100.0)
+    ap.add_argument("--load-ms", type=float, default=100.0)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import torch
+    import sputnik_amd as sp
+    from sputnik_amd import ops
+
+    assert torch.cuda.is_available(), "needs a GPU: there is no CPU timing"
+    gen = torch.Generator(device="cuda").manual_seed(29)
+    dt = torch.bfloat16
+    hidden = EXPERTS * D_FF
+
+    def rand(*shape, scale=1.0):
+        return (torch.randn(*shape, generator=gen, device="cuda",
+                            dtype=torch.float32) * scale).to(dt)
+
+    def window(fn, calls):
+        s = torch.cuda.Event(enable_timing=True)
+        e = torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(calls):
+            fn()
+        e.record()
+        torch.cuda.synchronize()
+        return s.elapsed_time(e) * 1e3 / calls  # us per call
+
+    w1, w2 = rand(D_MODEL, hidden, scale=1 / 64), rand(hidden, D_MODEL,
+                                                        scale=1 / 64)
+    w1q, w2q = ops.quantize_weight(w1), ops.quantize_weight(w2)
+    lines = []
+    for shape in a.shapes.split(","):
+        per_expert = SHAPES[shape]
+        rows = EXPERTS * per_expert
+        padded_bins = torch.arange(1, EXPERTS + 1, dtype=torch.int32,
+                                   device="cuda") * per_expert
+        topo = ops.expert_topology(padded_bins, D_FF // 128, rows // 128,
+                                   dtype=dt)
+        blocks = topo.nnz_blocks
+        x = rand(rows, D_MODEL)
+        xq, xs = ops.quantize_rows(x)
+        g16 = topo.with_data(ops._sdd(x, w1, topo))
+        h16 = g16.with_data(sp.BlockActivation(g16.data, "gelu"))
+        hq = ops.quantize_sparse(g16, "gelu")
+        arms = {
+            "sdd_bf16": lambda: ops._sdd(x, w1, topo),
+            "sdd_fp8": lambda: ops.sdd_fp8(xq, xs, w1q, topo, dt),
+            "dsd_bf16": lambda: ops._dsd(h16, w2),
+            "dsd_fp8": lambda: ops.dsd_fp8(hq, w2q, dt),
+            "quantize_rows": lambda: ops.quantize_rows(x),
+            "quantize_sparse_gelu": lambda: ops.quantize_sparse(g16, "gelu"),
+        }
+        calls = {}
+        for name, fn in arms.items():
+            fn()
+            torch.cuda.synchronize()
+            once = window(fn, 3)
+            calls[name] = max(3, math.ceil(a.load_ms * 1e3 / once))
+            spent = 0.0
+            while spent < a.warm_ms * 1e3:
+                spent += window(fn, calls[name]) * calls[name]
+        times = {name: [] for name in arms}
+        for _ in range(a.rounds):
+            for name, fn in arms.items():
+                times[name].append(window(fn, calls[name]))
+        flops = 2.0 * blocks * 128 * 128
+        work = {"sdd_bf16": flops * D_MODEL, "sdd_fp8": flops * D_MODEL,
+                "dsd_bf16": flops * D_MODEL, "dsd_fp8": flops * D_MODEL}
+        moved = {"quantize_rows": rows * D_MODEL * 3 + rows * D_MODEL // 32,
+                 "quantize_sparse_gelu": blocks * 16384 * 3 + blocks * 512}
+        line = {"shape": shape, "rows": rows, "blocks": blocks,
+                "build": sp.build_hash(), "rounds": a.rounds, "arms": {}}
+        for name in arms:
+            med = statistics.median(times[name])
+            arm = {"us": round(med, 2), "min_us": round(min(times[name]), 2),
+                   "max_us": round(max(times[name]), 2),
+                   "calls": calls[name]}
+            if name in work:
+                arm["tflops"] = round(work[name] / med / 1e6, 1)
+            else:
+                tbs = moved[name] / med / 1e6
+                arm["tb_per_s"] = round(tbs, 3)
+                arm["hbm_share"] = round(tbs / HBM_TBS, 3)
+            line["arms"][name] = arm
+        for op in ("sdd", "dsd"):
+            line[f"{op}_fp8_over_bf16"] = round(
+                line["arms"][f"{op}_fp8"]["us"]
+                / line["arms"][f"{op}_bf16"]["us"], 3)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -223,6 +223,22 @@ _SIGNATURES = {
     "sputnik_moe_sort_workspace_bytes": [ctypes.c_int, ctypes.c_int],
     "sputnik_moe_sort": [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P,
                          _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
+    # fp8 products: (x, rows, cols, [act,] q, scales, pow2, dtype, stream);
+    # gated: (x, gate, rows, cols, act, q, ...); (w, k, n, transpose, q,
+    # scales, pow2, dtype, stream); (aq, a_scales, k, bq, b_scales, c, dtype,
+    # stream); (s, s_scales, bq, b_scales, c, dtype, stream)
+    "sputnik_quantize_rows": [_P, ctypes.c_int, ctypes.c_int, _P, _P,
+                              ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_quantize_rows_act": [_P, ctypes.c_int, ctypes.c_int,
+                                  ctypes.c_int, _P, _P, ctypes.c_int,
+                                  ctypes.c_int, _P],
+    "sputnik_quantize_rows_gated": [_P, _P, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, _P, _P, ctypes.c_int,
+                                    ctypes.c_int, _P],
+    "sputnik_quantize_weight": [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                _P, _P, ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_sdd_fp8": [_P, _P, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P],
+    "sputnik_dsd_fp8": [_P, _P, _P, _P, _P, ctypes.c_int, _P],
     "sputnik_can_implement": [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_abi_block_matrix_size": [],
     "sputnik_abi_block_matrix_offset": [ctypes.c_int],
@@ -1710,6 +1726,142 @@ from .gather import (allgather_concat, gather_block_runs,  # noqa: E402
                      gather_col_panels, gather_row_panels)
 
 
+# ---- fp8 products (sputnik/block/fp8.h) --------------------------------------
+
+def _fp8_buffer(t, dtype, shape, what: str) -> None:
+    """A buffer of an fp8 call: `dtype`, `shape`, contiguous. Raises before
+    any library call."""
+    if getattr(t, "dtype", None) != dtype:
+        raise TypeError(f"{what} is {getattr(t, 'dtype', None)}, expected "
+                        f"{dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} has shape {tuple(t.shape)}, expected "
+                         f"{tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+
+
+def _fp8_tiles(n: int, what: str) -> int:
+    if n % 128:
+        raise ValueError(f"{what} = {n} is not a multiple of 128")
+    return n // 128
+
+
+def QuantizeRows(x, q, scales, pow2=False, activation=None, gate=None,  # noqa: N802
+                 stream=None):
+    """q (torch.float8_e4m3fn, x's shape) and scales (fp32 [rows, cols /
+    128]) of x [rows, cols] (fp16 / bf16), one scale per 1 x 128 tile:
+    scale = max(amax / 448, 2^-126), or with `pow2` the smallest power of two
+    that keeps amax / scale <= 448; q = rne(x / scale) (sputnik_quantize_rows;
+    sputnik/block/fp8.h has the format). With `activation` the rows of
+    act(x), or with `gate` (x's shape and dtype) of x * act(gate), are
+    quantised, each evaluated as BlockActivation / BlockGate evaluate it.
+    Type and shape errors are raised before the library is called."""
+    import torch
+
+    _moe_matrix(x, None, None, "x")
+    dtype = _dtype_code(x)
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    tiles = _fp8_tiles(cols, "QuantizeRows: cols")
+    _fp8_buffer(q, torch.float8_e4m3fn, (rows, cols), "q")
+    _fp8_buffer(scales, torch.float32, (rows, tiles), "scales")
+    if gate is not None:
+        if activation is None:
+            raise ValueError("QuantizeRows: a gate needs its activation")
+        _fp8_buffer(gate, x.dtype, (rows, cols), "gate")
+    act = None if activation is None else _act_code(activation)
+    L, p2, st = lib(), int(bool(pow2)), _stream(stream)
+    if gate is not None:
+        code = L.sputnik_quantize_rows_gated(
+            _ptr(x), _ptr(gate), rows, cols, act, _ptr(q), _ptr(scales), p2,
+            dtype, st)
+    elif act is not None:
+        code = L.sputnik_quantize_rows_act(
+            _ptr(x), rows, cols, act, _ptr(q), _ptr(scales), p2, dtype, st)
+    else:
+        code = L.sputnik_quantize_rows(_ptr(x), rows, cols, _ptr(q),
+                                       _ptr(scales), p2, dtype, st)
+    _check(code, "QuantizeRows")
+
+
+def QuantizeWeight(w, q, scales, transpose=False, pow2=False, stream=None):  # noqa: N802
+    """q (torch.float8_e4m3fn [n, k], k-contiguous) and scales (fp32 [k / 128,
+    n / 128], one per 128 x 128 block) of the weight w [k, n] (fp16 / bf16);
+    with `transpose` the tensor passed holds w^T, [n, k]
+    (sputnik_quantize_weight)."""
+    import torch
+
+    _moe_matrix(w, None, None, "w")
+    k, n = int(w.shape[0]), int(w.shape[1])
+    if transpose:
+        k, n = n, k
+    kb, nb = _fp8_tiles(k, "QuantizeWeight: k"), _fp8_tiles(n, "QuantizeWeight: n")
+    _fp8_buffer(q, torch.float8_e4m3fn, (n, k), "q")
+    _fp8_buffer(scales, torch.float32, (kb, nb), "scales")
+    _check(lib().sputnik_quantize_weight(
+        _ptr(w), k, n, int(bool(transpose)), _ptr(q), _ptr(scales),
+        int(bool(pow2)), _dtype_code(w), _stream(stream)), "QuantizeWeight")
+
+
+def _fp8_weight(bq, b_scales, what: str):
+    """(n, k) of a quantised weight: bq e4m3 [n, k], b_scales fp32 [k / 128,
+    n / 128]."""
+    import torch
+
+    if getattr(bq, "dtype", None) != torch.float8_e4m3fn or bq.dim() != 2:
+        raise TypeError(f"{what}: bq must be a 2-D torch.float8_e4m3fn tensor")
+    n, k = int(bq.shape[0]), int(bq.shape[1])
+    _fp8_buffer(bq, torch.float8_e4m3fn, (n, k), "bq")
+    _fp8_buffer(b_scales, torch.float32,
+                (_fp8_tiles(k, f"{what}: k"), _fp8_tiles(n, f"{what}: n")),
+                "b_scales")
+    return n, k
+
+
+def SddFp8(aq, a_scales, bq, b_scales, c, stream=None):  # noqa: N802
+    """C (BlockMatrix of fp16 / bf16 block values, with row_indices) = Aq .
+    Bq at C's stored blocks: aq e4m3 [c.rows, k] with a_scales fp32 [c.rows,
+    k / 128] (QuantizeRows), bq e4m3 [c.cols, k] with b_scales fp32 [k / 128,
+    c.cols / 128] (QuantizeWeight). acc = fma(sa * sb, P, acc) per k-block
+    in fp32, rounded once (sputnik_sdd_fp8)."""
+    import torch
+
+    if not isinstance(c, BlockMatrix):
+        raise TypeError("SddFp8 writes a BlockMatrix")
+    n, k = _fp8_weight(bq, b_scales, "SddFp8")
+    if n != c.cols:
+        raise ValueError(f"SddFp8: bq has {n} rows, C {c.cols} columns")
+    _fp8_buffer(aq, torch.float8_e4m3fn, (c.rows, k), "aq")
+    _fp8_buffer(a_scales, torch.float32, (c.rows, k // 128), "a_scales")
+    cc = c._c()
+    _check(lib().sputnik_sdd_fp8(
+        _ptr(aq), _ptr(a_scales), k, _ptr(bq), _ptr(b_scales),
+        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "SddFp8")
+
+
+def DsdFp8(s, s_scales, bq, b_scales, c, stream=None):  # noqa: N802
+    """C (Matrix of fp16 / bf16, [s.rows, n]) = Sq . Bq: s a BlockMatrix whose
+    data holds e4m3 block values with s_scales fp32 [blocks * 128], one per
+    row of each stored block in storage order (QuantizeRows over the block
+    values as [blocks * 128, 128]); bq / b_scales as SddFp8, k = s.cols. A
+    block row without blocks gives +0 rows (sputnik_dsd_fp8)."""
+    import torch
+
+    if not isinstance(s, BlockMatrix) or not isinstance(c, Matrix):
+        raise TypeError("DsdFp8 takes a BlockMatrix and writes a Matrix")
+    n, k = _fp8_weight(bq, b_scales, "DsdFp8")
+    if k != s.cols or n != c.cols or c.rows != s.rows:
+        raise ValueError(f"DsdFp8 shapes [{s.rows}, {s.cols}] x [{k}, {n}] "
+                         f"-> [{c.rows}, {c.cols}]")
+    if getattr(s.data, "dtype", None) != torch.float8_e4m3fn:
+        raise TypeError("DsdFp8: s.data must be torch.float8_e4m3fn")
+    _fp8_buffer(s_scales, torch.float32, (s.num_blocks * 128,), "s_scales")
+    cs, cc = s._c(), c._c()
+    _check(lib().sputnik_dsd_fp8(
+        ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales),
+        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "DsdFp8")
+
+
 __all__ = [
     "AllocateBitmaskBuffers", "AllocateRowIndicesBuffer",
     "AllocateTransposeBuffers", "AsInt", "Bitmask", "FreeBitmaskBuffers",
@@ -1727,6 +1879,7 @@ __all__ = [
     "SPUTNIK_ACT_SILU", "sdd_act_route",
     "MatmulGated", "MatmulGatedGrad", "BlockGate", "BlockGateGrad",
     "MatmulBias", "MatmulBiasActivation", "MatmulBiasGated", "BlockColumnSum",
+    "QuantizeRows", "QuantizeWeight", "SddFp8", "DsdFp8",
     "PaddedScatterBias", "PaddedScatterBiasWeightGrad",
     "PaddedScatterBiasGrad",
     "MoeBins", "MoeRowMap", "PaddedGather", "PaddedScatter",

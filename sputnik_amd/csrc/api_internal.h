@@ -111,6 +111,20 @@ hipError_t LaunchBlockEpilogue(int dtype, int mode, int act, const void *x,
                                const short *column_indices = nullptr,
                                int col_blocks = 0);
 
+// The fp8 block GEMM (sputnik/block/fp8.h, fp8_gemm.hip), arguments already
+// validated by SddFp8 / DsdFp8 (block_api.cpp). SDD (`dsd` false): a = Aq
+// [m, k] with a_scales [m, k / 128], one workgroup per stored block of C
+// (indices, row_indices; offsets unused). DSD: a = the sparse operand's e4m3
+// blocks with a_scales [nnz_blocks * 128], offsets / indices its BCSR
+// metadata, c dense [m, n]. b = Bq [n, k] with b_scales [k / 128, n / 128].
+// Sizes in blocks of 128.
+hipError_t LaunchFp8Gemm(bool dsd, int dtype, const void *a,
+                         const float *a_scales, const void *b,
+                         const float *b_scales, void *c, const int *offsets,
+                         const short *indices, const short *row_indices,
+                         int m_blocks, int n_blocks, int k_blocks,
+                         int nnz_blocks, hipStream_t stream);
+
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.
 hipError_t SetStreamWorkspace(hipStream_t stream, void *ptr, size_t bytes);

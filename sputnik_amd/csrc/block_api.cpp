@@ -1,5 +1,8 @@
 // sputnik-amd: the sputnik::block C++ overload set (drop-in for the
 // reference's), over the Run* entry points of dispatch.cpp.
+#include <cstdint>
+#include <initializer_list>
+
 #include "api_internal.h"
 #include "dispatch_internal.h"
 #include "metadata.h"
@@ -383,6 +386,70 @@ hipError_t Bitmask(BlockMatrix m, hipStream_t stream) {
       static_cast<const int *>(trans ? m.offsets_t : m.offsets),
       static_cast<const short *>(trans ? m.indices_t : m.indices),
       static_cast<unsigned long long *>(m.bitmask), stream);
+}
+
+// ---- fp8 products (sputnik/block/fp8.h): never abort ----
+
+namespace {
+
+bool Fp8SizesOk(const BlockMatrix &s, int other, int dtype) {
+  return s.block_size == BlockSize::k128 && s.rows >= 0 && s.cols >= 0 &&
+         s.nonzeros >= 0 && other >= 0 && s.rows % 128 == 0 &&
+         s.cols % 128 == 0 && other % 128 == 0 &&
+         s.nonzeros % (128 * 128) == 0 && (dtype == 0 || dtype == 1);
+}
+
+// (the DMA, the fragment reads and the output stores move 16 bytes)
+bool Aligned16(std::initializer_list<const void *> ps) {
+  uintptr_t bits = 0;
+  for (const void *p : ps) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & 15) == 0;
+}
+
+}  // namespace
+
+hipError_t SddFp8(const void *aq, const float *a_scales, int k,
+                  const void *bq, const float *b_scales, BlockMatrix c,
+                  DataType dtype, hipStream_t stream) {
+  if (!Fp8SizesOk(c, k, (int)dtype)) return hipErrorInvalidValue;
+  if (c.nonzeros == 0) return hipSuccess;
+  if (c.data == nullptr || c.indices == nullptr || c.row_indices == nullptr ||
+      (k > 0 && (aq == nullptr || a_scales == nullptr || bq == nullptr ||
+                 b_scales == nullptr)))
+    return hipErrorInvalidValue;
+  for (const void *in : {aq, (const void *)a_scales, bq,
+                         (const void *)b_scales, (const void *)c.indices,
+                         (const void *)c.row_indices})
+    if (c.data == in) return hipErrorInvalidValue;
+  if (!Aligned16({aq, bq, c.data})) return hipErrorInvalidValue;
+  return sputnik_amd::LaunchFp8Gemm(
+      false, (int)dtype, aq, a_scales, bq, b_scales, c.data, nullptr,
+      static_cast<const short *>(c.indices),
+      static_cast<const short *>(c.row_indices), c.rows / 128, c.cols / 128,
+      k / 128, c.nonzeros / (128 * 128), stream);
+}
+
+hipError_t DsdFp8(const BlockMatrix s, const float *s_scales, const void *bq,
+                  const float *b_scales, Matrix c, DataType dtype,
+                  hipStream_t stream) {
+  if (!Fp8SizesOk(s, c.cols, (int)dtype) || c.rows != s.rows)
+    return hipErrorInvalidValue;
+  if (c.rows == 0 || c.cols == 0) return hipSuccess;
+  if (c.data == nullptr || s.offsets == nullptr ||
+      (s.nonzeros > 0 && (s.data == nullptr || s.indices == nullptr ||
+                          s_scales == nullptr || bq == nullptr ||
+                          b_scales == nullptr)))
+    return hipErrorInvalidValue;
+  for (const void *in : {(const void *)s.data, (const void *)s_scales, bq,
+                         (const void *)b_scales, (const void *)s.offsets,
+                         (const void *)s.indices})
+    if (c.data == in) return hipErrorInvalidValue;
+  if (!Aligned16({s.data, bq, c.data})) return hipErrorInvalidValue;
+  return sputnik_amd::LaunchFp8Gemm(
+      true, (int)dtype, s.data, s_scales, bq, b_scales, c.data,
+      static_cast<const int *>(s.offsets),
+      static_cast<const short *>(s.indices), nullptr, s.rows / 128,
+      c.cols / 128, s.cols / 128, s.nonzeros / (128 * 128), stream);
 }
 
 hipError_t Transpose(BlockMatrix a, hipStream_t stream) {

@@ -641,6 +641,60 @@ int sputnik_padded_scatter_bias_grad(const void *dout, const int32_t *indices,
       static_cast<hipStream_t>(stream));
 }
 
+// FP8 products (sputnik/block/fp8.h): fp8_quantize.hip and block_api.cpp
+// validate.
+int sputnik_quantize_rows(const void *x, int rows, int cols, void *q,
+                          float *scales, int pow2, int dtype, void *stream) {
+  return sputnik::block::QuantizeRows(x, rows, cols, q, scales, pow2 != 0,
+                                      static_cast<DataType>(dtype),
+                                      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_quantize_rows_act(const void *x, int rows, int cols, int act,
+                              void *q, float *scales, int pow2, int dtype,
+                              void *stream) {
+  return sputnik::block::QuantizeRowsActivation(
+      x, rows, cols, static_cast<sputnik::block::Activation>(act), q, scales,
+      pow2 != 0, static_cast<DataType>(dtype),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_quantize_rows_gated(const void *x, const void *gate, int rows,
+                                int cols, int act, void *q, float *scales,
+                                int pow2, int dtype, void *stream) {
+  return sputnik::block::QuantizeRowsGated(
+      x, gate, rows, cols, static_cast<sputnik::block::Activation>(act), q,
+      scales, pow2 != 0, static_cast<DataType>(dtype),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_quantize_weight(const void *w, int k, int n, int transpose,
+                            void *q, float *scales, int pow2, int dtype,
+                            void *stream) {
+  return sputnik::block::QuantizeWeight(w, k, n, transpose != 0, q, scales,
+                                        pow2 != 0,
+                                        static_cast<DataType>(dtype),
+                                        static_cast<hipStream_t>(stream));
+}
+
+int sputnik_sdd_fp8(const void *aq, const float *a_scales, int k,
+                    const void *bq, const float *b_scales,
+                    const sputnik_block_matrix_t *c, int dtype, void *stream) {
+  if (!c) return hipErrorInvalidValue;
+  return sputnik::block::SddFp8(aq, a_scales, k, bq, b_scales, ToCpp(c),
+                                static_cast<DataType>(dtype),
+                                static_cast<hipStream_t>(stream));
+}
+
+int sputnik_dsd_fp8(const sputnik_block_matrix_t *s, const float *s_scales,
+                    const void *bq, const float *b_scales,
+                    const sputnik_matrix_t *c, int dtype, void *stream) {
+  if (!s || !c) return hipErrorInvalidValue;
+  return sputnik::block::DsdFp8(ToCpp(s), s_scales, bq, b_scales, ToCpp(c),
+                                static_cast<DataType>(dtype),
+                                static_cast<hipStream_t>(stream));
+}
+
 // MoE router and device sort (sputnik/block/router.h): moe_router.hip
 // validates.
 int sputnik_router_topk(const void *logits, int32_t *top_experts,

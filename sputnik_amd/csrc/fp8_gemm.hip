@@ -1,0 +1,304 @@
+// sputnik-amd: the fp8 (e4m3) block GEMM of sputnik/block/fp8.h: one kernel
+// template, two tile sources (SDD and DSD). Both operands arrive
+// k-contiguous, so no transposed LDS read is needed.
+//
+// One 256-thread workgroup (2 x 2 waves, 64 x 64 each) per 128 x 128 output
+// tile. A step is one scale interval, a 128 x 128 e4m3 tile of each operand
+// (16 KiB) plus the 128 row scales of A:
+//
+//   staging  16-byte LDS-DMA (global_load_lds) into a ring of kStages stages.
+//            The DMA's LDS image is lane-linear, so the swizzle sits on the
+//            source address: the lane that lands on 16-byte slot p of row r
+//            fetches chunk p ^ key(r) of that row, key(r) = (r >> 1) & 7.
+//            8 lanes still read one whole 128-byte line. The row scales go
+//            the same way, 4 bytes per lane, so the loop has no
+//            register-destination load beside the DMA.
+//   reads    lane l of a wave (r = l % 16, g = l / 16) takes chunks g and
+//            g + 4 of row r of a 16-row fragment with two ds_read_b128. With
+//            128-byte rows two rows share a 256-byte bank row, and with that
+//            key every 16-lane group of ds_read_b128 covers its 16 slots
+//            once: conflict-free.
+//   MFMA     the e4m3 bytes are converted to fp16 in registers, exactly
+//            (v_cvt_scalef32_pk_f16_fp8 with scale 1: every e4m3 value is
+//            an fp16 value), and an interval is four
+//            v_mfma_f32_16x16x32_f16 chained from zero. The fp8 forms
+//            (v_mfma_scale_f32_16x16x128_f8f6f4, v_mfma_f32_16x16x32_fp8_fp8)
+//            pass the exact lane-map test but do not sum in fp32: addends
+//            far below the largest product of their group are dropped, an
+//            error of up to 2^-12.4 of sum |terms| on e4m3 data (DESIGN has
+//            the measurement), past the contract's 2^-23 per operation. A
+//            and B take the same (g, byte) -> k assignment, so the sum runs
+//            over matching k whatever that assignment is; rows and columns
+//            are l % 16 and the C/D map is the usual 16 x 16 one.
+//   scaling  acc = fma(sa[row] * sb, P, acc) in fp32 with P the interval's
+//            MFMA sum from zero.
+//   output   round_T(acc) once, through LDS, as 16-byte row pieces.
+//
+// The step order is the k order (SDD) or the row's storage order (DSD), no
+// split-K and no atomics: the same inputs give the same bits. Every index
+// read from device memory is checked before it is used as an address.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdint>
+#include <type_traits>
+
+#include "api_internal.h"
+
+namespace sputnik_amd {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kB = 128;                  // block edge = scale interval
+constexpr int kTileBytes = kB * kB;      // one e4m3 operand tile
+constexpr int kScaleBytes = kB * 4;      // the row scales of an A tile
+constexpr int kStageBytes = 2 * kTileBytes + kScaleBytes;
+// Two stages (65 KiB) leave room for two workgroups per CU (the registers
+// allow two waves per SIMD), which hide each other's barriers; the output
+// tile reuses the ring.
+constexpr int kStages = 2;
+constexpr int kLdsBytes = kStages * kStageBytes;
+static_assert(kB * kB * 2 <= kLdsBytes, "the output tile reuses the ring");
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+#define SPUTNIK_FP8_LDS(p) ((__attribute__((address_space(3))) void *)(p))
+#define SPUTNIK_FP8_GLOBAL(p) \
+  ((const __attribute__((address_space(1))) void *)(p))
+
+// Wave-uniform loads through the scalar cache: metadata and weight scales
+// are read-only for the whole launch.
+__device__ __forceinline__ int scalar_int(const int *p) {
+  return *(const __attribute__((address_space(4))) int *)p;
+}
+__device__ __forceinline__ float scalar_float(const float *p) {
+  return *(const __attribute__((address_space(4))) float *)p;
+}
+// (an int16 entry from its aligned dword: any 2-byte-aligned base works)
+__device__ __forceinline__ int scalar_short(const short *p) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  const int v = *reinterpret_cast<const __attribute__((address_space(4))) int *>(
+      a & ~uintptr_t(3));
+  return (short)((a & 2) ? (v >> 16) : v);
+}
+
+__device__ __forceinline__ int swizzle_key(int row) { return (row >> 1) & 7; }
+
+// 8 e4m3 bytes as 8 fp16 values, exactly (NaN bytes stay NaN).
+__device__ __forceinline__ f16x8 e4m3_to_f16x8(int lo, int hi) {
+  const f16x2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false);
+  const f16x2 b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true);
+  const f16x2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false);
+  const f16x2 d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true);
+  return f16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+struct Fp8GemmParams {
+  const char *a;          // SDD: Aq [m, k]; DSD: the stored blocks of Sq
+  const float *a_scales;  // SDD: [m, k / 128]; DSD: [nnz_blocks * 128]
+  const char *b;          // Bq [n, k]
+  const float *b_scales;  // [k / 128, n / 128]
+  void *c;                // SDD: block values of C; DSD: C [m, n]
+  const int *offsets;     // DSD: the sparse operand's row offsets
+  const short *indices;   // SDD: C's column indices; DSD: Sq's
+  const short *row_indices;  // SDD: C's
+  int m_blocks, n_blocks, k_blocks, nnz_blocks;
+};
+
+template <typename T, bool kDsd>
+__global__ void __launch_bounds__(kThreads)
+    fp8_gemm_kernel(const Fp8GemmParams p) {
+  __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long k_bytes = (long long)p.k_blocks * kB;
+
+  // The output tile and its steps.
+  int rb, nb, first = 0, steps;
+  if constexpr (kDsd) {
+    rb = blockIdx.x / p.n_blocks;
+    nb = blockIdx.x % p.n_blocks;
+    int begin = scalar_int(p.offsets + rb), end = scalar_int(p.offsets + rb + 1);
+    begin = begin < 0 ? 0 : begin;
+    end = end > p.nnz_blocks ? p.nnz_blocks : end;
+    first = begin;
+    steps = end > begin ? end - begin : 0;
+  } else {
+    rb = scalar_short(p.row_indices + blockIdx.x);
+    nb = scalar_short(p.indices + blockIdx.x);
+    if (rb < 0 || rb >= p.m_blocks || nb < 0 || nb >= p.n_blocks) return;
+    steps = p.k_blocks;
+  }
+  // The k-block of step i, or -1 for a stored block to skip.
+  auto k_block = [&](int i) {
+    if constexpr (!kDsd) return i;
+    const int kb = scalar_short(p.indices + first + i);
+    return kb >= 0 && kb < p.k_blocks ? kb : -1;
+  };
+
+  // One step's DMA into `stage`.
+  auto issue = [&](int i, char *stage) {
+    const int kb = k_block(i);
+    if (kb < 0) return;
+    const char *a_tile;
+    long long a_pitch;
+    const float *a_scale;
+    long long a_scale_stride;
+    if constexpr (kDsd) {
+      a_tile = p.a + (long long)(first + i) * kTileBytes;
+      a_pitch = kB;
+      a_scale = p.a_scales + (long long)(first + i) * kB;
+      a_scale_stride = 1;
+    } else {
+      a_tile = p.a + (long long)rb * kB * k_bytes + (long long)kb * kB;
+      a_pitch = k_bytes;
+      a_scale = p.a_scales + (long long)rb * kB * p.k_blocks + kb;
+      a_scale_stride = p.k_blocks;
+    }
+    const char *b_tile = p.b + (long long)nb * kB * k_bytes + (long long)kb * kB;
+#pragma unroll
+    for (int pass = 0; pass < kTileBytes / (kThreads * 16); ++pass) {
+      // (a wave's 64 x 16 bytes are 8 rows of the image)
+      const int piece = pass * (kThreads * 16) + wave * 1024;
+      const int row = (piece >> 7) + (lane >> 3);
+      const int chunk = (lane & 7) ^ swizzle_key(row);
+      __builtin_amdgcn_global_load_lds(
+          SPUTNIK_FP8_GLOBAL(a_tile + row * a_pitch + chunk * 16),
+          SPUTNIK_FP8_LDS(stage + piece), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(
+          SPUTNIK_FP8_GLOBAL(b_tile + row * k_bytes + chunk * 16),
+          SPUTNIK_FP8_LDS(stage + kTileBytes + piece), 16, 0, 0);
+    }
+    if (wave < kB / 64) {
+      const int row = wave * 64 + lane;
+      __builtin_amdgcn_global_load_lds(
+          SPUTNIK_FP8_GLOBAL(a_scale + row * a_scale_stride),
+          SPUTNIK_FP8_LDS(stage + 2 * kTileBytes + wave * 256), 4, 0, 0);
+    }
+  };
+
+  const int wm = wave >> 1, wn = wave & 1;
+  const int r = lane & 15, g = lane >> 4;
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  // A 16-row fragment of an operand image: chunks g and g + 4 of row r, as
+  // the operands of the interval's four MFMAs (8 bytes each).
+  struct Fragment { f16x8 k[4]; };
+  auto fragment = [&](const char *image, int row0) {
+    const int row = row0 + r;
+    const char *at = image + row * kB;
+    const int key = swizzle_key(row);
+    const i32x4 lo = *reinterpret_cast<const i32x4 *>(at + ((g ^ key) << 4));
+    const i32x4 hi =
+        *reinterpret_cast<const i32x4 *>(at + (((g + 4) ^ key) << 4));
+    return Fragment{{e4m3_to_f16x8(lo[0], lo[1]), e4m3_to_f16x8(lo[2], lo[3]),
+                     e4m3_to_f16x8(hi[0], hi[1]), e4m3_to_f16x8(hi[2], hi[3])}};
+  };
+
+  auto compute = [&](int i, const char *stage) {
+    const int kb = k_block(i);
+    if (kb < 0) return;
+    const float sb = scalar_float(p.b_scales + (long long)kb * p.n_blocks + nb);
+    const float *sa_lds =
+        reinterpret_cast<const float *>(stage + 2 * kTileBytes);
+    Fragment a[4];
+    f32x4 s[4];
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti) {
+      a[ti] = fragment(stage, wm * 64 + ti * 16);
+      // (the lane's four accumulator rows of this fragment)
+      s[ti] = *reinterpret_cast<const f32x4 *>(sa_lds + wm * 64 + ti * 16 +
+                                               4 * g) * sb;
+    }
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) {
+      const Fragment b = fragment(stage + kTileBytes, wn * 64 + tj * 16);
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti) {
+        f32x4 sum{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          sum = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ti].k[q], b.k[q],
+                                                       sum, 0, 0, 0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          acc[ti][tj][e] = __builtin_fmaf(s[ti][e], sum[e], acc[ti][tj][e]);
+      }
+    }
+  };
+
+  // Stage i lands while stage i - 1 is consumed: the barrier that follows
+  // the wait also says every wave is done with the stage about to be
+  // refilled.
+  if (steps > 0) issue(0, lds);
+  for (int i = 0; i < steps; ++i) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (i + 1 < steps) issue(i + 1, lds + ((i + 1) % kStages) * kStageBytes);
+    compute(i, lds + (i % kStages) * kStageBytes);
+  }
+
+  // round_T(acc) into a [128][128] image of T, then 16-byte row pieces.
+  __syncthreads();
+  T *image = reinterpret_cast<T *>(lds);
+#pragma unroll
+  for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        image[(wm * 64 + ti * 16 + 4 * g + e) * kB + wn * 64 + tj * 16 + r] =
+            (T)acc[ti][tj][e];
+  __syncthreads();
+  char *out;
+  long long out_pitch;  // bytes
+  if constexpr (kDsd) {
+    out_pitch = (long long)p.n_blocks * kB * 2;
+    out = static_cast<char *>(p.c) + (long long)rb * kB * out_pitch +
+          (long long)nb * kB * 2;
+  } else {
+    out_pitch = kB * 2;
+    out = static_cast<char *>(p.c) + (long long)blockIdx.x * kB * kB * 2;
+  }
+  for (int id = threadIdx.x; id < kB * kB * 2 / 16; id += kThreads) {
+    const int row = id >> 4, piece = (id & 15) * 16;
+    *reinterpret_cast<i32x4 *>(out + row * out_pitch + piece) =
+        *reinterpret_cast<const i32x4 *>(lds + row * kB * 2 + piece);
+  }
+}
+
+}  // namespace
+
+hipError_t LaunchFp8Gemm(bool dsd, int dtype, const void *a,
+                         const float *a_scales, const void *b,
+                         const float *b_scales, void *c, const int *offsets,
+                         const short *indices, const short *row_indices,
+                         int m_blocks, int n_blocks, int k_blocks,
+                         int nnz_blocks, hipStream_t stream) {
+  const long long tiles =
+      dsd ? (long long)m_blocks * n_blocks : (long long)nnz_blocks;
+  if (tiles == 0) return hipSuccess;
+  if (tiles > INT_MAX) return hipErrorInvalidValue;
+  const Fp8GemmParams p{static_cast<const char *>(a), a_scales,
+                        static_cast<const char *>(b), b_scales, c, offsets,
+                        indices, row_indices, m_blocks, n_blocks, k_blocks,
+                        nnz_blocks};
+  auto launch = [&](auto t, auto d) {
+    hipLaunchKernelGGL((fp8_gemm_kernel<decltype(t), decltype(d)::value>),
+                       dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
+    return hipGetLastError();
+  };
+  if (dsd)
+    return dtype == 1 ? launch(__bf16{}, std::true_type{})
+                      : launch(_Float16{}, std::true_type{});
+  return dtype == 1 ? launch(__bf16{}, std::false_type{})
+                    : launch(_Float16{}, std::false_type{});
+}
+
+}  // namespace sputnik_amd

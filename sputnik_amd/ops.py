@@ -45,6 +45,11 @@ product's epilogue, `column_sum(sparse)` is its gradient, `mlp_bias(..., b1=)`
 `moe_mlp_bias` / `moe_layer_bias` / `moe_layer_aux_bias` /
 `moe_score_layer_bias(..., b1=, bv1=, b2=)` carry them through the expert
 MLP and the scatter.
+The fp8 forward path (sputnik/block/fp8.h; e4m3 elements with fp32 block
+scales, forward only) is `quantize_rows`, `quantize_sparse` and
+`quantize_weight` -> `Fp8Weight`, the products `sdd_fp8` / `dsd_fp8`, and
+`moe_mlp_fp8`, moe_mlp with its expert products in fp8 while gather, scatter
+and router stay 16-bit.
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -73,6 +78,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                BlockColumnSum, MatmulBias, MatmulBiasActivation,
                MatmulBiasGated, PaddedScatterBias, PaddedScatterBiasGrad,
                PaddedScatterBiasWeightGrad,
+               QuantizeRows, QuantizeWeight, SddFp8, DsdFp8,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
                RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
                MOE_SORT_CHUNK, ROUTER_AUX_TOKENS, ROUTER_MAX_EXPERTS,
@@ -1257,9 +1263,12 @@ def _check_moe_biases(x, w1, v1, num_experts: int, biases, what: str):
         _check_bias(b2, x, (num_experts, int(x.shape[-1])), f"{what}: b2")
 
 
-def _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
-             activation, v1, rows, b1=None, bv1=None, b2=None):
-    """moe_mlp's checks and chain; returns the output and the route."""
+def _moe_args(x, top_experts, expert_weights, w1, w2, v1, num_experts, rows,
+              fp8: bool = False):
+    """The checks moe_mlp and moe_mlp_fp8 share, up to the route: returns
+    (the MoeRoute passed in or None, the expert weights' hidden columns).
+    The weights are tensors of x's dtype or, with `fp8`, Fp8Weights (their
+    shape is the [k, n] of the weight they hold)."""
     route = top_experts if isinstance(top_experts, MoeRoute) else None
     if route is None:
         tokens, top_k = _top_experts(top_experts, num_experts)
@@ -1273,13 +1282,18 @@ def _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
                              f"{route.rows}")
     _check_rows(x, tokens, "moe_mlp: x")
     ws = (w1, w2) if v1 is None else (w1, v1, w2)
-    _check_dtypes(x, *ws)
+    if fp8:
+        if not all(isinstance(w, Fp8Weight) for w in ws):
+            raise TypeError("moe_mlp_fp8: the expert weights are Fp8Weights "
+                            "(quantize_weight, Fp8Weight.from_tensors)")
+    else:
+        _check_dtypes(x, *ws)
     d_model = int(x.shape[1])
     if any(w.dim() != 2 for w in ws):
         raise ValueError("moe_mlp: the expert weights are 2-D")
     hidden = int(w1.shape[1])
     if (int(w1.shape[0]) != d_model or tuple(w2.shape) != (hidden, d_model)
-            or (v1 is not None and v1.shape != w1.shape)):
+            or (v1 is not None and tuple(v1.shape) != tuple(w1.shape))):
         raise ValueError("moe_mlp: w1 / v1 [d_model, E * ffn], w2 [E * ffn, "
                          "d_model]")
     if hidden == 0 or hidden % (num_experts * BLOCK):
@@ -1291,6 +1305,14 @@ def _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
                         "torch.float32")
     if int(expert_weights.numel()) != tokens * top_k:
         raise ValueError("moe_mlp: one expert weight per (token, k)")
+    return route, hidden
+
+
+def _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
+             activation, v1, rows, b1=None, bv1=None, b2=None):
+    """moe_mlp's checks and chain; returns the output and the route."""
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1, w2, v1,
+                              num_experts, rows)
     _check_moe_biases(x, w1, v1, num_experts, (b1, bv1, b2), "moe_mlp")
     act = None if activation is None else _act_code(activation)
     if route is None:
@@ -1342,6 +1364,239 @@ def moe_mlp_bias(x: torch.Tensor, top_experts: torch.Tensor,
     Differentiable in each. Without biases it is moe_mlp."""
     return _moe_mlp(x, top_experts, expert_weights, w1, w2, num_experts,
                     activation, v1, rows, b1, bv1, b2)[0]
+
+
+# ---- FP8 (e4m3) expert products, forward only --------------------------------
+
+@dataclass
+class Fp8Weight:
+    """A weight [k, n] quantised for the fp8 products (sputnik/block/fp8.h):
+    `q` torch.float8_e4m3fn [n, k] (k-contiguous) and `scales` fp32 [k / 128,
+    n / 128], one per 128 x 128 block, value = float(q) * scale. `shape` is
+    the (k, n) of the weight it stands for."""
+
+    q: torch.Tensor
+    scales: torch.Tensor
+    k: int
+    n: int
+
+    @property
+    def shape(self):
+        return (self.k, self.n)
+
+    def dim(self) -> int:
+        return 2
+
+    @classmethod
+    def from_tensors(cls, q: torch.Tensor, scales: torch.Tensor
+                     ) -> "Fp8Weight":
+        """Checkpoint data as it is: `q` [n, k] (out features x in features)
+        of torch.float8_e4m3fn, or of torch.uint8 holding those bytes, and
+        `scales` fp32 [k / 128, n / 128]. Nothing is copied unless a tensor
+        is not contiguous."""
+        if not isinstance(q, torch.Tensor) or q.dim() != 2:
+            raise ValueError("Fp8Weight: q is a 2-D tensor [n, k]")
+        if q.dtype == torch.uint8:
+            q = q.view(torch.float8_e4m3fn)
+        if q.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"Fp8Weight: q is {q.dtype}, expected "
+                            "torch.float8_e4m3fn (or its bytes as uint8)")
+        n, k = int(q.shape[0]), int(q.shape[1])
+        if n % BLOCK or k % BLOCK:
+            raise ValueError(f"Fp8Weight: [n, k] = [{n}, {k}] is not a "
+                             "multiple of 128")
+        if (not isinstance(scales, torch.Tensor)
+                or scales.dtype != torch.float32):
+            raise TypeError("Fp8Weight: scales must be a torch.float32 tensor")
+        if tuple(scales.shape) != (k // BLOCK, n // BLOCK):
+            raise ValueError(f"Fp8Weight: scales have shape "
+                             f"{tuple(scales.shape)}, expected "
+                             f"{(k // BLOCK, n // BLOCK)} ([k / 128, n / 128])")
+        return cls(q.contiguous(), scales.contiguous(), k, n)
+
+
+class Fp8SparseMatrix(SparseMatrix):
+    """A SparseMatrix whose block values are e4m3 bytes, with `scales` fp32
+    [nnz_blocks * 128]: one per row of each stored block, in storage order
+    (quantize_sparse). The operand of dsd_fp8."""
+
+    def __init__(self, topo: SparseMatrix, q: torch.Tensor,
+                 scales: torch.Tensor):
+        m = topo._meta
+        super().__init__((m.rows, m.cols), q, m.offsets, m.indices, _meta=m)
+        self.scales = scales
+
+
+def _no_grad(what: str, *ts):
+    if torch.is_grad_enabled() and any(
+            isinstance(t, torch.Tensor) and t.requires_grad for t in ts):
+        raise ValueError(f"{what} is forward only: an input requires grad "
+                         "and no gradient would reach it (use torch.no_grad() "
+                         "or detach())")
+
+
+def quantize_rows(x: torch.Tensor, pow2: bool = False
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(q, scales) of x [rows, cols] (fp16 / bf16, cols a multiple of 128):
+    q torch.float8_e4m3fn of x's shape, scales fp32 [rows, cols / 128], one
+    per 1 x 128 tile, x ~ float(q) * scale. scale = max(amax / 448, 2^-126)
+    or, with `pow2`, the smallest power of two that fits (dequantisation is
+    then exact); sputnik/block/fp8.h has the format. Forward only."""
+    _check_dtypes(x)
+    _no_grad("quantize_rows", x)
+    if x.dim() != 2 or int(x.shape[1]) % BLOCK:
+        raise ValueError("quantize_rows: x is [rows, a multiple of 128]")
+    x = x.contiguous()
+    q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    scales = torch.empty(x.shape[0], x.shape[1] // BLOCK,
+                         dtype=torch.float32, device=x.device)
+    QuantizeRows(x, q, scales, pow2)
+    return q, scales
+
+
+def quantize_sparse(sparse: SparseMatrix, activation=None,
+                    gate: Optional[SparseMatrix] = None,
+                    pow2: bool = False) -> Fp8SparseMatrix:
+    """The block values of `sparse` (fp16 / bf16) quantised row by row of
+    each stored block, as the matrix [nnz_blocks * 128, 128]. With
+    `activation` alone the values of act(sparse) are quantised, with `gate`
+    (same topology and dtype) those of sparse * act(gate), each evaluated as
+    sdd_act / sdd_gated evaluate it, so the result is the quantisation of the
+    hidden matrix the 16-bit MLP stores, which is never written here. Forward
+    only."""
+    if not isinstance(sparse, SparseMatrix) or sparse.is_transposed():
+        raise TypeError("quantize_sparse takes a SparseMatrix (not a .t() "
+                        "view)")
+    _check_dtypes(sparse.data)
+    _no_grad("quantize_sparse", sparse.data,
+             None if gate is None else gate.data)
+    g = None
+    if gate is not None:
+        if (not isinstance(gate, SparseMatrix)
+                or gate._meta is not sparse._meta or gate.is_transposed()
+                or gate.dtype != sparse.dtype):
+            raise ValueError("quantize_sparse: gate must share sparse's "
+                             "topology and dtype")
+        if activation is None:
+            raise ValueError("quantize_sparse: a gate needs its activation")
+        g = gate.data.contiguous().view(-1, BLOCK)
+    nb = sparse.nnz_blocks
+    x = sparse.data.contiguous().view(nb * BLOCK, BLOCK)
+    q = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
+                    device=x.device)
+    scales = torch.empty(nb * BLOCK, dtype=torch.float32, device=x.device)
+    QuantizeRows(x, q.view(nb * BLOCK, BLOCK), scales.view(nb * BLOCK, 1),
+                 pow2, None if activation is None else _act_code(activation),
+                 g)
+    return Fp8SparseMatrix(sparse, q, scales)
+
+
+def quantize_weight(w: torch.Tensor, transpose: bool = False,
+                    pow2: bool = False) -> Fp8Weight:
+    """The Fp8Weight of w [k, n] (fp16 / bf16, both multiples of 128); with
+    `transpose` the tensor passed is w^T, [n, k], as checkpoints store a
+    linear layer. One scale per 128 x 128 block. Runs once, at load time."""
+    _check_dtypes(w)
+    _no_grad("quantize_weight", w)
+    if w.dim() != 2 or int(w.shape[0]) % BLOCK or int(w.shape[1]) % BLOCK:
+        raise ValueError("quantize_weight: w is 2-D with multiples of 128")
+    w = w.contiguous()
+    k, n = (int(w.shape[1]), int(w.shape[0])) if transpose else (
+        int(w.shape[0]), int(w.shape[1]))
+    q = torch.empty(n, k, dtype=torch.float8_e4m3fn, device=w.device)
+    scales = torch.empty(k // BLOCK, n // BLOCK, dtype=torch.float32,
+                         device=w.device)
+    QuantizeWeight(w, q, scales, transpose, pow2)
+    return Fp8Weight(q, scales, k, n)
+
+
+def _out_dtype(out_dtype, what: str):
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{what}: out_dtype must be torch.float16 or "
+                        "torch.bfloat16")
+
+
+def sdd_fp8(xq: torch.Tensor, xs: torch.Tensor, w: Fp8Weight,
+            topo: SparseMatrix, out_dtype=torch.bfloat16) -> SparseMatrix:
+    """(xq . w) at topo's nonzero blocks, the product in fp8: xq / xs from
+    quantize_rows ([m, k] and [m, k / 128]), w an Fp8Weight of [k, n], topo
+    [m, n]. Per 128-wide k-block the e4m3 products are summed by the matrix
+    cores in fp32 and added as (xs * w.scales) * sum; the block values are
+    rounded once to `out_dtype`. Bitwise reproducible. Forward only."""
+    if not isinstance(w, Fp8Weight):
+        raise TypeError("sdd_fp8: w must be an Fp8Weight")
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError("sdd_fp8: topo must be a SparseMatrix (not a .t() "
+                        "view)")
+    _out_dtype(out_dtype, "sdd_fp8")
+    _no_grad("sdd_fp8", xs)
+    if (not isinstance(xq, torch.Tensor) or xq.dim() != 2
+            or (int(xq.shape[0]), w.n) != tuple(topo.shape)
+            or int(xq.shape[1]) != w.k):
+        raise ValueError(f"sdd_fp8 shapes {tuple(getattr(xq, 'shape', ()))} "
+                         f"x {w.shape} -> {topo.shape}")
+    data = torch.empty(topo.nnz_blocks, BLOCK, BLOCK, dtype=out_dtype,
+                       device=xq.device)
+    topo._meta.ensure_row_indices(data)
+    SddFp8(xq, xs, w.q, w.scales, topo._meta.descriptor(data))
+    return topo.with_data(data)
+
+
+def dsd_fp8(sq: Fp8SparseMatrix, w: Fp8Weight,
+            out_dtype=torch.bfloat16) -> torch.Tensor:
+    """sq . w as a dense [m, n] tensor of `out_dtype`, the product in fp8:
+    sq from quantize_sparse ([m, k]), w an Fp8Weight of [k, n]. Arithmetic as
+    sdd_fp8, over the stored blocks of each block row in storage order; a
+    block row without blocks gives +0 rows. Forward only."""
+    if not isinstance(sq, Fp8SparseMatrix):
+        raise TypeError("dsd_fp8: sq must come from quantize_sparse")
+    if not isinstance(w, Fp8Weight):
+        raise TypeError("dsd_fp8: w must be an Fp8Weight")
+    _out_dtype(out_dtype, "dsd_fp8")
+    if sq.shape[1] != w.k:
+        raise ValueError(f"dsd_fp8 shapes {sq.shape} x {w.shape}")
+    out = torch.empty(sq.shape[0], w.n, dtype=out_dtype, device=sq.device)
+    DsdFp8(sq._descriptor(), sq.scales, w.q, w.scales,
+           Matrix(out.shape[0], out.shape[1], out))
+    return out
+
+
+def moe_mlp_fp8(x: torch.Tensor, top_experts: torch.Tensor,
+                expert_weights: torch.Tensor, w1q: Fp8Weight, w2q: Fp8Weight,
+                num_experts: int, activation=None,
+                v1q: Optional[Fp8Weight] = None,
+                rows: Optional[int] = None) -> torch.Tensor:
+    """moe_mlp with the expert products in fp8 (e4m3 elements, fp32 scales
+    per 1 x 128 activation tile and per 128 x 128 weight block, the recipe of
+    DeepSeek-V3 checkpoints; sputnik/block/fp8.h): padded_gather ->
+    quantize_rows -> sdd_fp8 with `w1q` (and with `v1q` for a GLU) ->
+    quantize_sparse with the activation (or the gate) -> dsd_fp8 with `w2q`
+    -> padded_scatter. The two (three) expert products run in fp8 with fp32
+    accumulation; the gather, the activation, the scatter with
+    `expert_weights` and the router stay in x's 16-bit dtype, which is also
+    the products' output type. `w1q` / `v1q` stand for [d_model,
+    num_experts * ffn] and `w2q` for [num_experts * ffn, d_model]
+    (quantize_weight, Fp8Weight.from_tensors). Arguments, defaults and route
+    handling are moe_mlp's; there are no biases. Forward only: the output
+    carries no gradient, and a tensor that requires grad while grad mode is
+    on is a ValueError."""
+    _no_grad("moe_mlp_fp8", x, expert_weights)
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1q, w2q, v1q,
+                              num_experts, rows, fp8=True)
+    act = None if activation is None else _act_code(activation)
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    xq, xs = quantize_rows(xp)
+    g = sdd_fp8(xq, xs, w1q, topo, x.dtype)
+    if v1q is None:
+        hq = quantize_sparse(g, "gelu" if act is None else act)
+    else:
+        u = sdd_fp8(xq, xs, v1q, topo, x.dtype)
+        hq = quantize_sparse(u, "silu" if act is None else act, gate=g)
+    return padded_scatter(dsd_fp8(hq, w2q, x.dtype), route, expert_weights)
 
 
 # ---- MoE router -------------------------------------------------------------
@@ -1823,4 +2078,6 @@ __all__ = ["MoeAux", "MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_a
            "padded_scatter_bias", "moe_mlp_bias", "moe_layer_bias",
            "moe_layer_aux_bias", "moe_score_layer_bias",
            "padded_scatter", "sdd", "sdd_act", "sdd_gated",
+           "Fp8Weight", "Fp8SparseMatrix", "quantize_rows", "quantize_sparse",
+           "quantize_weight", "sdd_fp8", "dsd_fp8", "moe_mlp_fp8",
            "topology_from_mask"]
