@@ -66,7 +66,8 @@ def _within(got, ref, absum, k, dtype, what):
 
 
 @pytest.mark.parametrize("explicit_rows", [False, True], ids=["exact", "bound"])
-@pytest.mark.parametrize("ffn", [128, 256])
+# (ffn 384: 3 DSD steps per expert row, past the ring's two stages)
+@pytest.mark.parametrize("ffn", [128, 256, 384])
 @pytest.mark.parametrize("glu", [False, True], ids=["gelu-mlp", "silu-glu"])
 @pytest.mark.parametrize("dtype", M.DTYPES)
 def test_moe_mlp_fp8_equals_its_chain_and_every_stage_its_reference(
