@@ -36,16 +36,16 @@ struct Workspace {
 // plain call would, never split mode, never the transposed-B route).
 enum class OutMode { kStore = 0, kAccT = 1, kAccF32 = 2 };
 
-// Validate, optionally build transposed metadata, launch. A non-kOk *status
-// means nothing was launched.
+// Validate, build the transposed metadata a sparse input is read through
+// when its descriptor's create_metadata is set (the ...Ex forms clear it on
+// their copy), launch. A non-kOk *status means nothing was launched.
 hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
-                  const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *status, Workspace ws = Workspace{},
+                  const Matrix &c, int dtype, hipStream_t stream,
+                  Status *status, Workspace ws = Workspace{},
                   OutMode out = OutMode::kStore);
 hipError_t RunDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
-                  const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *status,
-                  OutMode out = OutMode::kStore);
+                  const Matrix &c, int dtype, hipStream_t stream,
+                  Status *status, OutMode out = OutMode::kStore);
 hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                   const BlockMatrix &c, int dtype, hipStream_t stream,
                   Status *status, Workspace ws = Workspace{});
@@ -143,15 +143,14 @@ unsigned long long InCallEvents();
 unsigned long long BtLaunches();
 
 hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
-                  const BlockMatrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *status);
+                  const BlockMatrix &c, int dtype, hipStream_t stream,
+                  Status *status);
 hipError_t RunSds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
-                  const BlockMatrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *status);
-
+                  const BlockMatrix &c, int dtype, hipStream_t stream,
+                  Status *status);
 hipError_t RunDss(const BlockMatrix &a, bool ta, const BlockMatrix &b,
-                  bool tb, const Matrix &c, int dtype, bool build_meta_a,
-                  bool build_meta_b, hipStream_t stream, Status *status);
+                  bool tb, const Matrix &c, int dtype, hipStream_t stream,
+                  Status *status);
 
 // hipError_t value the C-ABI returns for a status (never aborts).
 int StatusCode(Status st);

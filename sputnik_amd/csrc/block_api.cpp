@@ -46,7 +46,7 @@ hipError_t Matmul(const BlockMatrix a, bool transpose_a, const Matrix b,
   Status st;
   const hipError_t e =
       sputnik_amd::RunDsd(a, transpose_a, b, transpose_b, c, (int)dtype,
-                          a.create_metadata, stream, &st);
+                          stream, &st);
   return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dsd");
 }
 
@@ -74,7 +74,7 @@ hipError_t Matmul(const Matrix a, bool transpose_a, const BlockMatrix b,
   Status st;
   const hipError_t e =
       sputnik_amd::RunDds(a, transpose_a, b, transpose_b, c, (int)dtype,
-                          b.create_metadata, stream, &st);
+                          stream, &st);
   return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dds");
 }
 
@@ -109,8 +109,8 @@ hipError_t MatmulAccumulate(const BlockMatrix a, bool transpose_a,
                             hipStream_t stream) {
   Status st;
   const hipError_t e = sputnik_amd::RunDsd(
-      a, transpose_a, b, transpose_b, c, (int)dtype, a.create_metadata, stream,
-      &st, sputnik_amd::Workspace{}, AccMode(c_type));
+      a, transpose_a, b, transpose_b, c, (int)dtype, stream, &st,
+      sputnik_amd::Workspace{}, AccMode(c_type));
   return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dsd (accumulate)");
 }
 
@@ -130,8 +130,8 @@ hipError_t MatmulAccumulate(const Matrix a, bool transpose_a,
                             hipStream_t stream) {
   Status st;
   const hipError_t e = sputnik_amd::RunDds(
-      a, transpose_a, b, transpose_b, c, (int)dtype, b.create_metadata, stream,
-      &st, AccMode(c_type));
+      a, transpose_a, b, transpose_b, c, (int)dtype, stream, &st,
+      AccMode(c_type));
   return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dds (accumulate)");
 }
 
@@ -267,7 +267,7 @@ hipError_t Matmul(const BlockMatrix a, bool transpose_a, const Matrix b,
   Status st;
   const hipError_t e =
       sputnik_amd::RunSsd(a, transpose_a, b, transpose_b, c, (int)dtype,
-                          a.create_metadata, stream, &st);
+                          stream, &st);
   return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "ssd");
 }
 
@@ -295,7 +295,7 @@ hipError_t Matmul(const Matrix a, bool transpose_a, const BlockMatrix b,
   Status st;
   const hipError_t e =
       sputnik_amd::RunSds(a, transpose_a, b, transpose_b, c, (int)dtype,
-                          b.create_metadata, stream, &st);
+                          stream, &st);
   return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "sds");
 }
 
@@ -322,9 +322,8 @@ hipError_t Matmul(const BlockMatrix a, bool transpose_a, const BlockMatrix b,
                   bool transpose_b, Matrix c, DataType dtype,
                   hipStream_t stream) {
   Status st;
-  const hipError_t e = sputnik_amd::RunDss(
-      a, transpose_a, b, transpose_b, c, (int)dtype, a.create_metadata,
-      b.create_metadata, stream, &st);
+  const hipError_t e = sputnik_amd::RunDss(a, transpose_a, b, transpose_b, c,
+                                           (int)dtype, stream, &st);
   return st == Status::kOk ? e : sputnik_amd::OrAbort(st, "dss");
 }
 

@@ -56,68 +56,78 @@ int Code(hipError_t launch, int status_code) {
 
 extern "C" {
 
+// DSD / DDS, plain or accumulating (out). ex: the ...Ex forms use the
+// transposed metadata as it is (create_metadata cleared on the copy).
+static int DsdEntry(bool ex, const sputnik_block_matrix_t *a, int transpose_a,
+                    const sputnik_matrix_t *b, int transpose_b,
+                    const sputnik_matrix_t *c, int dtype, void *ws,
+                    size_t ws_bytes, void *stream,
+                    sputnik_amd::OutMode out = sputnik_amd::OutMode::kStore) {
+  if (!a || !b || !c) return hipErrorInvalidValue;
+  BlockMatrix ca = ToCpp(a);
+  if (ex) ca.create_metadata = false;
+  sputnik_amd::Status st;
+  const hipError_t e = sputnik_amd::RunDsd(
+      ca, transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
+      static_cast<hipStream_t>(stream), &st,
+      sputnik_amd::Workspace{ws, ws_bytes}, out);
+  return Code(e, sputnik_amd::StatusCode(st));
+}
+
+static int DdsEntry(bool ex, const sputnik_matrix_t *a, int transpose_a,
+                    const sputnik_block_matrix_t *b, int transpose_b,
+                    const sputnik_matrix_t *c, int dtype, void *stream,
+                    sputnik_amd::OutMode out = sputnik_amd::OutMode::kStore) {
+  if (!a || !b || !c) return hipErrorInvalidValue;
+  BlockMatrix cb = ToCpp(b);
+  if (ex) cb.create_metadata = false;
+  sputnik_amd::Status st;
+  const hipError_t e = sputnik_amd::RunDds(
+      ToCpp(a), transpose_a != 0, cb, transpose_b != 0, ToCpp(c), dtype,
+      static_cast<hipStream_t>(stream), &st, out);
+  return Code(e, sputnik_amd::StatusCode(st));
+}
+
 int sputnik_dsd_ws(const sputnik_block_matrix_t *a, int transpose_a,
                    const sputnik_matrix_t *b, int transpose_b,
                    const sputnik_matrix_t *c, int dtype, void *ws,
                    size_t ws_bytes, void *stream) {
-  if (!a || !b || !c) return hipErrorInvalidValue;
-  const BlockMatrix ca = ToCpp(a);
-  sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunDsd(
-      ca, transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      ca.create_metadata, static_cast<hipStream_t>(stream), &st,
-      sputnik_amd::Workspace{ws, ws_bytes});
-  return Code(e, sputnik_amd::StatusCode(st));
+  return DsdEntry(false, a, transpose_a, b, transpose_b, c, dtype, ws,
+                  ws_bytes, stream);
 }
 
 int sputnik_dsd(const sputnik_block_matrix_t *a, int transpose_a,
                 const sputnik_matrix_t *b, int transpose_b,
                 const sputnik_matrix_t *c, int dtype, void *stream) {
-  return sputnik_dsd_ws(a, transpose_a, b, transpose_b, c, dtype, nullptr, 0,
-                        stream);
+  return DsdEntry(false, a, transpose_a, b, transpose_b, c, dtype, nullptr, 0,
+                  stream);
 }
 
 int sputnik_dsd_ex_ws(const sputnik_block_matrix_t *a, int transpose_a,
                       const sputnik_matrix_t *b, int transpose_b,
                       const sputnik_matrix_t *c, int dtype, void *ws,
                       size_t ws_bytes, void *stream) {
-  if (!a || !b || !c) return hipErrorInvalidValue;
-  sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunDsd(
-      ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      false, static_cast<hipStream_t>(stream), &st,
-      sputnik_amd::Workspace{ws, ws_bytes});
-  return Code(e, sputnik_amd::StatusCode(st));
+  return DsdEntry(true, a, transpose_a, b, transpose_b, c, dtype, ws, ws_bytes,
+                  stream);
 }
 
 int sputnik_dsd_ex(const sputnik_block_matrix_t *a, int transpose_a,
                    const sputnik_matrix_t *b, int transpose_b,
                    const sputnik_matrix_t *c, int dtype, void *stream) {
-  return sputnik_dsd_ex_ws(a, transpose_a, b, transpose_b, c, dtype, nullptr,
-                           0, stream);
+  return DsdEntry(true, a, transpose_a, b, transpose_b, c, dtype, nullptr, 0,
+                  stream);
 }
 
 int sputnik_dds(const sputnik_matrix_t *a, int transpose_a,
                 const sputnik_block_matrix_t *b, int transpose_b,
                 const sputnik_matrix_t *c, int dtype, void *stream) {
-  if (!a || !b || !c) return hipErrorInvalidValue;
-  const BlockMatrix cb = ToCpp(b);
-  sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunDds(
-      ToCpp(a), transpose_a != 0, cb, transpose_b != 0, ToCpp(c), dtype,
-      cb.create_metadata, static_cast<hipStream_t>(stream), &st);
-  return Code(e, sputnik_amd::StatusCode(st));
+  return DdsEntry(false, a, transpose_a, b, transpose_b, c, dtype, stream);
 }
 
 int sputnik_dds_ex(const sputnik_matrix_t *a, int transpose_a,
                    const sputnik_block_matrix_t *b, int transpose_b,
                    const sputnik_matrix_t *c, int dtype, void *stream) {
-  if (!a || !b || !c) return hipErrorInvalidValue;
-  sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunDds(
-      ToCpp(a), transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      false, static_cast<hipStream_t>(stream), &st);
-  return Code(e, sputnik_amd::StatusCode(st));
+  return DdsEntry(true, a, transpose_a, b, transpose_b, c, dtype, stream);
 }
 
 // Accumulating DSD / DDS. c_type: SPUTNIK_OUT_OPERAND / SPUTNIK_OUT_F32.
@@ -138,14 +148,9 @@ static int DsdAcc(bool ex, const sputnik_block_matrix_t *a, int transpose_a,
                   const sputnik_matrix_t *c, int dtype, int c_type,
                   void *stream) {
   sputnik_amd::OutMode out;
-  if (!a || !b || !c || !AccOutMode(c_type, &out)) return hipErrorInvalidValue;
-  const BlockMatrix ca = ToCpp(a);
-  sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunDsd(
-      ca, transpose_a != 0, ToCpp(b), transpose_b != 0, ToCpp(c), dtype,
-      !ex && ca.create_metadata, static_cast<hipStream_t>(stream), &st,
-      sputnik_amd::Workspace{}, out);
-  return Code(e, sputnik_amd::StatusCode(st));
+  if (!AccOutMode(c_type, &out)) return hipErrorInvalidValue;
+  return DsdEntry(ex, a, transpose_a, b, transpose_b, c, dtype, nullptr, 0,
+                  stream, out);
 }
 
 static int DdsAcc(bool ex, const sputnik_matrix_t *a, int transpose_a,
@@ -153,13 +158,8 @@ static int DdsAcc(bool ex, const sputnik_matrix_t *a, int transpose_a,
                   const sputnik_matrix_t *c, int dtype, int c_type,
                   void *stream) {
   sputnik_amd::OutMode out;
-  if (!a || !b || !c || !AccOutMode(c_type, &out)) return hipErrorInvalidValue;
-  const BlockMatrix cb = ToCpp(b);
-  sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunDds(
-      ToCpp(a), transpose_a != 0, cb, transpose_b != 0, ToCpp(c), dtype,
-      !ex && cb.create_metadata, static_cast<hipStream_t>(stream), &st, out);
-  return Code(e, sputnik_amd::StatusCode(st));
+  if (!AccOutMode(c_type, &out)) return hipErrorInvalidValue;
+  return DdsEntry(ex, a, transpose_a, b, transpose_b, c, dtype, stream, out);
 }
 
 int sputnik_dsd_acc(const sputnik_block_matrix_t *a, int transpose_a,
@@ -427,14 +427,13 @@ static int SparseInOut(bool ssd, bool ex, const void *a, int ta,
     if (ex) ca.create_metadata = false;
     e = sputnik_amd::RunSsd(ca, ta != 0,
                             ToCpp(static_cast<const sputnik_matrix_t *>(b)),
-                            tb != 0, ToCpp(c), dtype, ca.create_metadata,
+                            tb != 0, ToCpp(c), dtype,
                             static_cast<hipStream_t>(stream), &st);
   } else {
     BlockMatrix cb = ToCpp(static_cast<const sputnik_block_matrix_t *>(b));
     if (ex) cb.create_metadata = false;
     e = sputnik_amd::RunSds(ToCpp(static_cast<const sputnik_matrix_t *>(a)),
                             ta != 0, cb, tb != 0, ToCpp(c), dtype,
-                            cb.create_metadata,
                             static_cast<hipStream_t>(stream), &st);
   }
   return Code(e, sputnik_amd::StatusCode(st));
@@ -475,9 +474,9 @@ static int DssEntry(bool ex, const sputnik_block_matrix_t *a, int ta,
   BlockMatrix ca = ToCpp(a), cb = ToCpp(b);
   if (ex) ca.create_metadata = cb.create_metadata = false;
   sputnik_amd::Status st;
-  const hipError_t e = sputnik_amd::RunDss(
-      ca, ta != 0, cb, tb != 0, ToCpp(c), dtype, ca.create_metadata,
-      cb.create_metadata, static_cast<hipStream_t>(stream), &st);
+  const hipError_t e =
+      sputnik_amd::RunDss(ca, ta != 0, cb, tb != 0, ToCpp(c), dtype,
+                          static_cast<hipStream_t>(stream), &st);
   return Code(e, sputnik_amd::StatusCode(st));
 }
 

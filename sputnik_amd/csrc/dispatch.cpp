@@ -18,9 +18,10 @@
 // A sparse S read in column order (DSD TN/TT, DDS NN/TN) uses the transposed
 // metadata (offsets_t, indices_t, block_offsets), exactly like the reference.
 //
-// One function per product (RouteDsd / RouteDds / RouteSdd) decides which
-// kernel runs with which GemmParams; the Run* entry points execute that
-// route and the queries (DsdPlan, DdsPlan, SddPlan, SddKernel, SddActRoute,
+// operands.cpp states that mapping once (Bind) and says which descriptors a
+// product accepts. One function per product (RouteDsd / RouteDds / RouteSdd)
+// decides which kernel runs the bound product with which GemmParams; the
+// Run* entry points execute that route and the queries (DsdPlan, DdsPlan, SddPlan, SddKernel, SddActRoute,
 // the *WorkspaceBytes) report it. The knobs live in knobs.cpp, every kept or
 // borrowed piece of device memory in workspaces.cpp, the sputnik::block
 // overload set in block_api.cpp.
@@ -132,258 +133,7 @@ static void PreparePairs(GemmParams *p, long long blocks, hipStream_t stream,
   if (split > 1) p->grid = split * p->num_tiles;
 }
 
-namespace {
-
 using sputnik::block::AsInt;
-using sputnik::block::BlockSize;
-using sputnik::block::MatmulShape;
-using sputnik::block::ValidMatmul;
-
-constexpr long long kMaxLaneOffset = 0x7fffffffLL;  // 31-bit buffer offsets
-
-bool DenseOk(const Matrix &m) {
-  return m.rows >= 0 && m.cols >= 0 &&
-         (m.data != nullptr || (long long)m.rows * m.cols == 0);
-}
-
-bool SparseOk(const BlockMatrix &s) {
-  const int b = AsInt(s.block_size);
-  if (b != 128) return false;
-  if (s.rows < 0 || s.cols < 0 || s.nonzeros < 0) return false;
-  if (s.rows % b != 0 || s.cols % b != 0 || s.nonzeros % (b * b) != 0)
-    return false;
-  if ((s.cols / b) > 32767 || (s.rows / b) > 32767) return false;  // int16
-  if (s.offsets == nullptr) return false;
-  if (s.nonzeros > 0 && (s.data == nullptr || s.indices == nullptr))
-    return false;
-  return true;
-}
-
-// The reference's BlockGemm::can_implement: m, n, k multiples of 8
-// (block_gemm.h:728-745; 8 x fp16 = one 16-byte access).
-bool Aligned8(const MatmulShape &s) {
-  return s.m % 8 == 0 && s.n % 8 == 0 && s.k % 8 == 0 && s.m >= 0 &&
-         s.n >= 0 && s.k >= 0;
-}
-
-// Rows of one DMA tile times the byte stride must fit a 31-bit lane offset.
-bool StrideOk(long long rows_in_tile, long long ld_elems) {
-  return rows_in_tile * ld_elems * 2 <= kMaxLaneOffset;
-}
-
-Status PrepareDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
-                  const Matrix &c, GemmParams *p, bool *needs_meta) {
-  if (a.block_size != BlockSize::k128) return Status::kNotSupported;
-  if (!SparseOk(a) || !DenseOk(b) || !DenseOk(c)) return Status::kNoKernel;
-  if (!ValidMatmul(a, ta, b, tb, c)) return Status::kNoKernel;
-  const MatmulShape s(a, ta, b, tb);
-  if (!Aligned8(s)) return Status::kNoKernel;
-  const bool d_kc = tb;  // B^T stored [N][K]: k-contiguous
-  if (!StrideOk(d_kc ? CfgSparse::kBN : 64, s.ldb)) return Status::kNoKernel;
-  *needs_meta = ta;
-  if (ta && (a.offsets_t == nullptr || a.indices_t == nullptr ||
-             a.block_offsets == nullptr))
-    return Status::kMissingMetadata;
-
-  *p = GemmParams{};
-  p->s_data = static_cast<const char *>(a.data);
-  p->s_offsets = static_cast<const int *>(ta ? a.offsets_t : a.offsets);
-  p->s_indices = static_cast<const short *>(ta ? a.indices_t : a.indices);
-  p->s_block_offsets =
-      ta ? static_cast<const int *>(a.block_offsets) : nullptr;
-  p->s_blocks = (int)(a.nonzeros / (kBlock * kBlock));
-  p->d_data = static_cast<const char *>(b.data);
-  p->d_ld = (long long)s.ldb * 2;
-  p->c_data = static_cast<char *>(c.data);
-  p->c_ld = (long long)s.ldc * 2;
-  p->num_rows = s.m / kBM;
-  p->num_jtiles = (s.n + CfgSparse::kBN - 1) / CfgSparse::kBN;
-  p->j_limit = s.n;
-  p->num_tiles = p->num_rows * p->num_jtiles;
-  return Status::kOk;
-}
-
-Status PrepareDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
-                  const Matrix &c, GemmParams *p, bool *needs_meta) {
-  if (b.block_size != BlockSize::k128) return Status::kNotSupported;
-  if (!SparseOk(b) || !DenseOk(a) || !DenseOk(c)) return Status::kNoKernel;
-  if (!ValidMatmul(a, ta, b, tb, c)) return Status::kNoKernel;
-  const MatmulShape s(a, ta, b, tb);
-  if (!Aligned8(s)) return Status::kNoKernel;
-  const bool d_kc = !ta;  // op(A)^T rows are A's rows when A is [M][K]
-  if (!StrideOk(d_kc ? CfgSparse::kBN : 64, s.lda)) return Status::kNoKernel;
-  // Row n of op(B)^T is column n of B when B is stored [K][N] (tb == false).
-  const bool col_order = !tb;
-  *needs_meta = col_order;
-  if (col_order && (b.offsets_t == nullptr || b.indices_t == nullptr ||
-                    b.block_offsets == nullptr))
-    return Status::kMissingMetadata;
-
-  *p = GemmParams{};
-  p->s_data = static_cast<const char *>(b.data);
-  p->s_offsets = static_cast<const int *>(col_order ? b.offsets_t : b.offsets);
-  p->s_indices =
-      static_cast<const short *>(col_order ? b.indices_t : b.indices);
-  p->s_block_offsets =
-      col_order ? static_cast<const int *>(b.block_offsets) : nullptr;
-  p->d_data = static_cast<const char *>(a.data);
-  p->d_ld = (long long)s.lda * 2;
-  p->c_data = static_cast<char *>(c.data);
-  p->c_ld = (long long)s.ldc * 2;
-  p->s_blocks = (int)(b.nonzeros / (kBlock * kBlock));
-  p->num_rows = s.n / kBM;
-  p->num_jtiles = (s.m + CfgSparse::kBN - 1) / CfgSparse::kBN;
-  p->j_limit = s.m;
-  p->num_tiles = p->num_rows * p->num_jtiles;
-  return Status::kOk;
-}
-
-Status PrepareSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
-                  const BlockMatrix &c, GemmParams *p) {
-  if (c.block_size != BlockSize::k128) return Status::kNotSupported;
-  if (!SparseOk(c) || !DenseOk(a) || !DenseOk(b)) return Status::kNoKernel;
-  if (!ValidMatmul(a, ta, b, tb, c)) return Status::kNoKernel;
-  const MatmulShape s(a, ta, b, tb);
-  if (!Aligned8(s)) return Status::kNoKernel;
-  if (!StrideOk(ta ? 64 : 128, s.lda) || !StrideOk(tb ? 128 : 64, s.ldb))
-    return Status::kNoKernel;
-  const int blocks = c.nonzeros / (kBlock * kBlock);
-  if (blocks > 0 && c.row_indices == nullptr)
-    return Status::kMissingRowIndices;
-
-  *p = GemmParams{};
-  p->s_data = static_cast<const char *>(a.data);
-  p->s_ld = (long long)s.lda * 2;
-  p->d_data = static_cast<const char *>(b.data);
-  p->d_ld = (long long)s.ldb * 2;
-  p->c_data = static_cast<char *>(c.data);
-  p->c_row_indices = static_cast<const short *>(c.row_indices);
-  p->c_indices = static_cast<const short *>(c.indices);
-  p->num_rows = s.m / kBM;
-  p->j_limit = s.n;
-  p->k_limit = s.k;
-  p->num_tiles = blocks;
-  return Status::kOk;
-}
-
-// SSD / SDS: a sparse operand as in DSD / DDS, a sparse output as in SDD
-// (reference ssd.cu:7-24 and sds.cu:7-24; their *_align8.cu variants need
-// the sparse input's transposed metadata exactly where DSD / DDS do, and
-// c.row_indices always).
-Status PrepareSparseOut(const BlockMatrix &c, GemmParams *p) {
-  if (c.block_size != BlockSize::k128) return Status::kNotSupported;
-  if (!SparseOk(c)) return Status::kNoKernel;
-  const int blocks = c.nonzeros / (kBlock * kBlock);
-  if (blocks > 0 && c.row_indices == nullptr)
-    return Status::kMissingRowIndices;
-  p->c_data = static_cast<char *>(c.data);
-  p->c_row_indices = static_cast<const short *>(c.row_indices);
-  p->c_indices = static_cast<const short *>(c.indices);
-  p->num_tiles = blocks;
-  return Status::kOk;
-}
-
-Status PrepareSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
-                  const BlockMatrix &c, GemmParams *p, bool *needs_meta) {
-  if (a.block_size != BlockSize::k128) return Status::kNotSupported;
-  if (!SparseOk(a) || !DenseOk(b)) return Status::kNoKernel;
-  if (!ValidMatmul(a, ta, b, tb, c)) return Status::kNoKernel;
-  const MatmulShape s(a, ta, b, tb);
-  if (!Aligned8(s)) return Status::kNoKernel;
-  if (!StrideOk(tb ? kBlock : 64, s.ldb)) return Status::kNoKernel;
-  *needs_meta = ta;
-  if (ta && (a.offsets_t == nullptr || a.indices_t == nullptr ||
-             a.block_offsets == nullptr))
-    return Status::kMissingMetadata;
-  *p = GemmParams{};
-  const Status st = PrepareSparseOut(c, p);
-  if (st != Status::kOk) return st;
-  p->s_data = static_cast<const char *>(a.data);
-  p->s_offsets = static_cast<const int *>(ta ? a.offsets_t : a.offsets);
-  p->s_indices = static_cast<const short *>(ta ? a.indices_t : a.indices);
-  p->s_block_offsets =
-      ta ? static_cast<const int *>(a.block_offsets) : nullptr;
-  p->d_data = static_cast<const char *>(b.data);
-  p->d_ld = (long long)s.ldb * 2;
-  p->num_rows = s.m / kBM;
-  p->j_limit = s.n;
-  return Status::kOk;
-}
-
-Status PrepareSds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
-                  const BlockMatrix &c, GemmParams *p, bool *needs_meta) {
-  if (b.block_size != BlockSize::k128) return Status::kNotSupported;
-  if (!SparseOk(b) || !DenseOk(a)) return Status::kNoKernel;
-  if (!ValidMatmul(a, ta, b, tb, c)) return Status::kNoKernel;
-  const MatmulShape s(a, ta, b, tb);
-  if (!Aligned8(s)) return Status::kNoKernel;
-  if (!StrideOk(!ta ? kBlock : 64, s.lda)) return Status::kNoKernel;
-  const bool col_order = !tb;
-  *needs_meta = col_order;
-  if (col_order && (b.offsets_t == nullptr || b.indices_t == nullptr ||
-                    b.block_offsets == nullptr))
-    return Status::kMissingMetadata;
-  *p = GemmParams{};
-  const Status st = PrepareSparseOut(c, p);
-  if (st != Status::kOk) return st;
-  p->s_data = static_cast<const char *>(b.data);
-  p->s_offsets = static_cast<const int *>(col_order ? b.offsets_t : b.offsets);
-  p->s_indices =
-      static_cast<const short *>(col_order ? b.indices_t : b.indices);
-  p->s_block_offsets =
-      col_order ? static_cast<const int *>(b.block_offsets) : nullptr;
-  p->d_data = static_cast<const char *>(a.data);
-  p->d_ld = (long long)s.lda * 2;
-  p->num_rows = s.n / kBM;
-  p->j_limit = s.m;
-  return Status::kOk;
-}
-
-// DSS: C = op(A_bcsr) op(B_bcsr), dense (reference dss.cu:9-24). op(A)'s
-// rows use A's transposed metadata when transpose_a; op(B)'s columns use B's
-// transposed metadata unless transpose_b (dss_*_align8.cu). K <= 32768
-// (dss_nn:67). The reference's bitmask workspaces are not needed: the
-// intersection is built per tile in LDS.
-constexpr int kDssMaxK = 32768;
-Status PrepareDss(const BlockMatrix &a, bool ta, const BlockMatrix &b, bool tb,
-                  const Matrix &c, GemmParams *p, bool *meta_a,
-                  bool *meta_b) {
-  if (a.block_size != BlockSize::k128 || b.block_size != BlockSize::k128)
-    return Status::kNotSupported;
-  if (!SparseOk(a) || !SparseOk(b) || !DenseOk(c)) return Status::kNoKernel;
-  if (!ValidMatmul(a, ta, b, tb, c)) return Status::kNoKernel;
-  const MatmulShape s(a, ta, b, tb);
-  if (!Aligned8(s) || s.k > kDssMaxK) return Status::kNoKernel;
-  *meta_a = ta;
-  *meta_b = !tb;
-  if (ta && (a.offsets_t == nullptr || a.indices_t == nullptr ||
-             a.block_offsets == nullptr))
-    return Status::kMissingMetadata;
-  if (!tb && (b.offsets_t == nullptr || b.indices_t == nullptr ||
-              b.block_offsets == nullptr))
-    return Status::kMissingMetadata;
-  *p = GemmParams{};
-  p->s_data = static_cast<const char *>(a.data);
-  p->s_offsets = static_cast<const int *>(ta ? a.offsets_t : a.offsets);
-  p->s_indices = static_cast<const short *>(ta ? a.indices_t : a.indices);
-  p->s_block_offsets =
-      ta ? static_cast<const int *>(a.block_offsets) : nullptr;
-  p->d_data = static_cast<const char *>(b.data);
-  p->d_ld = kBlock * 2;  // inside one stored 128x128 block
-  p->d_offsets = static_cast<const int *>(tb ? b.offsets : b.offsets_t);
-  p->d_indices = static_cast<const short *>(tb ? b.indices : b.indices_t);
-  p->d_block_offsets =
-      tb ? nullptr : static_cast<const int *>(b.block_offsets);
-  p->c_data = static_cast<char *>(c.data);
-  p->c_ld = (long long)s.ldc * 2;
-  p->num_rows = s.m / kBM;
-  p->num_jtiles = s.n / kBlock;
-  p->j_limit = s.n;
-  p->num_tiles = p->num_rows * p->num_jtiles;
-  return Status::kOk;
-}
-
-}  // namespace
 
 hipError_t BuildTransposed(const BlockMatrix &a, hipStream_t stream) {
   const int b = AsInt(a.block_size);
@@ -536,9 +286,9 @@ bool UseTall(GemmParams *p) {
 // zero-filled after, an equal share per workgroup. Needs whole 512-column
 // panels, at most 128 blocks and 64 zero chunks per workgroup, and rows that
 // fit the LDS copy of the offsets.
-static bool UseTallPipe(const GemmParams &p, long long blocks, long long row_max, bool ta,
-                        bool tb) {
-  if (Knob(kKnobTall4w) == 0 || !Dsd4wEnabled() || ta || tb) return false;
+static bool UseTallPipe(const GemmParams &p, long long blocks, long long row_max, bool s_kc,
+                        bool d_kc) {
+  if (Knob(kKnobTall4w) == 0 || !Dsd4wEnabled() || !s_kc || d_kc) return false;
   if (p.pair != 0 || p.pair_split > 1 || CfgSparse::kBN != 512) return false;
   if (p.j_limit % 512 != 0 || p.num_rows > 32767 || blocks <= 0) return false;
   int dev = 0;
@@ -591,31 +341,31 @@ static bool BtViewOpen(BtView view, hipStream_t stream) {
 // is left undecided here. code: what DsdPlan / DdsPlan report, 0 the 8-wave
 // 128 x 512 tile, 1 the 4-wave kernel, 2 the tall configuration, 3 split
 // mode on the 8-wave kernel, 4 (DSD) the tall pipeline, -1 rejected.
-struct DenseRoute {
-  Status status = Status::kNoKernel;
-  bool needs_meta = false;
+struct DenseRoute : Product {
+  explicit DenseRoute(const Product &bound) : Product(bound) {}
   bool bt = false;
   int code = -1;
   bool tall = false;
   int epi = 0;  // the 4-wave kernel's epilogue variant (codes 1 and 4)
-  GemmParams p;
 };
 
-// The chain both dense-output products share, on r->p as prepared. dds: the
-// transposed-output product (S = op(B)^T). Accumulating calls (out !=
-// kStore): always the 8-wave kernel, with pairs where PreparePairs grants
-// them (never split mode) or the tall configuration; fp32 C has rows of
-// ldc x 4 bytes.
-static void RouteDenseOut(DenseRoute *r, bool dds, long long blocks, long long row_max,
-                          bool ta, bool tb, hipStream_t stream, OutMode out, bool dry) {
+// The chain both dense-output products share, on r->p as bound (r->out_t:
+// DDS, the transposed-output product). Accumulating calls (out != kStore):
+// always the 8-wave kernel, with pairs where PreparePairs grants them (never
+// split mode) or the tall configuration; fp32 C has rows of ldc x 4 bytes.
+static void RouteDenseOut(DenseRoute *r, hipStream_t stream, OutMode out, bool dry) {
   GemmParams &p = r->p;
+  const bool dds = r->out_t;
+  const long long blocks = r->s_sparse->nonzeros / (kBlock * kBlock);
   const bool acc = out != OutMode::kStore;
   if (out == OutMode::kAccF32) p.c_ld *= 2;
   if (!acc) p.xcd_rows = Knob(kKnobXcdRows);
   PreparePairs(&p, blocks, stream, dry, /*allow_split=*/!acc);
   GemmParams t = p;  // (p stays as it is before the tall configuration)
   r->tall = UseTall(&t);
-  if (r->tall && !acc && !dds && UseTallPipe(p, blocks, row_max, ta, tb)) {
+  if (r->tall && !acc && !dds &&
+      UseTallPipe(p, blocks, ((long long)r->s_sparse->cols + kBlock - 1) / kBlock, r->s_kc,
+                  r->d_kc)) {
     p.persistent = 0;
     p.num_jtiles = p.j_limit / 512;
     p.tall_flush_w = Knob(kKnobTallFlushW);
@@ -634,8 +384,7 @@ static void RouteDenseOut(DenseRoute *r, bool dds, long long blocks, long long r
   }
   const long long blocks4w = Dsd4wForced() ? (1LL << 40) : blocks;
   if (acc || !Dsd4wEnabled() ||
-      !(dds ? Dds4wApplies(p, blocks4w, tb, !ta, true, r->tall)
-            : Dsd4wApplies(p, blocks4w, !ta, tb, false, r->tall))) {
+      !(dds ? Dds4wApplies : Dsd4wApplies)(p, blocks4w, r->s_kc, r->d_kc, dds, r->tall)) {
     r->code = r->tall ? 2 : p.pair != 0 && p.pair_split > 1 ? 3 : 0;
     return;
   }
@@ -671,23 +420,18 @@ static bool BtAppliesDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb
 static DenseRoute RouteDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
                            const Matrix &c, hipStream_t stream, OutMode out, bool dry,
                            BtView view) {
-  DenseRoute r;
-  r.status = PrepareDsd(a, ta, b, tb, c, &r.p, &r.needs_meta);
+  DenseRoute r(Bind(a, ta, b, tb, c));
   if (r.status != Status::kOk) return r;
   r.bt = out == OutMode::kStore && view != BtView::kOff && BtAppliesDsd(a, ta, b, tb) &&
          BtViewOpen(view, stream);
-  if (!r.bt)
-    RouteDenseOut(&r, false, a.nonzeros / (kBlock * kBlock),
-                  ((long long)a.cols + kBlock - 1) / kBlock, ta, tb, stream, out, dry);
+  if (!r.bt) RouteDenseOut(&r, stream, out, dry);
   return r;
 }
 
 static DenseRoute RouteDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
                            const Matrix &c, hipStream_t stream, OutMode out, bool dry) {
-  DenseRoute r;
-  r.status = PrepareDds(a, ta, b, tb, c, &r.p, &r.needs_meta);
-  if (r.status == Status::kOk)
-    RouteDenseOut(&r, true, b.nonzeros / (kBlock * kBlock), 0, ta, tb, stream, out, dry);
+  DenseRoute r(Bind(a, ta, b, tb, c));
+  if (r.status == Status::kOk) RouteDenseOut(&r, stream, out, dry);
   return r;
 }
 
@@ -698,14 +442,12 @@ static DenseRoute RouteDds(const Matrix &a, bool ta, const BlockMatrix &b, bool 
 // rejected. kernel: what SddKernel reports, 0 the 8-wave k-split tile, 1
 // grouped tiles on the 8-wave kernel, 2 the 4-wave K-split, 3 grouped tiles
 // on the 4-wave kernel, 4 B transposed first, -1 rejected.
-struct SddRoute {
-  Status status = Status::kNoKernel;
+struct SddRoute : Product {
   bool bt = false;
   bool grouped = false;
   int plan = -1;
   int kernel = -1;
   bool tail = false;  // kernel 3: the tail split's second launch follows
-  GemmParams p;
 };
 
 static bool BtAppliesSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
@@ -718,7 +460,7 @@ static SddRoute RouteSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
                          bool fused = false) {
   SddRoute r;
   GemmParams &p = r.p;
-  r.status = PrepareSdd(a, ta, b, tb, c, &p);
+  static_cast<Product &>(r) = Bind(a, ta, b, tb, c);
   if (r.status != Status::kOk) return r;
   if (!fused && view != BtView::kOff && BtAppliesSdd(a, ta, b, tb, c, stream) &&
       BtViewOpen(view, stream)) {
@@ -794,10 +536,42 @@ size_t DsdWorkspaceBytes(const BlockMatrix &a, bool ta, const Matrix &b, bool tb
 
 // ---- shared entry points: execute the route ---------------------------------
 
+// What every product with a sparse input does between its route and its
+// launch: the transposed metadata a flagged operand is read through is built
+// when its descriptor says so (create_metadata; the ...Ex forms clear it on
+// their copy), S's before D's.
+static hipError_t BeforeLaunch(Product *r, hipStream_t stream) {
+  for (const BlockMatrix *m : {r->s_meta ? r->s_sparse : nullptr, r->d_meta ? r->d_sparse : nullptr})
+    if (m != nullptr && m->create_metadata) {
+      const hipError_t e = BuildTransposed(*m, stream);
+      if (e != hipSuccess) return e;
+    }
+  r->p.debug = g_debug;
+  return hipSuccess;
+}
+
+// DSD and DDS once routed. (ta, tb pick the 4-wave kernel's variant: NT, TN
+// or TT of the problem as the caller states it.)
+static hipError_t LaunchDenseOut(DenseRoute *r, bool ta, bool tb, int dtype, OutMode out,
+                                 hipStream_t stream) {
+  const hipError_t e = BeforeLaunch(r, stream);
+  if (e != hipSuccess) return e;
+  if (out != OutMode::kStore)
+    return LaunchBlockGemmAcc(dtype, r->s_kc, r->d_kc, r->out_t, r->tall,
+                              out == OutMode::kAccF32 ? kOutAccF32 : kOutAccT, r->p, stream);
+  switch (r->code) {
+    case 4: return LaunchDsd4w(dtype, r->p, r->epi, false, stream, false, false);
+    case 1:
+      return (r->out_t ? LaunchDds4w : LaunchDsd4w)(dtype, r->p, r->epi, tb && !ta, stream,
+                                                    ta && !tb, ta && tb);
+    default:
+      return LaunchBlockGemm(dtype, false, r->s_kc, r->d_kc, r->out_t, r->tall, r->p, stream);
+  }
+}
+
 hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
-                  const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *st_out, Workspace ws,
-                  OutMode out) {
+                  const Matrix &c, int dtype, hipStream_t stream,
+                  Status *st_out, Workspace ws, OutMode out) {
   const InProduct in_product;
   DenseRoute r = RouteDsd(a, ta, b, tb, c, stream, out, /*dry=*/false, BtView::kProblem);
   *st_out = r.status;
@@ -806,46 +580,21 @@ hipError_t RunDsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
     const BtCopy copy = TransposeB(b, stream, ws);
     if (copy.error != hipSuccess) return copy.error;
     if (copy.data != nullptr)
-      return RunDsd(a, ta, Matrix(b.cols, b.rows, copy.data), false, c, dtype, build_meta,
-                    stream, st_out, Workspace{}, OutMode::kStore);
+      return RunDsd(a, ta, Matrix(b.cols, b.rows, copy.data), false, c, dtype, stream, st_out,
+                    Workspace{}, OutMode::kStore);
     r = RouteDsd(a, ta, b, tb, c, stream, out, /*dry=*/false, BtView::kOff);
   }
-  if (r.needs_meta && build_meta) {
-    const hipError_t e = BuildTransposed(a, stream);
-    if (e != hipSuccess) return e;
-  }
-  r.p.debug = g_debug;
-  if (out != OutMode::kStore)
-    return LaunchBlockGemmAcc(dtype, !ta, tb, false, r.tall,
-                              out == OutMode::kAccF32 ? kOutAccF32 : kOutAccT, r.p, stream);
-  switch (r.code) {
-    case 4: return LaunchDsd4w(dtype, r.p, r.epi, false, stream, false, false);
-    case 1: return LaunchDsd4w(dtype, r.p, r.epi, tb && !ta, stream, ta && !tb, ta && tb);
-    default: return LaunchBlockGemm(dtype, false, !ta, tb, false, r.tall, r.p, stream);
-  }
+  return LaunchDenseOut(&r, ta, tb, dtype, out, stream);
 }
 
 hipError_t RunDds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
-                  const Matrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *st_out, OutMode out) {
+                  const Matrix &c, int dtype, hipStream_t stream,
+                  Status *st_out, OutMode out) {
   const InProduct in_product;
   DenseRoute r = RouteDds(a, ta, b, tb, c, stream, out, /*dry=*/false);
   *st_out = r.status;
   if (r.status != Status::kOk) return hipSuccess;
-  if (r.needs_meta && build_meta) {
-    const hipError_t e = BuildTransposed(b, stream);
-    if (e != hipSuccess) return e;
-  }
-  r.p.debug = g_debug;
-  if (out != OutMode::kStore)
-    return LaunchBlockGemmAcc(dtype, /*s_kc=*/tb, /*d_kc=*/!ta, /*out_t=*/true, r.tall,
-                              out == OutMode::kAccF32 ? kOutAccF32 : kOutAccT, r.p, stream);
-  switch (r.code) {
-    case 1: return LaunchDds4w(dtype, r.p, r.epi, tb && !ta, stream, ta && !tb, ta && tb);
-    default:
-      return LaunchBlockGemm(dtype, false, /*s_kc=*/tb, /*d_kc=*/!ta, /*out_t=*/true, r.tall,
-                             r.p, stream);
-  }
+  return LaunchDenseOut(&r, ta, tb, dtype, out, stream);
 }
 
 hipError_t RunSdd(const Matrix &a, bool ta, const Matrix &b, bool tb,
@@ -1052,61 +801,34 @@ hipError_t RunSddEpilogueBias(const Matrix &a, bool ta, const Matrix &b,
                         nullptr, bias, stream, st_out, ws);
 }
 
-hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
-                  const BlockMatrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *st_out) {
+// SSD, SDS and DSS: no route to decide, one kernel each.
+static hipError_t RunBound(Product r, int dtype, hipStream_t stream, Status *st_out) {
   const InProduct in_product;
-  GemmParams p;
-  bool needs_meta = false;
-  const Status st = PrepareSsd(a, ta, b, tb, c, &p, &needs_meta);
-  *st_out = st;
-  if (st != Status::kOk) return hipSuccess;
-  if (needs_meta && build_meta) {
-    const hipError_t e = BuildTransposed(a, stream);
-    if (e != hipSuccess) return e;
-  }
-  p.debug = g_debug;
-  return LaunchBlockGemmSparseIn(dtype, /*s_kc=*/!ta, /*d_kc=*/tb,
-                                 /*out_t=*/false, p, stream);
+  *st_out = r.status;
+  if (r.status != Status::kOk) return hipSuccess;
+  const hipError_t e = BeforeLaunch(&r, stream);
+  if (e != hipSuccess) return e;
+  return r.d_sparse != nullptr
+             ? LaunchBlockGemmDss(dtype, r.s_kc, r.d_kc, r.p, stream)
+             : LaunchBlockGemmSparseIn(dtype, r.s_kc, r.d_kc, r.out_t, r.p, stream);
+}
+
+hipError_t RunSsd(const BlockMatrix &a, bool ta, const Matrix &b, bool tb,
+                  const BlockMatrix &c, int dtype, hipStream_t stream,
+                  Status *st_out) {
+  return RunBound(Bind(a, ta, b, tb, c), dtype, stream, st_out);
 }
 
 hipError_t RunSds(const Matrix &a, bool ta, const BlockMatrix &b, bool tb,
-                  const BlockMatrix &c, int dtype, bool build_meta,
-                  hipStream_t stream, Status *st_out) {
-  const InProduct in_product;
-  GemmParams p;
-  bool needs_meta = false;
-  const Status st = PrepareSds(a, ta, b, tb, c, &p, &needs_meta);
-  *st_out = st;
-  if (st != Status::kOk) return hipSuccess;
-  if (needs_meta && build_meta) {
-    const hipError_t e = BuildTransposed(b, stream);
-    if (e != hipSuccess) return e;
-  }
-  p.debug = g_debug;
-  return LaunchBlockGemmSparseIn(dtype, /*s_kc=*/tb, /*d_kc=*/!ta,
-                                 /*out_t=*/true, p, stream);
+                  const BlockMatrix &c, int dtype, hipStream_t stream,
+                  Status *st_out) {
+  return RunBound(Bind(a, ta, b, tb, c), dtype, stream, st_out);
 }
 
 hipError_t RunDss(const BlockMatrix &a, bool ta, const BlockMatrix &b,
-                  bool tb, const Matrix &c, int dtype, bool build_meta_a,
-                  bool build_meta_b, hipStream_t stream, Status *st_out) {
-  const InProduct in_product;
-  GemmParams p;
-  bool meta_a = false, meta_b = false;
-  const Status st = PrepareDss(a, ta, b, tb, c, &p, &meta_a, &meta_b);
-  *st_out = st;
-  if (st != Status::kOk) return hipSuccess;
-  if (meta_a && build_meta_a) {
-    const hipError_t e = BuildTransposed(a, stream);
-    if (e != hipSuccess) return e;
-  }
-  if (meta_b && build_meta_b) {
-    const hipError_t e = BuildTransposed(b, stream);
-    if (e != hipSuccess) return e;
-  }
-  p.debug = g_debug;
-  return LaunchBlockGemmDss(dtype, /*s_kc=*/!ta, /*d_kc=*/tb, p, stream);
+                  bool tb, const Matrix &c, int dtype, hipStream_t stream,
+                  Status *st_out) {
+  return RunBound(Bind(a, ta, b, tb, c), dtype, stream, st_out);
 }
 
 int StatusCode(Status st) { return AsCode(st); }
@@ -1167,37 +889,15 @@ int DsdPlan(const void *a, bool ta, const void *b, bool tb, const void *c,
 // descriptors share the C++ layout (static_asserts in c_api.cpp).
 bool CanImplement(int op, const void *a, bool ta, const void *b, bool tb,
                   const void *c) {
-  if (!a || !b || !c) return false;
-  GemmParams p;
-  bool meta = false;
-  Status st = Status::kNoKernel;
-  if (op == 0) {
-    st = PrepareDsd(*static_cast<const BlockMatrix *>(a), ta,
-                    *static_cast<const Matrix *>(b), tb,
-                    *static_cast<const Matrix *>(c), &p, &meta);
-  } else if (op == 1) {
-    st = PrepareDds(*static_cast<const Matrix *>(a), ta,
-                    *static_cast<const BlockMatrix *>(b), tb,
-                    *static_cast<const Matrix *>(c), &p, &meta);
-  } else if (op == 2) {
-    st = PrepareSdd(*static_cast<const Matrix *>(a), ta,
-                    *static_cast<const Matrix *>(b), tb,
-                    *static_cast<const BlockMatrix *>(c), &p);
-  } else if (op == 3) {
-    st = PrepareSsd(*static_cast<const BlockMatrix *>(a), ta,
-                    *static_cast<const Matrix *>(b), tb,
-                    *static_cast<const BlockMatrix *>(c), &p, &meta);
-  } else if (op == 4) {
-    st = PrepareSds(*static_cast<const Matrix *>(a), ta,
-                    *static_cast<const BlockMatrix *>(b), tb,
-                    *static_cast<const BlockMatrix *>(c), &p, &meta);
-  } else if (op == 5) {
-    bool meta_b = false;
-    st = PrepareDss(*static_cast<const BlockMatrix *>(a), ta,
-                    *static_cast<const BlockMatrix *>(b), tb,
-                    *static_cast<const Matrix *>(c), &p, &meta, &meta_b);
-  }
-  return st == Status::kOk;
+  static const bool kIsBlock[6][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1},
+                                    {1, 0, 1}, {0, 1, 1}, {1, 1, 0}};
+  if (!a || !b || !c || op < 0 || op > 5) return false;
+  const auto as = [](const void *x, bool block) {
+    return block ? Operand(*static_cast<const BlockMatrix *>(x))
+                 : Operand(*static_cast<const Matrix *>(x));
+  };
+  return Bind(as(a, kIsBlock[op][0]), ta, as(b, kIsBlock[op][1]), tb, as(c, kIsBlock[op][2]))
+             .status == Status::kOk;
 }
 
 }  // namespace sputnik_amd

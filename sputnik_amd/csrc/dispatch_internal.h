@@ -1,8 +1,9 @@
 // sputnik-amd: what the host files of the dispatcher share (host only, not
 // part of include/): knobs.cpp (the tuning knobs), workspaces.cpp (every
-// piece of device memory the library keeps, and the caller's), dispatch.cpp
-// (prepare, route, run, the queries) and block_api.cpp (the sputnik::block
-// overload set).
+// piece of device memory the library keeps, and the caller's), operands.cpp
+// (which descriptors a product accepts and how they bind to GemmParams: pure
+// host arithmetic), dispatch.cpp (route, run, the queries) and block_api.cpp
+// (the sputnik::block overload set).
 #ifndef SPUTNIK_AMD_DISPATCH_INTERNAL_H_
 #define SPUTNIK_AMD_DISPATCH_INTERNAL_H_
 
@@ -61,6 +62,38 @@ struct BtCopy {
   void *data = nullptr;  // [b.cols][b.rows]
 };
 BtCopy TransposeB(const Matrix &b, hipStream_t stream, Workspace ws);
+
+// ---- operands.cpp ----
+constexpr long long kMaxLaneOffset = 0x7fffffffLL;  // 31-bit buffer offsets
+constexpr int kDssMaxK = 32768;
+
+// One operand of a product as the caller described it: a dense matrix
+// (sparse == nullptr) or a BCSR one, whose descriptor must outlive the
+// Product bound from it.
+struct Operand {
+  int rows, cols;
+  const void *data;
+  const BlockMatrix *sparse;
+  Operand(const Matrix &m) : rows(m.rows), cols(m.cols), data(m.data), sparse(nullptr) {}
+  Operand(const BlockMatrix &m) : rows(m.rows), cols(m.cols), data(m.data), sparse(&m) {}
+};
+
+// A product in the kernel's terms, O = S . D over 128-row tiles of the row
+// operand S (the table is at Bind, operands.cpp). Which of A, B, C are sparse
+// says which of the six products it is.
+struct Product {
+  Status status = Status::kNoKernel;
+  // What the launches take: S / D k-contiguous in memory, O written
+  // transposed (DDS / SDS: S = op(B)^T, D = op(A)^T).
+  bool s_kc = false, d_kc = false, out_t = false;
+  // The sparse descriptor behind S / D (nullptr: dense), and whether it is
+  // read through its transposed metadata, which a launch builds first when
+  // the descriptor's create_metadata is set.
+  const BlockMatrix *s_sparse = nullptr, *d_sparse = nullptr;
+  bool s_meta = false, d_meta = false;
+  GemmParams p{};  // valid when status == kOk
+};
+Product Bind(const Operand &a, bool ta, const Operand &b, bool tb, const Operand &c);
 
 // ---- dispatch.cpp ----
 hipError_t BuildTransposed(const BlockMatrix &a, hipStream_t stream);

@@ -21,7 +21,7 @@ constexpr int kDsd4wMinMean = 2;
 bool Dsd4wApplies(const GemmParams &p, long long blocks, bool s_kc, bool d_kc,
                   bool out_t, bool tall);
 
-// Launches it; p as prepared for the 8-wave kernel (PrepareDsd +
+// Launches it; p as prepared for the 8-wave kernel (operands.cpp Bind +
 // PreparePairs): the same grid, workspaces and epochs.
 // epi: 0 one workgroup-wide staging image copied out after a barrier; 1
 // every wave stages and stores its own 128 x 128 block (no barrier); 2 the
