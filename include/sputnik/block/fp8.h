@@ -61,11 +61,77 @@
 //   round_T(acc), rounded once. Every product and every partial sum of P is
 //   held to fp32 precision (the operands are widened to fp16, exactly, in
 //   front of the matrix cores; the fp8 MFMA forms of gfx950 drop small
-//   addends and are not used), so |C - exact| <= 2^-p |exact| + (K + 2 K /
+//   addends and are used only in the opt-in mode below), so |C - exact| <= 2^-p |exact| + (K + 2 K /
 //   128) 2^-23 sum |terms| with p = 11 (fp16) or 8 (bf16). No split-K, no
 //   atomics, no hand-off between workgroups: the same inputs give the same
 //   bits. A stored block whose row or column index is out of range is
 //   skipped (SDD: left unwritten; DSD: contributes zero).
+//
+// Accumulation modes (Fp8Accumulate; the overloads of SddFp8 and DsdFp8 that
+// take one, and Fp8IntervalSums). The overloads without it mean kFp32, the
+// arithmetic above, bit for bit. Any other value of the enum is
+// hipErrorInvalidValue with nothing launched.
+//
+//   kFast   opt-in: twice the matrix-core rate and no conversion, with an
+//           interval sum of limited precision, as DeepSeek-V3's fp8 GEMMs
+//           have. Everything outside P is as above: the format and the
+//           scales, the interval order (SDD ascending, DSD in storage order),
+//           s = float32(sa * sb), one fp32 fma per interval, round_T once,
+//           the skipping of out-of-range blocks, no split-K and no atomics,
+//           the argument checks. Only P changes. P[i, j] of an interval is
+//           what one v_mfma_scale_f32_16x16x128_f8f6f4 of gfx950 returns for
+//           the 16 x 16 tile that holds (i, j) when
+//             - both operands are e4m3 (cbsz = blgp = 0),
+//             - both e8m0 scales are 2^0 (0x7F),
+//             - the accumulator input is +0,
+//             - lane l (row or column l % 16 of the tile, group g = l / 16)
+//               holds in its 32 operand bytes k = 16 g .. 16 g + 15 of the
+//               interval followed by k = 64 + 16 g .. 64 + 16 g + 15, in A
+//               and in B alike (the kernel's two 16-byte reads),
+//           and D[e] of lane l is P[4 g + e, l % 16]. With that assignment
+//           the mode is defined bit for bit by the hardware:
+//           Fp8IntervalSums(kFast) is that P as a callable, and C =
+//           round_T of the fma chain over it. The same inputs give the same
+//           bits from run to run, and SDD and DSD give the same bits for the
+//           same interval operands in the same order.
+//
+//           The instruction does not sum in fp32: addends far below the
+//           largest product of their group are dropped. The error is
+//             |C - exact| <= 2^-p |exact|
+//                            + (eps_fast + (2 K / 128 + 1) 2^-23) sum |terms|
+//           with eps_fast = 2^-7, measured, not chosen: the worst
+//           |P - exact| / sum |products| of Fp8IntervalSums(kFast) against
+//           the float64 dot product of the decoded bytes was 2^-8.24, over
+//           random finite bytes (2^-12.18), bytes quantised from normal data
+//           (2^-12.73), one large product among small ones at every k
+//           position and ratio 2^-1 .. 2^-17 (2^-8.28) and two cancelling
+//           large products (2^-8.24) (DESIGN 3.6,
+//           profiles/fp8/accum_probe.jsonl); eps_fast is the smallest power
+//           of two at or above twice that, because a sampled maximum over a
+//           sum the hardware does not document is not a proof. The worst
+//           case is a product 2^11 times its neighbours: from that ratio on
+//           seven of the 127 small addends are dropped, none at 2^10. Data
+//           without such outliers inside an interval sees the 2^-12 figures.
+//
+//           A NaN byte makes NaN exactly the outputs of its row (a byte of A
+//           or S) or of its column (a byte of B) in that interval's 128 x
+//           128 tile, and makes nothing else NaN.
+//
+//           Out of scope in this mode: a CPU model of the instruction's
+//           internal sum (the tests hold the product to Fp8IntervalSums, and
+//           Fp8IntervalSums to float64 within eps_fast), the non-scaled
+//           v_mfma_f32_16x16x32_fp8_fp8 form, e8m0 hardware scales carrying
+//           real scale values, gradients and other layouts.
+//
+//   Fp8IntervalSums   P [k / 128, m, n], fp32, of aq [m, k] and bq [n, k]:
+//                     P[kb] is the interval sum of k-block kb as the product
+//                     kernels form it in the given mode (kFp32: the four
+//                     fp16 MFMAs chained from +0 over the byte quarters k =
+//                     16 g .., 16 g + 8 .., 64 + 16 g .., 64 + 16 g + 8 .. of
+//                     lane group g, in that order). A cold kernel, one wave
+//                     per tile and interval; it is what "P" means above.
+//                     m, n and k multiples of 128; aq, bq and p non-null,
+//                     16-byte aligned, p none of the inputs.
 //
 // `dtype` is T, the 16-bit type (DataType keeps its two values). Every call
 // is stream-ordered, allocates nothing and never synchronises or aborts:
@@ -87,6 +153,10 @@
 
 namespace sputnik {
 namespace block {
+
+// How an interval's P is summed (above): kFp32, the default, or the opt-in
+// kFast.
+enum class Fp8Accumulate { kFp32 = 0, kFast = 1 };
 
 hipError_t QuantizeRows(const void *x, int rows, int cols, void *q,
                         float *scales, bool pow2, DataType dtype,
@@ -113,6 +183,20 @@ hipError_t SddFp8(const void *aq, const float *a_scales, int k,
 hipError_t DsdFp8(const BlockMatrix s, const float *s_scales, const void *bq,
                   const float *b_scales, Matrix c, DataType dtype,
                   hipStream_t stream);
+
+// The same with the accumulation mode of P (above).
+hipError_t SddFp8(const void *aq, const float *a_scales, int k,
+                  const void *bq, const float *b_scales, BlockMatrix c,
+                  DataType dtype, Fp8Accumulate accumulate,
+                  hipStream_t stream);
+
+hipError_t DsdFp8(const BlockMatrix s, const float *s_scales, const void *bq,
+                  const float *b_scales, Matrix c, DataType dtype,
+                  Fp8Accumulate accumulate, hipStream_t stream);
+
+hipError_t Fp8IntervalSums(const void *aq, const void *bq, int m, int n,
+                           int k, Fp8Accumulate accumulate, float *p,
+                           hipStream_t stream);
 
 }  // namespace block
 }  // namespace sputnik

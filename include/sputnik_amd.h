@@ -630,6 +630,26 @@ int sputnik_sdd_fp8(const void *aq, const float *a_scales, int k,
 int sputnik_dsd_fp8(const sputnik_block_matrix_t *s, const float *s_scales,
                     const void *bq, const float *b_scales,
                     const sputnik_matrix_t *c, int dtype, void *stream);
+/* The two products with the accumulation mode of P (Fp8Accumulate in
+ * sputnik/block/fp8.h): `accumulate` 0 is the fp32 sum of the entry points
+ * above, bit for bit; 1 is the opt-in fast mode, where P is what one
+ * v_mfma_scale_f32_16x16x128_f8f6f4 returns for the interval (unit scales,
+ * from +0; fp8.h has the lane assignment, the error bound with its measured
+ * eps_fast and the NaN rule). Any other value: hipErrorInvalidValue, nothing
+ * launched. sputnik_fp8_interval_sums writes that P itself, fp32 [k / 128, m,
+ * n], of aq [m, k] and bq [n, k] (m, n, k multiples of 128; aq, bq, p
+ * non-null, 16-byte aligned, p none of the inputs): a cold kernel, the
+ * definition the fast products are tested against. */
+int sputnik_sdd_fp8_acc(const void *aq, const float *a_scales, int k,
+                        const void *bq, const float *b_scales,
+                        const sputnik_block_matrix_t *c, int dtype,
+                        int accumulate, void *stream);
+int sputnik_dsd_fp8_acc(const sputnik_block_matrix_t *s, const float *s_scales,
+                        const void *bq, const float *b_scales,
+                        const sputnik_matrix_t *c, int dtype, int accumulate,
+                        void *stream);
+int sputnik_fp8_interval_sums(const void *aq, const void *bq, int m, int n,
+                              int k, int accumulate, float *p, void *stream);
 
 /* ---- Host-only queries (no GPU work; safe without a device) */
 /* 1 when the reference would accept the problem (same rules as

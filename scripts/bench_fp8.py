@@ -2,7 +2,11 @@
 the 16-bit SDD and DSD it stands beside: sdd_fp8, dsd_fp8 and the two hot
 quantisers (quantize_rows of the gathered activations, quantize_sparse with
 gelu of the SDD output) next to ops' raw bf16 sdd and dsd on the same
-topology. Recorded, not gated (DESIGN "FP8 forward path").
+topology, and the two products in the opt-in fast accumulation
+(accumulate="fast", Fp8Accumulate::kFast). With --parent-lib the fp32-mode
+products of another build of libsputnik.so (the commit before a change) run
+as two more arms of the same process and rounds, through the same Python
+path. Recorded, not gated (DESIGN "FP8 forward path").
 
 Protocol: one process, HIP events, every arm warmed for at
 least --warm-ms of device time, then --rounds interleaved rounds, each window
@@ -20,9 +24,11 @@ products, and for the quantisers the achieved bytes per second (2 bytes read,
 1 written per element, 4 per scale) as a share of the 6.3 TB/s achievable HBM
 rate. One JSON line per shape.
 
-python scripts/bench_fp8.py [--shapes c4,decode] [--out profiles/fp8/bench_fp8.jsonl]
+python scripts/bench_fp8.py [--shapes c4,decode] [--parent-lib PATH]
+                            [--out profiles/fp8/bench_fp8.jsonl]
 """
 import argparse
+import ctypes
 import json
 import math
 import os
@@ -43,6 +49,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warm-ms", type=float, default=100.0)
     ap.add_argument("--load-ms", type=float, default=100.0)
+    ap.add_argument("--parent-lib", default="",
+                    help="another libsputnik.so: its sdd_fp8 / dsd_fp8 run as "
+                         "the *_parent arms")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -71,6 +80,26 @@ def main():
     w1, w2 = rand(D_MODEL, hidden, scale=1 / 64), rand(hidden, D_MODEL,
                                                         scale=1 / 64)
     w1q, w2q = ops.quantize_weight(w1), ops.quantize_weight(w2)
+    sp.lib()
+    parent = None
+    if a.parent_lib:
+        # (a second copy of the library in this process: its own kernels,
+        # the same HIP runtime)
+        parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
+        for name in ("sputnik_sdd_fp8", "sputnik_dsd_fp8"):
+            fn = getattr(parent, name)
+            fn.argtypes, fn.restype = sp._SIGNATURES[name], ctypes.c_int
+        parent.sputnik_build_hash.restype = ctypes.c_char_p
+
+    def through_parent(fn):
+        def run():
+            ours, sp._lib = sp._lib, parent
+            try:
+                return fn()
+            finally:
+                sp._lib = ours
+        return run
+
     lines = []
     for shape in a.shapes.split(","):
         per_expert = SHAPES[shape]
@@ -90,9 +119,16 @@ def main():
             "sdd_fp8": lambda: ops.sdd_fp8(xq, xs, w1q, topo, dt),
             "dsd_bf16": lambda: ops._dsd(h16, w2),
             "dsd_fp8": lambda: ops.dsd_fp8(hq, w2q, dt),
+            "sdd_fp8_fast": lambda: ops.sdd_fp8(xq, xs, w1q, topo, dt,
+                                                accumulate="fast"),
+            "dsd_fp8_fast": lambda: ops.dsd_fp8(hq, w2q, dt,
+                                                accumulate="fast"),
             "quantize_rows": lambda: ops.quantize_rows(x),
             "quantize_sparse_gelu": lambda: ops.quantize_sparse(g16, "gelu"),
         }
+        if parent is not None:
+            arms["sdd_fp8_parent"] = through_parent(arms["sdd_fp8"])
+            arms["dsd_fp8_parent"] = through_parent(arms["dsd_fp8"])
         calls = {}
         for name, fn in arms.items():
             fn()
@@ -107,12 +143,14 @@ def main():
             for name, fn in arms.items():
                 times[name].append(window(fn, calls[name]))
         flops = 2.0 * blocks * 128 * 128
-        work = {"sdd_bf16": flops * D_MODEL, "sdd_fp8": flops * D_MODEL,
-                "dsd_bf16": flops * D_MODEL, "dsd_fp8": flops * D_MODEL}
+        work = {name: flops * D_MODEL for name in arms
+                if name.startswith(("sdd_", "dsd_"))}
         moved = {"quantize_rows": rows * D_MODEL * 3 + rows * D_MODEL // 32,
                  "quantize_sparse_gelu": blocks * 16384 * 3 + blocks * 512}
         line = {"shape": shape, "rows": rows, "blocks": blocks,
                 "build": sp.build_hash(), "rounds": a.rounds, "arms": {}}
+        if parent is not None:
+            line["parent_build"] = parent.sputnik_build_hash().decode()
         for name in arms:
             med = statistics.median(times[name])
             arm = {"us": round(med, 2), "min_us": round(min(times[name]), 2),
@@ -126,9 +164,18 @@ def main():
                 arm["hbm_share"] = round(tbs / HBM_TBS, 3)
             line["arms"][name] = arm
         for op in ("sdd", "dsd"):
+            us = {name: arm["us"] for name, arm in line["arms"].items()}
             line[f"{op}_fp8_over_bf16"] = round(
-                line["arms"][f"{op}_fp8"]["us"]
-                / line["arms"][f"{op}_bf16"]["us"], 3)
+                us[f"{op}_fp8"] / us[f"{op}_bf16"], 3)
+            line[f"{op}_fp8_fast_over_bf16"] = round(
+                us[f"{op}_fp8_fast"] / us[f"{op}_bf16"], 3)
+            line[f"{op}_fp8_fast_over_fp8"] = round(
+                us[f"{op}_fp8_fast"] / us[f"{op}_fp8"], 3)
+            if parent is not None:
+                line[f"{op}_fp8_over_parent"] = round(
+                    us[f"{op}_fp8"] / us[f"{op}_fp8_parent"], 3)
+                line[f"{op}_fp8_fast_over_parent"] = round(
+                    us[f"{op}_fp8_fast"] / us[f"{op}_fp8_parent"], 3)
         print(json.dumps(line), flush=True)
         lines.append(line)
     if a.out:

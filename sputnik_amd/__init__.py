@@ -239,6 +239,14 @@ _SIGNATURES = {
                                 _P, _P, ctypes.c_int, ctypes.c_int, _P],
     "sputnik_sdd_fp8": [_P, _P, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P],
     "sputnik_dsd_fp8": [_P, _P, _P, _P, _P, ctypes.c_int, _P],
+    # ... with the accumulation mode in front of the stream, and P itself:
+    # (aq, bq, m, n, k, accumulate, p, stream)
+    "sputnik_sdd_fp8_acc": [_P, _P, ctypes.c_int, _P, _P, _P, ctypes.c_int,
+                            ctypes.c_int, _P],
+    "sputnik_dsd_fp8_acc": [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
+                            _P],
+    "sputnik_fp8_interval_sums": [_P, _P, ctypes.c_int, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, _P, _P],
     "sputnik_can_implement": [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_abi_block_matrix_size": [],
     "sputnik_abi_block_matrix_offset": [ctypes.c_int],
@@ -1818,14 +1826,30 @@ def _fp8_weight(bq, b_scales, what: str):
     return n, k
 
 
-def SddFp8(aq, a_scales, bq, b_scales, c, stream=None):  # noqa: N802
+FP8_ACCUMULATE = {"fp32": 0, "fast": 1}
+
+
+def _fp8_accumulate(accumulate, what: str) -> int:
+    """The Fp8Accumulate code of "fp32" / "fast"; raises before any library
+    call."""
+    if not isinstance(accumulate, str) or accumulate not in FP8_ACCUMULATE:
+        raise ValueError(f"{what}: accumulate must be 'fp32' or 'fast', not "
+                         f"{accumulate!r}")
+    return FP8_ACCUMULATE[accumulate]
+
+
+def SddFp8(aq, a_scales, bq, b_scales, c, stream=None,  # noqa: N802
+           accumulate="fp32"):
     """C (BlockMatrix of fp16 / bf16 block values, with row_indices) = Aq .
     Bq at C's stored blocks: aq e4m3 [c.rows, k] with a_scales fp32 [c.rows,
     k / 128] (QuantizeRows), bq e4m3 [c.cols, k] with b_scales fp32 [k / 128,
     c.cols / 128] (QuantizeWeight). acc = fma(sa * sb, P, acc) per k-block
-    in fp32, rounded once (sputnik_sdd_fp8)."""
+    in fp32, rounded once (sputnik_sdd_fp8). `accumulate`: "fp32" (P summed
+    in fp32) or "fast" (P from the scaled e4m3 MFMA, Fp8Accumulate::kFast of
+    sputnik/block/fp8.h; sputnik_sdd_fp8_acc)."""
     import torch
 
+    mode = _fp8_accumulate(accumulate, "SddFp8")
     if not isinstance(c, BlockMatrix):
         raise TypeError("SddFp8 writes a BlockMatrix")
     n, k = _fp8_weight(bq, b_scales, "SddFp8")
@@ -1834,19 +1858,28 @@ def SddFp8(aq, a_scales, bq, b_scales, c, stream=None):  # noqa: N802
     _fp8_buffer(aq, torch.float8_e4m3fn, (c.rows, k), "aq")
     _fp8_buffer(a_scales, torch.float32, (c.rows, k // 128), "a_scales")
     cc = c._c()
-    _check(lib().sputnik_sdd_fp8(
-        _ptr(aq), _ptr(a_scales), k, _ptr(bq), _ptr(b_scales),
-        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "SddFp8")
+    if mode == 0:
+        code = lib().sputnik_sdd_fp8(
+            _ptr(aq), _ptr(a_scales), k, _ptr(bq), _ptr(b_scales),
+            ctypes.byref(cc), _dtype_code(c.data), _stream(stream))
+    else:
+        code = lib().sputnik_sdd_fp8_acc(
+            _ptr(aq), _ptr(a_scales), k, _ptr(bq), _ptr(b_scales),
+            ctypes.byref(cc), _dtype_code(c.data), mode, _stream(stream))
+    _check(code, "SddFp8")
 
 
-def DsdFp8(s, s_scales, bq, b_scales, c, stream=None):  # noqa: N802
+def DsdFp8(s, s_scales, bq, b_scales, c, stream=None,  # noqa: N802
+           accumulate="fp32"):
     """C (Matrix of fp16 / bf16, [s.rows, n]) = Sq . Bq: s a BlockMatrix whose
     data holds e4m3 block values with s_scales fp32 [blocks * 128], one per
     row of each stored block in storage order (QuantizeRows over the block
     values as [blocks * 128, 128]); bq / b_scales as SddFp8, k = s.cols. A
-    block row without blocks gives +0 rows (sputnik_dsd_fp8)."""
+    block row without blocks gives +0 rows (sputnik_dsd_fp8). `accumulate`
+    as SddFp8 (sputnik_dsd_fp8_acc)."""
     import torch
 
+    mode = _fp8_accumulate(accumulate, "DsdFp8")
     if not isinstance(s, BlockMatrix) or not isinstance(c, Matrix):
         raise TypeError("DsdFp8 takes a BlockMatrix and writes a Matrix")
     n, k = _fp8_weight(bq, b_scales, "DsdFp8")
@@ -1857,9 +1890,43 @@ def DsdFp8(s, s_scales, bq, b_scales, c, stream=None):  # noqa: N802
         raise TypeError("DsdFp8: s.data must be torch.float8_e4m3fn")
     _fp8_buffer(s_scales, torch.float32, (s.num_blocks * 128,), "s_scales")
     cs, cc = s._c(), c._c()
-    _check(lib().sputnik_dsd_fp8(
-        ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales),
-        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "DsdFp8")
+    if mode == 0:
+        code = lib().sputnik_dsd_fp8(
+            ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales),
+            ctypes.byref(cc), _dtype_code(c.data), _stream(stream))
+    else:
+        code = lib().sputnik_dsd_fp8_acc(
+            ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales),
+            ctypes.byref(cc), _dtype_code(c.data), mode, _stream(stream))
+    _check(code, "DsdFp8")
+
+
+def Fp8IntervalSums(aq, bq, p, accumulate="fp32", stream=None):  # noqa: N802
+    """P (fp32 [k / 128, m, n]) of aq e4m3 [m, k] and bq e4m3 [n, k]: per
+    k-block the interval sum from +0 as SddFp8 / DsdFp8 form it under
+    `accumulate` ("fp32" or "fast"). The definition of P in
+    sputnik/block/fp8.h as a callable; a cold kernel
+    (sputnik_fp8_interval_sums)."""
+    import torch
+
+    mode = _fp8_accumulate(accumulate, "Fp8IntervalSums")
+    if getattr(aq, "dtype", None) != torch.float8_e4m3fn or aq.dim() != 2:
+        raise TypeError("Fp8IntervalSums: aq must be a 2-D "
+                        "torch.float8_e4m3fn tensor")
+    m, k = int(aq.shape[0]), int(aq.shape[1])
+    if getattr(bq, "dtype", None) != torch.float8_e4m3fn or bq.dim() != 2:
+        raise TypeError("Fp8IntervalSums: bq must be a 2-D "
+                        "torch.float8_e4m3fn tensor")
+    n = int(bq.shape[0])
+    _fp8_tiles(m, "Fp8IntervalSums: m")
+    _fp8_tiles(n, "Fp8IntervalSums: n")
+    kb = _fp8_tiles(k, "Fp8IntervalSums: k")
+    _fp8_buffer(aq, torch.float8_e4m3fn, (m, k), "aq")
+    _fp8_buffer(bq, torch.float8_e4m3fn, (n, k), "bq")
+    _fp8_buffer(p, torch.float32, (kb, m, n), "p")
+    _check(lib().sputnik_fp8_interval_sums(
+        _ptr(aq), _ptr(bq), m, n, k, mode, _ptr(p), _stream(stream)),
+        "Fp8IntervalSums")
 
 
 __all__ = [
@@ -1879,7 +1946,8 @@ __all__ = [
     "SPUTNIK_ACT_SILU", "sdd_act_route",
     "MatmulGated", "MatmulGatedGrad", "BlockGate", "BlockGateGrad",
     "MatmulBias", "MatmulBiasActivation", "MatmulBiasGated", "BlockColumnSum",
-    "QuantizeRows", "QuantizeWeight", "SddFp8", "DsdFp8",
+    "QuantizeRows", "QuantizeWeight", "SddFp8", "DsdFp8", "Fp8IntervalSums",
+    "FP8_ACCUMULATE",
     "PaddedScatterBias", "PaddedScatterBiasWeightGrad",
     "PaddedScatterBiasGrad",
     "MoeBins", "MoeRowMap", "PaddedGather", "PaddedScatter",

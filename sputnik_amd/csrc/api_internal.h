@@ -117,13 +117,19 @@ hipError_t LaunchBlockEpilogue(int dtype, int mode, int act, const void *x,
 // (indices, row_indices; offsets unused). DSD: a = the sparse operand's e4m3
 // blocks with a_scales [nnz_blocks * 128], offsets / indices its BCSR
 // metadata, c dense [m, n]. b = Bq [n, k] with b_scales [k / 128, n / 128].
-// Sizes in blocks of 128.
-hipError_t LaunchFp8Gemm(bool dsd, int dtype, const void *a,
+// Sizes in blocks of 128. `fast` selects Fp8Accumulate::kFast, the scaled
+// e4m3 MFMA per interval.
+hipError_t LaunchFp8Gemm(bool dsd, bool fast, int dtype, const void *a,
                          const float *a_scales, const void *b,
                          const float *b_scales, void *c, const int *offsets,
                          const short *indices, const short *row_indices,
                          int m_blocks, int n_blocks, int k_blocks,
                          int nnz_blocks, hipStream_t stream);
+// P [k / 128, m, n] of Fp8IntervalSums, arguments already validated
+// (block_api.cpp): m, n and k multiples of 128.
+hipError_t LaunchFp8IntervalSums(const void *aq, const void *bq, int m, int n,
+                                 int k, bool fast, float *out,
+                                 hipStream_t stream);
 
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.

@@ -405,11 +405,25 @@ bool Aligned16(std::initializer_list<const void *> ps) {
   return (bits & 15) == 0;
 }
 
+bool Fp8AccumulateOk(Fp8Accumulate accumulate) {
+  return accumulate == Fp8Accumulate::kFp32 ||
+         accumulate == Fp8Accumulate::kFast;
+}
+
 }  // namespace
 
 hipError_t SddFp8(const void *aq, const float *a_scales, int k,
                   const void *bq, const float *b_scales, BlockMatrix c,
                   DataType dtype, hipStream_t stream) {
+  return SddFp8(aq, a_scales, k, bq, b_scales, c, dtype, Fp8Accumulate::kFp32,
+                stream);
+}
+
+hipError_t SddFp8(const void *aq, const float *a_scales, int k,
+                  const void *bq, const float *b_scales, BlockMatrix c,
+                  DataType dtype, Fp8Accumulate accumulate,
+                  hipStream_t stream) {
+  if (!Fp8AccumulateOk(accumulate)) return hipErrorInvalidValue;
   if (!Fp8SizesOk(c, k, (int)dtype)) return hipErrorInvalidValue;
   if (c.nonzeros == 0) return hipSuccess;
   if (c.data == nullptr || c.indices == nullptr || c.row_indices == nullptr ||
@@ -422,7 +436,7 @@ hipError_t SddFp8(const void *aq, const float *a_scales, int k,
     if (c.data == in) return hipErrorInvalidValue;
   if (!Aligned16({aq, bq, c.data})) return hipErrorInvalidValue;
   return sputnik_amd::LaunchFp8Gemm(
-      false, (int)dtype, aq, a_scales, bq, b_scales, c.data, nullptr,
+      false, accumulate == Fp8Accumulate::kFast, (int)dtype, aq, a_scales, bq, b_scales, c.data, nullptr,
       static_cast<const short *>(c.indices),
       static_cast<const short *>(c.row_indices), c.rows / 128, c.cols / 128,
       k / 128, c.nonzeros / (128 * 128), stream);
@@ -431,6 +445,14 @@ hipError_t SddFp8(const void *aq, const float *a_scales, int k,
 hipError_t DsdFp8(const BlockMatrix s, const float *s_scales, const void *bq,
                   const float *b_scales, Matrix c, DataType dtype,
                   hipStream_t stream) {
+  return DsdFp8(s, s_scales, bq, b_scales, c, dtype, Fp8Accumulate::kFp32,
+                stream);
+}
+
+hipError_t DsdFp8(const BlockMatrix s, const float *s_scales, const void *bq,
+                  const float *b_scales, Matrix c, DataType dtype,
+                  Fp8Accumulate accumulate, hipStream_t stream) {
+  if (!Fp8AccumulateOk(accumulate)) return hipErrorInvalidValue;
   if (!Fp8SizesOk(s, c.cols, (int)dtype) || c.rows != s.rows)
     return hipErrorInvalidValue;
   if (c.rows == 0 || c.cols == 0) return hipSuccess;
@@ -445,10 +467,26 @@ hipError_t DsdFp8(const BlockMatrix s, const float *s_scales, const void *bq,
     if (c.data == in) return hipErrorInvalidValue;
   if (!Aligned16({s.data, bq, c.data})) return hipErrorInvalidValue;
   return sputnik_amd::LaunchFp8Gemm(
-      true, (int)dtype, s.data, s_scales, bq, b_scales, c.data,
-      static_cast<const int *>(s.offsets),
+      true, accumulate == Fp8Accumulate::kFast, (int)dtype, s.data, s_scales,
+      bq, b_scales, c.data, static_cast<const int *>(s.offsets),
       static_cast<const short *>(s.indices), nullptr, s.rows / 128,
       c.cols / 128, s.cols / 128, s.nonzeros / (128 * 128), stream);
+}
+
+hipError_t Fp8IntervalSums(const void *aq, const void *bq, int m, int n,
+                           int k, Fp8Accumulate accumulate, float *p,
+                           hipStream_t stream) {
+  if (!Fp8AccumulateOk(accumulate)) return hipErrorInvalidValue;
+  if (m < 0 || n < 0 || k < 0 || m % 128 != 0 || n % 128 != 0 ||
+      k % 128 != 0)
+    return hipErrorInvalidValue;
+  if (m == 0 || n == 0 || k == 0) return hipSuccess;
+  if (aq == nullptr || bq == nullptr || p == nullptr)
+    return hipErrorInvalidValue;
+  if (p == aq || p == bq) return hipErrorInvalidValue;
+  if (!Aligned16({aq, bq, p})) return hipErrorInvalidValue;
+  return sputnik_amd::LaunchFp8IntervalSums(
+      aq, bq, m, n, k, accumulate == Fp8Accumulate::kFast, p, stream);
 }
 
 hipError_t Transpose(BlockMatrix a, hipStream_t stream) {

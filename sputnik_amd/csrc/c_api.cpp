@@ -694,6 +694,35 @@ int sputnik_dsd_fp8(const sputnik_block_matrix_t *s, const float *s_scales,
                                 static_cast<hipStream_t>(stream));
 }
 
+int sputnik_sdd_fp8_acc(const void *aq, const float *a_scales, int k,
+                        const void *bq, const float *b_scales,
+                        const sputnik_block_matrix_t *c, int dtype,
+                        int accumulate, void *stream) {
+  if (!c) return hipErrorInvalidValue;
+  return sputnik::block::SddFp8(
+      aq, a_scales, k, bq, b_scales, ToCpp(c), static_cast<DataType>(dtype),
+      static_cast<sputnik::block::Fp8Accumulate>(accumulate),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_dsd_fp8_acc(const sputnik_block_matrix_t *s, const float *s_scales,
+                        const void *bq, const float *b_scales,
+                        const sputnik_matrix_t *c, int dtype, int accumulate,
+                        void *stream) {
+  if (!s || !c) return hipErrorInvalidValue;
+  return sputnik::block::DsdFp8(
+      ToCpp(s), s_scales, bq, b_scales, ToCpp(c), static_cast<DataType>(dtype),
+      static_cast<sputnik::block::Fp8Accumulate>(accumulate),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_fp8_interval_sums(const void *aq, const void *bq, int m, int n,
+                              int k, int accumulate, float *p, void *stream) {
+  return sputnik::block::Fp8IntervalSums(
+      aq, bq, m, n, k, static_cast<sputnik::block::Fp8Accumulate>(accumulate),
+      p, static_cast<hipStream_t>(stream));
+}
+
 // MoE router and device sort (sputnik/block/router.h): moe_router.hip
 // validates.
 int sputnik_router_topk(const void *logits, int32_t *top_experts,

@@ -18,25 +18,32 @@
 //            128-byte rows two rows share a 256-byte bank row, and with that
 //            key every 16-lane group of ds_read_b128 covers its 16 slots
 //            once: conflict-free.
-//   MFMA     the e4m3 bytes are converted to fp16 in registers, exactly
-//            (v_cvt_scalef32_pk_f16_fp8 with scale 1: every e4m3 value is
-//            an fp16 value), and an interval is four
+//   MFMA     kFp32 (the default): the e4m3 bytes are converted to fp16 in
+//            registers, exactly (v_cvt_scalef32_pk_f16_fp8 with scale 1:
+//            every e4m3 value is an fp16 value), and an interval is four
 //            v_mfma_f32_16x16x32_f16 chained from zero. The fp8 forms
 //            (v_mfma_scale_f32_16x16x128_f8f6f4, v_mfma_f32_16x16x32_fp8_fp8)
 //            pass the exact lane-map test but do not sum in fp32: addends
-//            far below the largest product of their group are dropped, an
-//            error of up to 2^-12.4 of sum |terms| on e4m3 data (DESIGN has
-//            the measurement), past the contract's 2^-23 per operation. A
-//            and B take the same (g, byte) -> k assignment, so the sum runs
-//            over matching k whatever that assignment is; rows and columns
-//            are l % 16 and the C/D map is the usual 16 x 16 one.
+//            far below the largest product of their group are dropped
+//            (DESIGN has the measurement), past that mode's 2^-23 per
+//            operation. kFast (Fp8Accumulate::kFast) is the scaled form: the
+//            32 bytes of the two reads go to one
+//            v_mfma_scale_f32_16x16x128_f8f6f4 as they come, both e8m0
+//            scales 2^0, from +0; no convert, twice the MFMA rate. A and B
+//            take the same (g, byte) -> k assignment, so the sum runs over
+//            matching k whatever that assignment is; rows and columns are
+//            l % 16 and the C/D map is the usual 16 x 16 one.
 //   scaling  acc = fma(sa[row] * sb, P, acc) in fp32 with P the interval's
-//            MFMA sum from zero.
+//            MFMA sum from zero, in both modes.
 //   output   round_T(acc) once, through LDS, as 16-byte row pieces.
 //
 // The step order is the k order (SDD) or the row's storage order (DSD), no
 // split-K and no atomics: the same inputs give the same bits. Every index
 // read from device memory is checked before it is used as an address.
+//
+// fp8_interval_sums_kernel is the P of the contract as a callable
+// (Fp8IntervalSums): cold, one wave per 16 x 16 tile and interval, the same
+// two 16-byte reads per lane straight from global memory.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -61,6 +68,7 @@ constexpr int kLdsBytes = kStages * kStageBytes;
 static_assert(kB * kB * 2 <= kLdsBytes, "the output tile reuses the ring");
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -96,6 +104,45 @@ __device__ __forceinline__ f16x8 e4m3_to_f16x8(int lo, int hi) {
   return f16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// The operands of an interval's MFMAs from a lane's two 16-byte reads (k =
+// 16 g .. 16 g + 15 and 64 + 16 g .. 64 + 16 g + 15): four fp16 quarters
+// (kFp32), or the 32 bytes as they come (kFast).
+template <bool kFast>
+struct Fragment;
+template <>
+struct Fragment<false> {
+  f16x8 k[4];
+  __device__ __forceinline__ Fragment() = default;
+  __device__ __forceinline__ Fragment(i32x4 lo, i32x4 hi)
+      : k{e4m3_to_f16x8(lo[0], lo[1]), e4m3_to_f16x8(lo[2], lo[3]),
+          e4m3_to_f16x8(hi[0], hi[1]), e4m3_to_f16x8(hi[2], hi[3])} {}
+};
+template <>
+struct Fragment<true> {
+  i32x8 v;
+  __device__ __forceinline__ Fragment() = default;
+  __device__ __forceinline__ Fragment(i32x4 lo, i32x4 hi)
+      : v{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]} {}
+};
+
+// P of one interval and one 16 x 16 tile, from +0.
+constexpr int kE8m0One = 0x7F7F7F7F;  // 2^0 in every byte
+__device__ __forceinline__ f32x4 interval_sum(const Fragment<false> &a,
+                                              const Fragment<false> &b) {
+  f32x4 sum{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    sum = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.k[q], b.k[q], sum, 0, 0, 0);
+  return sum;
+}
+__device__ __forceinline__ f32x4 interval_sum(const Fragment<true> &a,
+                                              const Fragment<true> &b) {
+  // (cbsz = blgp = 0: both operands e4m3; opsel 0: the scales' byte 0)
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+      a.v, b.v, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0, kE8m0One, 0,
+      kE8m0One);
+}
+
 struct Fp8GemmParams {
   const char *a;          // SDD: Aq [m, k]; DSD: the stored blocks of Sq
   const float *a_scales;  // SDD: [m, k / 128]; DSD: [nnz_blocks * 128]
@@ -108,7 +155,7 @@ struct Fp8GemmParams {
   int m_blocks, n_blocks, k_blocks, nnz_blocks;
 };
 
-template <typename T, bool kDsd>
+template <typename T, bool kDsd, bool kFast>
 __global__ void __launch_bounds__(kThreads)
     fp8_gemm_kernel(const Fp8GemmParams p) {
   __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
@@ -187,9 +234,8 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
-  // A 16-row fragment of an operand image: chunks g and g + 4 of row r, as
-  // the operands of the interval's four MFMAs (8 bytes each).
-  struct Fragment { f16x8 k[4]; };
+  // A 16-row fragment of an operand image: chunks g and g + 4 of row r.
+  using Frag = Fragment<kFast>;
   auto fragment = [&](const char *image, int row0) {
     const int row = row0 + r;
     const char *at = image + row * kB;
@@ -197,8 +243,7 @@ __global__ void __launch_bounds__(kThreads)
     const i32x4 lo = *reinterpret_cast<const i32x4 *>(at + ((g ^ key) << 4));
     const i32x4 hi =
         *reinterpret_cast<const i32x4 *>(at + (((g + 4) ^ key) << 4));
-    return Fragment{{e4m3_to_f16x8(lo[0], lo[1]), e4m3_to_f16x8(lo[2], lo[3]),
-                     e4m3_to_f16x8(hi[0], hi[1]), e4m3_to_f16x8(hi[2], hi[3])}};
+    return Frag(lo, hi);
   };
 
   auto compute = [&](int i, const char *stage) {
@@ -207,7 +252,7 @@ __global__ void __launch_bounds__(kThreads)
     const float sb = scalar_float(p.b_scales + (long long)kb * p.n_blocks + nb);
     const float *sa_lds =
         reinterpret_cast<const float *>(stage + 2 * kTileBytes);
-    Fragment a[4];
+    Frag a[4];
     f32x4 s[4];
 #pragma unroll
     for (int ti = 0; ti < 4; ++ti) {
@@ -218,14 +263,10 @@ __global__ void __launch_bounds__(kThreads)
     }
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj) {
-      const Fragment b = fragment(stage + kTileBytes, wn * 64 + tj * 16);
+      const Frag b = fragment(stage + kTileBytes, wn * 64 + tj * 16);
 #pragma unroll
       for (int ti = 0; ti < 4; ++ti) {
-        f32x4 sum{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          sum = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ti].k[q], b.k[q],
-                                                       sum, 0, 0, 0);
+        const f32x4 sum = interval_sum(a[ti], b);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           acc[ti][tj][e] = __builtin_fmaf(s[ti][e], sum[e], acc[ti][tj][e]);
@@ -273,9 +314,50 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// P [k / 128, m, n] of aq [m, k] and bq [n, k]: workgroup (kb, tm, tn) is
+// one wave and one 16 x 16 tile of one interval.
+template <bool kFast>
+__global__ void __launch_bounds__(64)
+    fp8_interval_sums_kernel(const char *aq, const char *bq, float *out,
+                             int m, int n, int k) {
+  const int lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+  const int tiles_n = n >> 4, tiles_m = m >> 4;
+  const int tn = blockIdx.x % tiles_n;
+  const int tm = blockIdx.x / tiles_n % tiles_m;
+  const int kb = blockIdx.x / tiles_n / tiles_m;
+  auto fragment = [&](const char *base, int row0) {
+    const char *at = base + (long long)(row0 + r) * k + (long long)kb * kB;
+    return Fragment<kFast>(
+        *reinterpret_cast<const i32x4 *>(at + 16 * g),
+        *reinterpret_cast<const i32x4 *>(at + 64 + 16 * g));
+  };
+  const f32x4 sum =
+      interval_sum(fragment(aq, tm * 16), fragment(bq, tn * 16));
+  float *tile = out + ((long long)kb * m + tm * 16 + 4 * g) * n + tn * 16 + r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) tile[(long long)e * n] = sum[e];
+}
+
 }  // namespace
 
-hipError_t LaunchFp8Gemm(bool dsd, int dtype, const void *a,
+hipError_t LaunchFp8IntervalSums(const void *aq, const void *bq, int m, int n,
+                                 int k, bool fast, float *out,
+                                 hipStream_t stream) {
+  const long long tiles = (long long)(m / 16) * (n / 16) * (k / kB);
+  if (tiles == 0) return hipSuccess;
+  if (tiles > INT_MAX) return hipErrorInvalidValue;
+  const char *a = static_cast<const char *>(aq);
+  const char *b = static_cast<const char *>(bq);
+  if (fast)
+    hipLaunchKernelGGL(fp8_interval_sums_kernel<true>, dim3((unsigned)tiles),
+                       dim3(64), 0, stream, a, b, out, m, n, k);
+  else
+    hipLaunchKernelGGL(fp8_interval_sums_kernel<false>, dim3((unsigned)tiles),
+                       dim3(64), 0, stream, a, b, out, m, n, k);
+  return hipGetLastError();
+}
+
+hipError_t LaunchFp8Gemm(bool dsd, bool fast, int dtype, const void *a,
                          const float *a_scales, const void *b,
                          const float *b_scales, void *c, const int *offsets,
                          const short *indices, const short *row_indices,
@@ -289,16 +371,21 @@ hipError_t LaunchFp8Gemm(bool dsd, int dtype, const void *a,
                         static_cast<const char *>(b), b_scales, c, offsets,
                         indices, row_indices, m_blocks, n_blocks, k_blocks,
                         nnz_blocks};
-  auto launch = [&](auto t, auto d) {
-    hipLaunchKernelGGL((fp8_gemm_kernel<decltype(t), decltype(d)::value>),
+  auto launch = [&](auto t, auto d, auto f) {
+    hipLaunchKernelGGL((fp8_gemm_kernel<decltype(t), decltype(d)::value,
+                                        decltype(f)::value>),
                        dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
     return hipGetLastError();
   };
+  auto kind = [&](auto t, auto d) {
+    return fast ? launch(t, d, std::true_type{})
+                : launch(t, d, std::false_type{});
+  };
   if (dsd)
-    return dtype == 1 ? launch(__bf16{}, std::true_type{})
-                      : launch(_Float16{}, std::true_type{});
-  return dtype == 1 ? launch(__bf16{}, std::false_type{})
-                    : launch(_Float16{}, std::false_type{});
+    return dtype == 1 ? kind(__bf16{}, std::true_type{})
+                      : kind(_Float16{}, std::true_type{});
+  return dtype == 1 ? kind(__bf16{}, std::false_type{})
+                    : kind(_Float16{}, std::false_type{});
 }
 
 }  // namespace sputnik_amd

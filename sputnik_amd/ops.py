@@ -49,7 +49,8 @@ The fp8 forward path (sputnik/block/fp8.h; e4m3 elements with fp32 block
 scales, forward only) is `quantize_rows`, `quantize_sparse` and
 `quantize_weight` -> `Fp8Weight`, the products `sdd_fp8` / `dsd_fp8`, and
 `moe_mlp_fp8`, moe_mlp with its expert products in fp8 while gather, scatter
-and router stay 16-bit.
+and router stay 16-bit; the three take `accumulate="fp32"` (the default) or
+`"fast"`, the scaled e4m3 MFMA per k-block (Fp8Accumulate in fp8.h).
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -78,7 +79,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                BlockColumnSum, MatmulBias, MatmulBiasActivation,
                MatmulBiasGated, PaddedScatterBias, PaddedScatterBiasGrad,
                PaddedScatterBiasWeightGrad,
-               QuantizeRows, QuantizeWeight, SddFp8, DsdFp8,
+               QuantizeRows, QuantizeWeight, SddFp8, DsdFp8, FP8_ACCUMULATE,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
                RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
                MOE_SORT_CHUNK, ROUTER_AUX_TOKENS, ROUTER_MAX_EXPERTS,
@@ -1516,13 +1517,27 @@ def _out_dtype(out_dtype, what: str):
                         "torch.bfloat16")
 
 
+def _accumulate(accumulate, what: str) -> str:
+    """"fp32" or "fast" (sputnik/block/fp8.h, Fp8Accumulate); raises before
+    any GPU call."""
+    if not isinstance(accumulate, str) or accumulate not in FP8_ACCUMULATE:
+        raise ValueError(f"{what}: accumulate must be 'fp32' or 'fast', not "
+                         f"{accumulate!r}")
+    return accumulate
+
+
 def sdd_fp8(xq: torch.Tensor, xs: torch.Tensor, w: Fp8Weight,
-            topo: SparseMatrix, out_dtype=torch.bfloat16) -> SparseMatrix:
+            topo: SparseMatrix, out_dtype=torch.bfloat16,
+            accumulate: str = "fp32") -> SparseMatrix:
     """(xq . w) at topo's nonzero blocks, the product in fp8: xq / xs from
     quantize_rows ([m, k] and [m, k / 128]), w an Fp8Weight of [k, n], topo
     [m, n]. Per 128-wide k-block the e4m3 products are summed by the matrix
     cores in fp32 and added as (xs * w.scales) * sum; the block values are
-    rounded once to `out_dtype`. Bitwise reproducible. Forward only."""
+    rounded once to `out_dtype`. Bitwise reproducible. Forward only.
+    `accumulate="fast"` opts into the scaled e4m3 MFMA for the k-block sums:
+    twice the matrix-core rate, the sums at that instruction's limited
+    precision (fp8.h has the bound), still bitwise reproducible."""
+    _accumulate(accumulate, "sdd_fp8")
     if not isinstance(w, Fp8Weight):
         raise TypeError("sdd_fp8: w must be an Fp8Weight")
     if not isinstance(topo, SparseMatrix) or topo.is_transposed():
@@ -1538,16 +1553,19 @@ def sdd_fp8(xq: torch.Tensor, xs: torch.Tensor, w: Fp8Weight,
     data = torch.empty(topo.nnz_blocks, BLOCK, BLOCK, dtype=out_dtype,
                        device=xq.device)
     topo._meta.ensure_row_indices(data)
-    SddFp8(xq, xs, w.q, w.scales, topo._meta.descriptor(data))
+    SddFp8(xq, xs, w.q, w.scales, topo._meta.descriptor(data),
+           accumulate=accumulate)
     return topo.with_data(data)
 
 
-def dsd_fp8(sq: Fp8SparseMatrix, w: Fp8Weight,
-            out_dtype=torch.bfloat16) -> torch.Tensor:
+def dsd_fp8(sq: Fp8SparseMatrix, w: Fp8Weight, out_dtype=torch.bfloat16,
+            accumulate: str = "fp32") -> torch.Tensor:
     """sq . w as a dense [m, n] tensor of `out_dtype`, the product in fp8:
     sq from quantize_sparse ([m, k]), w an Fp8Weight of [k, n]. Arithmetic as
     sdd_fp8, over the stored blocks of each block row in storage order; a
-    block row without blocks gives +0 rows. Forward only."""
+    block row without blocks gives +0 rows. Forward only. `accumulate` as
+    sdd_fp8."""
+    _accumulate(accumulate, "dsd_fp8")
     if not isinstance(sq, Fp8SparseMatrix):
         raise TypeError("dsd_fp8: sq must come from quantize_sparse")
     if not isinstance(w, Fp8Weight):
@@ -1557,7 +1575,7 @@ def dsd_fp8(sq: Fp8SparseMatrix, w: Fp8Weight,
         raise ValueError(f"dsd_fp8 shapes {sq.shape} x {w.shape}")
     out = torch.empty(sq.shape[0], w.n, dtype=out_dtype, device=sq.device)
     DsdFp8(sq._descriptor(), sq.scales, w.q, w.scales,
-           Matrix(out.shape[0], out.shape[1], out))
+           Matrix(out.shape[0], out.shape[1], out), accumulate=accumulate)
     return out
 
 
@@ -1565,7 +1583,8 @@ def moe_mlp_fp8(x: torch.Tensor, top_experts: torch.Tensor,
                 expert_weights: torch.Tensor, w1q: Fp8Weight, w2q: Fp8Weight,
                 num_experts: int, activation=None,
                 v1q: Optional[Fp8Weight] = None,
-                rows: Optional[int] = None) -> torch.Tensor:
+                rows: Optional[int] = None,
+                accumulate: str = "fp32") -> torch.Tensor:
     """moe_mlp with the expert products in fp8 (e4m3 elements, fp32 scales
     per 1 x 128 activation tile and per 128 x 128 weight block, the recipe of
     DeepSeek-V3 checkpoints; sputnik/block/fp8.h): padded_gather ->
@@ -1579,7 +1598,9 @@ def moe_mlp_fp8(x: torch.Tensor, top_experts: torch.Tensor,
     (quantize_weight, Fp8Weight.from_tensors). Arguments, defaults and route
     handling are moe_mlp's; there are no biases. Forward only: the output
     carries no gradient, and a tensor that requires grad while grad mode is
-    on is a ValueError."""
+    on is a ValueError. `accumulate` ("fp32", the default, or "fast") is
+    passed to the two (three) products; everything else is unchanged."""
+    _accumulate(accumulate, "moe_mlp_fp8")
     _no_grad("moe_mlp_fp8", x, expert_weights)
     route, hidden = _moe_args(x, top_experts, expert_weights, w1q, w2q, v1q,
                               num_experts, rows, fp8=True)
@@ -1590,13 +1611,14 @@ def moe_mlp_fp8(x: torch.Tensor, top_experts: torch.Tensor,
     topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
                            route.rows // BLOCK, dtype=x.dtype)
     xq, xs = quantize_rows(xp)
-    g = sdd_fp8(xq, xs, w1q, topo, x.dtype)
+    g = sdd_fp8(xq, xs, w1q, topo, x.dtype, accumulate)
     if v1q is None:
         hq = quantize_sparse(g, "gelu" if act is None else act)
     else:
-        u = sdd_fp8(xq, xs, v1q, topo, x.dtype)
+        u = sdd_fp8(xq, xs, v1q, topo, x.dtype, accumulate)
         hq = quantize_sparse(u, "silu" if act is None else act, gate=g)
-    return padded_scatter(dsd_fp8(hq, w2q, x.dtype), route, expert_weights)
+    return padded_scatter(dsd_fp8(hq, w2q, x.dtype, accumulate), route,
+                          expert_weights)
 
 
 # ---- MoE router -------------------------------------------------------------
