@@ -1,8 +1,11 @@
-// sputnik-amd: FP8 (e4m3) expert products with DeepSeek-style block scales,
-// forward only: quantisers, an fp8 SDD and an fp8 DSD. The 128 x 128 BCSR
-// block is the scale block of that recipe: a weight scale block is a sparse
-// block, an activation scale tile is one row of a block, one k-step of the
-// kernel is one scale interval. No counterpart in the reference.
+// sputnik-amd: FP8 (e4m3) expert products with DeepSeek-style block scales:
+// quantisers, an fp8 SDD and an fp8 DSD for the forward pass, and for the
+// gradients (below, "Gradients") quantisers along the token dimension, an
+// exact transpose of a quantised weight and a DSD whose dense operand is
+// scaled per column. The 128 x 128 BCSR block is the scale block of that
+// recipe: a weight scale block is a sparse block, an activation scale tile
+// is one row of a block, one k-step of the kernel is one scale interval.
+// Extensions, all of them: no counterpart in the reference.
 //
 // Format (part of the contract):
 //
@@ -133,6 +136,82 @@
 //                     m, n and k multiples of 128; aq, bq and p non-null,
 //                     16-byte aligned, p none of the inputs.
 //
+// Gradients (extensions like everything here; the table reads X [T, h], W1t
+// [F, h], W2 [F, h], topology [T, F], Z = X W1t^T at the blocks, H = act(Z),
+// Y = H W2):
+//
+//   dH  = dY W2^T at the blocks   SddFp8: dY in row tiles (QuantizeRows), W2
+//                                 as [n = F, k = h] bytes
+//   dZ  = dH * act'(Z)            QuantizeBlocks, stage kActivationGrad
+//   dX  = dZ W1t                  DsdFp8: dZ in row tiles, storage order;
+//                                 W1t as [n = h, k = F] bytes
+//   dW2  = H^T dY   [F, h]        DsdFp8Wgrad: H^T's blocks in the transposed
+//   dW1t = dZ^T X   [F, h]        order with one scale per source column
+//                                 (QuantizeBlocks' column outputs), dY / X in
+//                                 128 x 1 column tiles, stored [h, T]
+//                                 (QuantizeTiles' column outputs)
+//
+//   QuantizeTiles  x [rows, cols] of T, both multiples of 128, read once, one
+//                  workgroup per 128 x 128 tile. Row outputs q [rows, cols],
+//                  scales [rows, cols / 128]: QuantizeRows' bits. Column
+//                  outputs qt [cols, rows] (the bytes of a column contiguous
+//                  along the rows) and scales_t [rows / 128, cols]: the tile
+//                  of scales_t[rb, c] is x[128 rb : 128 rb + 128, c], scale
+//                  and element rules as above. Either pair may be null (both
+//                  pointers of it), not both pairs.
+//   QuantizeBlocks the block values [nnz_blocks, 128, 128] of s (s.data, T)
+//                  after a stage: kNone; kActivation, act(x) as
+//                  QuantizeRowsActivation evaluates it; kActivationGrad, x *
+//                  act'(z) as MatmulActivationGrad's elementwise stage
+//                  evaluates it (z: block values of the same layout), rounded
+//                  to T before it is quantised. Row outputs q [nnz_blocks,
+//                  128, 128], scales [nnz_blocks 128], in storage order:
+//                  the row quantisers' bits on the same values. Column
+//                  outputs in the transposed order: output block j is source
+//                  block s.block_offsets[j] stored transposed ([column][row])
+//                  with scales_t[128 j + c] for source column c. They are
+//                  the Sq / s_scales of a DSD over the descriptor {rows =
+//                  s.cols, cols = s.rows, offsets = s.offsets_t, indices =
+//                  s.indices_t}. Column outputs need s.block_offsets
+//                  (Transpose), hipErrorInvalidValue without; an entry
+//                  outside [0, nnz_blocks) leaves its output block unwritten.
+//                  The workgroup of output block j also writes the row
+//                  outputs of its source block when both pairs are asked
+//                  for, so block_offsets is then a permutation, as Transpose
+//                  leaves it. Only s.data, s.nonzeros, s.block_size and
+//                  s.block_offsets are read.
+//   TransposeWeightFp8
+//                  q [n, k] with scales [k / 128, n / 128] -> qt [k, n] with
+//                  scales_t [n / 128, k / 128]: a byte transpose, exact. A
+//                  block's scale depends on the block's amax alone, so the
+//                  result is QuantizeWeight of the transposed 16-bit weight,
+//                  bit for bit: the backward layout of a weight that exists
+//                  only as fp8.
+//   DsdFp8Wgrad    C [m, n] = Sq . Bq as DsdFp8, with b_scales [k / 128, n]:
+//                  one scale per interval and output column, as
+//                  QuantizeTiles' scales_t. Per interval, in the row's
+//                  storage order, s = float32(sa[row] * sb[kb, col]) and acc
+//                  = fma(s, P, acc); P as the mode defines it above, kFp32
+//                  and kFast alike. C = round_out(acc), or with `add`
+//                  round_out(acc + float(C_old)): one fp32 add, one rounding.
+//                  `out` (accumulate.h) is kOperand, C of T, or kF32, C of
+//                  fp32. A block row of s without stored blocks gives +0
+//                  rows, and with `add` is neither read nor written, as
+//                  MatmulAccumulate has it. No split-K, no atomics, no
+//                  hand-off between workgroups: the same inputs give the
+//                  same bits. Out-of-range indices, alignment (Sq, Bq and C
+//                  16 bytes), checks and zero-sized work as DsdFp8; C being
+//                  any input is rejected. Error, in the form above:
+//                    |C - exact| <= 2^-p |exact|
+//                                   + (K + 2 K / 128 + 1) 2^-23 sum |terms|
+//                  (kFast: eps_fast + (2 K / 128 + 2) 2^-23 in place of the
+//                  last factor): the scale product is still one rounding per
+//                  interval and the fma another; the + 1 is the fp32 add of
+//                  C_old, which with `add` is one of the terms, of exact and
+//                  of sum |terms| alike. p = 11 (fp16) or 8 (bf16); the
+//                  first summand is absent for fp32 output, which is not
+//                  rounded again.
+//
 // `dtype` is T, the 16-bit type (DataType keeps its two values). Every call
 // is stream-ordered, allocates nothing and never synchronises or aborts:
 // hipErrorInvalidValue, with nothing launched, for a null required buffer, a
@@ -141,12 +220,16 @@
 // also for an Aq / Sq / Bq / C that is not 16-byte aligned (the quantisers
 // take any alignment). Zero-sized work succeeds.
 //
-// Out of scope: gradients, e5m2, other operand layouts (weights are re-laid
-// once by QuantizeWeight), DDS / SSD / SDS / DSS in fp8, e8m0 hardware
-// scales, fp8 outputs from the GEMM epilogue.
+// Out of scope: GLU gradients in fp8 (the kOutGateGrad stage makes them a
+// follow-up with the same kernels), e5m2 (gradients included), other operand
+// layouts (weights are re-laid once by QuantizeWeight and
+// TransposeWeightFp8), DDS / SSD / SDS / DSS in fp8, e8m0 hardware scales,
+// fp8 outputs from the GEMM epilogue, caching quantised weights across
+// micro-batches, biases and the router.
 #ifndef SPUTNIK_BLOCK_FP8_H_
 #define SPUTNIK_BLOCK_FP8_H_
 
+#include "sputnik/block/accumulate.h"
 #include "sputnik/block/activation.h"
 #include "sputnik/block/arguments.h"
 #include "sputnik/block/dtype.h"
@@ -197,6 +280,31 @@ hipError_t DsdFp8(const BlockMatrix s, const float *s_scales, const void *bq,
 hipError_t Fp8IntervalSums(const void *aq, const void *bq, int m, int n,
                            int k, Fp8Accumulate accumulate, float *p,
                            hipStream_t stream);
+
+// ---- Gradients (above). Extensions: no counterpart in the reference. ----
+
+// What QuantizeBlocks applies to the block values before it quantises them.
+enum class Fp8Stage { kNone = 0, kActivation = 1, kActivationGrad = 2 };
+
+hipError_t QuantizeTiles(const void *x, int rows, int cols, void *q,
+                         float *scales, void *qt, float *scales_t, bool pow2,
+                         DataType dtype, hipStream_t stream);
+
+// `activation` is read when `stage` is not kNone, `z` when it is
+// kActivationGrad.
+hipError_t QuantizeBlocks(const BlockMatrix s, Fp8Stage stage,
+                          Activation activation, const void *z, void *q,
+                          float *scales, void *qt, float *scales_t, bool pow2,
+                          DataType dtype, hipStream_t stream);
+
+hipError_t TransposeWeightFp8(const void *q, const float *scales, int k,
+                              int n, void *qt, float *scales_t,
+                              hipStream_t stream);
+
+hipError_t DsdFp8Wgrad(const BlockMatrix s, const float *s_scales,
+                       const void *bq, const float *b_scales, Matrix c,
+                       DataType dtype, OutputType out, bool add,
+                       Fp8Accumulate accumulate, hipStream_t stream);
 
 }  // namespace block
 }  // namespace sputnik

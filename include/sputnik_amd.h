@@ -650,6 +650,45 @@ int sputnik_dsd_fp8_acc(const sputnik_block_matrix_t *s, const float *s_scales,
                         void *stream);
 int sputnik_fp8_interval_sums(const void *aq, const void *bq, int m, int n,
                               int k, int accumulate, float *p, void *stream);
+/* The gradients' pieces (sputnik/block/fp8.h, "Gradients", has the contract
+ * and the table of the backward pass).
+ *
+ *   sputnik_quantize_tiles   x [rows, cols] of T, both multiples of 128 ->
+ *                            the row outputs of sputnik_quantize_rows (q,
+ *                            scales) and / or the column outputs qt [cols,
+ *                            rows], scales_t [rows / 128, cols], one scale
+ *                            per 128 x 1 column tile. A pair may be null.
+ *   sputnik_quantize_blocks  the block values of s after `stage` (0 none,
+ *                            1 act(x), 2 x * act'(z)): row outputs in
+ *                            storage order (q, scales [blocks * 128]) and /
+ *                            or column outputs in the transposed order of
+ *                            s.block_offsets (qt: output block j is source
+ *                            block block_offsets[j] transposed; scales_t
+ *                            [blocks * 128], one per source column)
+ *   sputnik_fp8_transpose_weight
+ *                            q [n, k], scales [k / 128, n / 128] -> qt
+ *                            [k, n], scales_t [n / 128, k / 128], exact
+ *   sputnik_dsd_fp8_wgrad    sputnik_dsd_fp8_acc with b_scales [s.cols /
+ *                            128, c.cols], one per interval and column:
+ *                            acc = fma(sa[row] * sb[kb, col], P, acc). `out`
+ *                            0: C of T, 1: C of fp32; `add`: C = round(acc +
+ *                            float(C)), and block rows of s without blocks
+ *                            are left untouched. */
+int sputnik_quantize_tiles(const void *x, int rows, int cols, void *q,
+                           float *scales, void *qt, float *scales_t, int pow2,
+                           int dtype, void *stream);
+int sputnik_quantize_blocks(const sputnik_block_matrix_t *s, int stage,
+                            int act, const void *z, void *q, float *scales,
+                            void *qt, float *scales_t, int pow2, int dtype,
+                            void *stream);
+int sputnik_fp8_transpose_weight(const void *q, const float *scales, int k,
+                                 int n, void *qt, float *scales_t,
+                                 void *stream);
+int sputnik_dsd_fp8_wgrad(const sputnik_block_matrix_t *s,
+                          const float *s_scales, const void *bq,
+                          const float *b_scales, const sputnik_matrix_t *c,
+                          int dtype, int out, int add, int accumulate,
+                          void *stream);
 
 /* ---- Host-only queries (no GPU work; safe without a device) */
 /* 1 when the reference would accept the problem (same rules as

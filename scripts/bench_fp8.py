@@ -8,6 +8,14 @@ products of another build of libsputnik.so (the commit before a change) run
 as two more arms of the same process and rounds, through the same Python
 path. Recorded, not gated (DESIGN "FP8 forward path").
 
+With --backward the arms are those of the backward pass instead (DESIGN "FP8
+backward path"): quantize_tiles of dY and quantize_blocks with the
+activation gradient (both axes each), dsd_fp8_wgrad in both modes next to the
+16-bit H^T dY (ops' raw dsd of the transposed view), and the whole backward
+of ops.mlp_fp8 in both modes next to that of the 16-bit ops.mlp, each as
+torch.autograd.grad over a retained graph, so that only backward is timed.
+ops.mlp's code is the parent commit's, so it is the baseline as it stands.
+
 Protocol: one process, HIP events, every arm warmed for at
 least --warm-ms of device time, then --rounds interleaved rounds, each window
 long enough to hold at least --load-ms of back-to-back calls; medians and
@@ -52,6 +60,8 @@ def main():
     ap.add_argument("--parent-lib", default="",
                     help="another libsputnik.so: its sdd_fp8 / dsd_fp8 run as "
                          "the *_parent arms")
+    ap.add_argument("--backward", action="store_true",
+                    help="time the backward pass instead of the forward one")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -129,6 +139,38 @@ def main():
         if parent is not None:
             arms["sdd_fp8_parent"] = through_parent(arms["sdd_fp8"])
             arms["dsd_fp8_parent"] = through_parent(arms["dsd_fp8"])
+        if a.backward:
+            dy = rand(rows, D_MODEL)
+            dh16 = g16.with_data(rand(blocks, 128, 128))
+            _, _, dyqt, dyst = ops.quantize_tiles(dy, rows=False)
+            ht = ops.quantize_sparse_t(g16, "gelu")
+            w1t = w1.t().contiguous()
+
+            def backward_of(fn, *leaves):
+                leaves = [t.detach().requires_grad_() for t in leaves]
+                y = fn(*leaves)
+                return lambda: torch.autograd.grad(y, leaves, dy,
+                                                   retain_graph=True)
+
+            arms = {
+                "quantize_tiles": lambda: ops.quantize_tiles(dy),
+                "quantize_blocks_gelu_grad": lambda: ops._quantize_blocks(
+                    dh16, "act_grad", 1, g16.data, True, True, False),
+                "wgrad_bf16": lambda: ops._dsd(h16.t(), dy),
+                "wgrad_fp8": lambda: ops.dsd_fp8_wgrad(ht, dyqt, dyst,
+                                                       out_dtype=dt),
+                "wgrad_fp8_fast": lambda: ops.dsd_fp8_wgrad(
+                    ht, dyqt, dyst, out_dtype=dt, accumulate="fast"),
+                "mlp_bf16_backward": backward_of(
+                    lambda x_, a_, b_: ops.mlp(x_, a_, b_, topo, "gelu"),
+                    x, w1, w2),
+                "mlp_fp8_backward": backward_of(
+                    lambda x_, a_, b_: ops.mlp_fp8(x_, a_, b_, topo, "gelu"),
+                    x, w1t, w2),
+                "mlp_fp8_fast_backward": backward_of(
+                    lambda x_, a_, b_: ops.mlp_fp8(x_, a_, b_, topo, "gelu",
+                                                   "fast"), x, w1t, w2),
+            }
         calls = {}
         for name, fn in arms.items():
             fn()
@@ -144,9 +186,17 @@ def main():
                 times[name].append(window(fn, calls[name]))
         flops = 2.0 * blocks * 128 * 128
         work = {name: flops * D_MODEL for name in arms
-                if name.startswith(("sdd_", "dsd_"))}
+                if name.startswith(("sdd_", "dsd_", "wgrad_"))}
+        # (the backward of an MLP is four products of that size)
+        work.update({name: 4 * flops * D_MODEL for name in arms
+                     if name.endswith("_backward")})
+        # (both axes: 2 bytes read and 2 written per element and two scales
+        # per 128; the activation gradient reads Z as well)
         moved = {"quantize_rows": rows * D_MODEL * 3 + rows * D_MODEL // 32,
-                 "quantize_sparse_gelu": blocks * 16384 * 3 + blocks * 512}
+                 "quantize_sparse_gelu": blocks * 16384 * 3 + blocks * 512,
+                 "quantize_tiles": rows * D_MODEL * 4 + rows * D_MODEL // 16,
+                 "quantize_blocks_gelu_grad": blocks * 16384 * 6
+                 + blocks * 1024}
         line = {"shape": shape, "rows": rows, "blocks": blocks,
                 "build": sp.build_hash(), "rounds": a.rounds, "arms": {}}
         if parent is not None:
@@ -163,8 +213,16 @@ def main():
                 arm["tb_per_s"] = round(tbs, 3)
                 arm["hbm_share"] = round(tbs / HBM_TBS, 3)
             line["arms"][name] = arm
-        for op in ("sdd", "dsd"):
-            us = {name: arm["us"] for name, arm in line["arms"].items()}
+        us = {name: arm["us"] for name, arm in line["arms"].items()}
+        if a.backward:
+            line["pass"] = "backward"
+            for name in ("wgrad_fp8", "wgrad_fp8_fast"):
+                line[f"{name}_over_bf16"] = round(
+                    us[name] / us["wgrad_bf16"], 3)
+            for name in ("mlp_fp8_backward", "mlp_fp8_fast_backward"):
+                line[f"{name}_over_bf16"] = round(
+                    us[name] / us["mlp_bf16_backward"], 3)
+        for op in () if a.backward else ("sdd", "dsd"):
             line[f"{op}_fp8_over_bf16"] = round(
                 us[f"{op}_fp8"] / us[f"{op}_bf16"], 3)
             line[f"{op}_fp8_fast_over_bf16"] = round(

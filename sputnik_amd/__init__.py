@@ -247,6 +247,18 @@ _SIGNATURES = {
                             _P],
     "sputnik_fp8_interval_sums": [_P, _P, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_int, ctypes.c_int, _P, _P],
+    # the gradients' pieces: (x, rows, cols, q, scales, qt, scales_t, pow2,
+    # dtype, stream); (s, stage, act, z, q, scales, qt, scales_t, pow2, dtype,
+    # stream); (q, scales, k, n, qt, scales_t, stream); (s, s_scales, bq,
+    # b_scales, c, dtype, out, add, accumulate, stream)
+    "sputnik_quantize_tiles": [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
+                               ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_quantize_blocks": [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P,
+                                _P, _P, ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_fp8_transpose_weight": [_P, _P, ctypes.c_int, ctypes.c_int, _P,
+                                     _P, _P],
+    "sputnik_dsd_fp8_wgrad": [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
+                              ctypes.c_int, ctypes.c_int, _P],
     "sputnik_can_implement": [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_abi_block_matrix_size": [],
     "sputnik_abi_block_matrix_offset": [ctypes.c_int],
@@ -1929,6 +1941,131 @@ def Fp8IntervalSums(aq, bq, p, accumulate="fp32", stream=None):  # noqa: N802
         "Fp8IntervalSums")
 
 
+FP8_STAGES = {None: 0, "act": 1, "act_grad": 2}
+
+
+def _fp8_pair(q, scales, q_shape, s_shape, what: str):
+    """An output pair of a tile quantiser: both given or both None."""
+    import torch
+
+    if (q is None) != (scales is None):
+        raise ValueError(f"{what}: an output pair is given whole or not at "
+                         "all")
+    if q is not None:
+        _fp8_buffer(q, torch.float8_e4m3fn, q_shape, f"{what} bytes")
+        _fp8_buffer(scales, torch.float32, s_shape, f"{what} scales")
+    return _ptr(q) if q is not None else None, (
+        _ptr(scales) if scales is not None else None)
+
+
+def QuantizeTiles(x, q=None, scales=None, qt=None, scales_t=None,  # noqa: N802
+                  pow2=False, stream=None):
+    """x [rows, cols] (fp16 / bf16, both multiples of 128) quantised along
+    either axis or both, read once: the row pair q [rows, cols], scales
+    [rows, cols / 128] is QuantizeRows' bit for bit; the column pair qt
+    (e4m3 [cols, rows]) and scales_t (fp32 [rows / 128, cols]) has one scale
+    per 128 x 1 column tile (sputnik_quantize_tiles)."""
+    _moe_matrix(x, None, None, "x")
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    rt = _fp8_tiles(rows, "QuantizeTiles: rows")
+    ct = _fp8_tiles(cols, "QuantizeTiles: cols")
+    pq, ps = _fp8_pair(q, scales, (rows, cols), (rows, ct), "QuantizeTiles: row")
+    pt, pst = _fp8_pair(qt, scales_t, (cols, rows), (rt, cols),
+                        "QuantizeTiles: column")
+    if q is None and qt is None:
+        raise ValueError("QuantizeTiles: no output")
+    _check(lib().sputnik_quantize_tiles(
+        _ptr(x), rows, cols, pq, ps, pt, pst, int(bool(pow2)), _dtype_code(x),
+        _stream(stream)), "QuantizeTiles")
+
+
+def QuantizeBlocks(s, q=None, scales=None, qt=None, scales_t=None,  # noqa: N802
+                   stage=None, activation=None, z=None, pow2=False,
+                   stream=None):
+    """The block values of the BlockMatrix s (fp16 / bf16) after `stage`
+    (None; "act": act(x); "act_grad": x * act'(z), z block values like
+    s.data), quantised along either axis or both: the row pair q [blocks,
+    128, 128], scales [blocks * 128] in storage order, as QuantizeRows over
+    the same values; the column pair in the transposed order, output block j
+    being source block s.block_offsets[j] stored transposed, with scales_t
+    [blocks * 128] per source column (sputnik_quantize_blocks)."""
+    import torch
+
+    if not isinstance(s, BlockMatrix):
+        raise TypeError("QuantizeBlocks takes a BlockMatrix")
+    if stage not in FP8_STAGES:
+        raise ValueError(f"QuantizeBlocks: stage must be one of "
+                         f"{list(FP8_STAGES)}")
+    nb = s.num_blocks
+    if s.data.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("QuantizeBlocks: s.data must be fp16 / bf16")
+    act = 0 if stage is None else _act_code(activation)
+    if stage == "act_grad":
+        _fp8_buffer(z, s.data.dtype, tuple(s.data.shape), "z")
+    pq, ps = _fp8_pair(q, scales, (nb, 128, 128), (nb * 128,),
+                       "QuantizeBlocks: row")
+    pt, pst = _fp8_pair(qt, scales_t, (nb, 128, 128), (nb * 128,),
+                        "QuantizeBlocks: column")
+    if q is None and qt is None:
+        raise ValueError("QuantizeBlocks: no output")
+    cs = s._c()
+    _check(lib().sputnik_quantize_blocks(
+        ctypes.byref(cs), FP8_STAGES[stage], act,
+        _ptr(z) if stage == "act_grad" else None, pq, ps, pt, pst,
+        int(bool(pow2)), _dtype_code(s.data), _stream(stream)),
+        "QuantizeBlocks")
+
+
+def TransposeWeightFp8(q, scales, qt, scales_t, stream=None):  # noqa: N802
+    """qt (e4m3 [k, n]) and scales_t (fp32 [n / 128, k / 128]) of a quantised
+    weight q [n, k], scales [k / 128, n / 128]: the byte transpose, which is
+    QuantizeWeight of the transposed weight bit for bit
+    (sputnik_fp8_transpose_weight)."""
+    import torch
+
+    n, k = _fp8_weight(q, scales, "TransposeWeightFp8")
+    _fp8_buffer(qt, torch.float8_e4m3fn, (k, n), "qt")
+    _fp8_buffer(scales_t, torch.float32, (n // 128, k // 128), "scales_t")
+    _check(lib().sputnik_fp8_transpose_weight(
+        _ptr(q), _ptr(scales), k, n, _ptr(qt), _ptr(scales_t),
+        _stream(stream)), "TransposeWeightFp8")
+
+
+def DsdFp8Wgrad(s, s_scales, bq, b_scales, c, add=False,  # noqa: N802
+                accumulate="fp32", stream=None):
+    """C (Matrix [s.rows, n] of fp16 / bf16 / fp32) = Sq . Bq as DsdFp8 with
+    b_scales fp32 [s.cols / 128, n], one per k-block and output column
+    (QuantizeTiles' scales_t): acc = fma(sa[row] * sb[kb, col], P, acc). With
+    `add` C = round(acc + float(C)) and block rows of s without blocks are
+    left untouched. `dtype` is the 16-bit type: C's, or with an fp32 C
+    irrelevant to the result (sputnik_dsd_fp8_wgrad)."""
+    import torch
+
+    mode = _fp8_accumulate(accumulate, "DsdFp8Wgrad")
+    if not isinstance(s, BlockMatrix) or not isinstance(c, Matrix):
+        raise TypeError("DsdFp8Wgrad takes a BlockMatrix and writes a Matrix")
+    if getattr(bq, "dtype", None) != torch.float8_e4m3fn or bq.dim() != 2:
+        raise TypeError("DsdFp8Wgrad: bq must be a 2-D torch.float8_e4m3fn "
+                        "tensor")
+    n, k = int(bq.shape[0]), int(bq.shape[1])
+    _fp8_tiles(n, "DsdFp8Wgrad: n")
+    kb = _fp8_tiles(k, "DsdFp8Wgrad: k")
+    _fp8_buffer(bq, torch.float8_e4m3fn, (n, k), "bq")
+    _fp8_buffer(b_scales, torch.float32, (kb, n), "b_scales")
+    if k != s.cols or n != c.cols or c.rows != s.rows:
+        raise ValueError(f"DsdFp8Wgrad shapes [{s.rows}, {s.cols}] x [{k}, "
+                         f"{n}] -> [{c.rows}, {c.cols}]")
+    if getattr(s.data, "dtype", None) != torch.float8_e4m3fn:
+        raise TypeError("DsdFp8Wgrad: s.data must be torch.float8_e4m3fn")
+    _fp8_buffer(s_scales, torch.float32, (s.num_blocks * 128,), "s_scales")
+    f32 = c.data.dtype == torch.float32
+    cs, cc = s._c(), c._c()
+    _check(lib().sputnik_dsd_fp8_wgrad(
+        ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales),
+        ctypes.byref(cc), 0 if f32 else _dtype_code(c.data), int(f32),
+        int(bool(add)), mode, _stream(stream)), "DsdFp8Wgrad")
+
+
 __all__ = [
     "AllocateBitmaskBuffers", "AllocateRowIndicesBuffer",
     "AllocateTransposeBuffers", "AsInt", "Bitmask", "FreeBitmaskBuffers",
@@ -1947,7 +2084,8 @@ __all__ = [
     "MatmulGated", "MatmulGatedGrad", "BlockGate", "BlockGateGrad",
     "MatmulBias", "MatmulBiasActivation", "MatmulBiasGated", "BlockColumnSum",
     "QuantizeRows", "QuantizeWeight", "SddFp8", "DsdFp8", "Fp8IntervalSums",
-    "FP8_ACCUMULATE",
+    "FP8_ACCUMULATE", "QuantizeTiles", "QuantizeBlocks", "TransposeWeightFp8",
+    "DsdFp8Wgrad", "FP8_STAGES",
     "PaddedScatterBias", "PaddedScatterBiasWeightGrad",
     "PaddedScatterBiasGrad",
     "MoeBins", "MoeRowMap", "PaddedGather", "PaddedScatter",

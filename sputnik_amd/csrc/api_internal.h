@@ -125,6 +125,14 @@ hipError_t LaunchFp8Gemm(bool dsd, bool fast, int dtype, const void *a,
                          const short *indices, const short *row_indices,
                          int m_blocks, int n_blocks, int k_blocks,
                          int nnz_blocks, hipStream_t stream);
+// The same DSD with b_scales [k / 128, n], one per column and interval
+// (DsdFp8Wgrad): c holds T or, with `out_f32`, fp32; `add` accumulates into
+// it.
+hipError_t LaunchFp8Wgrad(bool fast, int dtype, bool out_f32, bool add,
+                          const void *s, const float *s_scales, const void *b,
+                          const float *b_scales, void *c, const int *offsets,
+                          const short *indices, int m_blocks, int n_blocks,
+                          int k_blocks, int nnz_blocks, hipStream_t stream);
 // P [k / 128, m, n] of Fp8IntervalSums, arguments already validated
 // (block_api.cpp): m, n and k multiples of 128.
 hipError_t LaunchFp8IntervalSums(const void *aq, const void *bq, int m, int n,

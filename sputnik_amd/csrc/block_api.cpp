@@ -473,6 +473,34 @@ hipError_t DsdFp8(const BlockMatrix s, const float *s_scales, const void *bq,
       c.cols / 128, s.cols / 128, s.nonzeros / (128 * 128), stream);
 }
 
+hipError_t DsdFp8Wgrad(const BlockMatrix s, const float *s_scales,
+                       const void *bq, const float *b_scales, Matrix c,
+                       DataType dtype, OutputType out, bool add,
+                       Fp8Accumulate accumulate, hipStream_t stream) {
+  if (!Fp8AccumulateOk(accumulate)) return hipErrorInvalidValue;
+  if (out != OutputType::kOperand && out != OutputType::kF32)
+    return hipErrorInvalidValue;
+  if (!Fp8SizesOk(s, c.cols, (int)dtype) || c.rows != s.rows)
+    return hipErrorInvalidValue;
+  if (c.rows == 0 || c.cols == 0) return hipSuccess;
+  if (c.data == nullptr || s.offsets == nullptr ||
+      (s.nonzeros > 0 && (s.data == nullptr || s.indices == nullptr ||
+                          s_scales == nullptr || bq == nullptr ||
+                          b_scales == nullptr)))
+    return hipErrorInvalidValue;
+  for (const void *in : {(const void *)s.data, (const void *)s_scales, bq,
+                         (const void *)b_scales, (const void *)s.offsets,
+                         (const void *)s.indices})
+    if (c.data == in) return hipErrorInvalidValue;
+  if (!Aligned16({s.data, bq, c.data})) return hipErrorInvalidValue;
+  return sputnik_amd::LaunchFp8Wgrad(
+      accumulate == Fp8Accumulate::kFast, (int)dtype, out == OutputType::kF32,
+      add, s.data, s_scales, bq, b_scales, c.data,
+      static_cast<const int *>(s.offsets),
+      static_cast<const short *>(s.indices), s.rows / 128, c.cols / 128,
+      s.cols / 128, s.nonzeros / (128 * 128), stream);
+}
+
 hipError_t Fp8IntervalSums(const void *aq, const void *bq, int m, int n,
                            int k, Fp8Accumulate accumulate, float *p,
                            hipStream_t stream) {

@@ -723,6 +723,47 @@ int sputnik_fp8_interval_sums(const void *aq, const void *bq, int m, int n,
       p, static_cast<hipStream_t>(stream));
 }
 
+// ... and their gradients' pieces.
+int sputnik_quantize_tiles(const void *x, int rows, int cols, void *q,
+                           float *scales, void *qt, float *scales_t, int pow2,
+                           int dtype, void *stream) {
+  return sputnik::block::QuantizeTiles(x, rows, cols, q, scales, qt, scales_t,
+                                       pow2 != 0, static_cast<DataType>(dtype),
+                                       static_cast<hipStream_t>(stream));
+}
+
+int sputnik_quantize_blocks(const sputnik_block_matrix_t *s, int stage,
+                            int act, const void *z, void *q, float *scales,
+                            void *qt, float *scales_t, int pow2, int dtype,
+                            void *stream) {
+  if (!s) return hipErrorInvalidValue;
+  return sputnik::block::QuantizeBlocks(
+      ToCpp(s), static_cast<sputnik::block::Fp8Stage>(stage),
+      static_cast<sputnik::block::Activation>(act), z, q, scales, qt,
+      scales_t, pow2 != 0, static_cast<DataType>(dtype),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_fp8_transpose_weight(const void *q, const float *scales, int k,
+                                 int n, void *qt, float *scales_t,
+                                 void *stream) {
+  return sputnik::block::TransposeWeightFp8(q, scales, k, n, qt, scales_t,
+                                            static_cast<hipStream_t>(stream));
+}
+
+int sputnik_dsd_fp8_wgrad(const sputnik_block_matrix_t *s,
+                          const float *s_scales, const void *bq,
+                          const float *b_scales, const sputnik_matrix_t *c,
+                          int dtype, int out, int add, int accumulate,
+                          void *stream) {
+  if (!s || !c) return hipErrorInvalidValue;
+  return sputnik::block::DsdFp8Wgrad(
+      ToCpp(s), s_scales, bq, b_scales, ToCpp(c), static_cast<DataType>(dtype),
+      static_cast<sputnik::block::OutputType>(out), add != 0,
+      static_cast<sputnik::block::Fp8Accumulate>(accumulate),
+      static_cast<hipStream_t>(stream));
+}
+
 // MoE router and device sort (sputnik/block/router.h): moe_router.hip
 // validates.
 int sputnik_router_topk(const void *logits, int32_t *top_experts,

@@ -41,6 +41,16 @@
 // split-K and no atomics: the same inputs give the same bits. Every index
 // read from device memory is checked before it is used as an address.
 //
+// kWgrad (DsdFp8Wgrad) is the DSD with a column-scaled dense operand: the
+// interval scale is sa[row] * sb[kb, col]. The 128 column scales of a step
+// ride in its stage behind the row scales, by the same 4-byte DMA (waves 2
+// and 3; waves 0 and 1 fetch the row scales), so the loop still has no
+// register-destination load; the stage grows by 512 bytes, two stages are
+// 66 KiB and two workgroups still share a CU's 160 KiB. The output leaves
+// through an fp32 image of the tile (64 KiB, inside the ring): round_out(acc)
+// or round_out(acc + float(C_old)), to T or fp32. The forward kernels are the
+// kWgrad = false instantiations, whose code does not change.
+//
 // fp8_interval_sums_kernel is the P of the contract as a callable
 // (Fp8IntervalSums): cold, one wave per 16 x 16 tile and interval, the same
 // two 16-byte reads per lane straight from global memory.
@@ -59,13 +69,21 @@ constexpr int kThreads = 256;
 constexpr int kB = 128;                  // block edge = scale interval
 constexpr int kTileBytes = kB * kB;      // one e4m3 operand tile
 constexpr int kScaleBytes = kB * 4;      // the row scales of an A tile
-constexpr int kStageBytes = 2 * kTileBytes + kScaleBytes;
-// Two stages (65 KiB) leave room for two workgroups per CU (the registers
-// allow two waves per SIMD), which hide each other's barriers; the output
-// tile reuses the ring.
+// (kWgrad: the column scales of the B tile follow the row scales)
+constexpr int StageBytes(bool wgrad) {
+  return 2 * kTileBytes + (wgrad ? 2 : 1) * kScaleBytes;
+}
+// Two stages (65 KiB; 66 KiB with column scales) leave room for two
+// workgroups per CU (the registers allow two waves per SIMD), which hide
+// each other's barriers; the output tile reuses the ring.
 constexpr int kStages = 2;
-constexpr int kLdsBytes = kStages * kStageBytes;
-static_assert(kB * kB * 2 <= kLdsBytes, "the output tile reuses the ring");
+constexpr int LdsBytes(bool wgrad) { return kStages * StageBytes(wgrad); }
+static_assert(kB * kB * 2 <= LdsBytes(false), "the output tile reuses the ring");
+// (the wgrad's fp32 image: four floats of padding per row put the four row
+// groups of a wave's store on different banks)
+constexpr int kImagePitch = kB + 4;
+static_assert(kB * kImagePitch * 4 <= LdsBytes(true), "... as fp32 too");
+static_assert(2 * LdsBytes(true) <= 160 * 1024, "two workgroups per CU");
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -147,17 +165,21 @@ struct Fp8GemmParams {
   const char *a;          // SDD: Aq [m, k]; DSD: the stored blocks of Sq
   const float *a_scales;  // SDD: [m, k / 128]; DSD: [nnz_blocks * 128]
   const char *b;          // Bq [n, k]
-  const float *b_scales;  // [k / 128, n / 128]
+  const float *b_scales;  // [k / 128, n / 128]; kWgrad: [k / 128, n]
   void *c;                // SDD: block values of C; DSD: C [m, n]
   const int *offsets;     // DSD: the sparse operand's row offsets
   const short *indices;   // SDD: C's column indices; DSD: Sq's
   const short *row_indices;  // SDD: C's
   int m_blocks, n_blocks, k_blocks, nnz_blocks;
+  int out_f32, add;       // kWgrad: C holds fp32; C += (accumulate.h)
 };
 
-template <typename T, bool kDsd, bool kFast>
+template <typename T, bool kDsd, bool kFast, bool kWgrad = false>
 __global__ void __launch_bounds__(kThreads)
     fp8_gemm_kernel(const Fp8GemmParams p) {
+  static_assert(kDsd || !kWgrad, "the column-scaled product is a DSD");
+  constexpr int kStageBytes = StageBytes(kWgrad);
+  constexpr int kLdsBytes = LdsBytes(kWgrad);
   __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const long long k_bytes = (long long)p.k_blocks * kB;
@@ -172,6 +194,8 @@ __global__ void __launch_bounds__(kThreads)
     end = end > p.nnz_blocks ? p.nnz_blocks : end;
     first = begin;
     steps = end > begin ? end - begin : 0;
+    // (accumulate.h: a block row without blocks is neither read nor written)
+    if constexpr (kWgrad) if (p.add && steps == 0) return;
   } else {
     rb = scalar_short(p.row_indices + blockIdx.x);
     nb = scalar_short(p.indices + blockIdx.x);
@@ -223,6 +247,12 @@ __global__ void __launch_bounds__(kThreads)
       __builtin_amdgcn_global_load_lds(
           SPUTNIK_FP8_GLOBAL(a_scale + row * a_scale_stride),
           SPUTNIK_FP8_LDS(stage + 2 * kTileBytes + wave * 256), 4, 0, 0);
+    } else if constexpr (kWgrad) {
+      const int col = (wave - kB / 64) * 64 + lane;
+      const long long n = (long long)p.n_blocks * kB;
+      __builtin_amdgcn_global_load_lds(
+          SPUTNIK_FP8_GLOBAL(p.b_scales + kb * n + (long long)nb * kB + col),
+          SPUTNIK_FP8_LDS(stage + 2 * kTileBytes + wave * 256), 4, 0, 0);
     }
   };
 
@@ -249,7 +279,9 @@ __global__ void __launch_bounds__(kThreads)
   auto compute = [&](int i, const char *stage) {
     const int kb = k_block(i);
     if (kb < 0) return;
-    const float sb = scalar_float(p.b_scales + (long long)kb * p.n_blocks + nb);
+    float sb = 1.0f;  // kWgrad: per column, from the stage
+    if constexpr (!kWgrad)
+      sb = scalar_float(p.b_scales + (long long)kb * p.n_blocks + nb);
     const float *sa_lds =
         reinterpret_cast<const float *>(stage + 2 * kTileBytes);
     Frag a[4];
@@ -264,12 +296,15 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj) {
       const Frag b = fragment(stage + kTileBytes, wn * 64 + tj * 16);
+      if constexpr (kWgrad) sb = sa_lds[kB + wn * 64 + tj * 16 + r];
 #pragma unroll
       for (int ti = 0; ti < 4; ++ti) {
         const f32x4 sum = interval_sum(a[ti], b);
+        // (kWgrad: s is sa alone so far; sa * sb is rounded, then the fma)
+        const f32x4 st = kWgrad ? s[ti] * sb : s[ti];
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          acc[ti][tj][e] = __builtin_fmaf(s[ti][e], sum[e], acc[ti][tj][e]);
+          acc[ti][tj][e] = __builtin_fmaf(st[e], sum[e], acc[ti][tj][e]);
       }
     }
   };
@@ -285,8 +320,51 @@ __global__ void __launch_bounds__(kThreads)
     compute(i, lds + (i % kStages) * kStageBytes);
   }
 
-  // round_T(acc) into a [128][128] image of T, then 16-byte row pieces.
   __syncthreads();
+  if constexpr (kWgrad) {
+    // acc into a [128][kImagePitch] fp32 image, then 16-byte row pieces of the
+    // output type: round_out(acc), or round_out(acc + float(C_old)).
+    float *image = reinterpret_cast<float *>(lds);
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          image[(wm * 64 + ti * 16 + 4 * g + e) * kImagePitch + wn * 64 +
+                tj * 16 + r] = acc[ti][tj][e];
+    __syncthreads();
+    const long long n = (long long)p.n_blocks * kB;
+    const long long at = (long long)rb * kB * n + (long long)nb * kB;
+    if (p.out_f32) {
+      float *out = static_cast<float *>(p.c) + at;
+      for (int id = threadIdx.x; id < kB * kB / 4; id += kThreads) {
+        const int row = id >> 5, col = (id & 31) * 4;
+        f32x4 v = *reinterpret_cast<const f32x4 *>(image + row * kImagePitch + col);
+        f32x4 *dst = reinterpret_cast<f32x4 *>(out + row * n + col);
+        if (p.add) v += *dst;
+        *dst = v;
+      }
+    } else {
+      typedef T t8 __attribute__((ext_vector_type(8)));
+      T *out = static_cast<T *>(p.c) + at;
+      for (int id = threadIdx.x; id < kB * kB / 8; id += kThreads) {
+        const int row = id >> 4, col = (id & 15) * 8;
+        t8 *dst = reinterpret_cast<t8 *>(out + row * n + col);
+        t8 old{}, res;
+        if (p.add) old = *dst;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float v = image[row * kImagePitch + col + i];
+          if (p.add) v += (float)old[i];
+          res[i] = (T)v;
+        }
+        *dst = res;
+      }
+    }
+    return;
+  }
+  // round_T(acc) into a [128][128] image of T, then 16-byte row pieces.
   T *image = reinterpret_cast<T *>(lds);
 #pragma unroll
   for (int ti = 0; ti < 4; ++ti)
@@ -370,7 +448,7 @@ hipError_t LaunchFp8Gemm(bool dsd, bool fast, int dtype, const void *a,
   const Fp8GemmParams p{static_cast<const char *>(a), a_scales,
                         static_cast<const char *>(b), b_scales, c, offsets,
                         indices, row_indices, m_blocks, n_blocks, k_blocks,
-                        nnz_blocks};
+                        nnz_blocks, 0, 0};
   auto launch = [&](auto t, auto d, auto f) {
     hipLaunchKernelGGL((fp8_gemm_kernel<decltype(t), decltype(d)::value,
                                         decltype(f)::value>),
@@ -386,6 +464,30 @@ hipError_t LaunchFp8Gemm(bool dsd, bool fast, int dtype, const void *a,
                       : kind(_Float16{}, std::true_type{});
   return dtype == 1 ? kind(__bf16{}, std::false_type{})
                     : kind(_Float16{}, std::false_type{});
+}
+
+hipError_t LaunchFp8Wgrad(bool fast, int dtype, bool out_f32, bool add,
+                          const void *s, const float *s_scales, const void *b,
+                          const float *b_scales, void *c, const int *offsets,
+                          const short *indices, int m_blocks, int n_blocks,
+                          int k_blocks, int nnz_blocks, hipStream_t stream) {
+  const long long tiles = (long long)m_blocks * n_blocks;
+  if (tiles == 0) return hipSuccess;
+  if (tiles > INT_MAX) return hipErrorInvalidValue;
+  const Fp8GemmParams p{static_cast<const char *>(s), s_scales,
+                        static_cast<const char *>(b), b_scales, c, offsets,
+                        indices, nullptr, m_blocks, n_blocks, k_blocks,
+                        nnz_blocks, out_f32, add};
+  auto launch = [&](auto t, auto f) {
+    hipLaunchKernelGGL((fp8_gemm_kernel<decltype(t), true, decltype(f)::value,
+                                        true>),
+                       dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
+    return hipGetLastError();
+  };
+  auto kind = [&](auto t) {
+    return fast ? launch(t, std::true_type{}) : launch(t, std::false_type{});
+  };
+  return dtype == 1 ? kind(__bf16{}) : kind(_Float16{});
 }
 
 }  // namespace sputnik_amd

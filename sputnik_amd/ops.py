@@ -51,6 +51,12 @@ scales, forward only) is `quantize_rows`, `quantize_sparse` and
 `moe_mlp_fp8`, moe_mlp with its expert products in fp8 while gather, scatter
 and router stay 16-bit; the three take `accumulate="fp32"` (the default) or
 `"fast"`, the scaled e4m3 MFMA per k-block (Fp8Accumulate in fp8.h).
+The fp8 path with gradients is `mlp_fp8(x, w1t, w2, topo, activation)` over
+16-bit tensors and `moe_mlp_fp8_train` around it; its pieces are
+`quantize_tiles` (row and 128 x 1 column tiles in one pass),
+`quantize_sparse_t` (a sparse operand's transpose with per-column scales),
+`Fp8Weight.t()` and `dsd_fp8_wgrad`, the DSD whose dense operand is scaled
+per column.
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -80,6 +86,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                MatmulBiasGated, PaddedScatterBias, PaddedScatterBiasGrad,
                PaddedScatterBiasWeightGrad,
                QuantizeRows, QuantizeWeight, SddFp8, DsdFp8, FP8_ACCUMULATE,
+               QuantizeTiles, QuantizeBlocks, TransposeWeightFp8, DsdFp8Wgrad,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
                RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
                MOE_SORT_CHUNK, ROUTER_AUX_TOKENS, ROUTER_MAX_EXPERTS,
@@ -1367,7 +1374,7 @@ def moe_mlp_bias(x: torch.Tensor, top_experts: torch.Tensor,
                     activation, v1, rows, b1, bv1, b2)[0]
 
 
-# ---- FP8 (e4m3) expert products, forward only --------------------------------
+# ---- FP8 (e4m3) expert products ----------------------------------------------
 
 @dataclass
 class Fp8Weight:
@@ -1414,6 +1421,17 @@ class Fp8Weight:
                              f"{tuple(scales.shape)}, expected "
                              f"{(k // BLOCK, n // BLOCK)} ([k / 128, n / 128])")
         return cls(q.contiguous(), scales.contiguous(), k, n)
+
+    def t(self) -> "Fp8Weight":
+        """The Fp8Weight of the transposed weight [n, k]: an exact byte
+        transpose, bit for bit quantize_weight of the transposed 16-bit
+        weight. The backward layout of a weight that exists only as fp8."""
+        qt = torch.empty(self.k, self.n, dtype=torch.float8_e4m3fn,
+                         device=self.q.device)
+        st = torch.empty(self.n // BLOCK, self.k // BLOCK,
+                         dtype=torch.float32, device=self.q.device)
+        TransposeWeightFp8(self.q, self.scales, qt, st)
+        return Fp8Weight(qt, st, self.n, self.k)
 
 
 class Fp8SparseMatrix(SparseMatrix):
@@ -1619,6 +1637,266 @@ def moe_mlp_fp8(x: torch.Tensor, top_experts: torch.Tensor,
         hq = quantize_sparse(u, "silu" if act is None else act, gate=g)
     return padded_scatter(dsd_fp8(hq, w2q, x.dtype, accumulate), route,
                           expert_weights)
+
+
+# ---- FP8 gradients (sputnik/block/fp8.h, "Gradients") ------------------------
+
+def quantize_tiles(x: torch.Tensor, rows: bool = True, cols: bool = True,
+                   pow2: bool = False):
+    """(q, scales, qt, scales_t) of x [rows, cols] (fp16 / bf16, both
+    multiples of 128), read once: q / scales as quantize_rows, bit for bit;
+    qt torch.float8_e4m3fn [cols, rows] and scales_t fp32 [rows / 128, cols]
+    with one scale per 128 x 1 column tile, the dense operand of
+    dsd_fp8_wgrad. A pair that is not asked for is (None, None)."""
+    _check_dtypes(x)
+    _no_grad("quantize_tiles", x)
+    if x.dim() != 2 or int(x.shape[0]) % BLOCK or int(x.shape[1]) % BLOCK:
+        raise ValueError("quantize_tiles: x is 2-D with multiples of 128")
+    if not (rows or cols):
+        raise ValueError("quantize_tiles: no output asked for")
+    x = x.contiguous()
+    m, n = int(x.shape[0]), int(x.shape[1])
+    q = s = qt = st = None
+    if rows:
+        q = torch.empty(m, n, dtype=torch.float8_e4m3fn, device=x.device)
+        s = torch.empty(m, n // BLOCK, dtype=torch.float32, device=x.device)
+    if cols:
+        qt = torch.empty(n, m, dtype=torch.float8_e4m3fn, device=x.device)
+        st = torch.empty(m // BLOCK, n, dtype=torch.float32, device=x.device)
+    QuantizeTiles(x, q, s, qt, st, pow2)
+    return q, s, qt, st
+
+
+def _quantize_blocks(sparse: SparseMatrix, stage, act, z, rows: bool,
+                     cols: bool, pow2: bool):
+    """QuantizeBlocks over sparse's block values: (the Fp8SparseMatrix of
+    sparse's topology or None, the Fp8SparseMatrix of the transposed
+    topology or None)."""
+    meta, nb = sparse._meta, sparse.nnz_blocks
+    data = sparse.data.contiguous()
+    dev = data.device
+    q = s = qt = st = None
+    if rows:
+        q = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
+                        device=dev)
+        s = torch.empty(nb * BLOCK, dtype=torch.float32, device=dev)
+    if cols:
+        meta.ensure_transposed(data)
+        qt = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
+                         device=dev)
+        st = torch.empty(nb * BLOCK, dtype=torch.float32, device=dev)
+    if nb:
+        QuantizeBlocks(meta.descriptor(data), q, s, qt, st, stage, act,
+                       None if z is None else z.contiguous(), pow2)
+    by_rows = Fp8SparseMatrix(sparse, q, s) if rows else None
+    by_cols = None
+    if cols:
+        by_cols = Fp8SparseMatrix(
+            SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
+                         meta.indices_t), qt, st)
+    return by_rows, by_cols
+
+
+def quantize_sparse_t(sparse: SparseMatrix, activation=None,
+                      z: Optional[SparseMatrix] = None,
+                      pow2: bool = False) -> Fp8SparseMatrix:
+    """The Fp8SparseMatrix of sparse^T, the sparse operand of dsd_fp8_wgrad:
+    its blocks are sparse's, transposed and in the transposed order, each
+    with 128 per-row scales, one per column of the source block (a 128 x 1
+    tile of sparse). With `activation` alone act(sparse) is quantised, as
+    quantize_sparse does it; with `z` (same topology and dtype) sparse *
+    act'(z), as sdd_act's gradient evaluates it, rounded to sparse's dtype
+    first."""
+    if not isinstance(sparse, SparseMatrix) or sparse.is_transposed():
+        raise TypeError("quantize_sparse_t takes a SparseMatrix (not a .t() "
+                        "view)")
+    _check_dtypes(sparse.data)
+    _no_grad("quantize_sparse_t", sparse.data, None if z is None else z.data)
+    stage = None
+    if z is not None:
+        if (not isinstance(z, SparseMatrix) or z._meta is not sparse._meta
+                or z.is_transposed() or z.dtype != sparse.dtype):
+            raise ValueError("quantize_sparse_t: z must share sparse's "
+                             "topology and dtype")
+        if activation is None:
+            raise ValueError("quantize_sparse_t: z needs its activation")
+        stage = "act_grad"
+    elif activation is not None:
+        stage = "act"
+    act = None if activation is None else _act_code(activation)
+    return _quantize_blocks(sparse, stage, act,
+                            None if z is None else z.data, False, True,
+                            pow2)[1]
+
+
+def dsd_fp8_wgrad(st: Fp8SparseMatrix, bqt: torch.Tensor, bst: torch.Tensor,
+                  out: Optional[torch.Tensor] = None, add: bool = False,
+                  out_dtype=torch.bfloat16,
+                  accumulate: str = "fp32") -> torch.Tensor:
+    """st . B as a dense [m, n] tensor, the weight-gradient product in fp8:
+    st from quantize_sparse_t ([m, k], k the token dimension), B [k, n] given
+    as quantize_tiles' column pair bqt [n, k], bst [k / 128, n]. Per k-block
+    in st's storage order acc = fma(st.scales[row] * bst[kb, col], P, acc);
+    `accumulate` as sdd_fp8. Writes `out` (contiguous [m, n], fp16 / bf16 /
+    fp32) or a new tensor of `out_dtype` (the same three); with `add`, out =
+    round(acc + out), rounded once, and rows that meet no block of st are
+    left untouched. Bitwise reproducible."""
+    _accumulate(accumulate, "dsd_fp8_wgrad")
+    if not isinstance(st, Fp8SparseMatrix):
+        raise TypeError("dsd_fp8_wgrad: st must come from quantize_sparse_t")
+    if not isinstance(bqt, torch.Tensor) or bqt.dim() != 2:
+        raise TypeError("dsd_fp8_wgrad: bqt is quantize_tiles' qt")
+    m, n = st.shape[0], int(bqt.shape[0])
+    if st.shape[1] != int(bqt.shape[1]):
+        raise ValueError(f"dsd_fp8_wgrad shapes {st.shape} x "
+                         f"{(int(bqt.shape[1]), n)}")
+    if out is None:
+        if add:
+            raise ValueError("dsd_fp8_wgrad: add needs `out`")
+        if out_dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            raise TypeError("dsd_fp8_wgrad: out_dtype must be torch.float16, "
+                            "torch.bfloat16 or torch.float32")
+        out = torch.empty(m, n, dtype=out_dtype, device=bqt.device)
+    else:
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != (m, n)
+                or not out.is_contiguous()):
+            raise ValueError(f"dsd_fp8_wgrad: out must be a contiguous "
+                             f"{(m, n)} tensor")
+        if out.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            raise TypeError("dsd_fp8_wgrad: out must be fp16, bf16 or fp32")
+    DsdFp8Wgrad(st._descriptor(), st.scales, bqt, bst, Matrix(m, n, out),
+                add=add, accumulate=accumulate)
+    return out
+
+
+class _MLPFp8(torch.autograd.Function):
+    """y = dsd_fp8(quantize_sparse(sdd_fp8(x, w1t^T), act), w2) and the
+    backward pass of fp8.h's table. Keeps Z, the column quantisation of X
+    (bytes, not the 16-bit X) and the backward layouts of the two weights."""
+
+    @staticmethod
+    def forward(ctx, x, w1t, w2, topo, act, accumulate, pow2, w1_sink,
+                w2_sink):
+        need_x, need_w1, need_w2 = ctx.needs_input_grad[:3]
+        need_w1 = need_w1 or w1_sink is not None
+        need_w2 = need_w2 or w2_sink is not None
+        ctx.topo, ctx.act, ctx.mode, ctx.pow2 = topo, act, accumulate, pow2
+        ctx.w1_sink, ctx.w2_sink = w1_sink, w2_sink
+        ctx.need = (need_x, need_w1, need_w2)
+        w1q = quantize_weight(w1t, transpose=True, pow2=pow2)   # [h, F]
+        w2q = quantize_weight(w2, pow2=pow2)                    # [F, h]
+        xq, xs, xqt, xst = quantize_tiles(x, cols=need_w1, pow2=pow2)
+        z = sdd_fp8(xq, xs, w1q, topo, x.dtype, accumulate)
+        y = dsd_fp8(quantize_sparse(z, act, pow2=pow2), w2q, x.dtype,
+                    accumulate)
+        if any(ctx.need):
+            # (dH = dY W2^T and dX = dZ W1t take the transposed layouts)
+            ctx.w2q_t = w2q.t() if need_x or need_w1 else None
+            ctx.w1q_t = w1q.t() if need_x else None
+            ctx.save_for_backward(z.data, xqt, xst)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z_data, xqt, xst = ctx.saved_tensors
+        need_x, need_w1, need_w2 = ctx.need
+        topo, act, mode, pow2 = ctx.topo, ctx.act, ctx.mode, ctx.pow2
+        z = topo.with_data(z_data)
+        dt = z_data.dtype
+        dx = dw1 = dw2 = None
+        need_dz = need_x or need_w1
+        dyq, dys, dyqt, dyst = quantize_tiles(dy, rows=need_dz, cols=need_w2,
+                                              pow2=pow2)
+        if need_w2:                                   # H^T dY
+            ht = _quantize_blocks(z, "act", act, None, False, True, pow2)[1]
+            if ctx.w2_sink is not None:
+                dsd_fp8_wgrad(ht, dyqt, dyst, ctx.w2_sink, True,
+                              accumulate=mode)
+            else:
+                dw2 = dsd_fp8_wgrad(ht, dyqt, dyst, out_dtype=dt,
+                                    accumulate=mode)
+            del ht
+        if need_dz:
+            dh = sdd_fp8(dyq, dys, ctx.w2q_t, topo, dt, mode)   # dY W2^T
+            # dZ = dH * act'(Z), quantised along both axes in one pass
+            dzq, dzt = _quantize_blocks(dh, "act_grad", act, z_data, need_x,
+                                        need_w1, pow2)
+            if need_x:
+                dx = dsd_fp8(dzq, ctx.w1q_t, dt, mode)          # dZ W1t
+            if ctx.w1_sink is not None:                         # dZ^T X
+                dsd_fp8_wgrad(dzt, xqt, xst, ctx.w1_sink, True,
+                              accumulate=mode)
+            elif need_w1:
+                dw1 = dsd_fp8_wgrad(dzt, xqt, xst, out_dtype=dt,
+                                    accumulate=mode)
+        return dx, dw1, dw2, None, None, None, None, None, None
+
+
+def mlp_fp8(x: torch.Tensor, w1t: torch.Tensor, w2: torch.Tensor,
+            topo: SparseMatrix, activation="gelu", accumulate: str = "fp32",
+            pow2: bool = False, w1t_grad_out: Optional[torch.Tensor] = None,
+            w2_grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The expert MLP with its three products in fp8, forward and backward:
+    y = act(x w1t^T at topo's blocks) w2 over 16-bit x [T, h], w1t [F, h] and
+    w2 [F, h] (MegaBlocks' orientation), topo [T, F]. Forward quantises the
+    weights (quantize_weight, and Fp8Weight.t() for the backward layouts)
+    and runs quantize_rows -> sdd_fp8 -> quantize_sparse(activation) ->
+    dsd_fp8, bit for bit. Backward (sputnik/block/fp8.h, "Gradients"): dH =
+    dY W2^T by sdd_fp8, dZ = dH * act'(Z) fused into the quantiser, dX = dZ
+    W1t by dsd_fp8, and dW2 = H^T dY, dW1t = dZ^T X by dsd_fp8_wgrad with
+    both operands scaled per 128 tokens x 1 column. The gradients are
+    straight-through: taken with respect to the 16-bit inputs, in their
+    dtype. A sink (`w1t_grad_out`, `w2_grad_out`: contiguous [F, h], x's
+    dtype or fp32) receives sink += gradient, rounded once, in place of a
+    returned gradient. What needs_input_grad does not ask for is skipped.
+    There are no biases and no GLU form."""
+    _accumulate(accumulate, "mlp_fp8")
+    _check_dtypes(x, w1t, w2)
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError("mlp_fp8: topo must be a SparseMatrix (not a .t() "
+                        "view)")
+    if (x.dim() != 2 or w1t.dim() != 2 or tuple(w1t.shape) != tuple(w2.shape)
+            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
+            or int(w1t.shape[1]) != int(x.shape[1])
+            or int(x.shape[1]) % BLOCK):
+        raise ValueError("mlp_fp8: x [T, h], w1t and w2 [F, h], topo [T, F], "
+                         "all multiples of 128")
+    for sink, what in ((w1t_grad_out, "w1t_grad_out"),
+                       (w2_grad_out, "w2_grad_out")):
+        if sink is not None:
+            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
+                        f"mlp_fp8: {what}")
+    return _MLPFp8.apply(x.contiguous(), w1t.contiguous(), w2.contiguous(),
+                         topo, _act_code(activation), accumulate, bool(pow2),
+                         w1t_grad_out, w2_grad_out)
+
+
+def moe_mlp_fp8_train(x: torch.Tensor, top_experts: torch.Tensor,
+                      expert_weights: torch.Tensor, w1t: torch.Tensor,
+                      w2: torch.Tensor, num_experts: int, activation=None,
+                      rows: Optional[int] = None, accumulate: str = "fp32",
+                      pow2: bool = False,
+                      w1t_grad_out: Optional[torch.Tensor] = None,
+                      w2_grad_out: Optional[torch.Tensor] = None
+                      ) -> torch.Tensor:
+    """moe_mlp with the expert products in fp8 and gradients: padded_gather
+    -> mlp_fp8 -> padded_scatter, the permutation with its existing
+    gradients. w1t and w2 are 16-bit [num_experts * ffn, d_model]; the other
+    arguments are moe_mlp's (activation None: "gelu"). Differentiable in x,
+    expert_weights, w1t and w2."""
+    _accumulate(accumulate, "moe_mlp_fp8_train")
+    if not isinstance(w1t, torch.Tensor) or w1t.dim() != 2:
+        raise ValueError("moe_mlp_fp8_train: w1t is [E * ffn, d_model]")
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
+                              None, num_experts, rows)
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    y = mlp_fp8(xp, w1t, w2, topo, "gelu" if activation is None else
+                activation, accumulate, pow2, w1t_grad_out, w2_grad_out)
+    return padded_scatter(y, route, expert_weights)
 
 
 # ---- MoE router -------------------------------------------------------------
@@ -2102,4 +2380,6 @@ __all__ = ["MoeAux", "MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_a
            "padded_scatter", "sdd", "sdd_act", "sdd_gated",
            "Fp8Weight", "Fp8SparseMatrix", "quantize_rows", "quantize_sparse",
            "quantize_weight", "sdd_fp8", "dsd_fp8", "moe_mlp_fp8",
+           "quantize_tiles", "quantize_sparse_t", "dsd_fp8_wgrad", "mlp_fp8",
+           "moe_mlp_fp8_train",
            "topology_from_mask"]
