@@ -124,7 +124,8 @@
 //           internal sum (the tests hold the product to Fp8IntervalSums, and
 //           Fp8IntervalSums to float64 within eps_fast), the non-scaled
 //           v_mfma_f32_16x16x32_fp8_fp8 form, e8m0 hardware scales carrying
-//           real scale values, gradients and other layouts.
+//           real scale values (sputnik/block/mx.h has them), gradients and
+//           other layouts.
 //
 //   Fp8IntervalSums   P [k / 128, m, n], fp32, of aq [m, k] and bq [n, k]:
 //                     P[kb] is the interval sum of k-block kb as the product
@@ -223,9 +224,10 @@
 // Out of scope: GLU gradients in fp8 (the kOutGateGrad stage makes them a
 // follow-up with the same kernels), e5m2 (gradients included), other operand
 // layouts (weights are re-laid once by QuantizeWeight and
-// TransposeWeightFp8), DDS / SSD / SDS / DSS in fp8, e8m0 hardware scales,
-// fp8 outputs from the GEMM epilogue, caching quantised weights across
-// micro-batches, biases and the router.
+// TransposeWeightFp8), DDS / SSD / SDS / DSS in fp8, e8m0 hardware scales
+// (the MX products of sputnik/block/mx.h), fp8 outputs from the GEMM
+// epilogue, caching quantised weights across micro-batches, biases and the
+// router.
 #ifndef SPUTNIK_BLOCK_FP8_H_
 #define SPUTNIK_BLOCK_FP8_H_
 

@@ -1,0 +1,146 @@
+// sputnik-amd: OCP Microscaling (MX) expert products for the forward pass:
+// MXFP8 (e4m3) activations against MXFP8 (e4m3) or MXFP4 (e2m1) weights, with
+// the e8m0 block scales applied by the matrix instruction itself. Quantisers,
+// an SDD and a DSD. Extensions, all of them: no counterpart in the reference.
+//
+// Format (part of the contract, bit for bit):
+//
+//   Elements  MxFormat::kE4M3  OCP e4m3fn, one byte each, exactly as fp8.h has
+//                              it (0x7F / 0xFF are NaN, no infinities).
+//             MxFormat::kE2M1  4 bits: 1 sign, 2 exponent, 1 mantissa. Code c
+//                              & 7 stands for {0, 0.5, 1, 1.5, 2, 3, 4, 6}[c &
+//                              7], bit 3 is the sign. No NaN, no Inf. Two per
+//                              byte: element 2 i in bits 3:0, element 2 i + 1
+//                              in bits 7:4, as torch.float4_e2m1fn_x2 and the
+//                              published MXFP4 checkpoints store them.
+//   Scales    one e8m0 byte per 32 consecutive k-elements of a row: value =
+//             2^(byte - 127); 0xFF is NaN. Activations [rows, k] have scales
+//             uint8 [rows, k / 32]. Weights are stored k-contiguous, [n, k]
+//             bytes (e2m1: [n, k / 2]), with scales uint8 [n, k / 32];
+//             checkpoint tensors in this layout are used as they are.
+//
+//   Scale of a 32-block: fp8.h's pow2 rule, without saturation, one rule per
+//   element type. With amax the largest finite |x| of the 32 elements, amax =
+//   m 2^e, m in [0.5, 1):
+//     e4m3   s = 2^(e-9) if m <= 0.875, otherwise 2^(e-8)   (amax / s <= 448)
+//     e2m1   s = 2^(e-3) if m <= 0.75,  otherwise 2^(e-2)   (amax / s <= 6)
+//   both floored at 2^-126 (byte 0x01), which also covers amax = 0.
+//   Element  q = rne(x / s), ties to even; the division is exact.
+//   Non-finite elements
+//     e4m3   the element becomes the NaN byte with its sign and is left out
+//            of amax, as QuantizeRows has it.
+//     e2m1   the block's scale byte becomes 0xFF and its elements code 0.
+//
+//   QuantizeRowsMx   x [rows, cols] of T, cols a multiple of 128 -> q [rows,
+//                    cols] e4m3 bytes and scales uint8 [rows, cols / 32].
+//                    `stage`: kNone; kActivation, H = act(x) evaluated as
+//                    QuantizeRowsActivation evaluates it; kGated, H = x *
+//                    act(gate) as QuantizeRowsGated. Block values [nnz_blocks,
+//                    128, 128] go in as [nnz_blocks 128, 128]: one scale dword
+//                    per stored-block row, in storage order. `gate` is read
+//                    for kGated, `activation` unless kNone.
+//   QuantizeWeightMx w [k, n] of T (transpose: the buffer holds w^T, [n, k])
+//                    -> q [n, k] bytes (kE2M1: [n, k / 2]) and scales uint8
+//                    [n, k / 32]. k and n multiples of 128.
+//   SddMx   C (BCSR, T) = Aq [m, k] . Bq at C's stored blocks, a_scales [m,
+//           k / 32], Bq / b_scales as QuantizeWeightMx leaves them in
+//           `b_format`; m = c.rows, n = c.cols.
+//   DsdMx   C [m, n] (T) = Sq (BCSR, e4m3 bytes in s.data) . Bq: s_scales
+//           [nnz_blocks 128, 4] as QuantizeRowsMx leaves them, k = s.cols.
+//   A / S is always e4m3. Shapes, index checks, the skipping of out-of-range
+//   blocks, +0 rows for empty block rows and alias rejection follow SddFp8 /
+//   DsdFp8; Aq / Sq / Bq / C are 16-byte and the scale arrays 4-byte aligned
+//   (a step's four scale bytes of a row are fetched as one dword).
+//
+//   Arithmetic of both: a step is one k-block of 128 (SDD ascending, DSD in
+//   the row's storage order). P is what one
+//   v_mfma_scale_f32_16x16x128_f8f6f4 returns from a +0 accumulator for the
+//   16 x 16 tile when lane l (row / column l % 16, group g = l / 16) passes
+//   the e8m0 byte of 32-block g of its row (A) or column (B) and
+//     an e4m3 operand (8 registers) as k = 16 g .. 16 g + 15 of the step in
+//       registers 0 - 3 and k = 64 + 16 g .. 64 + 16 g + 15 in registers 4 -
+//       7, bytes in memory order;
+//     an e2m1 operand (4 registers) as k = 32 g .. 32 g + 31, nibbles in
+//       memory order, low first;
+//   D[e] of lane l is P[4 g + e, l % 16]. That is the instruction's map as
+//   measured on the hardware with one-hot rows and a scale ramp: element k
+//   meets element k and the scale byte of block k / 32. (A lane that holds 32
+//   contiguous e4m3 bytes instead gets half of each block multiplied by a
+//   neighbour's scale.) The known-answer tests (tests/test_gpu_mx.py) hold
+//   the kernels to it: scales that differ per (row, 32-block) and per (column,
+//   32-block), one-hot rows per 32-block and per nibble. acc = acc + P is one
+//   fp32 add per step, C = round_T(acc), rounded once. No split-K, no atomics,
+//   no hand-off: the same inputs give the same bits, and SDD and DSD give the
+//   same bits for the same step operands in the same order. P starts from +0
+//   on purpose: what the instruction does with a large accumulator input has
+//   not been measured, so the accumulator is not chained through the MFMA.
+//
+//   Error: |C - exact| <= 2^-p |exact| + (eps_fast + (K / 128 + 1) 2^-23)
+//   sum |terms|, eps_fast = 2^-7 as fp8.h has it, p = 11 (fp16) or 8 (bf16).
+//   e8m0 scaling is exact, so a step is the instruction fp8.h characterised
+//   with products that span a wider ratio (profiles/fp8/accum_probe.jsonl,
+//   family (c), covers ratios out to 2^-17). Measured on SddMx with fp16
+//   output, the rounding to fp16 (up to 2^-12 |exact|) included, both weight
+//   formats (scripts/probe_mx_accum.py, profiles/mx/accum_probe.jsonl):
+//   worst |C - exact| / sum |terms| 2^-11.6 on bytes quantised from normal
+//   data with block scales over 16 binades (K = 640), 2^-10.9 on uniformly
+//   random finite bytes under scales over 8 binades, and 2^-11.1 on one
+//   product 2^11 .. 2^17 above its 127 neighbours with the gap split between
+//   its element and its block's scale (2^-11.1 at 2^11, halving with every
+//   doubling of the gap: the output rounding alone; with part of the gap in
+//   the scale no neighbour was lost). No family passes 2^-8, so eps_mx =
+//   eps_fast = 2^-7 stands: an outlier inside one 32-block, all of its gap
+//   in the elements, is fp8.h's own worst case (2^-8.28). The tests assert
+//   eps_fast / 2 = 2^-8 on their data.
+//
+//   A NaN byte of A / S makes NaN exactly its row of that step's tile, a 0xFF
+//   scale byte of B exactly its column (the OCP rule).
+//
+// `dtype` is T, the 16-bit type. Every call is stream-ordered, allocates
+// nothing and never synchronises or aborts: hipErrorInvalidValue, with nothing
+// launched, for a null required buffer, a negative size, a dimension that is
+// not a multiple of 128, a block size other than 128, an MxFormat / MxStage /
+// Activation outside its enum, a misaligned buffer (above; the quantisers take
+// any alignment) or an output that is one of the inputs. Zero-sized work
+// succeeds.
+//
+// Out of scope: gradients; e5m2, e3m2 and e2m3 elements; MXFP4 activations;
+// DDS / SSD / SDS / DSS; chaining the accumulator through the MFMA; a CPU
+// model of the instruction's internal sum; biases; a C++ example.
+#ifndef SPUTNIK_BLOCK_MX_H_
+#define SPUTNIK_BLOCK_MX_H_
+
+#include <cstdint>
+
+#include "sputnik/block/activation.h"
+#include "sputnik/block/arguments.h"
+#include "sputnik/block/dtype.h"
+
+namespace sputnik {
+namespace block {
+
+enum class MxFormat { kE4M3 = 0, kE2M1 = 1 };
+
+// What QuantizeRowsMx applies to x before it quantises.
+enum class MxStage { kNone = 0, kActivation = 1, kGated = 2 };
+
+hipError_t QuantizeRowsMx(const void *x, const void *gate, int rows, int cols,
+                          MxStage stage, Activation activation, void *q,
+                          uint8_t *scales, DataType dtype, hipStream_t stream);
+
+hipError_t QuantizeWeightMx(const void *w, int k, int n, bool transpose,
+                            MxFormat format, void *q, uint8_t *scales,
+                            DataType dtype, hipStream_t stream);
+
+hipError_t SddMx(const void *aq, const uint8_t *a_scales, int k,
+                 const void *bq, const uint8_t *b_scales, MxFormat b_format,
+                 BlockMatrix c, DataType dtype, hipStream_t stream);
+
+hipError_t DsdMx(const BlockMatrix s, const uint8_t *s_scales, const void *bq,
+                 const uint8_t *b_scales, MxFormat b_format, Matrix c,
+                 DataType dtype, hipStream_t stream);
+
+}  // namespace block
+}  // namespace sputnik
+
+#endif  // SPUTNIK_BLOCK_MX_H_

@@ -13,6 +13,7 @@
 #include "sputnik/block/fp8.h"
 #include "sputnik/block/gated.h"
 #include "sputnik/block/moe.h"
+#include "sputnik/block/mx.h"
 #include "sputnik/block/router.h"
 #include "sputnik/block/dds/dds.h"
 #include "sputnik/block/sdd/sdd.h"

@@ -690,6 +690,40 @@ int sputnik_dsd_fp8_wgrad(const sputnik_block_matrix_t *s,
                           int dtype, int out, int add, int accumulate,
                           void *stream);
 
+/* ---- MX (OCP Microscaling) expert products, forward (sputnik/block/mx.h has
+ * the contract). Elements are e4m3 bytes or, for weights, e2m1 nibbles packed
+ * two per byte, low nibble first (`format` 0 e4m3, 1 e2m1); every 32
+ * k-elements of a row share one e8m0 scale byte, value 2^(byte - 127), which
+ * the matrix instruction applies.
+ *
+ *   sputnik_quantize_rows_mx    x [rows, cols] of T after `stage` (0 none,
+ *                               1 act(x), 2 x * act(gate)) -> q [rows, cols]
+ *                               e4m3, scales uint8 [rows, cols / 32]
+ *   sputnik_quantize_weight_mx  w [k, n] of T (transpose: the buffer is [n, k])
+ *                               -> q [n, k] (e2m1: [n, k / 2]), scales uint8
+ *                               [n, k / 32]
+ *   sputnik_sdd_mx   C (BCSR, T) = Aq [c.rows, k] . Bq at C's stored blocks;
+ *                    a_scales [c.rows, k / 32]
+ *   sputnik_dsd_mx   C [s.rows, c.cols] (T) = Sq (BCSR, e4m3 bytes in s.data,
+ *                    s_scales [blocks * 128, 4]) . Bq
+ *
+ * Per k-block in ascending (SDD) or storage (DSD) order acc = acc + P in fp32,
+ * P one v_mfma_scale_f32_16x16x128_f8f6f4 from +0; C = round_T(acc). Bitwise
+ * reproducible. Checks as the fp8 calls; the products also want 4-byte
+ * aligned scale arrays. */
+int sputnik_quantize_rows_mx(const void *x, const void *gate, int rows,
+                             int cols, int stage, int act, void *q,
+                             uint8_t *scales, int dtype, void *stream);
+int sputnik_quantize_weight_mx(const void *w, int k, int n, int transpose,
+                               int format, void *q, uint8_t *scales, int dtype,
+                               void *stream);
+int sputnik_sdd_mx(const void *aq, const uint8_t *a_scales, int k,
+                   const void *bq, const uint8_t *b_scales, int b_format,
+                   const sputnik_block_matrix_t *c, int dtype, void *stream);
+int sputnik_dsd_mx(const sputnik_block_matrix_t *s, const uint8_t *s_scales,
+                   const void *bq, const uint8_t *b_scales, int b_format,
+                   const sputnik_matrix_t *c, int dtype, void *stream);
+
 /* ---- Host-only queries (no GPU work; safe without a device) */
 /* 1 when the reference would accept the problem (same rules as
  * can_launch_* + ValidMatmul), 0 otherwise. op: 0=DSD 1=DDS 2=SDD. */

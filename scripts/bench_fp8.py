@@ -16,6 +16,11 @@ of ops.mlp_fp8 in both modes next to that of the 16-bit ops.mlp, each as
 torch.autograd.grad over a retained graph, so that only backward is timed.
 ops.mlp's code is the parent commit's, so it is the baseline as it stands.
 
+With --mx the arms are those of the MX path (sputnik/block/mx.h, DESIGN "MX
+forward path"): sdd_mx and dsd_mx for MXFP8 and MXFP4 weights and
+quantize_rows_mx, beside the bf16 products and the fast fp8 products; with
+--parent-lib the fast fp8 products of that build run as *_parent arms.
+
 Protocol: one process, HIP events, every arm warmed for at
 least --warm-ms of device time, then --rounds interleaved rounds, each window
 long enough to hold at least --load-ms of back-to-back calls; medians and
@@ -34,6 +39,8 @@ rate. One JSON line per shape.
 
 python scripts/bench_fp8.py [--shapes c4,decode] [--parent-lib PATH]
                             [--out profiles/fp8/bench_fp8.jsonl]
+python scripts/bench_fp8.py --mx [--parent-lib PATH]
+                            [--out profiles/mx/bench_mx.jsonl]
 """
 import argparse
 import ctypes
@@ -62,6 +69,8 @@ def main():
                          "the *_parent arms")
     ap.add_argument("--backward", action="store_true",
                     help="time the backward pass instead of the forward one")
+    ap.add_argument("--mx", action="store_true",
+                    help="time the MX products beside bf16 and fast fp8")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -96,7 +105,8 @@ def main():
         # (a second copy of the library in this process: its own kernels,
         # the same HIP runtime)
         parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
-        for name in ("sputnik_sdd_fp8", "sputnik_dsd_fp8"):
+        for name in ("sputnik_sdd_fp8", "sputnik_dsd_fp8",
+                     "sputnik_sdd_fp8_acc", "sputnik_dsd_fp8_acc"):
             fn = getattr(parent, name)
             fn.argtypes, fn.restype = sp._SIGNATURES[name], ctypes.c_int
         parent.sputnik_build_hash.restype = ctypes.c_char_p
@@ -139,6 +149,23 @@ def main():
         if parent is not None:
             arms["sdd_fp8_parent"] = through_parent(arms["sdd_fp8"])
             arms["dsd_fp8_parent"] = through_parent(arms["dsd_fp8"])
+        if a.mx:
+            mxw = {f: (ops.quantize_weight_mx(w1, format=f),
+                       ops.quantize_weight_mx(w2, format=f))
+                   for f in ("e4m3", "e2m1")}
+            mq, ms = ops.quantize_rows_mx(x)
+            hmx = ops.quantize_sparse_mx(g16, "gelu")
+            fast = {k: arms[k] for k in ("sdd_fp8_fast", "dsd_fp8_fast")}
+            arms = {"sdd_bf16": arms["sdd_bf16"], "dsd_bf16": arms["dsd_bf16"],
+                    **fast,
+                    "quantize_rows_mx": lambda: ops.quantize_rows_mx(x)}
+            for f, (a1, a2) in mxw.items():
+                arms[f"sdd_mx_{f}"] = (
+                    lambda a1=a1: ops.sdd_mx(mq, ms, a1, topo, dt))
+                arms[f"dsd_mx_{f}"] = lambda a2=a2: ops.dsd_mx(hmx, a2, dt)
+            if parent is not None:
+                for k, fn in fast.items():
+                    arms[f"{k}_parent"] = through_parent(fn)
         if a.backward:
             dy = rand(rows, D_MODEL)
             dh16 = g16.with_data(rand(blocks, 128, 128))
@@ -193,6 +220,8 @@ def main():
         # (both axes: 2 bytes read and 2 written per element and two scales
         # per 128; the activation gradient reads Z as well)
         moved = {"quantize_rows": rows * D_MODEL * 3 + rows * D_MODEL // 32,
+                 "quantize_rows_mx": rows * D_MODEL * 3
+                 + rows * D_MODEL // 32,
                  "quantize_sparse_gelu": blocks * 16384 * 3 + blocks * 512,
                  "quantize_tiles": rows * D_MODEL * 4 + rows * D_MODEL // 16,
                  "quantize_blocks_gelu_grad": blocks * 16384 * 6
@@ -222,7 +251,15 @@ def main():
             for name in ("mlp_fp8_backward", "mlp_fp8_fast_backward"):
                 line[f"{name}_over_bf16"] = round(
                     us[name] / us["mlp_bf16_backward"], 3)
-        for op in () if a.backward else ("sdd", "dsd"):
+        for op in ("sdd", "dsd") if a.mx else ():
+            for f in ("e4m3", "e2m1"):
+                for base in ("bf16", "fp8_fast"):
+                    line[f"{op}_mx_{f}_over_{base}"] = round(
+                        us[f"{op}_mx_{f}"] / us[f"{op}_{base}"], 3)
+            if parent is not None:
+                line[f"{op}_fp8_fast_over_parent"] = round(
+                    us[f"{op}_fp8_fast"] / us[f"{op}_fp8_fast_parent"], 3)
+        for op in () if a.backward or a.mx else ("sdd", "dsd"):
             line[f"{op}_fp8_over_bf16"] = round(
                 us[f"{op}_fp8"] / us[f"{op}_bf16"], 3)
             line[f"{op}_fp8_fast_over_bf16"] = round(

@@ -259,6 +259,19 @@ _SIGNATURES = {
                                      _P, _P],
     "sputnik_dsd_fp8_wgrad": [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
                               ctypes.c_int, ctypes.c_int, _P],
+    # MX products: (x, gate, rows, cols, stage, act, q, scales, dtype, stream);
+    # (w, k, n, transpose, format, q, scales, dtype, stream); (aq, a_scales, k,
+    # bq, b_scales, b_format, c, dtype, stream); (s, s_scales, bq, b_scales,
+    # b_format, c, dtype, stream)
+    "sputnik_quantize_rows_mx": [_P, _P, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_int, ctypes.c_int, _P, _P,
+                                 ctypes.c_int, _P],
+    "sputnik_quantize_weight_mx": [_P, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int, ctypes.c_int, _P, _P,
+                                   ctypes.c_int, _P],
+    "sputnik_sdd_mx": [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P,
+                       ctypes.c_int, _P],
+    "sputnik_dsd_mx": [_P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_can_implement": [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_abi_block_matrix_size": [],
     "sputnik_abi_block_matrix_offset": [ctypes.c_int],
@@ -2066,7 +2079,124 @@ def DsdFp8Wgrad(s, s_scales, bq, b_scales, c, add=False,  # noqa: N802
         int(bool(add)), mode, _stream(stream)), "DsdFp8Wgrad")
 
 
+# ---- MX products (sputnik/block/mx.h) ----------------------------------------
+
+MX_FORMATS = {"e4m3": 0, "e2m1": 1}
+
+
+def _mx_format(fmt, what: str) -> int:
+    if not isinstance(fmt, str) or fmt not in MX_FORMATS:
+        raise ValueError(f"{what}: format must be 'e4m3' or 'e2m1', not "
+                         f"{fmt!r}")
+    return MX_FORMATS[fmt]
+
+
+def _mx_weight(bq, b_scales, fmt, what: str):
+    """(code, n, k) of an MX weight: bq uint8 [n, k / 2] (e2m1) or
+    torch.float8_e4m3fn [n, k], b_scales uint8 [n, k / 32]."""
+    import torch
+
+    code = _mx_format(fmt, what)
+    want = torch.uint8 if code else torch.float8_e4m3fn
+    if getattr(bq, "dtype", None) != want or bq.dim() != 2:
+        raise TypeError(f"{what}: bq must be a 2-D {want} tensor")
+    n, k = int(bq.shape[0]), int(bq.shape[1]) * (2 if code else 1)
+    _fp8_tiles(n, f"{what}: n")
+    _fp8_tiles(k, f"{what}: k")
+    _fp8_buffer(bq, want, tuple(bq.shape), "bq")
+    _fp8_buffer(b_scales, torch.uint8, (n, k // 32), "b_scales")
+    return code, n, k
+
+
+def QuantizeRowsMx(x, q, scales, activation=None, gate=None, stream=None):  # noqa: N802
+    """q (torch.float8_e4m3fn, x's shape) and scales (uint8 [rows, cols /
+    32], e8m0) of x [rows, cols] (fp16 / bf16, cols a multiple of 128): one
+    power-of-two scale per 32 elements, q = rne(x / scale). `activation` and
+    `gate` as QuantizeRows (sputnik_quantize_rows_mx; sputnik/block/mx.h has
+    the format)."""
+    import torch
+
+    _moe_matrix(x, None, None, "x")
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    _fp8_tiles(cols, "QuantizeRowsMx: cols")
+    _fp8_buffer(q, torch.float8_e4m3fn, (rows, cols), "q")
+    _fp8_buffer(scales, torch.uint8, (rows, cols // 32), "scales")
+    if gate is not None:
+        if activation is None:
+            raise ValueError("QuantizeRowsMx: a gate needs its activation")
+        _fp8_buffer(gate, x.dtype, (rows, cols), "gate")
+    act = 0 if activation is None else _act_code(activation)
+    stage = 2 if gate is not None else 0 if activation is None else 1
+    _check(lib().sputnik_quantize_rows_mx(
+        _ptr(x), None if gate is None else _ptr(gate), rows, cols, stage, act,
+        _ptr(q), _ptr(scales), _dtype_code(x), _stream(stream)),
+        "QuantizeRowsMx")
+
+
+def QuantizeWeightMx(w, q, scales, transpose=False, format="e4m3",  # noqa: N802
+                     stream=None):
+    """q ([n, k] torch.float8_e4m3fn, or for "e2m1" uint8 [n, k / 2], two
+    codes per byte, low nibble first) and scales (uint8 [n, k / 32], e8m0) of
+    the weight w [k, n] (fp16 / bf16); with `transpose` the tensor passed
+    holds w^T, [n, k] (sputnik_quantize_weight_mx)."""
+    _moe_matrix(w, None, None, "w")
+    k, n = int(w.shape[0]), int(w.shape[1])
+    if transpose:
+        k, n = n, k
+    code, qn, qk = _mx_weight(q, scales, format, "QuantizeWeightMx")
+    if (qn, qk) != (n, k):
+        raise ValueError(f"QuantizeWeightMx: q stands for [n, k] = [{qn}, "
+                         f"{qk}], w for [{n}, {k}]")
+    _check(lib().sputnik_quantize_weight_mx(
+        _ptr(w), k, n, int(bool(transpose)), code, _ptr(q), _ptr(scales),
+        _dtype_code(w), _stream(stream)), "QuantizeWeightMx")
+
+
+def SddMx(aq, a_scales, bq, b_scales, c, format="e4m3", stream=None):  # noqa: N802
+    """C (BlockMatrix of fp16 / bf16 block values, with row_indices) = Aq . Bq
+    at C's stored blocks: aq e4m3 [c.rows, k] with a_scales uint8 [c.rows,
+    k / 32] (QuantizeRowsMx), bq / b_scales an MX weight of `format`
+    (QuantizeWeightMx). Per k-block one scaled MFMA from +0 and one fp32 add,
+    rounded once (sputnik_sdd_mx)."""
+    import torch
+
+    if not isinstance(c, BlockMatrix):
+        raise TypeError("SddMx writes a BlockMatrix")
+    code, n, k = _mx_weight(bq, b_scales, format, "SddMx")
+    if n != c.cols:
+        raise ValueError(f"SddMx: bq has {n} rows, C {c.cols} columns")
+    _fp8_buffer(aq, torch.float8_e4m3fn, (c.rows, k), "aq")
+    _fp8_buffer(a_scales, torch.uint8, (c.rows, k // 32), "a_scales")
+    cc = c._c()
+    _check(lib().sputnik_sdd_mx(
+        _ptr(aq), _ptr(a_scales), k, _ptr(bq), _ptr(b_scales), code,
+        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "SddMx")
+
+
+def DsdMx(s, s_scales, bq, b_scales, c, format="e4m3", stream=None):  # noqa: N802
+    """C (Matrix of fp16 / bf16, [s.rows, n]) = Sq . Bq: s a BlockMatrix whose
+    data holds e4m3 block values with s_scales uint8 [blocks * 128, 4]
+    (QuantizeRowsMx over the block values as [blocks * 128, 128]); bq /
+    b_scales as SddMx, k = s.cols (sputnik_dsd_mx)."""
+    import torch
+
+    if not isinstance(s, BlockMatrix) or not isinstance(c, Matrix):
+        raise TypeError("DsdMx takes a BlockMatrix and writes a Matrix")
+    code, n, k = _mx_weight(bq, b_scales, format, "DsdMx")
+    if k != s.cols or n != c.cols or c.rows != s.rows:
+        raise ValueError(f"DsdMx shapes [{s.rows}, {s.cols}] x [{k}, {n}] "
+                         f"-> [{c.rows}, {c.cols}]")
+    if getattr(s.data, "dtype", None) != torch.float8_e4m3fn:
+        raise TypeError("DsdMx: s.data must be torch.float8_e4m3fn")
+    _fp8_buffer(s_scales, torch.uint8, (s.num_blocks * 128, 4), "s_scales")
+    cs, cc = s._c(), c._c()
+    _check(lib().sputnik_dsd_mx(
+        ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales), code,
+        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "DsdMx")
+
+
 __all__ = [
+    "QuantizeRowsMx", "QuantizeWeightMx", "SddMx", "DsdMx", "MX_FORMATS",
     "AllocateBitmaskBuffers", "AllocateRowIndicesBuffer",
     "AllocateTransposeBuffers", "AsInt", "Bitmask", "FreeBitmaskBuffers",
     "build_hash", "capture_workspaces", "pair_errors", "sdd_plan", "sdd_kernel",

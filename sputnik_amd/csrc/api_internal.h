@@ -3,6 +3,7 @@
 #define SPUTNIK_AMD_API_INTERNAL_H_
 
 #include <cstddef>
+#include <cstdint>
 
 #include "sputnik/block/arguments.h"
 
@@ -138,6 +139,17 @@ hipError_t LaunchFp8Wgrad(bool fast, int dtype, bool out_f32, bool add,
 hipError_t LaunchFp8IntervalSums(const void *aq, const void *bq, int m, int n,
                                  int k, bool fast, float *out,
                                  hipStream_t stream);
+
+// The MX block GEMM (sputnik/block/mx.h, mx_gemm.hip), arguments already
+// validated by SddMx / DsdMx (block_api.cpp); operands as LaunchFp8Gemm's with
+// e8m0 scale bytes: a_scales [m, k / 32] (DSD: [nnz_blocks * 128, 4]), b = Bq
+// [n, k] or, with `b4` (e2m1), [n, k / 2], b_scales [n, k / 32].
+hipError_t LaunchMxGemm(bool dsd, bool b4, int dtype, const void *a,
+                        const uint8_t *a_scales, const void *b,
+                        const uint8_t *b_scales, void *c, const int *offsets,
+                        const short *indices, const short *row_indices,
+                        int m_blocks, int n_blocks, int k_blocks,
+                        int nnz_blocks, hipStream_t stream);
 
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.

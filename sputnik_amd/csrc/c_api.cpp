@@ -764,6 +764,46 @@ int sputnik_dsd_fp8_wgrad(const sputnik_block_matrix_t *s,
       static_cast<hipStream_t>(stream));
 }
 
+// MX products (sputnik/block/mx.h): mx_quantize.hip and block_api.cpp
+// validate.
+int sputnik_quantize_rows_mx(const void *x, const void *gate, int rows,
+                             int cols, int stage, int act, void *q,
+                             uint8_t *scales, int dtype, void *stream) {
+  return sputnik::block::QuantizeRowsMx(
+      x, gate, rows, cols, static_cast<sputnik::block::MxStage>(stage),
+      static_cast<sputnik::block::Activation>(act), q, scales,
+      static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
+}
+
+int sputnik_quantize_weight_mx(const void *w, int k, int n, int transpose,
+                               int format, void *q, uint8_t *scales, int dtype,
+                               void *stream) {
+  return sputnik::block::QuantizeWeightMx(
+      w, k, n, transpose != 0, static_cast<sputnik::block::MxFormat>(format),
+      q, scales, static_cast<DataType>(dtype),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_sdd_mx(const void *aq, const uint8_t *a_scales, int k,
+                   const void *bq, const uint8_t *b_scales, int b_format,
+                   const sputnik_block_matrix_t *c, int dtype, void *stream) {
+  if (!c) return hipErrorInvalidValue;
+  return sputnik::block::SddMx(
+      aq, a_scales, k, bq, b_scales,
+      static_cast<sputnik::block::MxFormat>(b_format), ToCpp(c),
+      static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
+}
+
+int sputnik_dsd_mx(const sputnik_block_matrix_t *s, const uint8_t *s_scales,
+                   const void *bq, const uint8_t *b_scales, int b_format,
+                   const sputnik_matrix_t *c, int dtype, void *stream) {
+  if (!s || !c) return hipErrorInvalidValue;
+  return sputnik::block::DsdMx(
+      ToCpp(s), s_scales, bq, b_scales,
+      static_cast<sputnik::block::MxFormat>(b_format), ToCpp(c),
+      static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
+}
+
 // MoE router and device sort (sputnik/block/router.h): moe_router.hip
 // validates.
 int sputnik_router_topk(const void *logits, int32_t *top_experts,

@@ -87,6 +87,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                PaddedScatterBiasWeightGrad,
                QuantizeRows, QuantizeWeight, SddFp8, DsdFp8, FP8_ACCUMULATE,
                QuantizeTiles, QuantizeBlocks, TransposeWeightFp8, DsdFp8Wgrad,
+               QuantizeRowsMx, QuantizeWeightMx, SddMx, DsdMx, MX_FORMATS,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
                RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
                MOE_SORT_CHUNK, ROUTER_AUX_TOKENS, ROUTER_MAX_EXPERTS,
@@ -1272,11 +1273,12 @@ def _check_moe_biases(x, w1, v1, num_experts: int, biases, what: str):
 
 
 def _moe_args(x, top_experts, expert_weights, w1, w2, v1, num_experts, rows,
-              fp8: bool = False):
-    """The checks moe_mlp and moe_mlp_fp8 share, up to the route: returns
-    (the MoeRoute passed in or None, the expert weights' hidden columns).
-    The weights are tensors of x's dtype or, with `fp8`, Fp8Weights (their
-    shape is the [k, n] of the weight they hold)."""
+              fp8: bool = False, mx: bool = False):
+    """The checks moe_mlp, moe_mlp_fp8 and moe_mlp_mx share, up to the route:
+    returns (the MoeRoute passed in or None, the expert weights' hidden
+    columns). The weights are tensors of x's dtype or, with `fp8` / `mx`,
+    Fp8Weights / MxWeights (their shape is the [k, n] of the weight they
+    hold)."""
     route = top_experts if isinstance(top_experts, MoeRoute) else None
     if route is None:
         tokens, top_k = _top_experts(top_experts, num_experts)
@@ -1290,7 +1292,11 @@ def _moe_args(x, top_experts, expert_weights, w1, w2, v1, num_experts, rows,
                              f"{route.rows}")
     _check_rows(x, tokens, "moe_mlp: x")
     ws = (w1, w2) if v1 is None else (w1, v1, w2)
-    if fp8:
+    if mx:
+        if not all(isinstance(w, MxWeight) for w in ws):
+            raise TypeError("moe_mlp_mx: the expert weights are MxWeights "
+                            "(quantize_weight_mx, MxWeight.from_tensors)")
+    elif fp8:
         if not all(isinstance(w, Fp8Weight) for w in ws):
             raise TypeError("moe_mlp_fp8: the expert weights are Fp8Weights "
                             "(quantize_weight, Fp8Weight.from_tensors)")
@@ -1637,6 +1643,213 @@ def moe_mlp_fp8(x: torch.Tensor, top_experts: torch.Tensor,
         hq = quantize_sparse(u, "silu" if act is None else act, gate=g)
     return padded_scatter(dsd_fp8(hq, w2q, x.dtype, accumulate), route,
                           expert_weights)
+
+
+# ---- MX expert products (sputnik/block/mx.h) ---------------------------------
+
+@dataclass
+class MxWeight:
+    """A weight [k, n] in an MX format (sputnik/block/mx.h): `q` k-contiguous,
+    torch.float8_e4m3fn [n, k] ("e4m3") or uint8 [n, k / 2] holding two e2m1
+    codes per byte, low nibble first ("e2m1"); `scales` uint8 [n, k / 32],
+    one e8m0 byte per 32 k-elements."""
+
+    q: torch.Tensor
+    scales: torch.Tensor
+    k: int
+    n: int
+    format: str
+
+    @property
+    def shape(self):
+        return (self.k, self.n)
+
+    def dim(self) -> int:
+        return 2
+
+    @classmethod
+    def from_tensors(cls, q: torch.Tensor, scales: torch.Tensor,
+                     format: str = "e4m3") -> "MxWeight":
+        """Checkpoint data as it is: `q` [n, k] (e2m1: [n, k / 2], as uint8 or
+        torch.float4_e2m1fn_x2) and `scales` [n, k / 32] as uint8 (or
+        torch.float8_e8m0fnu). Nothing is copied unless a tensor is not
+        contiguous."""
+        if format not in MX_FORMATS:
+            raise ValueError("MxWeight: format must be 'e4m3' or 'e2m1'")
+        if not isinstance(q, torch.Tensor) or q.dim() != 2:
+            raise ValueError("MxWeight: q is a 2-D tensor")
+        if not isinstance(scales, torch.Tensor) or scales.dim() != 2:
+            raise ValueError("MxWeight: scales is a 2-D tensor")
+        if q.element_size() != 1 or scales.element_size() != 1:
+            raise TypeError("MxWeight: q and scales hold one byte per entry")
+        q = q.contiguous().view(
+            torch.uint8 if format == "e2m1" else torch.float8_e4m3fn)
+        scales = scales.contiguous().view(torch.uint8)
+        n, k = int(q.shape[0]), int(q.shape[1]) * (2 if format == "e2m1" else 1)
+        if n % BLOCK or k % BLOCK:
+            raise ValueError(f"MxWeight: [n, k] = [{n}, {k}] is not a "
+                             "multiple of 128")
+        if tuple(scales.shape) != (n, k // 32):
+            raise ValueError(f"MxWeight: scales have shape "
+                             f"{tuple(scales.shape)}, expected {(n, k // 32)}")
+        return cls(q, scales, k, n, format)
+
+
+class MxSparseMatrix(SparseMatrix):
+    """A SparseMatrix whose block values are e4m3 bytes, with `scales` uint8
+    [nnz_blocks * 128, 4]: the four e8m0 bytes of each stored-block row, in
+    storage order (quantize_sparse_mx). The operand of dsd_mx."""
+
+    def __init__(self, topo: SparseMatrix, q: torch.Tensor,
+                 scales: torch.Tensor):
+        m = topo._meta
+        super().__init__((m.rows, m.cols), q, m.offsets, m.indices, _meta=m)
+        self.scales = scales
+
+
+def quantize_rows_mx(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(q, scales) of x [rows, cols] (fp16 / bf16, cols a multiple of 128) as
+    MXFP8: q torch.float8_e4m3fn of x's shape, scales uint8 [rows, cols /
+    32], x ~ float(q) * 2^(scale - 127). Forward only."""
+    _check_dtypes(x)
+    _no_grad("quantize_rows_mx", x)
+    if x.dim() != 2 or int(x.shape[1]) % BLOCK:
+        raise ValueError("quantize_rows_mx: x is [rows, a multiple of 128]")
+    x = x.contiguous()
+    q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    scales = torch.empty(x.shape[0], x.shape[1] // 32, dtype=torch.uint8,
+                         device=x.device)
+    QuantizeRowsMx(x, q, scales)
+    return q, scales
+
+
+def quantize_sparse_mx(sparse: SparseMatrix, activation=None,
+                       gate: Optional[SparseMatrix] = None) -> MxSparseMatrix:
+    """quantize_sparse in MXFP8: the block values of `sparse` (or of
+    act(sparse), or of sparse * act(gate)) as the matrix [nnz_blocks * 128,
+    128], one e8m0 scale per 32 elements of a stored-block row. Forward
+    only."""
+    if not isinstance(sparse, SparseMatrix) or sparse.is_transposed():
+        raise TypeError("quantize_sparse_mx takes a SparseMatrix (not a .t() "
+                        "view)")
+    _check_dtypes(sparse.data)
+    _no_grad("quantize_sparse_mx", sparse.data,
+             None if gate is None else gate.data)
+    g = None
+    if gate is not None:
+        if (not isinstance(gate, SparseMatrix)
+                or gate._meta is not sparse._meta or gate.is_transposed()
+                or gate.dtype != sparse.dtype):
+            raise ValueError("quantize_sparse_mx: gate must share sparse's "
+                             "topology and dtype")
+        if activation is None:
+            raise ValueError("quantize_sparse_mx: a gate needs its activation")
+        g = gate.data.contiguous().view(-1, BLOCK)
+    nb = sparse.nnz_blocks
+    x = sparse.data.contiguous().view(nb * BLOCK, BLOCK)
+    q = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
+                    device=x.device)
+    scales = torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=x.device)
+    QuantizeRowsMx(x, q.view(nb * BLOCK, BLOCK), scales,
+                   None if activation is None else _act_code(activation), g)
+    return MxSparseMatrix(sparse, q, scales)
+
+
+def quantize_weight_mx(w: torch.Tensor, transpose: bool = False,
+                       format: str = "e4m3") -> MxWeight:
+    """The MxWeight of w [k, n] (fp16 / bf16, both multiples of 128) in
+    `format` ("e4m3": MXFP8, "e2m1": MXFP4); with `transpose` the tensor
+    passed is w^T, [n, k]. Runs once, at load time."""
+    _check_dtypes(w)
+    _no_grad("quantize_weight_mx", w)
+    if format not in MX_FORMATS:
+        raise ValueError("quantize_weight_mx: format must be 'e4m3' or 'e2m1'")
+    if w.dim() != 2 or int(w.shape[0]) % BLOCK or int(w.shape[1]) % BLOCK:
+        raise ValueError("quantize_weight_mx: w is 2-D with multiples of 128")
+    w = w.contiguous()
+    k, n = (int(w.shape[1]), int(w.shape[0])) if transpose else (
+        int(w.shape[0]), int(w.shape[1]))
+    if format == "e2m1":
+        q = torch.empty(n, k // 2, dtype=torch.uint8, device=w.device)
+    else:
+        q = torch.empty(n, k, dtype=torch.float8_e4m3fn, device=w.device)
+    scales = torch.empty(n, k // 32, dtype=torch.uint8, device=w.device)
+    QuantizeWeightMx(w, q, scales, transpose, format)
+    return MxWeight(q, scales, k, n, format)
+
+
+def sdd_mx(xq: torch.Tensor, xs: torch.Tensor, w: MxWeight,
+           topo: SparseMatrix, out_dtype=torch.bfloat16) -> SparseMatrix:
+    """(xq . w) at topo's nonzero blocks with MX operands: xq / xs from
+    quantize_rows_mx, w an MxWeight of [k, n] in either format, topo [m, n].
+    The matrix cores apply the e8m0 scales; per 128-wide k-block one scaled
+    MFMA from zero and one fp32 add, rounded once to `out_dtype`. Bitwise
+    reproducible. Forward only."""
+    if not isinstance(w, MxWeight):
+        raise TypeError("sdd_mx: w must be an MxWeight")
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError("sdd_mx: topo must be a SparseMatrix (not a .t() "
+                        "view)")
+    _out_dtype(out_dtype, "sdd_mx")
+    if (not isinstance(xq, torch.Tensor) or xq.dim() != 2
+            or (int(xq.shape[0]), w.n) != tuple(topo.shape)
+            or int(xq.shape[1]) != w.k):
+        raise ValueError(f"sdd_mx shapes {tuple(getattr(xq, 'shape', ()))} "
+                         f"x {w.shape} -> {topo.shape}")
+    data = torch.empty(topo.nnz_blocks, BLOCK, BLOCK, dtype=out_dtype,
+                       device=xq.device)
+    topo._meta.ensure_row_indices(data)
+    SddMx(xq, xs, w.q, w.scales, topo._meta.descriptor(data), w.format)
+    return topo.with_data(data)
+
+
+def dsd_mx(sq: MxSparseMatrix, w: MxWeight,
+           out_dtype=torch.bfloat16) -> torch.Tensor:
+    """sq . w as a dense [m, n] tensor of `out_dtype` with MX operands: sq
+    from quantize_sparse_mx, w an MxWeight of [k, n]. Arithmetic as sdd_mx,
+    over the stored blocks of each block row in storage order; a block row
+    without blocks gives +0 rows. Forward only."""
+    if not isinstance(sq, MxSparseMatrix):
+        raise TypeError("dsd_mx: sq must come from quantize_sparse_mx")
+    if not isinstance(w, MxWeight):
+        raise TypeError("dsd_mx: w must be an MxWeight")
+    _out_dtype(out_dtype, "dsd_mx")
+    if sq.shape[1] != w.k:
+        raise ValueError(f"dsd_mx shapes {sq.shape} x {w.shape}")
+    out = torch.empty(sq.shape[0], w.n, dtype=out_dtype, device=sq.device)
+    DsdMx(sq._descriptor(), sq.scales, w.q, w.scales,
+          Matrix(out.shape[0], out.shape[1], out), w.format)
+    return out
+
+
+def moe_mlp_mx(x: torch.Tensor, top_experts: torch.Tensor,
+               expert_weights: torch.Tensor, w1q: MxWeight, w2q: MxWeight,
+               num_experts: int, activation=None,
+               v1q: Optional[MxWeight] = None,
+               rows: Optional[int] = None) -> torch.Tensor:
+    """moe_mlp with the expert products in MX formats (sputnik/block/mx.h):
+    padded_gather -> quantize_rows_mx -> sdd_mx with `w1q` (and with `v1q`
+    for a GLU) -> quantize_sparse_mx with the activation (or the gate) ->
+    dsd_mx with `w2q` -> padded_scatter: moe_mlp_fp8's chain and defaults.
+    The activations are MXFP8; each weight is MXFP8 or MXFP4
+    (quantize_weight_mx, MxWeight.from_tensors). Forward only."""
+    _no_grad("moe_mlp_mx", x, expert_weights)
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1q, w2q, v1q,
+                              num_experts, rows, mx=True)
+    act = None if activation is None else _act_code(activation)
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    xq, xs = quantize_rows_mx(xp)
+    g = sdd_mx(xq, xs, w1q, topo, x.dtype)
+    if v1q is None:
+        hq = quantize_sparse_mx(g, "gelu" if act is None else act)
+    else:
+        u = sdd_mx(xq, xs, v1q, topo, x.dtype)
+        hq = quantize_sparse_mx(u, "silu" if act is None else act, gate=g)
+    return padded_scatter(dsd_mx(hq, w2q, x.dtype), route, expert_weights)
 
 
 # ---- FP8 gradients (sputnik/block/fp8.h, "Gradients") ------------------------
@@ -2382,4 +2595,7 @@ __all__ = ["MoeAux", "MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_a
            "quantize_weight", "sdd_fp8", "dsd_fp8", "moe_mlp_fp8",
            "quantize_tiles", "quantize_sparse_t", "dsd_fp8_wgrad", "mlp_fp8",
            "moe_mlp_fp8_train",
+           "MxWeight", "MxSparseMatrix", "quantize_rows_mx",
+           "quantize_sparse_mx", "quantize_weight_mx", "sdd_mx", "dsd_mx",
+           "moe_mlp_mx",
            "topology_from_mask"]
