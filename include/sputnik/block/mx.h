@@ -1,7 +1,9 @@
-// sputnik-amd: OCP Microscaling (MX) expert products for the forward pass:
-// MXFP8 (e4m3) activations against MXFP8 (e4m3) or MXFP4 (e2m1) weights, with
-// the e8m0 block scales applied by the matrix instruction itself. Quantisers,
-// an SDD and a DSD. Extensions, all of them: no counterpart in the reference.
+// sputnik-amd: OCP Microscaling (MX) expert products: MXFP8 (e4m3)
+// activations against MXFP8 (e4m3) or MXFP4 (e2m1) weights, with the e8m0
+// block scales applied by the matrix instruction itself. Quantisers, an SDD
+// and a DSD for the forward pass; for the gradients (below, "Gradients")
+// quantisers along the token dimension and a DSD into gradient sinks, MXFP8
+// throughout. Extensions, all of them: no counterpart in the reference.
 //
 // Format (part of the contract, bit for bit):
 //
@@ -96,22 +98,102 @@
 //   A NaN byte of A / S makes NaN exactly its row of that step's tile, a 0xFF
 //   scale byte of B exactly its column (the OCP rule).
 //
+// Gradients (e4m3 throughout; the table reads X [T, h], W1t [F, h], W2 [F,
+// h], topology [T, F], Z = X W1t^T at the blocks, H = act(Z), Y = H W2). MX
+// scales belong to one operand and run along k, so every product is SddMx /
+// DsdMx's step with operands that arrive contiguous along its own k:
+//
+//   dH  = dY W2^T at the blocks   SddMx: dY [T, k = h] (QuantizeTilesMx' row
+//                                 outputs), W2 as [n = F, k = h] bytes
+//                                 (QuantizeWeightMx(w2, transpose))
+//   dZ  = dH * act'(Z)            QuantizeBlocksMx, stage kActivationGrad
+//   dX  = dZ W1t                  DsdMx: dZ's row outputs, storage order; W1t
+//                                 as [n = h, k = F] bytes (QuantizeWeightMx(
+//                                 w1t), from the buffer read as [k = F, n = h])
+//   dW2  = H^T dY   [F, h]        DsdMxWgrad: H^T's / dZ^T's blocks in the
+//   dW1t = dZ^T X   [F, h]        transposed order, scaled along the tokens
+//                                 (QuantizeBlocksMx' column outputs; H from
+//                                 stage kActivation of Z), dY / X as [n = h,
+//                                 k = T] with one byte per column and 32
+//                                 tokens (QuantizeTilesMx' column outputs)
+//
+//   An MX weight cannot be transposed exactly (its scale groups are 1 x 32,
+//   not square), so the backward layouts of the weights are quantised from
+//   the 16-bit master weights by QuantizeWeightMx.
+//
+//   QuantizeTilesMx  x [rows, cols] of T, both multiples of 128, read once,
+//                    one workgroup per 128 x 128 tile. Row outputs q [rows,
+//                    cols], scales [rows, cols / 32]: QuantizeRowsMx(kNone)'s
+//                    bits. Column outputs qt [cols, rows] (the bytes of a
+//                    column contiguous along the rows) and scales_t [cols,
+//                    rows / 32]: the group of scales_t[c, g] is x[32 g : 32 g
+//                    + 32, c], scale, element and non-finite rules as above
+//                    for e4m3. qt / scales_t are a Bq [n = cols, k = rows] /
+//                    b_scales of SddMx / DsdMx / DsdMxWgrad as they stand.
+//                    Either pair may be null (both pointers of it), not both
+//                    pairs.
+//   QuantizeBlocksMx the block values [nnz_blocks, 128, 128] of s (s.data, T)
+//                    after a stage: kNone; kActivation, act(x) as
+//                    QuantizeRowsMx(kActivation) evaluates it;
+//                    kActivationGrad, x * act'(z) as MatmulActivationGrad's
+//                    elementwise stage evaluates it (z: block values of the
+//                    same layout), rounded to T before it is quantised. Row
+//                    outputs q [nnz_blocks, 128, 128], scales [nnz_blocks 128,
+//                    4], in storage order: QuantizeRowsMx's bits on the same
+//                    values, the Sq / s_scales of DsdMx. Column outputs in the
+//                    transposed order: output block j is source block
+//                    s.block_offsets[j] stored transposed ([column][row]),
+//                    scales_t[128 j + c] the dword of the four 32-row groups
+//                    of source column c. They are the Sq / s_scales of a DSD
+//                    over the descriptor {rows = s.cols, cols = s.rows,
+//                    offsets = s.offsets_t, indices = s.indices_t}. Column
+//                    outputs need s.block_offsets (Transpose),
+//                    hipErrorInvalidValue without; an entry outside [0,
+//                    nnz_blocks) leaves its output block unwritten. The
+//                    workgroup of output block j also writes the row outputs
+//                    of its source block when both pairs are asked for, so
+//                    block_offsets is then a permutation, as Transpose leaves
+//                    it. Only s.data, s.nonzeros, s.block_size and
+//                    s.block_offsets are read.
+//   DsdMxWgrad       C [m, n] = Sq . Bq as DsdMx with an e4m3 B: the steps in
+//                    the row's storage order, the k map, the +0 accumulator
+//                    input and the one fp32 add per step are DsdMx's. C =
+//                    round_out(acc), or with `add` round_out(acc +
+//                    float(C_old)): one fp32 add, one rounding. `out`
+//                    (accumulate.h) is kOperand, C of T, or kF32, C of fp32.
+//                    With kOperand and no `add` the bits are DsdMx's. A block
+//                    row of s without stored blocks gives +0 rows, and with
+//                    `add` is neither read nor written, as MatmulAccumulate
+//                    has it. No split-K, no atomics, no hand-off: the same
+//                    inputs give the same bits. Out-of-range indices,
+//                    alignment (Sq, Bq and C 16 bytes, scales 4), checks and
+//                    zero-sized work as DsdMx; C being any input is rejected.
+//                    Error, K the tokens of the row (128 per stored block):
+//                      |C - exact| <= 2^-p |exact|
+//                          + (eps_fast + (K / 128 + 1 + add) 2^-23) sum |terms|
+//                    the + add is the fp32 add of C_old, which with `add` is
+//                    one of the terms, of exact and of sum |terms| alike; the
+//                    first summand is absent for fp32 output, which is not
+//                    rounded again.
+//
 // `dtype` is T, the 16-bit type. Every call is stream-ordered, allocates
 // nothing and never synchronises or aborts: hipErrorInvalidValue, with nothing
 // launched, for a null required buffer, a negative size, a dimension that is
 // not a multiple of 128, a block size other than 128, an MxFormat / MxStage /
-// Activation outside its enum, a misaligned buffer (above; the quantisers take
-// any alignment) or an output that is one of the inputs. Zero-sized work
-// succeeds.
+// MxBlockStage / OutputType / Activation outside its enum, a misaligned
+// buffer (above; the quantisers take any alignment) or an output that is one
+// of the inputs. Zero-sized work succeeds.
 //
-// Out of scope: gradients; e5m2, e3m2 and e2m3 elements; MXFP4 activations;
-// DDS / SSD / SDS / DSS; chaining the accumulator through the MFMA; a CPU
-// model of the instruction's internal sum; biases; a C++ example.
+// Out of scope: the backward of MXFP4 weights; GLU gradients; e5m2, e3m2 and
+// e2m3 elements; MXFP4 activations; DDS / SSD / SDS / DSS; chaining the
+// accumulator through the MFMA; a CPU model of the instruction's internal
+// sum; biases; a C++ example.
 #ifndef SPUTNIK_BLOCK_MX_H_
 #define SPUTNIK_BLOCK_MX_H_
 
 #include <cstdint>
 
+#include "sputnik/block/accumulate.h"
 #include "sputnik/block/activation.h"
 #include "sputnik/block/arguments.h"
 #include "sputnik/block/dtype.h"
@@ -139,6 +221,27 @@ hipError_t SddMx(const void *aq, const uint8_t *a_scales, int k,
 hipError_t DsdMx(const BlockMatrix s, const uint8_t *s_scales, const void *bq,
                  const uint8_t *b_scales, MxFormat b_format, Matrix c,
                  DataType dtype, hipStream_t stream);
+
+// ---- Gradients (above). ----
+
+// What QuantizeBlocksMx applies to the block values before it quantises them.
+enum class MxBlockStage { kNone = 0, kActivation = 1, kActivationGrad = 2 };
+
+hipError_t QuantizeTilesMx(const void *x, int rows, int cols, void *q,
+                           uint8_t *scales, void *qt, uint8_t *scales_t,
+                           DataType dtype, hipStream_t stream);
+
+// `activation` is read when `stage` is not kNone, `z` when it is
+// kActivationGrad.
+hipError_t QuantizeBlocksMx(const BlockMatrix s, MxBlockStage stage,
+                            Activation activation, const void *z, void *q,
+                            uint8_t *scales, void *qt, uint8_t *scales_t,
+                            DataType dtype, hipStream_t stream);
+
+hipError_t DsdMxWgrad(const BlockMatrix s, const uint8_t *s_scales,
+                      const void *bq, const uint8_t *b_scales, Matrix c,
+                      OutputType out, bool add, DataType dtype,
+                      hipStream_t stream);
 
 }  // namespace block
 }  // namespace sputnik

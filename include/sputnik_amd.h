@@ -724,6 +724,39 @@ int sputnik_dsd_mx(const sputnik_block_matrix_t *s, const uint8_t *s_scales,
                    const void *bq, const uint8_t *b_scales, int b_format,
                    const sputnik_matrix_t *c, int dtype, void *stream);
 
+/* The MX gradients' pieces (sputnik/block/mx.h, "Gradients", has the contract
+ * and the table of the backward pass). Elements are e4m3.
+ *
+ *   sputnik_quantize_tiles_mx   x [rows, cols] of T, both multiples of 128 ->
+ *                               the row outputs of sputnik_quantize_rows_mx
+ *                               (q, scales) and / or the column outputs qt
+ *                               [cols, rows], scales_t [cols, rows / 32], one
+ *                               e8m0 byte per column and 32 rows. A pair may
+ *                               be null.
+ *   sputnik_quantize_blocks_mx  the block values of s after `stage` (0 none,
+ *                               1 act(x), 2 x * act'(z)): row outputs in
+ *                               storage order (q, scales [blocks * 128, 4])
+ *                               and / or column outputs in the transposed
+ *                               order of s.block_offsets (qt: output block j
+ *                               is source block block_offsets[j] transposed;
+ *                               scales_t [blocks * 128, 4], a dword per source
+ *                               column)
+ *   sputnik_dsd_mx_wgrad        sputnik_dsd_mx with an e4m3 B into a gradient
+ *                               sink. `out` 0: C of T, 1: C of fp32; `add`:
+ *                               C = round(acc + float(C)), and block rows of
+ *                               s without blocks are left untouched. */
+int sputnik_quantize_tiles_mx(const void *x, int rows, int cols, void *q,
+                              uint8_t *scales, void *qt, uint8_t *scales_t,
+                              int dtype, void *stream);
+int sputnik_quantize_blocks_mx(const sputnik_block_matrix_t *s, int stage,
+                               int act, const void *z, void *q,
+                               uint8_t *scales, void *qt, uint8_t *scales_t,
+                               int dtype, void *stream);
+int sputnik_dsd_mx_wgrad(const sputnik_block_matrix_t *s,
+                         const uint8_t *s_scales, const void *bq,
+                         const uint8_t *b_scales, const sputnik_matrix_t *c,
+                         int out, int add, int dtype, void *stream);
+
 /* ---- Host-only queries (no GPU work; safe without a device) */
 /* 1 when the reference would accept the problem (same rules as
  * can_launch_* + ValidMatmul), 0 otherwise. op: 0=DSD 1=DDS 2=SDD. */

@@ -21,6 +21,13 @@ forward path"): sdd_mx and dsd_mx for MXFP8 and MXFP4 weights and
 quantize_rows_mx, beside the bf16 products and the fast fp8 products; with
 --parent-lib the fast fp8 products of that build run as *_parent arms.
 
+With --mx --backward the arms are those of the MX backward pass (DESIGN "MX
+backward path"): quantize_tiles_mx of dY and QuantizeBlocksMx with the gelu
+gradient (both axes each), dsd_mx_wgrad next to the 16-bit H^T dY and the fast
+dsd_fp8_wgrad, and the whole backward of ops.mlp_mx next to ops.mlp's and
+ops.mlp_fp8's (both modes). The bf16 and fp8 arms are the parent commit's
+code.
+
 Protocol: one process, HIP events, every arm warmed for at
 least --warm-ms of device time, then --rounds interleaved rounds, each window
 long enough to hold at least --load-ms of back-to-back calls; medians and
@@ -41,6 +48,8 @@ python scripts/bench_fp8.py [--shapes c4,decode] [--parent-lib PATH]
                             [--out profiles/fp8/bench_fp8.jsonl]
 python scripts/bench_fp8.py --mx [--parent-lib PATH]
                             [--out profiles/mx/bench_mx.jsonl]
+python scripts/bench_fp8.py --mx --backward
+                            [--out profiles/mx/bench_mx_grad.jsonl]
 """
 import argparse
 import ctypes
@@ -149,7 +158,7 @@ def main():
         if parent is not None:
             arms["sdd_fp8_parent"] = through_parent(arms["sdd_fp8"])
             arms["dsd_fp8_parent"] = through_parent(arms["dsd_fp8"])
-        if a.mx:
+        if a.mx and not a.backward:
             mxw = {f: (ops.quantize_weight_mx(w1, format=f),
                        ops.quantize_weight_mx(w2, format=f))
                    for f in ("e4m3", "e2m1")}
@@ -198,6 +207,23 @@ def main():
                     lambda x_, a_, b_: ops.mlp_fp8(x_, a_, b_, topo, "gelu",
                                                    "fast"), x, w1t, w2),
             }
+        if a.backward and a.mx:
+            _, _, myqt, myst = ops.quantize_tiles_mx(dy, rows=False)
+            hmt = ops.quantize_sparse_mx_t(g16, "gelu")[1]
+            keep = ("wgrad_bf16", "wgrad_fp8_fast", "mlp_bf16_backward",
+                    "mlp_fp8_backward", "mlp_fp8_fast_backward")
+            arms = {
+                "quantize_tiles_mx": lambda: ops.quantize_tiles_mx(dy),
+                "quantize_blocks_mx_gelu_grad":
+                    lambda: ops._quantize_blocks_mx(dh16, "act_grad", 1,
+                                                    g16.data, True, True),
+                "wgrad_mx": lambda: ops.dsd_mx_wgrad(hmt, myqt, myst,
+                                                     out_dtype=dt),
+                **{k: arms[k] for k in keep},
+                "mlp_mx_backward": backward_of(
+                    lambda x_, a_, b_: ops.mlp_mx(x_, a_, b_, topo, "gelu"),
+                    x, w1t, w2),
+            }
         calls = {}
         for name, fn in arms.items():
             fn()
@@ -225,6 +251,9 @@ def main():
                  "quantize_sparse_gelu": blocks * 16384 * 3 + blocks * 512,
                  "quantize_tiles": rows * D_MODEL * 4 + rows * D_MODEL // 16,
                  "quantize_blocks_gelu_grad": blocks * 16384 * 6
+                 + blocks * 1024,
+                 "quantize_tiles_mx": rows * D_MODEL * 4 + rows * D_MODEL // 16,
+                 "quantize_blocks_mx_gelu_grad": blocks * 16384 * 6
                  + blocks * 1024}
         line = {"shape": shape, "rows": rows, "blocks": blocks,
                 "build": sp.build_hash(), "rounds": a.rounds, "arms": {}}
@@ -243,7 +272,15 @@ def main():
                 arm["hbm_share"] = round(tbs / HBM_TBS, 3)
             line["arms"][name] = arm
         us = {name: arm["us"] for name, arm in line["arms"].items()}
-        if a.backward:
+        if a.backward and a.mx:
+            line["pass"] = "mx backward"
+            for base in ("bf16", "fp8_fast"):
+                line[f"wgrad_mx_over_{base}"] = round(
+                    us["wgrad_mx"] / us[f"wgrad_{base}"], 3)
+            for base in ("bf16", "fp8", "fp8_fast"):
+                line[f"mlp_mx_backward_over_{base}"] = round(
+                    us["mlp_mx_backward"] / us[f"mlp_{base}_backward"], 3)
+        elif a.backward:
             line["pass"] = "backward"
             for name in ("wgrad_fp8", "wgrad_fp8_fast"):
                 line[f"{name}_over_bf16"] = round(
@@ -251,7 +288,7 @@ def main():
             for name in ("mlp_fp8_backward", "mlp_fp8_fast_backward"):
                 line[f"{name}_over_bf16"] = round(
                     us[name] / us["mlp_bf16_backward"], 3)
-        for op in ("sdd", "dsd") if a.mx else ():
+        for op in ("sdd", "dsd") if a.mx and not a.backward else ():
             for f in ("e4m3", "e2m1"):
                 for base in ("bf16", "fp8_fast"):
                     line[f"{op}_mx_{f}_over_{base}"] = round(

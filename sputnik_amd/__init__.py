@@ -272,6 +272,15 @@ _SIGNATURES = {
     "sputnik_sdd_mx": [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P,
                        ctypes.c_int, _P],
     "sputnik_dsd_mx": [_P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_int, _P],
+    # their gradients' pieces: (x, rows, cols, q, scales, qt, scales_t, dtype,
+    # stream); (s, stage, act, z, q, scales, qt, scales_t, dtype, stream); (s,
+    # s_scales, bq, b_scales, c, out, add, dtype, stream)
+    "sputnik_quantize_tiles_mx": [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P,
+                                  _P, ctypes.c_int, _P],
+    "sputnik_quantize_blocks_mx": [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P,
+                                   _P, _P, ctypes.c_int, _P],
+    "sputnik_dsd_mx_wgrad": [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
+                             ctypes.c_int, _P],
     "sputnik_can_implement": [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_abi_block_matrix_size": [],
     "sputnik_abi_block_matrix_offset": [ctypes.c_int],
@@ -2195,8 +2204,106 @@ def DsdMx(s, s_scales, bq, b_scales, c, format="e4m3", stream=None):  # noqa: N8
         ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "DsdMx")
 
 
+def _mx_pair(q, scales, q_shape, s_shape, what: str):
+    """An output pair of an MX tile quantiser: both given or both None."""
+    import torch
+
+    if (q is None) != (scales is None):
+        raise ValueError(f"{what}: an output pair is given whole or not at "
+                         "all")
+    if q is None:
+        return None, None
+    _fp8_buffer(q, torch.float8_e4m3fn, q_shape, f"{what} bytes")
+    _fp8_buffer(scales, torch.uint8, s_shape, f"{what} scales")
+    return _ptr(q), _ptr(scales)
+
+
+def QuantizeTilesMx(x, q=None, scales=None, qt=None, scales_t=None,  # noqa: N802
+                    stream=None):
+    """x [rows, cols] (fp16 / bf16, both multiples of 128) as MXFP8 along
+    either axis or both, read once: the row pair q [rows, cols], scales uint8
+    [rows, cols / 32] is QuantizeRowsMx's bit for bit; the column pair qt
+    (e4m3 [cols, rows]) and scales_t (uint8 [cols, rows / 32]) has one e8m0
+    byte per column and 32 rows: an MX weight [n = cols, k = rows] as it
+    stands (sputnik_quantize_tiles_mx)."""
+    _moe_matrix(x, None, None, "x")
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    _fp8_tiles(rows, "QuantizeTilesMx: rows")
+    _fp8_tiles(cols, "QuantizeTilesMx: cols")
+    pq, ps = _mx_pair(q, scales, (rows, cols), (rows, cols // 32),
+                      "QuantizeTilesMx: row")
+    pt, pst = _mx_pair(qt, scales_t, (cols, rows), (cols, rows // 32),
+                       "QuantizeTilesMx: column")
+    if q is None and qt is None:
+        raise ValueError("QuantizeTilesMx: no output")
+    _check(lib().sputnik_quantize_tiles_mx(
+        _ptr(x), rows, cols, pq, ps, pt, pst, _dtype_code(x),
+        _stream(stream)), "QuantizeTilesMx")
+
+
+def QuantizeBlocksMx(s, q=None, scales=None, qt=None, scales_t=None,  # noqa: N802
+                     stage=None, activation=None, z=None, stream=None):
+    """QuantizeBlocks in MXFP8: the block values of the BlockMatrix s (fp16 /
+    bf16) after `stage` (None; "act"; "act_grad" with z). The row pair q
+    [blocks, 128, 128], scales uint8 [blocks * 128, 4] in storage order, as
+    QuantizeRowsMx over the same values; the column pair in the transposed
+    order, output block j being source block s.block_offsets[j] stored
+    transposed, with scales_t uint8 [blocks * 128, 4]: per source column the
+    bytes of its four 32-row groups (sputnik_quantize_blocks_mx)."""
+    import torch
+
+    if not isinstance(s, BlockMatrix):
+        raise TypeError("QuantizeBlocksMx takes a BlockMatrix")
+    if stage not in FP8_STAGES:
+        raise ValueError(f"QuantizeBlocksMx: stage must be one of "
+                         f"{list(FP8_STAGES)}")
+    nb = s.num_blocks
+    if s.data.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("QuantizeBlocksMx: s.data must be fp16 / bf16")
+    act = 0 if stage is None else _act_code(activation)
+    if stage == "act_grad":
+        _fp8_buffer(z, s.data.dtype, tuple(s.data.shape), "z")
+    pq, ps = _mx_pair(q, scales, (nb, 128, 128), (nb * 128, 4),
+                      "QuantizeBlocksMx: row")
+    pt, pst = _mx_pair(qt, scales_t, (nb, 128, 128), (nb * 128, 4),
+                       "QuantizeBlocksMx: column")
+    if q is None and qt is None:
+        raise ValueError("QuantizeBlocksMx: no output")
+    cs = s._c()
+    _check(lib().sputnik_quantize_blocks_mx(
+        ctypes.byref(cs), FP8_STAGES[stage], act,
+        _ptr(z) if stage == "act_grad" else None, pq, ps, pt, pst,
+        _dtype_code(s.data), _stream(stream)), "QuantizeBlocksMx")
+
+
+def DsdMxWgrad(s, s_scales, bq, b_scales, c, add=False, stream=None):  # noqa: N802
+    """C (Matrix [s.rows, n] of fp16 / bf16 / fp32) = Sq . Bq as DsdMx with an
+    e4m3 B, into a gradient sink: with `add` C = round(acc + float(C)) and
+    block rows of s without blocks are left untouched. The operands are
+    token-contiguous: s from QuantizeBlocksMx' column pair, bq / b_scales
+    from QuantizeTilesMx' (sputnik_dsd_mx_wgrad)."""
+    import torch
+
+    if not isinstance(s, BlockMatrix) or not isinstance(c, Matrix):
+        raise TypeError("DsdMxWgrad takes a BlockMatrix and writes a Matrix")
+    _, n, k = _mx_weight(bq, b_scales, "e4m3", "DsdMxWgrad")
+    if k != s.cols or n != c.cols or c.rows != s.rows:
+        raise ValueError(f"DsdMxWgrad shapes [{s.rows}, {s.cols}] x [{k}, "
+                         f"{n}] -> [{c.rows}, {c.cols}]")
+    if getattr(s.data, "dtype", None) != torch.float8_e4m3fn:
+        raise TypeError("DsdMxWgrad: s.data must be torch.float8_e4m3fn")
+    _fp8_buffer(s_scales, torch.uint8, (s.num_blocks * 128, 4), "s_scales")
+    f32 = c.data.dtype == torch.float32
+    cs, cc = s._c(), c._c()
+    _check(lib().sputnik_dsd_mx_wgrad(
+        ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales),
+        ctypes.byref(cc), int(f32), int(bool(add)),
+        0 if f32 else _dtype_code(c.data), _stream(stream)), "DsdMxWgrad")
+
+
 __all__ = [
     "QuantizeRowsMx", "QuantizeWeightMx", "SddMx", "DsdMx", "MX_FORMATS",
+    "QuantizeTilesMx", "QuantizeBlocksMx", "DsdMxWgrad",
     "AllocateBitmaskBuffers", "AllocateRowIndicesBuffer",
     "AllocateTransposeBuffers", "AsInt", "Bitmask", "FreeBitmaskBuffers",
     "build_hash", "capture_workspaces", "pair_errors", "sdd_plan", "sdd_kernel",

@@ -150,6 +150,13 @@ hipError_t LaunchMxGemm(bool dsd, bool b4, int dtype, const void *a,
                         const short *indices, const short *row_indices,
                         int m_blocks, int n_blocks, int k_blocks,
                         int nnz_blocks, hipStream_t stream);
+// The e4m3 DSD of LaunchMxGemm into a gradient sink (DsdMxWgrad): c holds T
+// or, with `out_f32`, fp32; `add` accumulates into it.
+hipError_t LaunchMxWgrad(int dtype, bool out_f32, bool add, const void *s,
+                         const uint8_t *s_scales, const void *b,
+                         const uint8_t *b_scales, void *c, const int *offsets,
+                         const short *indices, int m_blocks, int n_blocks,
+                         int k_blocks, int nnz_blocks, hipStream_t stream);
 
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.

@@ -582,6 +582,33 @@ hipError_t DsdMx(const BlockMatrix s, const uint8_t *s_scales, const void *bq,
       c.cols / 128, s.cols / 128, s.nonzeros / (128 * 128), stream);
 }
 
+hipError_t DsdMxWgrad(const BlockMatrix s, const uint8_t *s_scales,
+                      const void *bq, const uint8_t *b_scales, Matrix c,
+                      OutputType out, bool add, DataType dtype,
+                      hipStream_t stream) {
+  if (out != OutputType::kOperand && out != OutputType::kF32)
+    return hipErrorInvalidValue;
+  if (!Fp8SizesOk(s, c.cols, (int)dtype) || c.rows != s.rows)
+    return hipErrorInvalidValue;
+  if (c.rows == 0 || c.cols == 0) return hipSuccess;
+  if (c.data == nullptr || s.offsets == nullptr ||
+      (s.nonzeros > 0 && (s.data == nullptr || s.indices == nullptr ||
+                          s_scales == nullptr || bq == nullptr ||
+                          b_scales == nullptr)))
+    return hipErrorInvalidValue;
+  for (const void *in : {(const void *)s.data, (const void *)s_scales, bq,
+                         (const void *)b_scales, (const void *)s.offsets,
+                         (const void *)s.indices})
+    if (c.data == in) return hipErrorInvalidValue;
+  if (!Aligned16({s.data, bq, c.data}) || !Aligned4({s_scales, b_scales}))
+    return hipErrorInvalidValue;
+  return sputnik_amd::LaunchMxWgrad(
+      (int)dtype, out == OutputType::kF32, add, s.data, s_scales, bq, b_scales,
+      c.data, static_cast<const int *>(s.offsets),
+      static_cast<const short *>(s.indices), s.rows / 128, c.cols / 128,
+      s.cols / 128, s.nonzeros / (128 * 128), stream);
+}
+
 hipError_t Transpose(BlockMatrix a, hipStream_t stream) {
   // transpose.cu:107-109 checks the three workspaces; with no nonzero block
   // the two per-block ones are legitimately empty.

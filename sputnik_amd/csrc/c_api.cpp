@@ -804,6 +804,37 @@ int sputnik_dsd_mx(const sputnik_block_matrix_t *s, const uint8_t *s_scales,
       static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
 }
 
+// ... and their gradients' pieces.
+int sputnik_quantize_tiles_mx(const void *x, int rows, int cols, void *q,
+                              uint8_t *scales, void *qt, uint8_t *scales_t,
+                              int dtype, void *stream) {
+  return sputnik::block::QuantizeTilesMx(x, rows, cols, q, scales, qt,
+                                         scales_t, static_cast<DataType>(dtype),
+                                         static_cast<hipStream_t>(stream));
+}
+
+int sputnik_quantize_blocks_mx(const sputnik_block_matrix_t *s, int stage,
+                               int act, const void *z, void *q,
+                               uint8_t *scales, void *qt, uint8_t *scales_t,
+                               int dtype, void *stream) {
+  if (!s) return hipErrorInvalidValue;
+  return sputnik::block::QuantizeBlocksMx(
+      ToCpp(s), static_cast<sputnik::block::MxBlockStage>(stage),
+      static_cast<sputnik::block::Activation>(act), z, q, scales, qt, scales_t,
+      static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
+}
+
+int sputnik_dsd_mx_wgrad(const sputnik_block_matrix_t *s,
+                         const uint8_t *s_scales, const void *bq,
+                         const uint8_t *b_scales, const sputnik_matrix_t *c,
+                         int out, int add, int dtype, void *stream) {
+  if (!s || !c) return hipErrorInvalidValue;
+  return sputnik::block::DsdMxWgrad(
+      ToCpp(s), s_scales, bq, b_scales, ToCpp(c),
+      static_cast<sputnik::block::OutputType>(out), add != 0,
+      static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
+}
+
 // MoE router and device sort (sputnik/block/router.h): moe_router.hip
 // validates.
 int sputnik_router_topk(const void *logits, int32_t *top_experts,

@@ -48,6 +48,24 @@
 // The step order is the k order (SDD) or the row's storage order (DSD), no
 // split-K and no atomics: the same inputs give the same bits. Every index
 // read from device memory is checked before it is used as an address.
+//
+// kWgrad (DsdMxWgrad) is the e4m3 DSD with a gradient sink for an output. MX
+// scales belong to one operand and run along k, so the steps, the k map and
+// the adds are the DSD's, untouched: only the epilogue differs. The sink may
+// hold fp32 and may be added into, and round_out(acc + float(C_old)) needs
+// the unrounded acc next to C_old, so the tile leaves the registers as an
+// fp32 image. 128 rows of 512 bytes are 64 KiB; the 66 KiB ring leaves
+// exactly 16 bytes of padding per row (pitch 132 dwords). A wave's store of
+// acc[ti][tj][e] puts lane (r, g) at row 4 g + e, column r of a 16 x 16 tile:
+// dword 132 (4 g) + r, bank (16 g + r) % 64: 64 lanes, 64 banks, once each (in
+// halves of 32 lanes on a 32-bank view: banks r and 16 + r). Without the
+// padding the four lane groups would meet on one bank. The image then leaves
+// as 16-byte pieces of the output type: a lane reads 16 (fp32: 4 x f32) or 32
+// (T: 8 x f32 -> 8 x T) consecutive bytes of an image row, consecutive lanes
+// consecutive pieces, so both the LDS reads and the global accesses of C and
+// C_old are row-contiguous. A block row without stored blocks is left alone
+// under `add` (neither read nor written) and is +0 otherwise. The kWgrad =
+// false instantiations keep their code.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -78,6 +96,11 @@ static_assert(3 * StageBytes(false) * 2 > 160 * 1024,
               "a third e4m3 stage would cost the second workgroup");
 static_assert(kB * kB * 2 <= LdsBytes(false) && kB * kB * 2 <= LdsBytes(true),
               "the output tile reuses the ring");
+// (the wgrad's fp32 image: four floats of padding per row put the four row
+// groups of a 16 x 16 accumulator store on different banks)
+constexpr int kImagePitch = kB + 4;
+static_assert(kB * kImagePitch * 4 <= LdsBytes(false),
+              "the fp32 image of the wgrad reuses the e4m3 ring");
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -113,11 +136,13 @@ struct MxGemmParams {
   const short *indices;     // SDD: C's column indices; DSD: Sq's
   const short *row_indices;  // SDD: C's
   int m_blocks, n_blocks, k_blocks, nnz_blocks;
+  int out_f32, add;  // kWgrad: C holds fp32; C += (accumulate.h)
 };
 
-template <typename T, bool kDsd, bool kB4>
+template <typename T, bool kDsd, bool kB4, bool kWgrad = false>
 __global__ void __launch_bounds__(kThreads)
     mx_gemm_kernel(const MxGemmParams p) {
+  static_assert(!kWgrad || (kDsd && !kB4), "the wgrad is the e4m3 DSD");
   constexpr int kStageBytes = StageBytes(kB4);
   constexpr int kBOff = kATileBytes;
   constexpr int kScaleOff = kATileBytes + BTileBytes(kB4);
@@ -137,6 +162,7 @@ __global__ void __launch_bounds__(kThreads)
     end = end > p.nnz_blocks ? p.nnz_blocks : end;
     first = begin;
     steps = end > begin ? end - begin : 0;
+    if constexpr (kWgrad) if (p.add && steps == 0) return;
   } else {
     rb = scalar_short(p.row_indices + blockIdx.x);
     nb = scalar_short(p.indices + blockIdx.x);
@@ -277,6 +303,53 @@ __global__ void __launch_bounds__(kThreads)
   }
 
   __syncthreads();
+  if constexpr (kWgrad) {
+    // acc into a [128][kImagePitch] fp32 image, then 16-byte row pieces of the
+    // output type: round_out(acc), or round_out(acc + float(C_old)).
+    float *image = reinterpret_cast<float *>(lds);
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          image[(wm * 64 + ti * 16 + 4 * g + e) * kImagePitch + wn * 64 +
+                tj * 16 + r] = acc[ti][tj][e];
+    __syncthreads();
+    const long long n = (long long)p.n_blocks * kB;
+    const long long at = (long long)rb * kB * n + (long long)nb * kB;
+    if (p.out_f32) {
+      float *out = static_cast<float *>(p.c) + at;
+      for (int id = threadIdx.x; id < kB * kB / 4; id += kThreads) {
+        const int row = id >> 5, col = (id & 31) * 4;
+        f32x4 v =
+            *reinterpret_cast<const f32x4 *>(image + row * kImagePitch + col);
+        f32x4 *dst = reinterpret_cast<f32x4 *>(out + row * n + col);
+        if (p.add) v += *dst;
+        *dst = v;
+      }
+    } else {
+      typedef T t8 __attribute__((ext_vector_type(8)));
+      T *out = static_cast<T *>(p.c) + at;
+      for (int id = threadIdx.x; id < kB * kB / 8; id += kThreads) {
+        const int row = id >> 4, col = (id & 15) * 8;
+        const float *from = image + row * kImagePitch + col;
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(from);
+        const f32x4 hi = *reinterpret_cast<const f32x4 *>(from + 4);
+        t8 *dst = reinterpret_cast<t8 *>(out + row * n + col);
+        t8 old{}, res;
+        if (p.add) old = *dst;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float v = i < 4 ? lo[i] : hi[i - 4];
+          if (p.add) v += (float)old[i];
+          res[i] = (T)v;
+        }
+        *dst = res;
+      }
+    }
+    return;
+  }
   // round_T(acc) into a [128][128] image of T, then 16-byte row pieces.
   T *image = reinterpret_cast<T *>(lds);
 #pragma unroll
@@ -320,7 +393,7 @@ hipError_t LaunchMxGemm(bool dsd, bool b4, int dtype, const void *a,
   const MxGemmParams p{static_cast<const char *>(a), a_scales,
                        static_cast<const char *>(b), b_scales, c, offsets,
                        indices, row_indices, m_blocks, n_blocks, k_blocks,
-                       nnz_blocks};
+                       nnz_blocks, 0, 0};
   auto launch = [&](auto t, auto d, auto f) {
     hipLaunchKernelGGL((mx_gemm_kernel<decltype(t), decltype(d)::value,
                                        decltype(f)::value>),
@@ -336,6 +409,26 @@ hipError_t LaunchMxGemm(bool dsd, bool b4, int dtype, const void *a,
                       : kind(_Float16{}, std::true_type{});
   return dtype == 1 ? kind(__bf16{}, std::false_type{})
                     : kind(_Float16{}, std::false_type{});
+}
+
+hipError_t LaunchMxWgrad(int dtype, bool out_f32, bool add, const void *a,
+                         const uint8_t *a_scales, const void *b,
+                         const uint8_t *b_scales, void *c, const int *offsets,
+                         const short *indices, int m_blocks, int n_blocks,
+                         int k_blocks, int nnz_blocks, hipStream_t stream) {
+  const long long tiles = (long long)m_blocks * n_blocks;
+  if (tiles == 0) return hipSuccess;
+  if (tiles > INT_MAX) return hipErrorInvalidValue;
+  const MxGemmParams p{static_cast<const char *>(a), a_scales,
+                       static_cast<const char *>(b), b_scales, c, offsets,
+                       indices, nullptr, m_blocks, n_blocks, k_blocks,
+                       nnz_blocks, out_f32, add};
+  auto launch = [&](auto t) {
+    hipLaunchKernelGGL((mx_gemm_kernel<decltype(t), true, false, true>),
+                       dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
+    return hipGetLastError();
+  };
+  return dtype == 1 ? launch(__bf16{}) : launch(_Float16{});
 }
 
 }  // namespace sputnik_amd

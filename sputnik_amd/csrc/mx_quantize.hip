@@ -13,6 +13,12 @@
 // block through an LDS image in [n][k] order (the 2-byte transpose when the
 // source is [k, n]); then one thread per (row n, 32-block): amax, scale byte,
 // 32 elements as 32 e4m3 bytes or 16 bytes of e2m1 pairs, low nibble first.
+//
+// quantize_tiles_mx_kernel (QuantizeTilesMx, QuantizeBlocksMx) is the backward
+// pass's: one 128 x 128 tile per workgroup, read once with 16-byte loads,
+// quantised in 1 x 32 groups along the rows, in 32 x 1 groups down the
+// columns, or both. quantize_tile_mx has the thread map and the LDS bank
+// argument.
 #include <climits>
 #include <cstdint>
 #include <initializer_list>
@@ -160,10 +166,234 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
+// One 128 x 128 tile of 16-bit values per workgroup, read once, quantised
+// along the rows, down the columns or both. `rows` x `cols` is the matrix the
+// tiles cut: x itself (QuantizeTilesMx) or the block values as [nnz_blocks
+// 128, 128] (QuantizeBlocksMx), whose column outputs go out in the transposed
+// order: workgroup j takes source block block_offsets[j].
+struct MxTileParams {
+  const void *x, *z;
+  uint8_t *q, *scales, *qt, *scales_t;
+  const int *block_offsets;
+  long long rows, cols;
+  int nnz_blocks, act;
+  bool blocks, aligned, scales_aligned, aligned_t, scales_t_aligned;
+};
+
+// Where one tile's two images go: the address of the tile's first byte of
+// each output and the bytes between consecutive rows (q, scales) or
+// consecutive columns (qt, scales_t) of the tile.
+struct MxTileSinks {
+  uint8_t *q, *scales, *qt, *scales_t;
+  long long q_pitch, scales_pitch, qt_pitch, scales_t_pitch;
+};
+
+__device__ __forceinline__ void store16(uint8_t *p, const uint32_t *w,
+                                        bool aligned) {
+  if (aligned) {
+    *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    return;
+  }
+  store_bytes(p, w, 4, false);
+}
+
+// A 128 x 128 tile of T at `x` (`pitch` elements between rows; z likewise
+// for kOutActGrad) -> both MXFP8 images, the body QuantizeTilesMx and
+// QuantizeBlocksMx share. Every thread of the workgroup calls it.
+//
+// Rows: 8 passes of 16 rows; a row is 16 lanes of 8 elements, a 32-block 4
+// lanes: quantize_rows_mx_kernel's layout, shuffles and stores, so its bits.
+// Columns: the staged values wait in `image`, [row][column] of T, and thread
+// (wave u, lane l) owns the two units (column 2 l, rows 32 u .. 32 u + 31)
+// and (column 2 l + 1, the same rows): 256 threads, 512 units. It reads the
+// 32 dwords image[32 u + i][2 l .. 2 l + 1], has both amaxes and scales in
+// registers with no cross-lane step, and leaves each unit's 32 bytes, which
+// are contiguous along the tokens in qt, as two 16-byte stores. The four e8m0
+// bytes of a column belong to four waves: they meet in `col_scales` [column]
+// [u] and leave as one dword per column.
+//
+// LDS banks. The image needs neither padding nor a swizzle, because the lanes
+// run along the image's rows on both sides. Write: lane `sub` of a row puts
+// 16 bytes at byte 256 r + 16 sub and a wave covers rows 4 w' .. 4 w' + 3, so
+// the wave's 64 x 16 bytes are one contiguous, 16-byte aligned kilobyte: every
+// bank the same number of times, the minimum for that many bytes. Read: the
+// 64 lanes of a wave take dword l of image row 32 u + i, 64 consecutive
+// dwords: 64 banks once each (two rounds of 32 on a 32-bank view). A padded
+// pitch would only misalign the 16-byte writes. col_scales is written by
+// bytes, 2 per thread (columns 2 l and 2 l + 1 are dwords 2 l and 2 l + 1:
+// two lanes per bank, twice per tile) and read as consecutive dwords.
+template <typename T, int kMode>
+__device__ __forceinline__ void quantize_tile_mx(
+    const T *x, const T *z, long long pitch, int act, const MxTileSinks &o,
+    const MxTileParams &p, T *image, uint8_t *col_scales) {
+  typedef T t2 __attribute__((ext_vector_type(2)));
+  const int sub = threadIdx.x & 15;
+#pragma unroll 2
+  for (int pass = 0; pass < kTile * kTile / 8 / kThreads; ++pass) {
+    const int r = pass * (kThreads / 16) + (threadIdx.x >> 4);
+    const long long at = r * pitch + sub * 8;
+    act_t8<T> v = load8<T>(x + at, p.aligned);
+    if constexpr (kMode != kModeNone) {
+      using E = SddEpilogue<kMode>;
+      act_t8<T> g = v, h, unused;
+      if constexpr (E::kSideInputs >= 1) g = load8<T>(z + at, p.aligned);
+      E::template apply8<T>(act, v, g, v, &h, &unused);
+      v = h;
+    }
+    if (o.q != nullptr) {
+      float amax = 0.0f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float f = (float)v[i];
+        if (fp8_finite(f)) amax = fmaxf(amax, fabsf(f));
+      }
+      amax = fmaxf(amax, __shfl_xor(amax, 2));
+      amax = fmaxf(amax, __shfl_xor(amax, 1));
+      const float scale = mx_scale<false>(amax);
+      const uint32_t byte = mx_scale_byte(scale);
+      const int lane0 = (threadIdx.x & 63) & ~15;
+      const uint32_t dword = (uint32_t)__shfl((int)byte, lane0) |
+                             (uint32_t)__shfl((int)byte, lane0 + 4) << 8 |
+                             (uint32_t)__shfl((int)byte, lane0 + 8) << 16 |
+                             (uint32_t)__shfl((int)byte, lane0 + 12) << 24;
+      uint32_t w[2] = {0, 0};
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        w[i >> 2] |= fp8_quantize((float)v[i], scale) << (8 * (i & 3));
+      uint8_t *dst = o.q + r * o.q_pitch + sub * 8;
+      if (p.aligned) *reinterpret_cast<uint2 *>(dst) = make_uint2(w[0], w[1]);
+      else store_bytes(dst, w, 2, false);
+      if (sub == 0)
+        store_bytes(o.scales + r * o.scales_pitch, &dword, 1,
+                    p.scales_aligned);
+    }
+    if (o.qt != nullptr)
+      *reinterpret_cast<act_t8<T> *>(image + r * kTile + sub * 8) = v;
+  }
+  if (o.qt == nullptr) return;
+  __syncthreads();
+  const int u = threadIdx.x >> 6, pair = threadIdx.x & 63;
+  const T *from = image + u * kMxBlock * kTile + 2 * pair;
+  t2 v[kMxBlock];
+  float amax[2] = {0.0f, 0.0f};
+#pragma unroll
+  for (int i = 0; i < kMxBlock; ++i) {
+    v[i] = *reinterpret_cast<const t2 *>(from + i * kTile);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const float f = (float)v[i][j];
+      if (fp8_finite(f)) amax[j] = fmaxf(amax[j], fabsf(f));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = 2 * pair + j;
+    const float scale = mx_scale<false>(amax[j]);
+    col_scales[c * 4 + u] = (uint8_t)mx_scale_byte(scale);
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < kMxBlock; ++i)
+      w[i >> 2] |= fp8_quantize((float)v[i][j], scale) << (8 * (i & 3));
+    uint8_t *dst = o.qt + c * o.qt_pitch + u * kMxBlock;
+    store16(dst, w, p.aligned_t);
+    store16(dst + 16, w + 4, p.aligned_t);
+  }
+  __syncthreads();
+  if (threadIdx.x < kTile) {
+    const uint32_t dword = reinterpret_cast<const uint32_t *>(
+        col_scales)[threadIdx.x];
+    store_bytes(o.scales_t + threadIdx.x * o.scales_t_pitch, &dword, 1,
+                p.scales_t_aligned);
+  }
+}
+
+template <typename T, int kMode>
+__global__ void __launch_bounds__(kThreads)
+    quantize_tiles_mx_kernel(const MxTileParams p) {
+  __shared__ __attribute__((aligned(16))) T image[kTile * kTile];
+  __shared__ __attribute__((aligned(4))) uint8_t col_scales[kTile * 4];
+  const long long col_blocks = p.cols / kTile;
+  long long rb = blockIdx.x, cb = 0;
+  if (p.blocks) {
+    if (p.qt != nullptr) {
+      const int b = p.block_offsets[blockIdx.x];
+      if (b < 0 || b >= p.nnz_blocks) return;
+      rb = b;
+    }
+  } else {
+    rb = blockIdx.x / col_blocks;
+    cb = blockIdx.x % col_blocks;
+  }
+  const long long at = rb * kTile * p.cols + cb * kTile;
+  const long long scale_pitch = p.cols / kMxBlock;
+  MxTileSinks o{};
+  if (p.q != nullptr) {
+    o.q = p.q + at;
+    o.q_pitch = p.cols;
+    o.scales = p.scales + rb * kTile * scale_pitch + cb * 4;
+    o.scales_pitch = scale_pitch;
+  }
+  if (p.qt != nullptr) {
+    if (p.blocks) {  // output block blockIdx.x, [column][row]
+      o.qt = p.qt + (long long)blockIdx.x * kTile * kTile;
+      o.qt_pitch = kTile;
+      o.scales_t = p.scales_t + (long long)blockIdx.x * kTile * 4;
+      o.scales_t_pitch = 4;
+    } else {
+      o.qt = p.qt + cb * kTile * p.rows + rb * kTile;
+      o.qt_pitch = p.rows;
+      o.scales_t_pitch = p.rows / kMxBlock;
+      o.scales_t = p.scales_t + cb * kTile * o.scales_t_pitch + rb * 4;
+    }
+  }
+  const T *z = static_cast<const T *>(p.z);
+  quantize_tile_mx<T, kMode>(static_cast<const T *>(p.x) + at,
+                             z == nullptr ? nullptr : z + at, p.cols, p.act, o,
+                             p, image, col_scales);
+}
+
 bool Aligned(std::initializer_list<const void *> ps, uintptr_t mask) {
   uintptr_t bits = 0;
   for (const void *p : ps) bits |= reinterpret_cast<uintptr_t>(p);
   return (bits & mask) == 0;
+}
+
+// No output may be an input or another output.
+bool Distinct(std::initializer_list<const void *> outs,
+              std::initializer_list<const void *> ins) {
+  for (auto a = outs.begin(); a != outs.end(); ++a) {
+    if (*a == nullptr) continue;
+    for (const void *in : ins)
+      if (*a == in) return false;
+    for (auto b = a + 1; b != outs.end(); ++b)
+      if (*a == *b) return false;
+  }
+  return true;
+}
+
+// (a pair is given whole or not at all, and one of the two is given)
+bool PairsOk(const void *q, const void *scales, const void *qt,
+             const void *scales_t) {
+  return (q == nullptr) == (scales == nullptr) &&
+         (qt == nullptr) == (scales_t == nullptr) &&
+         (q != nullptr || qt != nullptr);
+}
+
+template <int kMode>
+hipError_t LaunchQuantizeTilesMx(MxTileParams p, long long tiles, int dtype,
+                                 hipStream_t stream) {
+  if (tiles > INT_MAX) return hipErrorInvalidValue;
+  p.aligned = Aligned({p.x, p.z}, 15) && Aligned({p.q}, 7);
+  p.scales_aligned = Aligned({p.scales}, 3);
+  p.aligned_t = Aligned({p.qt}, 15);
+  p.scales_t_aligned = Aligned({p.scales_t}, 3);
+  auto launch = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((quantize_tiles_mx_kernel<T, kMode>),
+                       dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
+    return hipGetLastError();
+  };
+  return dtype == 1 ? launch(__bf16{}) : launch(_Float16{});
 }
 
 template <int kMode>
@@ -253,6 +483,63 @@ hipError_t QuantizeWeightMx(const void *w, int k, int n, bool transpose,
                                      : launch(t, std::false_type{});
   };
   return (int)dtype == 1 ? kind(__bf16{}) : kind(_Float16{});
+}
+
+hipError_t QuantizeTilesMx(const void *x, int rows, int cols, void *q,
+                           uint8_t *scales, void *qt, uint8_t *scales_t,
+                           DataType dtype, hipStream_t stream) {
+  if (rows < 0 || cols < 0 || rows % kTile != 0 || cols % kTile != 0 ||
+      ((int)dtype != 0 && (int)dtype != 1))
+    return hipErrorInvalidValue;
+  if (!PairsOk(q, scales, qt, scales_t)) return hipErrorInvalidValue;
+  if (rows == 0 || cols == 0) return hipSuccess;
+  if (x == nullptr || !Distinct({q, scales, qt, scales_t}, {x}))
+    return hipErrorInvalidValue;
+  MxTileParams p{x, nullptr, static_cast<uint8_t *>(q), scales,
+                 static_cast<uint8_t *>(qt), scales_t, nullptr, rows, cols, 0,
+                 0, false, false, false, false, false};
+  return LaunchQuantizeTilesMx<kModeNone>(
+      p, (long long)(rows / kTile) * (cols / kTile), (int)dtype, stream);
+}
+
+hipError_t QuantizeBlocksMx(const BlockMatrix s, MxBlockStage stage,
+                            Activation activation, const void *z, void *q,
+                            uint8_t *scales, void *qt, uint8_t *scales_t,
+                            DataType dtype, hipStream_t stream) {
+  if (s.block_size != BlockSize::k128 || s.nonzeros < 0 ||
+      s.nonzeros % (kTile * kTile) != 0 ||
+      ((int)dtype != 0 && (int)dtype != 1))
+    return hipErrorInvalidValue;
+  if (stage != MxBlockStage::kNone && stage != MxBlockStage::kActivation &&
+      stage != MxBlockStage::kActivationGrad)
+    return hipErrorInvalidValue;
+  const int act = (int)activation;
+  if (stage != MxBlockStage::kNone && (act < kActRelu || act > kActSilu))
+    return hipErrorInvalidValue;
+  if (!PairsOk(q, scales, qt, scales_t)) return hipErrorInvalidValue;
+  if (s.nonzeros == 0) return hipSuccess;
+  if (s.data == nullptr ||
+      (stage == MxBlockStage::kActivationGrad && z == nullptr) ||
+      (qt != nullptr && s.block_offsets == nullptr))
+    return hipErrorInvalidValue;
+  if (!Distinct({q, scales, qt, scales_t},
+                {s.data, z, (const void *)s.block_offsets}))
+    return hipErrorInvalidValue;
+  const int blocks = s.nonzeros / (kTile * kTile);
+  MxTileParams p{s.data,
+                 stage == MxBlockStage::kActivationGrad ? z : nullptr,
+                 static_cast<uint8_t *>(q), scales, static_cast<uint8_t *>(qt),
+                 scales_t, static_cast<const int *>(s.block_offsets),
+                 (long long)blocks * kTile, kTile, blocks, act, true, false,
+                 false, false, false};
+  switch (stage) {
+    case MxBlockStage::kActivation:
+      return LaunchQuantizeTilesMx<kOutAct>(p, blocks, (int)dtype, stream);
+    case MxBlockStage::kActivationGrad:
+      return LaunchQuantizeTilesMx<kOutActGrad>(p, blocks, (int)dtype, stream);
+    default:
+      return LaunchQuantizeTilesMx<kModeNone>(p, blocks, (int)dtype, stream);
+  }
 }
 
 }  // namespace block

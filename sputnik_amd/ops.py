@@ -57,6 +57,12 @@ The fp8 path with gradients is `mlp_fp8(x, w1t, w2, topo, activation)` over
 `quantize_sparse_t` (a sparse operand's transpose with per-column scales),
 `Fp8Weight.t()` and `dsd_fp8_wgrad`, the DSD whose dense operand is scaled
 per column.
+The MX path with gradients (sputnik/block/mx.h, "Gradients") is `mlp_mx(x,
+w1t, w2, topo, activation)` and `moe_mlp_mx_train` around it, MXFP8 in all
+three products; its pieces are `quantize_tiles_mx` (1 x 32 row groups and 32 x
+1 column groups in one pass), `quantize_sparse_mx_t` (a sparse operand and its
+transpose, each scaled along its own k) and `dsd_mx_wgrad`, dsd_mx into a
+gradient sink.
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -88,6 +94,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                QuantizeRows, QuantizeWeight, SddFp8, DsdFp8, FP8_ACCUMULATE,
                QuantizeTiles, QuantizeBlocks, TransposeWeightFp8, DsdFp8Wgrad,
                QuantizeRowsMx, QuantizeWeightMx, SddMx, DsdMx, MX_FORMATS,
+               QuantizeTilesMx, QuantizeBlocksMx, DsdMxWgrad,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
                RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
                MOE_SORT_CHUNK, ROUTER_AUX_TOKENS, ROUTER_MAX_EXPERTS,
@@ -2113,6 +2120,256 @@ def moe_mlp_fp8_train(x: torch.Tensor, top_experts: torch.Tensor,
 
 
 # ---- MoE router -------------------------------------------------------------
+
+# ---- MX gradients (sputnik/block/mx.h, "Gradients") --------------------------
+
+def quantize_tiles_mx(x: torch.Tensor, rows: bool = True, cols: bool = True):
+    """(q, scales, qt, scales_t) of x [rows, cols] (fp16 / bf16, both
+    multiples of 128) as MXFP8, read once: q / scales as quantize_rows_mx,
+    bit for bit; qt torch.float8_e4m3fn [cols, rows] and scales_t uint8
+    [cols, rows / 32], one e8m0 byte per column and 32 rows: x^T as an MX
+    weight, the dense operand of dsd_mx_wgrad. A pair that is not asked for
+    is (None, None)."""
+    _check_dtypes(x)
+    _no_grad("quantize_tiles_mx", x)
+    if x.dim() != 2 or int(x.shape[0]) % BLOCK or int(x.shape[1]) % BLOCK:
+        raise ValueError("quantize_tiles_mx: x is 2-D with multiples of 128")
+    if not (rows or cols):
+        raise ValueError("quantize_tiles_mx: no output asked for")
+    x = x.contiguous()
+    m, n = int(x.shape[0]), int(x.shape[1])
+    q = s = qt = st = None
+    if rows:
+        q = torch.empty(m, n, dtype=torch.float8_e4m3fn, device=x.device)
+        s = torch.empty(m, n // 32, dtype=torch.uint8, device=x.device)
+    if cols:
+        qt = torch.empty(n, m, dtype=torch.float8_e4m3fn, device=x.device)
+        st = torch.empty(n, m // 32, dtype=torch.uint8, device=x.device)
+    QuantizeTilesMx(x, q, s, qt, st)
+    return q, s, qt, st
+
+
+def _quantize_blocks_mx(sparse: SparseMatrix, stage, act, z, rows: bool,
+                        cols: bool):
+    """QuantizeBlocksMx over sparse's block values: (the MxSparseMatrix of
+    sparse's topology or None, the MxSparseMatrix of the transposed topology
+    or None)."""
+    meta, nb = sparse._meta, sparse.nnz_blocks
+    data = sparse.data.contiguous()
+    dev = data.device
+    q = s = qt = st = None
+    if rows:
+        q = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
+                        device=dev)
+        s = torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=dev)
+    if cols:
+        meta.ensure_transposed(data)
+        qt = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
+                         device=dev)
+        st = torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=dev)
+    if nb:
+        QuantizeBlocksMx(meta.descriptor(data), q, s, qt, st, stage, act,
+                         None if z is None else z.contiguous())
+    by_rows = MxSparseMatrix(sparse, q, s) if rows else None
+    by_cols = None
+    if cols:
+        by_cols = MxSparseMatrix(
+            SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
+                         meta.indices_t), qt, st)
+    return by_rows, by_cols
+
+
+def quantize_sparse_mx_t(sparse: SparseMatrix, activation=None,
+                         z: Optional[SparseMatrix] = None
+                         ) -> Tuple[MxSparseMatrix, MxSparseMatrix]:
+    """(the MxSparseMatrix of `sparse`, the MxSparseMatrix of sparse^T) from
+    one pass over the block values. The first is quantize_sparse_mx's, bit
+    for bit, the operand of dsd_mx; the second holds sparse's blocks
+    transposed and in the transposed order, scaled per source column and 32
+    source rows, the sparse operand of dsd_mx_wgrad. With `activation` alone
+    act(sparse) is quantised; with `z` (same topology and dtype) sparse *
+    act'(z), as sdd_act's gradient evaluates it, rounded to sparse's dtype
+    first."""
+    if not isinstance(sparse, SparseMatrix) or sparse.is_transposed():
+        raise TypeError("quantize_sparse_mx_t takes a SparseMatrix (not a "
+                        ".t() view)")
+    _check_dtypes(sparse.data)
+    _no_grad("quantize_sparse_mx_t", sparse.data,
+             None if z is None else z.data)
+    stage = None
+    if z is not None:
+        if (not isinstance(z, SparseMatrix) or z._meta is not sparse._meta
+                or z.is_transposed() or z.dtype != sparse.dtype):
+            raise ValueError("quantize_sparse_mx_t: z must share sparse's "
+                             "topology and dtype")
+        if activation is None:
+            raise ValueError("quantize_sparse_mx_t: z needs its activation")
+        stage = "act_grad"
+    elif activation is not None:
+        stage = "act"
+    act = None if activation is None else _act_code(activation)
+    return _quantize_blocks_mx(sparse, stage, act,
+                               None if z is None else z.data, True, True)
+
+
+def dsd_mx_wgrad(st: MxSparseMatrix, bqt: torch.Tensor, bst: torch.Tensor,
+                 out: Optional[torch.Tensor] = None, add: bool = False,
+                 out_dtype=torch.bfloat16) -> torch.Tensor:
+    """st . B as a dense [m, n] tensor, the weight-gradient product in MXFP8:
+    st the transposed half of quantize_sparse_mx_t ([m, k], k the token
+    dimension), B [k, n] given as quantize_tiles_mx' column pair bqt [n, k],
+    bst [n, k / 32]. dsd_mx's arithmetic. Writes `out` (contiguous [m, n],
+    fp16 / bf16 / fp32) or a new tensor of `out_dtype` (the same three); with
+    `add`, out = round(acc + out), rounded once, and rows that meet no block
+    of st are left untouched. Bitwise reproducible."""
+    if not isinstance(st, MxSparseMatrix):
+        raise TypeError("dsd_mx_wgrad: st must come from "
+                        "quantize_sparse_mx_t")
+    if not isinstance(bqt, torch.Tensor) or bqt.dim() != 2:
+        raise TypeError("dsd_mx_wgrad: bqt is quantize_tiles_mx' qt")
+    m, n = st.shape[0], int(bqt.shape[0])
+    if st.shape[1] != int(bqt.shape[1]):
+        raise ValueError(f"dsd_mx_wgrad shapes {st.shape} x "
+                         f"{(int(bqt.shape[1]), n)}")
+    kinds = (torch.float16, torch.bfloat16, torch.float32)
+    if out is None:
+        if add:
+            raise ValueError("dsd_mx_wgrad: add needs `out`")
+        if out_dtype not in kinds:
+            raise TypeError("dsd_mx_wgrad: out_dtype must be torch.float16, "
+                            "torch.bfloat16 or torch.float32")
+        out = torch.empty(m, n, dtype=out_dtype, device=bqt.device)
+    else:
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != (m, n)
+                or not out.is_contiguous()):
+            raise ValueError(f"dsd_mx_wgrad: out must be a contiguous "
+                             f"{(m, n)} tensor")
+        if out.dtype not in kinds:
+            raise TypeError("dsd_mx_wgrad: out must be fp16, bf16 or fp32")
+    DsdMxWgrad(st._descriptor(), st.scales, bqt, bst, Matrix(m, n, out),
+               add=add)
+    return out
+
+
+class _MLPMx(torch.autograd.Function):
+    """y = dsd_mx(quantize_sparse_mx(sdd_mx(x, w1t^T), act), w2) and the
+    backward pass of mx.h's table. Keeps Z, the column quantisation of X
+    (bytes, not the 16-bit X) and the 16-bit weights: an MX weight has no
+    exact transpose, so the backward layouts are quantised in backward."""
+
+    @staticmethod
+    def forward(ctx, x, w1t, w2, topo, act, w1_sink, w2_sink):
+        need_x, need_w1, need_w2 = ctx.needs_input_grad[:3]
+        need_w1 = need_w1 or w1_sink is not None
+        need_w2 = need_w2 or w2_sink is not None
+        ctx.topo, ctx.act = topo, act
+        ctx.w1_sink, ctx.w2_sink = w1_sink, w2_sink
+        ctx.need = (need_x, need_w1, need_w2)
+        w1q = quantize_weight_mx(w1t, transpose=True)           # [h, F]
+        w2q = quantize_weight_mx(w2)                            # [F, h]
+        xq, xs, xqt, xst = quantize_tiles_mx(x, cols=need_w1)
+        z = sdd_mx(xq, xs, w1q, topo, x.dtype)
+        y = dsd_mx(quantize_sparse_mx(z, act), w2q, x.dtype)
+        if any(ctx.need):
+            ctx.save_for_backward(z.data, xqt, xst,
+                                  w1t if need_x else None,
+                                  w2 if need_x or need_w1 else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z_data, xqt, xst, w1t, w2 = ctx.saved_tensors
+        need_x, need_w1, need_w2 = ctx.need
+        topo, act = ctx.topo, ctx.act
+        z = topo.with_data(z_data)
+        dt = z_data.dtype
+        dx = dw1 = dw2 = None
+        need_dz = need_x or need_w1
+        dyq, dys, dyqt, dyst = quantize_tiles_mx(dy.contiguous(), rows=need_dz,
+                                                 cols=need_w2)
+        if need_w2:                                   # H^T dY
+            ht = _quantize_blocks_mx(z, "act", act, None, False, True)[1]
+            if ctx.w2_sink is not None:
+                dsd_mx_wgrad(ht, dyqt, dyst, ctx.w2_sink, True)
+            else:
+                dw2 = dsd_mx_wgrad(ht, dyqt, dyst, out_dtype=dt)
+            del ht
+        if need_dz:
+            # dY W2^T: W2 read as [n = F, k = h]
+            dh = sdd_mx(dyq, dys, quantize_weight_mx(w2, transpose=True),
+                        topo, dt)
+            # dZ = dH * act'(Z), quantised along both axes in one pass
+            dzq, dzt = _quantize_blocks_mx(dh, "act_grad", act, z_data,
+                                           need_x, need_w1)
+            if need_x:                                # dZ W1t: [k = F, n = h]
+                dx = dsd_mx(dzq, quantize_weight_mx(w1t), dt)
+            if ctx.w1_sink is not None:               # dZ^T X
+                dsd_mx_wgrad(dzt, xqt, xst, ctx.w1_sink, True)
+            elif need_w1:
+                dw1 = dsd_mx_wgrad(dzt, xqt, xst, out_dtype=dt)
+        return dx, dw1, dw2, None, None, None, None
+
+
+def mlp_mx(x: torch.Tensor, w1t: torch.Tensor, w2: torch.Tensor,
+           topo: SparseMatrix, activation="gelu",
+           dw1t_out: Optional[torch.Tensor] = None,
+           dw2_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The expert MLP with its three products in MXFP8, forward and backward:
+    y = act(x w1t^T at topo's blocks) w2 over 16-bit x [T, h], w1t [F, h] and
+    w2 [F, h] (MegaBlocks' orientation), topo [T, F]. Forward quantises the
+    weights (quantize_weight_mx) and runs quantize_rows_mx -> sdd_mx ->
+    quantize_sparse_mx(activation) -> dsd_mx, bit for bit. Backward
+    (sputnik/block/mx.h, "Gradients"): dH = dY W2^T by sdd_mx, dZ = dH *
+    act'(Z) fused into the quantiser, dX = dZ W1t by dsd_mx, and dW2 = H^T
+    dY, dW1t = dZ^T X by dsd_mx_wgrad with both operands scaled per 32 tokens
+    x 1 column; the weights' backward layouts are quantised from the 16-bit
+    weights. The gradients are straight-through: taken with respect to the
+    16-bit inputs, in their dtype. A sink (`dw1t_out`, `dw2_out`: contiguous
+    [F, h], x's dtype or fp32) receives sink += gradient, rounded once, in
+    place of a returned gradient. What needs_input_grad does not ask for is
+    skipped. There are no biases, no GLU form and no MXFP4 weights."""
+    _check_dtypes(x, w1t, w2)
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError("mlp_mx: topo must be a SparseMatrix (not a .t() "
+                        "view)")
+    if (x.dim() != 2 or w1t.dim() != 2 or tuple(w1t.shape) != tuple(w2.shape)
+            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
+            or int(w1t.shape[1]) != int(x.shape[1])
+            or int(x.shape[1]) % BLOCK):
+        raise ValueError("mlp_mx: x [T, h], w1t and w2 [F, h], topo [T, F], "
+                         "all multiples of 128")
+    for sink, what in ((dw1t_out, "dw1t_out"), (dw2_out, "dw2_out")):
+        if sink is not None:
+            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
+                        f"mlp_mx: {what}")
+    return _MLPMx.apply(x.contiguous(), w1t.contiguous(), w2.contiguous(),
+                        topo, _act_code(activation), dw1t_out, dw2_out)
+
+
+def moe_mlp_mx_train(x: torch.Tensor, top_experts: torch.Tensor,
+                     expert_weights: torch.Tensor, w1t: torch.Tensor,
+                     w2: torch.Tensor, num_experts: int, activation=None,
+                     rows: Optional[int] = None,
+                     dw1t_out: Optional[torch.Tensor] = None,
+                     dw2_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_mlp with the expert products in MXFP8 and gradients: padded_gather
+    -> mlp_mx -> padded_scatter, the permutation with its existing gradients.
+    w1t and w2 are 16-bit [num_experts * ffn, d_model]; the other arguments
+    are moe_mlp's (activation None: "gelu"). Differentiable in x,
+    expert_weights, w1t and w2."""
+    if not isinstance(w1t, torch.Tensor) or w1t.dim() != 2:
+        raise ValueError("moe_mlp_mx_train: w1t is [E * ffn, d_model]")
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
+                              None, num_experts, rows)
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    y = mlp_mx(xp, w1t, w2, topo, "gelu" if activation is None else
+               activation, dw1t_out, dw2_out)
+    return padded_scatter(y, route, expert_weights)
+
 
 def _router_forward(ctx, logits, top_k, normalize, dtype):
     """What _Router and _RouterAux begin with: (contiguous logits, top,
