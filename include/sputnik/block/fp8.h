@@ -213,6 +213,66 @@
 //                  first summand is absent for fp32 output, which is not
 //                  rounded again.
 //
+// Gradients of a gated expert (GLU: V1t [F, h] beside W1t, G = X W1t^T and
+// U = X V1t^T at the blocks, H = U * act(G), Y = H W2; ops.py's _GLUMLP calls
+// G z1 and U z2):
+//
+//   dW2  = H^T dY                 H from the kept G and U: QuantizeBlocksGated
+//                                 (column outputs) -> DsdFp8Wgrad
+//   D    = dY W2^T at the blocks  SddFp8, as above
+//   dG   = D * U * act'(G)        QuantizeBlocksGatedGrad: one read of D, G
+//   dU   = D * act(G)             and U, row and column images of both,
+//                                 neither stored as 16 bits
+//   dX   = dG W1t + dU V1t        DsdFp8Pair: one accumulator, one rounding
+//   dW1t = dG^T X, dV1t = dU^T X  DsdFp8Wgrad on the column images, X's
+//                                 column tiles from forward
+//
+//   Fp8Images      the outputs of a block quantiser, {q, scales, qt,
+//                  scales_t} with QuantizeBlocks' meaning and sizes: the row
+//                  pair in storage order, the column pair in the transposed
+//                  order. Either pair may be null (both pointers of it).
+//   QuantizeBlocksGated
+//                  the block values of H = x * act(gate), x = s.data, as
+//                  QuantizeRowsGated evaluates it: QuantizeBlocks with the
+//                  forward gate as its stage, and its rules (block_offsets
+//                  for the column pair, out-of-range entries, the row
+//                  outputs written by the workgroup of the output block).
+//                  Fp8Stage keeps its three values: the gated stages have
+//                  entry points of their own.
+//   QuantizeBlocksGatedGrad
+//                  (dG, dU) of the block values D = d.data, `gate` = G and
+//                  `up` = U (the same layout), exactly what MatmulGatedGrad's
+//                  elementwise stage stores for them (BlockGateGrad), rounded
+//                  to T, then quantised: every output is bit for bit
+//                  QuantizeBlocks(kNone) of that 16-bit tensor, which is
+//                  never written. `dg` and `du` are two Fp8Images; any of the
+//                  four pairs may be null, all four null is
+//                  hipErrorInvalidValue. A column pair needs
+//                  d.block_offsets; with a row pair beside it block_offsets
+//                  is a permutation. One workgroup per block, each input tile
+//                  read once; a null pair costs neither its divisions nor its
+//                  LDS traffic. No output may be an input or another output.
+//   DsdFp8Pair     C [m, n] (T) = S1q . B1q + S2q . B2q. S1 and S2 share one
+//                  topology: s1 carries the offsets, the indices and the
+//                  first pair's bytes, s2_data / s2_scales the second pair's
+//                  in the same storage order; B1q and B2q are two [n, k]
+//                  weights with [k / 128, n / 128] scales. The steps of a
+//                  block row are pair 1's stored blocks in storage order,
+//                  then pair 2's in storage order; each is DsdFp8's step,
+//                  acc = fma(float32(sa * sb), P, acc) in one fp32 chain, P
+//                  as the mode defines it (kFp32 or kFast); C = round_T(acc),
+//                  rounded once. So the result is, bit for bit, DsdFp8 over
+//                  the concatenated operands [S1 | S2] . [B1; B2], with no
+//                  concatenated copy of anything. Empty block rows give +0
+//                  rows; an out-of-range index contributes zero in both
+//                  pairs; no split-K, no atomics; alignment and alias checks
+//                  are DsdFp8's over both pairs. Error: DsdFp8's with 2 K in
+//                  place of K,
+//                    |C - exact| <= 2^-p |exact|
+//                                   + (2 K + 4 K / 128) 2^-23 sum |terms|
+//                  (kFast: eps_fast + (4 K / 128 + 1) 2^-23 in place of the
+//                  last factor).
+//
 // `dtype` is T, the 16-bit type (DataType keeps its two values). Every call
 // is stream-ordered, allocates nothing and never synchronises or aborts:
 // hipErrorInvalidValue, with nothing launched, for a null required buffer, a
@@ -221,8 +281,8 @@
 // also for an Aq / Sq / Bq / C that is not 16-byte aligned (the quantisers
 // take any alignment). Zero-sized work succeeds.
 //
-// Out of scope: GLU gradients in fp8 (the kOutGateGrad stage makes them a
-// follow-up with the same kernels), e5m2 (gradients included), other operand
+// Out of scope: folding the gated gradient into SddFp8's epilogue, so that D
+// is never written, e5m2 (gradients included), other operand
 // layouts (weights are re-laid once by QuantizeWeight and
 // TransposeWeightFp8), DDS / SSD / SDS / DSS in fp8, e8m0 hardware scales
 // (the MX products of sputnik/block/mx.h), fp8 outputs from the GEMM
@@ -307,6 +367,32 @@ hipError_t DsdFp8Wgrad(const BlockMatrix s, const float *s_scales,
                        const void *bq, const float *b_scales, Matrix c,
                        DataType dtype, OutputType out, bool add,
                        Fp8Accumulate accumulate, hipStream_t stream);
+
+// ---- Gradients of a gated expert (above) ----
+
+// The outputs of a block quantiser: the row pair and the column pair.
+struct Fp8Images {
+  void *q;
+  float *scales;
+  void *qt;
+  float *scales_t;
+};
+
+hipError_t QuantizeBlocksGated(const BlockMatrix s, const void *gate,
+                               Activation activation, Fp8Images h, bool pow2,
+                               DataType dtype, hipStream_t stream);
+
+hipError_t QuantizeBlocksGatedGrad(const BlockMatrix d, const void *gate,
+                                   const void *up, Activation activation,
+                                   Fp8Images dg, Fp8Images du, bool pow2,
+                                   DataType dtype, hipStream_t stream);
+
+hipError_t DsdFp8Pair(const BlockMatrix s1, const float *s1_scales,
+                      const void *b1q, const float *b1_scales,
+                      const void *s2_data, const float *s2_scales,
+                      const void *b2q, const float *b2_scales, Matrix c,
+                      DataType dtype, Fp8Accumulate accumulate,
+                      hipStream_t stream);
 
 }  // namespace block
 }  // namespace sputnik

@@ -689,6 +689,38 @@ int sputnik_dsd_fp8_wgrad(const sputnik_block_matrix_t *s,
                           const float *b_scales, const sputnik_matrix_t *c,
                           int dtype, int out, int add, int accumulate,
                           void *stream);
+/* The gradients of a gated (GLU) expert (sputnik/block/fp8.h has the table).
+ * Output pairs as sputnik_quantize_blocks: (q, scales) in storage order, (qt,
+ * scales_t) in the transposed order; a pair may be null, not all of them.
+ *
+ *   sputnik_quantize_blocks_gated
+ *                            the block values of s * act(gate), as
+ *                            sputnik_quantize_rows_gated evaluates it
+ *   sputnik_quantize_blocks_gated_grad
+ *                            dG = d * up * act'(gate) and dU = d * act(gate)
+ *                            as sputnik_block_gate_grad stores them, from one
+ *                            read of d, gate and up (block values of one
+ *                            layout); four output pairs, dG's then dU's
+ *   sputnik_dsd_fp8_pair     C = S1q . B1q + S2q . B2q through one
+ *                            accumulator, rounded once: s1 holds the shared
+ *                            topology and the first pair's bytes, s2_data /
+ *                            s2_scales the second pair's; bit for bit
+ *                            sputnik_dsd_fp8_acc over [S1 | S2] . [B1; B2] */
+int sputnik_quantize_blocks_gated(const sputnik_block_matrix_t *s,
+                                  const void *gate, int act, void *q,
+                                  float *scales, void *qt, float *scales_t,
+                                  int pow2, int dtype, void *stream);
+int sputnik_quantize_blocks_gated_grad(
+    const sputnik_block_matrix_t *d, const void *gate, const void *up, int act,
+    void *dg_q, float *dg_scales, void *dg_qt, float *dg_scales_t, void *du_q,
+    float *du_scales, void *du_qt, float *du_scales_t, int pow2, int dtype,
+    void *stream);
+int sputnik_dsd_fp8_pair(const sputnik_block_matrix_t *s1,
+                         const float *s1_scales, const void *b1q,
+                         const float *b1_scales, const void *s2_data,
+                         const float *s2_scales, const void *b2q,
+                         const float *b2_scales, const sputnik_matrix_t *c,
+                         int dtype, int accumulate, void *stream);
 
 /* ---- MX (OCP Microscaling) expert products, forward (sputnik/block/mx.h has
  * the contract). Elements are e4m3 bytes or, for weights, e2m1 nibbles packed

@@ -28,6 +28,16 @@ dsd_fp8_wgrad, and the whole backward of ops.mlp_mx next to ops.mlp's and
 ops.mlp_fp8's (both modes). The bf16 and fp8 arms are the parent commit's
 code.
 
+With --glu the arms are those of the gated expert's backward pass (DESIGN
+"FP8 GLU backward path"): QuantizeBlocksGatedGrad with all four pairs next to
+the composed route (BlockGateGrad, then QuantizeBlocks on each of its two
+outputs), dsd_fp8_pair next to two dsd_fp8 and a torch add, and the whole
+backward of ops.glu_mlp_fp8 in both modes next to that of the 16-bit
+ops.glu_mlp. The 16-bit backward writes dU over its saved U and refuses a
+second run, so its arm clears that mark before each call: from the second
+call on it differentiates through dU in U's place, which moves the values and
+not the work.
+
 Protocol: one process, HIP events, every arm warmed for at
 least --warm-ms of device time, then --rounds interleaved rounds, each window
 long enough to hold at least --load-ms of back-to-back calls; medians and
@@ -50,6 +60,7 @@ python scripts/bench_fp8.py --mx [--parent-lib PATH]
                             [--out profiles/mx/bench_mx.jsonl]
 python scripts/bench_fp8.py --mx --backward
                             [--out profiles/mx/bench_mx_grad.jsonl]
+python scripts/bench_fp8.py --glu [--out profiles/fp8/bench_fp8_glu.jsonl]
 """
 import argparse
 import ctypes
@@ -80,6 +91,8 @@ def main():
                     help="time the backward pass instead of the forward one")
     ap.add_argument("--mx", action="store_true",
                     help="time the MX products beside bf16 and fast fp8")
+    ap.add_argument("--glu", action="store_true",
+                    help="time the gated expert's backward pass")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -224,6 +237,62 @@ def main():
                     lambda x_, a_, b_: ops.mlp_mx(x_, a_, b_, topo, "gelu"),
                     x, w1t, w2),
             }
+        if a.glu:
+            dy = rand(rows, D_MODEL)
+            v1 = rand(D_MODEL, hidden, scale=1 / 64)
+            d16 = rand(blocks, 128, 128)
+            u16 = ops._sdd(x, v1, topo)
+            meta = topo._meta
+            meta.ensure_transposed(d16)
+            w1t, v1t = w1.t().contiguous(), v1.t().contiguous()
+            w1q_t = ops.quantize_weight(w1t)      # [F, h]: dX's weights
+            v1q_t = ops.quantize_weight(v1t)
+            dgq = ops.quantize_sparse(topo.with_data(d16))
+            duq = ops.quantize_sparse(topo.with_data(u16))
+
+            def gated_grad_fused():
+                dg = ops._fp8_images(blocks, True, True, "cuda")
+                du = ops._fp8_images(blocks, True, True, "cuda")
+                sp.QuantizeBlocksGatedGrad(meta.descriptor(d16), g16.data,
+                                           u16, "silu", dg, du)
+                return dg, du
+
+            def gated_grad_composed():
+                return [ops._quantize_blocks(topo.with_data(t), None, None,
+                                             None, True, True, False)
+                        for t in sp.BlockGateGrad(d16, g16.data, u16, "silu")]
+
+            def backward_of(fn, *leaves, rerun=False):
+                leaves = [t.detach().requires_grad_() for t in leaves]
+                y = fn(*leaves)
+
+                def run():
+                    if rerun:
+                        y.grad_fn.z2_consumed = False
+                    return torch.autograd.grad(y, leaves, dy,
+                                               retain_graph=True)
+                return run
+
+            def glu_fp8(mode):
+                return lambda x_, a_, b_, c_: ops.glu_mlp_fp8(
+                    x_, a_, b_, c_, topo, "silu", mode)
+
+            arms = {
+                "gated_grad_fused": gated_grad_fused,
+                "gated_grad_composed": gated_grad_composed,
+                "pair_fused": lambda: ops.dsd_fp8_pair(dgq, w1q_t, duq, v1q_t,
+                                                       dt),
+                "pair_composed": lambda: ops.dsd_fp8(dgq, w1q_t, dt)
+                + ops.dsd_fp8(duq, v1q_t, dt),
+                "glu_bf16_backward": backward_of(
+                    lambda x_, a_, b_, c_: ops.glu_mlp(x_, a_, b_, c_, topo,
+                                                       "silu"),
+                    x, w1, v1, w2, rerun=True),
+                "glu_fp8_backward": backward_of(glu_fp8("fp32"), x, w1t, v1t,
+                                                w2),
+                "glu_fp8_fast_backward": backward_of(glu_fp8("fast"), x, w1t,
+                                                     v1t, w2),
+            }
         calls = {}
         for name, fn in arms.items():
             fn()
@@ -243,6 +312,10 @@ def main():
         # (the backward of an MLP is four products of that size)
         work.update({name: 4 * flops * D_MODEL for name in arms
                      if name.endswith("_backward")})
+        # (a gated expert's: six; the paired dX: two)
+        work.update({name: (6 if name.endswith("_backward") else 2) * flops
+                     * D_MODEL for name in arms
+                     if name.startswith(("glu_", "pair_"))})
         # (both axes: 2 bytes read and 2 written per element and two scales
         # per 128; the activation gradient reads Z as well)
         moved = {"quantize_rows": rows * D_MODEL * 3 + rows * D_MODEL // 32,
@@ -255,6 +328,10 @@ def main():
                  "quantize_tiles_mx": rows * D_MODEL * 4 + rows * D_MODEL // 16,
                  "quantize_blocks_mx_gelu_grad": blocks * 16384 * 6
                  + blocks * 1024}
+        # (the gated gradients' algorithmic bytes, whatever the route: D, G
+        # and U read, four byte images and four scale arrays written)
+        moved.update({name: blocks * 16384 * 10 + blocks * 2048
+                      for name in ("gated_grad_fused", "gated_grad_composed")})
         line = {"shape": shape, "rows": rows, "blocks": blocks,
                 "build": sp.build_hash(), "rounds": a.rounds, "arms": {}}
         if parent is not None:
@@ -272,7 +349,15 @@ def main():
                 arm["hbm_share"] = round(tbs / HBM_TBS, 3)
             line["arms"][name] = arm
         us = {name: arm["us"] for name, arm in line["arms"].items()}
-        if a.backward and a.mx:
+        if a.glu:
+            line["pass"] = "glu backward"
+            for fused in ("gated_grad", "pair"):
+                line[f"{fused}_fused_over_composed"] = round(
+                    us[f"{fused}_fused"] / us[f"{fused}_composed"], 3)
+            for name in ("glu_fp8_backward", "glu_fp8_fast_backward"):
+                line[f"{name}_over_bf16"] = round(
+                    us[name] / us["glu_bf16_backward"], 3)
+        elif a.backward and a.mx:
             line["pass"] = "mx backward"
             for base in ("bf16", "fp8_fast"):
                 line[f"wgrad_mx_over_{base}"] = round(
@@ -296,7 +381,7 @@ def main():
             if parent is not None:
                 line[f"{op}_fp8_fast_over_parent"] = round(
                     us[f"{op}_fp8_fast"] / us[f"{op}_fp8_fast_parent"], 3)
-        for op in () if a.backward or a.mx else ("sdd", "dsd"):
+        for op in () if a.backward or a.mx or a.glu else ("sdd", "dsd"):
             line[f"{op}_fp8_over_bf16"] = round(
                 us[f"{op}_fp8"] / us[f"{op}_bf16"], 3)
             line[f"{op}_fp8_fast_over_bf16"] = round(

@@ -259,6 +259,15 @@ _SIGNATURES = {
                                      _P, _P],
     "sputnik_dsd_fp8_wgrad": [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
                               ctypes.c_int, ctypes.c_int, _P],
+    # a gated expert's: (s, gate, act, q, scales, qt, scales_t, pow2, dtype,
+    # stream); (d, gate, up, act, dG's four, dU's four, pow2, dtype, stream);
+    # (s1, s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q, b2_scales, c,
+    # dtype, accumulate, stream)
+    "sputnik_quantize_blocks_gated": [_P, _P, ctypes.c_int, _P, _P, _P, _P,
+                                      ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_quantize_blocks_gated_grad": [_P, _P, _P, ctypes.c_int] + [_P] * 8
+    + [ctypes.c_int, ctypes.c_int, _P],
+    "sputnik_dsd_fp8_pair": [_P] * 9 + [ctypes.c_int, ctypes.c_int, _P],
     # MX products: (x, gate, rows, cols, stage, act, q, scales, dtype, stream);
     # (w, k, n, transpose, format, q, scales, dtype, stream); (aq, a_scales, k,
     # bq, b_scales, b_format, c, dtype, stream); (s, s_scales, bq, b_scales,
@@ -2086,6 +2095,100 @@ def DsdFp8Wgrad(s, s_scales, bq, b_scales, c, add=False,  # noqa: N802
         ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales),
         ctypes.byref(cc), 0 if f32 else _dtype_code(c.data), int(f32),
         int(bool(add)), mode, _stream(stream)), "DsdFp8Wgrad")
+
+
+def _fp8_images(images, nb: int, what: str):
+    """The four pointers of an Fp8Images given as (q, scales, qt, scales_t),
+    None for a pair that is not asked for."""
+    q, scales, qt, scales_t = images
+    return (_fp8_pair(q, scales, (nb, 128, 128), (nb * 128,), f"{what} row")
+            + _fp8_pair(qt, scales_t, (nb, 128, 128), (nb * 128,),
+                        f"{what} column"))
+
+
+def QuantizeBlocksGated(s, gate, activation, q=None, scales=None, qt=None,  # noqa: N802
+                        scales_t=None, pow2=False, stream=None):
+    """QuantizeBlocks of H = s * act(gate) (`gate`: block values like
+    s.data), evaluated as QuantizeRows(..., activation, gate) evaluates it:
+    the hidden matrix of a gated expert along either axis or both, the
+    column pair being the sparse operand of dW2 = H^T dY
+    (sputnik_quantize_blocks_gated)."""
+    import torch
+
+    if not isinstance(s, BlockMatrix):
+        raise TypeError("QuantizeBlocksGated takes a BlockMatrix")
+    if s.data.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("QuantizeBlocksGated: s.data must be fp16 / bf16")
+    _fp8_buffer(gate, s.data.dtype, tuple(s.data.shape), "gate")
+    ptrs = _fp8_images((q, scales, qt, scales_t), s.num_blocks,
+                       "QuantizeBlocksGated:")
+    if q is None and qt is None:
+        raise ValueError("QuantizeBlocksGated: no output")
+    cs = s._c()
+    _check(lib().sputnik_quantize_blocks_gated(
+        ctypes.byref(cs), _ptr(gate), _act_code(activation), *ptrs,
+        int(bool(pow2)), _dtype_code(s.data), _stream(stream)),
+        "QuantizeBlocksGated")
+
+
+def QuantizeBlocksGatedGrad(d, gate, up, activation, dg=(None,) * 4,  # noqa: N802
+                            du=(None,) * 4, pow2=False, stream=None):
+    """Both gradients of a gated expert's hidden stage, quantised from one
+    read: with D the block values of the BlockMatrix d, `gate` = G and `up` =
+    U (block values like d.data), dG = D * U * act'(G) and dU = D * act(G) as
+    BlockGateGrad stores them, never written as 16 bits. `dg` and `du` are
+    (q, scales, qt, scales_t) tuples with QuantizeBlocks' shapes and
+    meaning; a pair left None is not computed, all four None is an error
+    (sputnik_quantize_blocks_gated_grad)."""
+    import torch
+
+    if not isinstance(d, BlockMatrix):
+        raise TypeError("QuantizeBlocksGatedGrad takes a BlockMatrix")
+    if d.data.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("QuantizeBlocksGatedGrad: d.data must be fp16 / bf16")
+    _fp8_buffer(gate, d.data.dtype, tuple(d.data.shape), "gate")
+    _fp8_buffer(up, d.data.dtype, tuple(d.data.shape), "up")
+    nb = d.num_blocks
+    ptrs = (_fp8_images(dg, nb, "QuantizeBlocksGatedGrad: dG")
+            + _fp8_images(du, nb, "QuantizeBlocksGatedGrad: dU"))
+    if all(p is None for p in ptrs):
+        raise ValueError("QuantizeBlocksGatedGrad: no output")
+    cd = d._c()
+    _check(lib().sputnik_quantize_blocks_gated_grad(
+        ctypes.byref(cd), _ptr(gate), _ptr(up), _act_code(activation), *ptrs,
+        int(bool(pow2)), _dtype_code(d.data), _stream(stream)),
+        "QuantizeBlocksGatedGrad")
+
+
+def DsdFp8Pair(s1, s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q,  # noqa: N802
+               b2_scales, c, accumulate="fp32", stream=None):
+    """C (Matrix of fp16 / bf16, [s1.rows, n]) = S1q . B1q + S2q . B2q
+    through one accumulator, rounded once: s1 / s1_scales as DsdFp8's sparse
+    operand, s2_data (e4m3, s1.data's shape) / s2_scales a second set of
+    block values on the same topology, b1q / b2q two weights as DsdFp8's. Bit
+    for bit DsdFp8 over the concatenated operands (sputnik_dsd_fp8_pair)."""
+    import torch
+
+    mode = _fp8_accumulate(accumulate, "DsdFp8Pair")
+    if not isinstance(s1, BlockMatrix) or not isinstance(c, Matrix):
+        raise TypeError("DsdFp8Pair takes a BlockMatrix and writes a Matrix")
+    n, k = _fp8_weight(b1q, b1_scales, "DsdFp8Pair")
+    if _fp8_weight(b2q, b2_scales, "DsdFp8Pair") != (n, k):
+        raise ValueError("DsdFp8Pair: b1q and b2q differ in shape")
+    if k != s1.cols or n != c.cols or c.rows != s1.rows:
+        raise ValueError(f"DsdFp8Pair shapes [{s1.rows}, {s1.cols}] x [{k}, "
+                         f"{n}] -> [{c.rows}, {c.cols}]")
+    if getattr(s1.data, "dtype", None) != torch.float8_e4m3fn:
+        raise TypeError("DsdFp8Pair: s1.data must be torch.float8_e4m3fn")
+    _fp8_buffer(s2_data, torch.float8_e4m3fn, tuple(s1.data.shape), "s2_data")
+    _fp8_buffer(s1_scales, torch.float32, (s1.num_blocks * 128,), "s1_scales")
+    _fp8_buffer(s2_scales, torch.float32, (s1.num_blocks * 128,), "s2_scales")
+    cs, cc = s1._c(), c._c()
+    _check(lib().sputnik_dsd_fp8_pair(
+        ctypes.byref(cs), _ptr(s1_scales), _ptr(b1q), _ptr(b1_scales),
+        _ptr(s2_data), _ptr(s2_scales), _ptr(b2q), _ptr(b2_scales),
+        ctypes.byref(cc), _dtype_code(c.data), mode, _stream(stream)),
+        "DsdFp8Pair")
 
 
 # ---- MX products (sputnik/block/mx.h) ----------------------------------------

@@ -134,6 +134,16 @@ hipError_t LaunchFp8Wgrad(bool fast, int dtype, bool out_f32, bool add,
                           const float *b_scales, void *c, const int *offsets,
                           const short *indices, int m_blocks, int n_blocks,
                           int k_blocks, int nnz_blocks, hipStream_t stream);
+// The DSD over two operand pairs of one topology through one accumulator
+// (DsdFp8Pair): s2 / s2_scales the second pair's blocks and row scales in
+// the same storage order, b2 / b2_scales its weight, shaped as b1's.
+hipError_t LaunchFp8Pair(bool fast, int dtype, const void *s1,
+                         const float *s1_scales, const void *b1,
+                         const float *b1_scales, const void *s2,
+                         const float *s2_scales, const void *b2,
+                         const float *b2_scales, void *c, const int *offsets,
+                         const short *indices, int m_blocks, int n_blocks,
+                         int k_blocks, int nnz_blocks, hipStream_t stream);
 // P [k / 128, m, n] of Fp8IntervalSums, arguments already validated
 // (block_api.cpp): m, n and k multiples of 128.
 hipError_t LaunchFp8IntervalSums(const void *aq, const void *bq, int m, int n,

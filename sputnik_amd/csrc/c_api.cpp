@@ -764,6 +764,45 @@ int sputnik_dsd_fp8_wgrad(const sputnik_block_matrix_t *s,
       static_cast<hipStream_t>(stream));
 }
 
+// ... and a gated expert's.
+int sputnik_quantize_blocks_gated(const sputnik_block_matrix_t *s,
+                                  const void *gate, int act, void *q,
+                                  float *scales, void *qt, float *scales_t,
+                                  int pow2, int dtype, void *stream) {
+  if (!s) return hipErrorInvalidValue;
+  return sputnik::block::QuantizeBlocksGated(
+      ToCpp(s), gate, static_cast<sputnik::block::Activation>(act),
+      {q, scales, qt, scales_t}, pow2 != 0, static_cast<DataType>(dtype),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_quantize_blocks_gated_grad(
+    const sputnik_block_matrix_t *d, const void *gate, const void *up, int act,
+    void *dg_q, float *dg_scales, void *dg_qt, float *dg_scales_t, void *du_q,
+    float *du_scales, void *du_qt, float *du_scales_t, int pow2, int dtype,
+    void *stream) {
+  if (!d) return hipErrorInvalidValue;
+  return sputnik::block::QuantizeBlocksGatedGrad(
+      ToCpp(d), gate, up, static_cast<sputnik::block::Activation>(act),
+      {dg_q, dg_scales, dg_qt, dg_scales_t},
+      {du_q, du_scales, du_qt, du_scales_t}, pow2 != 0,
+      static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
+}
+
+int sputnik_dsd_fp8_pair(const sputnik_block_matrix_t *s1,
+                         const float *s1_scales, const void *b1q,
+                         const float *b1_scales, const void *s2_data,
+                         const float *s2_scales, const void *b2q,
+                         const float *b2_scales, const sputnik_matrix_t *c,
+                         int dtype, int accumulate, void *stream) {
+  if (!s1 || !c) return hipErrorInvalidValue;
+  return sputnik::block::DsdFp8Pair(
+      ToCpp(s1), s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q, b2_scales,
+      ToCpp(c), static_cast<DataType>(dtype),
+      static_cast<sputnik::block::Fp8Accumulate>(accumulate),
+      static_cast<hipStream_t>(stream));
+}
+
 // MX products (sputnik/block/mx.h): mx_quantize.hip and block_api.cpp
 // validate.
 int sputnik_quantize_rows_mx(const void *x, const void *gate, int rows,

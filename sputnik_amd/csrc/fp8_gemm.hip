@@ -51,6 +51,15 @@
 // or round_out(acc + float(C_old)), to T or fp32. The forward kernels are the
 // kWgrad = false instantiations, whose code does not change.
 //
+// kPair (DsdFp8Pair) is the DSD over two operand pairs that share one
+// topology, C = S1 B1 + S2 B2 through one accumulator: the step count doubles,
+// steps [0, blocks) walk the block row with the first pair's pointers and
+// steps [blocks, 2 blocks) walk it again with the second pair's, the indices
+// coming through the scalar cache a second time. Which pair a step takes is
+// wave-uniform, so the ring, the DMA pattern and the fma chain are those of
+// the DSD: bit for bit DsdFp8 over [S1 | S2] . [B1; B2], with no copy of
+// either. The kPair = false instantiations compile to what they were.
+//
 // fp8_interval_sums_kernel is the P of the contract as a callable
 // (Fp8IntervalSums): cold, one wave per 16 x 16 tile and interval, the same
 // two 16-byte reads per lane straight from global memory.
@@ -172,12 +181,19 @@ struct Fp8GemmParams {
   const short *row_indices;  // SDD: C's
   int m_blocks, n_blocks, k_blocks, nnz_blocks;
   int out_f32, add;       // kWgrad: C holds fp32; C += (accumulate.h)
+  // kPair: the second pair's blocks, row scales, Bq and block scales
+  const char *a2;
+  const float *a2_scales;
+  const char *b2;
+  const float *b2_scales;
 };
 
-template <typename T, bool kDsd, bool kFast, bool kWgrad = false>
+template <typename T, bool kDsd, bool kFast, bool kWgrad = false,
+          bool kPair = false>
 __global__ void __launch_bounds__(kThreads)
     fp8_gemm_kernel(const Fp8GemmParams p) {
   static_assert(kDsd || !kWgrad, "the column-scaled product is a DSD");
+  static_assert((kDsd && !kWgrad) || !kPair, "the paired product is a DSD");
   constexpr int kStageBytes = StageBytes(kWgrad);
   constexpr int kLdsBytes = LdsBytes(kWgrad);
   __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
@@ -202,10 +218,22 @@ __global__ void __launch_bounds__(kThreads)
     if (rb < 0 || rb >= p.m_blocks || nb < 0 || nb >= p.n_blocks) return;
     steps = p.k_blocks;
   }
+  // kPair: step i takes stored block i - blocks of the second pair once i
+  // has passed the row's blocks.
+  [[maybe_unused]] const int blocks = steps;
+  if constexpr (kPair) steps *= 2;
+  auto second = [&](int i) {
+    if constexpr (kPair) return i >= blocks;
+    return false;
+  };
+  auto stored = [&](int i) {
+    if constexpr (kPair) return i >= blocks ? i - blocks : i;
+    return i;
+  };
   // The k-block of step i, or -1 for a stored block to skip.
   auto k_block = [&](int i) {
     if constexpr (!kDsd) return i;
-    const int kb = scalar_short(p.indices + first + i);
+    const int kb = scalar_short(p.indices + first + stored(i));
     return kb >= 0 && kb < p.k_blocks ? kb : -1;
   };
 
@@ -218,9 +246,10 @@ __global__ void __launch_bounds__(kThreads)
     const float *a_scale;
     long long a_scale_stride;
     if constexpr (kDsd) {
-      a_tile = p.a + (long long)(first + i) * kTileBytes;
+      const long long at = first + stored(i);
+      a_tile = (second(i) ? p.a2 : p.a) + at * kTileBytes;
       a_pitch = kB;
-      a_scale = p.a_scales + (long long)(first + i) * kB;
+      a_scale = (second(i) ? p.a2_scales : p.a_scales) + at * kB;
       a_scale_stride = 1;
     } else {
       a_tile = p.a + (long long)rb * kB * k_bytes + (long long)kb * kB;
@@ -228,7 +257,8 @@ __global__ void __launch_bounds__(kThreads)
       a_scale = p.a_scales + (long long)rb * kB * p.k_blocks + kb;
       a_scale_stride = p.k_blocks;
     }
-    const char *b_tile = p.b + (long long)nb * kB * k_bytes + (long long)kb * kB;
+    const char *b_tile = (second(i) ? p.b2 : p.b) +
+                         (long long)nb * kB * k_bytes + (long long)kb * kB;
 #pragma unroll
     for (int pass = 0; pass < kTileBytes / (kThreads * 16); ++pass) {
       // (a wave's 64 x 16 bytes are 8 rows of the image)
@@ -281,7 +311,8 @@ __global__ void __launch_bounds__(kThreads)
     if (kb < 0) return;
     float sb = 1.0f;  // kWgrad: per column, from the stage
     if constexpr (!kWgrad)
-      sb = scalar_float(p.b_scales + (long long)kb * p.n_blocks + nb);
+      sb = scalar_float((second(i) ? p.b2_scales : p.b_scales) +
+                        (long long)kb * p.n_blocks + nb);
     const float *sa_lds =
         reinterpret_cast<const float *>(stage + 2 * kTileBytes);
     Frag a[4];
@@ -448,7 +479,7 @@ hipError_t LaunchFp8Gemm(bool dsd, bool fast, int dtype, const void *a,
   const Fp8GemmParams p{static_cast<const char *>(a), a_scales,
                         static_cast<const char *>(b), b_scales, c, offsets,
                         indices, row_indices, m_blocks, n_blocks, k_blocks,
-                        nnz_blocks, 0, 0};
+                        nnz_blocks, 0, 0, nullptr, nullptr, nullptr, nullptr};
   auto launch = [&](auto t, auto d, auto f) {
     hipLaunchKernelGGL((fp8_gemm_kernel<decltype(t), decltype(d)::value,
                                         decltype(f)::value>),
@@ -477,10 +508,38 @@ hipError_t LaunchFp8Wgrad(bool fast, int dtype, bool out_f32, bool add,
   const Fp8GemmParams p{static_cast<const char *>(s), s_scales,
                         static_cast<const char *>(b), b_scales, c, offsets,
                         indices, nullptr, m_blocks, n_blocks, k_blocks,
-                        nnz_blocks, out_f32, add};
+                        nnz_blocks, out_f32, add, nullptr, nullptr, nullptr,
+                        nullptr};
   auto launch = [&](auto t, auto f) {
     hipLaunchKernelGGL((fp8_gemm_kernel<decltype(t), true, decltype(f)::value,
                                         true>),
+                       dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
+    return hipGetLastError();
+  };
+  auto kind = [&](auto t) {
+    return fast ? launch(t, std::true_type{}) : launch(t, std::false_type{});
+  };
+  return dtype == 1 ? kind(__bf16{}) : kind(_Float16{});
+}
+
+hipError_t LaunchFp8Pair(bool fast, int dtype, const void *s1,
+                         const float *s1_scales, const void *b1,
+                         const float *b1_scales, const void *s2,
+                         const float *s2_scales, const void *b2,
+                         const float *b2_scales, void *c, const int *offsets,
+                         const short *indices, int m_blocks, int n_blocks,
+                         int k_blocks, int nnz_blocks, hipStream_t stream) {
+  const long long tiles = (long long)m_blocks * n_blocks;
+  if (tiles == 0) return hipSuccess;
+  if (tiles > INT_MAX) return hipErrorInvalidValue;
+  const Fp8GemmParams p{static_cast<const char *>(s1), s1_scales,
+                        static_cast<const char *>(b1), b1_scales, c, offsets,
+                        indices, nullptr, m_blocks, n_blocks, k_blocks,
+                        nnz_blocks, 0, 0, static_cast<const char *>(s2),
+                        s2_scales, static_cast<const char *>(b2), b2_scales};
+  auto launch = [&](auto t, auto f) {
+    hipLaunchKernelGGL((fp8_gemm_kernel<decltype(t), true, decltype(f)::value,
+                                        false, true>),
                        dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
     return hipGetLastError();
   };

@@ -18,7 +18,9 @@
 // transpose_weight_fp8_kernel are the backward pass's: one 128 x 128 tile
 // per workgroup, quantised along the rows, the columns or both from one
 // read, and the byte transpose of a quantised weight. Their comments have
-// the LDS layouts.
+// the LDS layouts. quantize_gated_grad_kernel is the GLU backward's: both
+// gated gradients of a block from one read of D, G and U, each quantised
+// along either axis or both, neither ever stored as 16 bits.
 #include <climits>
 #include <cstdint>
 
@@ -188,13 +190,60 @@ __device__ __forceinline__ void store16(uint8_t *p, const uint32_t (&w)[4],
   for (int i = 0; i < 16; ++i) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
 }
 
+// One chunk of a row tile, as quantize_rows_kernel takes it: the row's 16
+// lanes meet for the amax, each stores its 8 bytes and lane 0 the scale.
+template <typename T>
+__device__ __forceinline__ void quantize_row_chunk(act_t8<T> v, int sub,
+                                                   uint8_t *q, float *scale,
+                                                   bool pow2, bool aligned) {
+  float amax = amax8<T>(v, 0.0f);
+#pragma unroll
+  for (int d = 8; d >= 1; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d));
+  const float s = fp8_scale(amax, pow2);
+  uint32_t lo, hi;
+  quantize8<T>(v, s, &lo, &hi);
+  store8(q, lo, hi, aligned);
+  if (sub == 0) *scale = s;
+}
+
+template <typename T>
+__device__ __forceinline__ void image_store8(T *at, act_t8<T> v) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) at[i] = v[i];
+}
+
+// The column pass over an LDS image of T, [row][column] with the image's
+// padding: a thread walks down one column, so consecutive lanes read
+// consecutive elements of one image row: no byte transpose and no bank
+// conflict. Thread (c, half) owns 64 rows of column c: the two halves meet
+// through an amax array, then each quantises its 64 bytes, which are
+// contiguous in qt.
+template <typename T>
+__device__ __forceinline__ float column_amax(const T *column) {
+  float amax = 0.0f;
+  for (int r = 0; r < kTile / 2; ++r) {
+    const float f = (float)column[r * kImageRow];
+    if (fp8_finite(f)) amax = fmaxf(amax, fabsf(f));
+  }
+  return amax;
+}
+
+template <typename T>
+__device__ __forceinline__ void column_bytes(const T *column, float scale,
+                                             uint8_t *dst, bool aligned) {
+  for (int piece = 0; piece < kTile / 2; piece += 16) {
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      w[i >> 2] |= fp8_quantize((float)column[(piece + i) * kImageRow], scale)
+                   << (8 * (i & 3));
+    store16(dst + piece, w, aligned);
+  }
+}
+
 // Rows: the tile's 128 row tiles exactly as quantize_rows_kernel takes them
-// (16 lanes per row, the same cross-lane amax). Columns: the values wait in
-// LDS as T, [row][column] with the image's padding, and a thread walks down
-// one column, so consecutive lanes read consecutive elements of one image
-// row: no byte transpose and no bank conflict. Thread (c, half) owns 64 rows
-// of column c: the two halves meet through col_amax, then each quantises its
-// 64 bytes, which are contiguous in qt.
+// (quantize_row_chunk). Columns: the values wait in LDS as T for the column
+// pass above.
 template <typename T, int kMode>
 __global__ void __launch_bounds__(kThreads)
     quantize_tiles_kernel(const TileParams p) {
@@ -225,31 +274,17 @@ __global__ void __launch_bounds__(kThreads)
       E::template apply8<T>(p.act, v, g, v, &h, &unused);
       v = h;
     }
-    if (p.q != nullptr) {
-      float amax = amax8<T>(v, 0.0f);
-#pragma unroll
-      for (int d = 8; d >= 1; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d));
-      const float scale = fp8_scale(amax, p.pow2);
-      uint32_t lo, hi;
-      quantize8<T>(v, scale, &lo, &hi);
-      store8(p.q + at, lo, hi, p.aligned);
-      if (sub == 0) p.scales[(rb * kTile + r) * col_blocks + cb] = scale;
-    }
-    if (p.qt != nullptr) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) image[r * kImageRow + c + i] = v[i];
-    }
+    if (p.q != nullptr)
+      quantize_row_chunk<T>(v, sub, p.q + at,
+                            p.scales + (rb * kTile + r) * col_blocks + cb,
+                            p.pow2, p.aligned);
+    if (p.qt != nullptr) image_store8<T>(image + r * kImageRow + c, v);
   }
   if (p.qt == nullptr) return;
   __syncthreads();
   const int c = threadIdx.x & (kTile - 1), half = threadIdx.x >> 7;
   const T *column = image + half * (kTile / 2) * kImageRow + c;
-  float amax = 0.0f;
-  for (int r = 0; r < kTile / 2; ++r) {
-    const float f = (float)column[r * kImageRow];
-    if (fp8_finite(f)) amax = fmaxf(amax, fabsf(f));
-  }
-  col_amax[half][c] = amax;
+  col_amax[half][c] = column_amax<T>(column);
   __syncthreads();
   const float scale =
       fp8_scale(fmaxf(col_amax[0][c], col_amax[1][c]), p.pow2);
@@ -261,14 +296,79 @@ __global__ void __launch_bounds__(kThreads)
     dst = p.qt + (cb * kTile + c) * p.rows + rb * kTile;
     if (half == 0) p.scales_t[rb * p.cols + cb * kTile + c] = scale;
   }
-  dst += half * (kTile / 2);
-  for (int piece = 0; piece < kTile / 2; piece += 16) {
-    uint32_t w[4] = {0, 0, 0, 0};
+  column_bytes<T>(column, scale, dst + half * (kTile / 2), p.aligned_t);
+}
+
+// QuantizeBlocksGatedGrad: one 128 x 128 block per workgroup, D, G and U read
+// once by 16-byte loads. The chunk's (dG, dU) come from the trait that
+// MatmulGatedGrad's elementwise stage calls, rounded to T; their row tiles
+// are quantised from registers, and for the column pass each waits in an LDS
+// image of its own (2 x 32.5 KiB: two workgroups still share a CU's 160
+// KiB). Set 0 is dG, set 1 dU. A pair that is null skips its divisions, its
+// stores and, for a column pair, its image: the tests are workgroup-uniform.
+struct GateGradParams {
+  const void *d, *g, *u;
+  uint8_t *q[2];
+  float *scales[2];
+  uint8_t *qt[2];
+  float *scales_t[2];
+  const int *block_offsets;
+  int nnz_blocks, act;
+  bool pow2, aligned, aligned_t;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+    quantize_gated_grad_kernel(const GateGradParams p) {
+  __shared__ T image[2][kTile * kImageRow];
+  __shared__ float col_amax[2][2][kTile];
+  static_assert(2 * (sizeof(image) + sizeof(col_amax)) <= 160 * 1024,
+                "two workgroups per CU");
+  const bool columns = p.qt[0] != nullptr || p.qt[1] != nullptr;
+  long long rb = blockIdx.x;
+  if (columns) {
+    const int b = p.block_offsets[blockIdx.x];
+    if (b < 0 || b >= p.nnz_blocks) return;
+    rb = b;
+  }
+  const T *d = static_cast<const T *>(p.d), *g = static_cast<const T *>(p.g),
+          *u = static_cast<const T *>(p.u);
+  const int sub = threadIdx.x & 15;
+  for (int id = threadIdx.x; id < kTile * kTile / 8; id += kThreads) {
+    const int r = id >> 4, c = sub * 8;
+    const long long row = rb * kTile + r, at = row * kTile + c;
+    act_t8<T> o[2];
+    SddEpilogue<kOutGateGrad>::template apply8<T>(
+        p.act, load8<T>(d + at, p.aligned), load8<T>(g + at, p.aligned),
+        load8<T>(u + at, p.aligned), &o[0], &o[1]);
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
-      w[i >> 2] |= fp8_quantize((float)column[(piece + i) * kImageRow], scale)
-                   << (8 * (i & 3));
-    store16(dst + piece, w, p.aligned_t);
+    for (int set = 0; set < 2; ++set) {
+      if (p.q[set] != nullptr)
+        quantize_row_chunk<T>(o[set], sub, p.q[set] + at,
+                              p.scales[set] + row, p.pow2, p.aligned);
+      if (p.qt[set] != nullptr)
+        image_store8<T>(image[set] + r * kImageRow + c, o[set]);
+    }
+  }
+  if (!columns) return;
+  __syncthreads();
+  const int c = threadIdx.x & (kTile - 1), half = threadIdx.x >> 7;
+  const int first = half * (kTile / 2) * kImageRow + c;
+#pragma unroll
+  for (int set = 0; set < 2; ++set)
+    if (p.qt[set] != nullptr)
+      col_amax[set][half][c] = column_amax<T>(image[set] + first);
+  __syncthreads();
+#pragma unroll
+  for (int set = 0; set < 2; ++set) {
+    if (p.qt[set] == nullptr) continue;
+    const float scale =
+        fp8_scale(fmaxf(col_amax[set][0][c], col_amax[set][1][c]), p.pow2);
+    if (half == 0) p.scales_t[set][(long long)blockIdx.x * kTile + c] = scale;
+    column_bytes<T>(image[set] + first, scale,
+                    p.qt[set] + (long long)blockIdx.x * kTile * kTile +
+                        c * kTile + half * (kTile / 2),
+                    p.aligned_t);
   }
 }
 
@@ -492,6 +592,86 @@ hipError_t QuantizeBlocks(const BlockMatrix s, Fp8Stage stage,
     default:
       return LaunchQuantizeTiles<kModeNone>(p, blocks, (int)dtype, stream);
   }
+}
+
+namespace {
+
+bool BlocksOk(const BlockMatrix &s, Activation activation, DataType dtype) {
+  const int act = (int)activation;
+  return s.block_size == BlockSize::k128 && s.nonzeros >= 0 &&
+         s.nonzeros % (kTile * kTile) == 0 &&
+         ((int)dtype == 0 || (int)dtype == 1) && act >= kActRelu &&
+         act <= kActSilu;
+}
+
+// Both pointers of each pair or neither, and `any`: one pair at least.
+bool PairsOk(const Fp8Images &o, bool *any) {
+  if ((o.q == nullptr) != (o.scales == nullptr) ||
+      (o.qt == nullptr) != (o.scales_t == nullptr))
+    return false;
+  *any = *any || o.q != nullptr || o.qt != nullptr;
+  return true;
+}
+
+}  // namespace
+
+hipError_t QuantizeBlocksGated(const BlockMatrix s, const void *gate,
+                               Activation activation, Fp8Images h, bool pow2,
+                               DataType dtype, hipStream_t stream) {
+  bool any = false;
+  if (!BlocksOk(s, activation, dtype) || !PairsOk(h, &any) || !any)
+    return hipErrorInvalidValue;
+  if (s.nonzeros == 0) return hipSuccess;
+  if (s.data == nullptr || gate == nullptr ||
+      (h.qt != nullptr && s.block_offsets == nullptr))
+    return hipErrorInvalidValue;
+  if (!Distinct({h.q, h.scales, h.qt, h.scales_t},
+                {s.data, gate, (const void *)s.block_offsets}))
+    return hipErrorInvalidValue;
+  const int blocks = s.nonzeros / (kTile * kTile);
+  TileParams p{s.data, gate, static_cast<uint8_t *>(h.q), h.scales,
+               static_cast<uint8_t *>(h.qt), h.scales_t,
+               static_cast<const int *>(s.block_offsets),
+               (long long)blocks * kTile, kTile, blocks, (int)activation,
+               pow2, true, false, false};
+  return LaunchQuantizeTiles<kOutGate>(p, blocks, (int)dtype, stream);
+}
+
+hipError_t QuantizeBlocksGatedGrad(const BlockMatrix d, const void *gate,
+                                   const void *up, Activation activation,
+                                   Fp8Images dg, Fp8Images du, bool pow2,
+                                   DataType dtype, hipStream_t stream) {
+  bool any = false;
+  if (!BlocksOk(d, activation, dtype) || !PairsOk(dg, &any) ||
+      !PairsOk(du, &any) || !any)
+    return hipErrorInvalidValue;
+  if (d.nonzeros == 0) return hipSuccess;
+  const bool columns = dg.qt != nullptr || du.qt != nullptr;
+  if (d.data == nullptr || gate == nullptr || up == nullptr ||
+      (columns && d.block_offsets == nullptr))
+    return hipErrorInvalidValue;
+  if (!Distinct({dg.q, dg.scales, dg.qt, dg.scales_t, du.q, du.scales, du.qt,
+                 du.scales_t},
+                {d.data, gate, up, (const void *)d.block_offsets}))
+    return hipErrorInvalidValue;
+  GateGradParams p{d.data, gate, up,
+                   {static_cast<uint8_t *>(dg.q), static_cast<uint8_t *>(du.q)},
+                   {dg.scales, du.scales},
+                   {static_cast<uint8_t *>(dg.qt),
+                    static_cast<uint8_t *>(du.qt)},
+                   {dg.scales_t, du.scales_t},
+                   static_cast<const int *>(d.block_offsets),
+                   d.nonzeros / (kTile * kTile), (int)activation, pow2,
+                   Aligned({d.data, gate, up}, 15) && Aligned({dg.q, du.q}, 7),
+                   Aligned({dg.qt, du.qt}, 15)};
+  auto launch = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((quantize_gated_grad_kernel<T>),
+                       dim3((unsigned)p.nnz_blocks), dim3(kThreads), 0, stream,
+                       p);
+    return hipGetLastError();
+  };
+  return (int)dtype == 1 ? launch(__bf16{}) : launch(_Float16{});
 }
 
 hipError_t TransposeWeightFp8(const void *q, const float *scales, int k,

@@ -93,6 +93,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                PaddedScatterBiasWeightGrad,
                QuantizeRows, QuantizeWeight, SddFp8, DsdFp8, FP8_ACCUMULATE,
                QuantizeTiles, QuantizeBlocks, TransposeWeightFp8, DsdFp8Wgrad,
+               QuantizeBlocksGated, QuantizeBlocksGatedGrad, DsdFp8Pair,
                QuantizeRowsMx, QuantizeWeightMx, SddMx, DsdMx, MX_FORMATS,
                QuantizeTilesMx, QuantizeBlocksMx, DsdMxWgrad,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
@@ -2069,7 +2070,7 @@ def mlp_fp8(x: torch.Tensor, w1t: torch.Tensor, w2: torch.Tensor,
     dtype. A sink (`w1t_grad_out`, `w2_grad_out`: contiguous [F, h], x's
     dtype or fp32) receives sink += gradient, rounded once, in place of a
     returned gradient. What needs_input_grad does not ask for is skipped.
-    There are no biases and no GLU form."""
+    There are no biases; glu_mlp_fp8 is the gated form."""
     _accumulate(accumulate, "mlp_fp8")
     _check_dtypes(x, w1t, w2)
     if not isinstance(topo, SparseMatrix) or topo.is_transposed():
@@ -2116,6 +2117,227 @@ def moe_mlp_fp8_train(x: torch.Tensor, top_experts: torch.Tensor,
                            route.rows // BLOCK, dtype=x.dtype)
     y = mlp_fp8(xp, w1t, w2, topo, "gelu" if activation is None else
                 activation, accumulate, pow2, w1t_grad_out, w2_grad_out)
+    return padded_scatter(y, route, expert_weights)
+
+
+# ---- FP8 gradients of a gated expert (fp8.h, "Gradients of a gated expert") ---
+
+def _fp8_images(nb: int, rows: bool, cols: bool, dev):
+    """(q, scales, qt, scales_t) buffers of a block quantiser, None for a
+    pair that is not asked for."""
+    out = []
+    for want in (rows, cols):
+        out += [torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
+                            device=dev) if want else None,
+                torch.empty(nb * BLOCK, dtype=torch.float32, device=dev)
+                if want else None]
+    return tuple(out)
+
+
+def _fp8_views(topo: SparseMatrix, images):
+    """(the Fp8SparseMatrix of topo's topology or None, that of the
+    transposed topology or None) over the images a block quantiser filled."""
+    q, s, qt, st = images
+    meta = topo._meta
+    by_rows = None if q is None else Fp8SparseMatrix(topo, q, s)
+    by_cols = None if qt is None else Fp8SparseMatrix(
+        SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
+                     meta.indices_t), qt, st)
+    return by_rows, by_cols
+
+
+def dsd_fp8_pair(sq1: Fp8SparseMatrix, w1: Fp8Weight, sq2: Fp8SparseMatrix,
+                 w2: Fp8Weight, out_dtype=torch.bfloat16,
+                 accumulate: str = "fp32") -> torch.Tensor:
+    """sq1 . w1 + sq2 . w2 as a dense [m, n] tensor of `out_dtype`, both
+    products in fp8 through one fp32 accumulator and rounded once: sq1 and
+    sq2 are quantised block values on one topology (the same metadata), w1
+    and w2 two Fp8Weights of [k, n]. Bit for bit dsd_fp8 over the
+    concatenated operands [sq1 | sq2] . [w1; w2], which are never formed: a
+    block row takes sq1's blocks in storage order, then sq2's. The dX of a
+    gated expert. Forward only. `accumulate` as sdd_fp8."""
+    _accumulate(accumulate, "dsd_fp8_pair")
+    if (not isinstance(sq1, Fp8SparseMatrix)
+            or not isinstance(sq2, Fp8SparseMatrix)):
+        raise TypeError("dsd_fp8_pair: sq1 and sq2 must be Fp8SparseMatrix")
+    if sq1._meta is not sq2._meta or sq1.is_transposed() != sq2.is_transposed():
+        raise ValueError("dsd_fp8_pair: sq1 and sq2 must share one topology")
+    if not isinstance(w1, Fp8Weight) or not isinstance(w2, Fp8Weight):
+        raise TypeError("dsd_fp8_pair: w1 and w2 must be Fp8Weights")
+    _out_dtype(out_dtype, "dsd_fp8_pair")
+    if sq1.shape[1] != w1.k or w1.shape != w2.shape:
+        raise ValueError(f"dsd_fp8_pair shapes {sq1.shape} x {w1.shape} + "
+                         f"{sq2.shape} x {w2.shape}")
+    out = torch.empty(sq1.shape[0], w1.n, dtype=out_dtype, device=sq1.device)
+    DsdFp8Pair(sq1._descriptor(), sq1.scales, w1.q, w1.scales, sq2.data,
+               sq2.scales, w2.q, w2.scales,
+               Matrix(out.shape[0], out.shape[1], out), accumulate=accumulate)
+    return out
+
+
+class _GLUMLPFp8(torch.autograd.Function):
+    """y = dsd_fp8(quantize_sparse(sdd_fp8(x, v1t^T), act, gate=sdd_fp8(x,
+    w1t^T)), w2) and the backward pass of fp8.h's gated table. Keeps G, U,
+    the column quantisation of X and the backward layouts of the weights."""
+
+    @staticmethod
+    def forward(ctx, x, w1t, v1t, w2, topo, act, accumulate, pow2, w1_sink,
+                v1_sink, w2_sink):
+        need_x, need_w1, need_v1, need_w2 = ctx.needs_input_grad[:4]
+        need_w1 = need_w1 or w1_sink is not None
+        need_v1 = need_v1 or v1_sink is not None
+        need_w2 = need_w2 or w2_sink is not None
+        ctx.topo, ctx.act, ctx.mode, ctx.pow2 = topo, act, accumulate, pow2
+        ctx.sinks = (w1_sink, v1_sink, w2_sink)
+        ctx.need = (need_x, need_w1, need_v1, need_w2)
+        w1q = quantize_weight(w1t, transpose=True, pow2=pow2)   # [h, F]
+        v1q = quantize_weight(v1t, transpose=True, pow2=pow2)   # [h, F]
+        w2q = quantize_weight(w2, pow2=pow2)                    # [F, h]
+        xq, xs, xqt, xst = quantize_tiles(x, cols=need_w1 or need_v1,
+                                          pow2=pow2)
+        g = sdd_fp8(xq, xs, w1q, topo, x.dtype, accumulate)
+        u = sdd_fp8(xq, xs, v1q, topo, x.dtype, accumulate)
+        y = dsd_fp8(quantize_sparse(u, act, gate=g, pow2=pow2), w2q, x.dtype,
+                    accumulate)
+        if any(ctx.need):
+            # (D = dY W2^T and dX = dG W1t + dU V1t take the transposed
+            # layouts)
+            ctx.w2q_t = w2q.t() if any(ctx.need[:3]) else None
+            ctx.w1q_t = w1q.t() if need_x else None
+            ctx.v1q_t = v1q.t() if need_x else None
+            ctx.save_for_backward(g.data, u.data, xqt, xst)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        g_data, u_data, xqt, xst = ctx.saved_tensors
+        need_x, need_w1, need_v1, need_w2 = ctx.need
+        w1_sink, v1_sink, w2_sink = ctx.sinks
+        topo, act, mode, pow2 = ctx.topo, ctx.act, ctx.mode, ctx.pow2
+        meta, nb, dt, dev = topo._meta, topo.nnz_blocks, g_data.dtype, dy.device
+        need_d = need_x or need_w1 or need_v1
+        dyq, dys, dyqt, dyst = quantize_tiles(dy, rows=need_d, cols=need_w2,
+                                              pow2=pow2)
+
+        def wgrad(st, bqt, bst, sink):
+            if sink is not None:
+                dsd_fp8_wgrad(st, bqt, bst, sink, True, accumulate=mode)
+                return None
+            return dsd_fp8_wgrad(st, bqt, bst, out_dtype=dt, accumulate=mode)
+
+        dx = dw1 = dv1 = dw2 = None
+        if need_w2:                                   # H^T dY
+            meta.ensure_transposed(u_data)
+            h = _fp8_images(nb, False, True, dev)
+            if nb:
+                QuantizeBlocksGated(meta.descriptor(u_data), g_data, act, *h,
+                                    pow2=pow2)
+            dw2 = wgrad(_fp8_views(topo, h)[1], dyqt, dyst, w2_sink)
+            del h
+        if need_d:
+            d = sdd_fp8(dyq, dys, ctx.w2q_t, topo, dt, mode)    # dY W2^T
+            # dG = D U act'(G) and dU = D act(G), each along the axes its
+            # products read, from one pass over D, G and U
+            if need_w1 or need_v1:
+                meta.ensure_transposed(u_data)
+            dg = _fp8_images(nb, need_x, need_w1, dev)
+            du = _fp8_images(nb, need_x, need_v1, dev)
+            if nb:
+                QuantizeBlocksGatedGrad(meta.descriptor(d.data), g_data,
+                                        u_data, act, dg, du, pow2)
+            dgq, dgt = _fp8_views(topo, dg)
+            duq, dut = _fp8_views(topo, du)
+            if need_x:                                # dG W1t + dU V1t
+                dx = dsd_fp8_pair(dgq, ctx.w1q_t, duq, ctx.v1q_t, dt, mode)
+            if need_w1:                               # dG^T X
+                dw1 = wgrad(dgt, xqt, xst, w1_sink)
+            if need_v1:                               # dU^T X
+                dv1 = wgrad(dut, xqt, xst, v1_sink)
+        return (dx, dw1, dv1, dw2) + (None,) * 7
+
+
+def _glu_fp8_sinks(x, w2, sinks, what: str):
+    for sink, name in zip(sinks, ("w1t_grad_out", "v1t_grad_out",
+                                  "w2_grad_out")):
+        if sink is not None:
+            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
+                        f"{what}: {name}")
+
+
+def glu_mlp_fp8(x: torch.Tensor, w1t: torch.Tensor, v1t: torch.Tensor,
+                w2: torch.Tensor, topo: SparseMatrix, activation="silu",
+                accumulate: str = "fp32", pow2: bool = False,
+                w1t_grad_out: Optional[torch.Tensor] = None,
+                v1t_grad_out: Optional[torch.Tensor] = None,
+                w2_grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gated expert MLP with its four products in fp8, forward and
+    backward: y = ((x v1t^T) * act(x w1t^T) at topo's blocks) w2 over 16-bit
+    x [T, h], w1t, v1t and w2 [F, h], topo [T, F]. Forward is quantize_weight
+    of the three weights, quantize_rows -> two sdd_fp8 -> quantize_sparse
+    with the gate -> dsd_fp8: the bits of moe_mlp_fp8's expert chain with
+    `v1q`. Backward (sputnik/block/fp8.h, "Gradients of a gated expert"): D =
+    dY W2^T by sdd_fp8; dG = D U act'(G) and dU = D act(G) formed and
+    quantised in one pass over D, G and U, never stored as 16 bits; dX = dG
+    W1t + dU V1t by dsd_fp8_pair, one accumulator and one rounding; dW2 = H^T
+    dY, dW1t = dG^T X and dV1t = dU^T X by dsd_fp8_wgrad. The gradients are
+    straight-through, in the 16-bit dtype. A sink (`w1t_grad_out`,
+    `v1t_grad_out`, `w2_grad_out`: contiguous [F, h], x's dtype or fp32)
+    receives sink += gradient in place of a returned gradient. What
+    needs_input_grad and the sinks do not ask for is skipped. There are no
+    biases."""
+    _accumulate(accumulate, "glu_mlp_fp8")
+    _check_dtypes(x, w1t, v1t, w2)
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError("glu_mlp_fp8: topo must be a SparseMatrix (not a "
+                        ".t() view)")
+    if (x.dim() != 2 or w1t.dim() != 2
+            or tuple(w1t.shape) != tuple(w2.shape)
+            or tuple(v1t.shape) != tuple(w2.shape)
+            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
+            or int(w1t.shape[1]) != int(x.shape[1])
+            or int(x.shape[1]) % BLOCK):
+        raise ValueError("glu_mlp_fp8: x [T, h], w1t, v1t and w2 [F, h], "
+                         "topo [T, F], all multiples of 128")
+    _glu_fp8_sinks(x, w2, (w1t_grad_out, v1t_grad_out, w2_grad_out),
+                   "glu_mlp_fp8")
+    return _GLUMLPFp8.apply(x.contiguous(), w1t.contiguous(),
+                            v1t.contiguous(), w2.contiguous(), topo,
+                            _act_code(activation), accumulate, bool(pow2),
+                            w1t_grad_out, v1t_grad_out, w2_grad_out)
+
+
+def moe_glu_mlp_fp8_train(x: torch.Tensor, top_experts: torch.Tensor,
+                          expert_weights: torch.Tensor, w1t: torch.Tensor,
+                          v1t: torch.Tensor, w2: torch.Tensor,
+                          num_experts: int, activation=None,
+                          rows: Optional[int] = None,
+                          accumulate: str = "fp32", pow2: bool = False,
+                          w1t_grad_out: Optional[torch.Tensor] = None,
+                          v1t_grad_out: Optional[torch.Tensor] = None,
+                          w2_grad_out: Optional[torch.Tensor] = None
+                          ) -> torch.Tensor:
+    """moe_mlp's gated form with the expert products in fp8 and gradients:
+    padded_gather -> glu_mlp_fp8 -> padded_scatter, the permutation with its
+    existing gradients. w1t, v1t and w2 are 16-bit [num_experts * ffn,
+    d_model]; the other arguments are moe_mlp's (activation None: "silu").
+    Differentiable in x, expert_weights, w1t, v1t and w2."""
+    _accumulate(accumulate, "moe_glu_mlp_fp8_train")
+    for w, name in ((w1t, "w1t"), (v1t, "v1t")):
+        if not isinstance(w, torch.Tensor) or w.dim() != 2:
+            raise ValueError(f"moe_glu_mlp_fp8_train: {name} is [E * ffn, "
+                             "d_model]")
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
+                              v1t.t(), num_experts, rows)
+    _glu_fp8_sinks(x, w2, (w1t_grad_out, v1t_grad_out, w2_grad_out),
+                   "moe_glu_mlp_fp8_train")
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    y = glu_mlp_fp8(xp, w1t, v1t, w2, topo, "silu" if activation is None else
+                    activation, accumulate, pow2, w1t_grad_out, v1t_grad_out,
+                    w2_grad_out)
     return padded_scatter(y, route, expert_weights)
 
 
