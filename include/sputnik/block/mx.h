@@ -176,6 +176,66 @@
 //                    first summand is absent for fp32 output, which is not
 //                    rounded again.
 //
+// Gradients of a gated expert (GLU: V1t [F, h] beside W1t, G = X W1t^T and
+// U = X V1t^T at the blocks, H = U * act(G), Y = H W2; e4m3 throughout, the
+// weights' backward layouts quantised from 16 bits as above):
+//
+//   dW2  = H^T dY                 H from the kept G and U:
+//                                 QuantizeBlocksMxGated (column outputs) ->
+//                                 DsdMxWgrad
+//   D    = dY W2^T at the blocks  SddMx, as dH above
+//   dG   = D * U * act'(G)        QuantizeBlocksMxGatedGrad: one read of D, G
+//   dU   = D * act(G)             and U, row and column images of both,
+//                                 neither stored as 16 bits
+//   dX   = dG W1t + dU V1t        DsdMxPair: one accumulator, one rounding;
+//                                 W1t and V1t as [n = h, k = F] bytes
+//   dW1t = dG^T X, dV1t = dU^T X  DsdMxWgrad on the column images, X's
+//                                 column outputs from forward
+//
+//   MxImages       the outputs of a block quantiser, {q, scales, qt,
+//                  scales_t} with QuantizeBlocksMx' meaning and sizes: the row
+//                  pair in storage order, the column pair in the transposed
+//                  order. Either pair may be null (both pointers of it).
+//   QuantizeBlocksMxGated
+//                  the block values of H = x * act(gate), x = s.data, as
+//                  QuantizeRowsMx(kGated) evaluates it: QuantizeBlocksMx with
+//                  the forward gate as its stage, and its rules
+//                  (block_offsets for the column pair, out-of-range entries,
+//                  the row outputs written by the workgroup of the output
+//                  block, either pair null but not both). MxBlockStage keeps
+//                  its three values: the gated stages have entry points of
+//                  their own.
+//   QuantizeBlocksMxGatedGrad
+//                  (dG, dU) of the block values D = d.data, `gate` = G and
+//                  `up` = U (the same layout), exactly what MatmulGatedGrad's
+//                  elementwise stage stores for them (BlockGateGrad), rounded
+//                  to T, then quantised: every output is bit for bit
+//                  QuantizeBlocksMx(kNone) of that 16-bit tensor, which is
+//                  never written. `dg` and `du` are two MxImages; any of the
+//                  four pairs may be null, all four null is
+//                  hipErrorInvalidValue. A column pair needs
+//                  d.block_offsets; with a row pair beside it block_offsets
+//                  is a permutation. One workgroup per block, each input tile
+//                  read once; a null pair costs neither its stores nor its
+//                  LDS traffic. No output may be an input or another output.
+//   DsdMxPair      C [m, n] (T) = S1q . B1q + S2q . B2q. S1 and S2 share one
+//                  topology: s1 carries the offsets, the indices and the
+//                  first pair's bytes, s2_data / s2_scales the second pair's
+//                  in the same storage order; B1q and B2q are two e4m3 [n, k]
+//                  weights with [n, k / 32] scales. The steps of a block row
+//                  are pair 1's stored blocks in storage order, then pair
+//                  2's in storage order; each is DsdMx's step (the k map, the
+//                  +0 accumulator input, one fp32 add); C = round_T(acc),
+//                  rounded once. So the result is, bit for bit, DsdMx over
+//                  the concatenated operands [S1 | S2] . [B1; B2], with no
+//                  concatenated copy of anything. Empty block rows give +0
+//                  rows; an out-of-range index contributes zero in both
+//                  pairs; no split-K, no atomics; alignment and alias checks
+//                  are DsdMx's over both pairs. Error: DsdMx's with 2 K in
+//                  place of K,
+//                    |C - exact| <= 2^-p |exact|
+//                        + (eps_fast + (2 K / 128 + 1) 2^-23) sum |terms|
+//
 // `dtype` is T, the 16-bit type. Every call is stream-ordered, allocates
 // nothing and never synchronises or aborts: hipErrorInvalidValue, with nothing
 // launched, for a null required buffer, a negative size, a dimension that is
@@ -184,10 +244,12 @@
 // buffer (above; the quantisers take any alignment) or an output that is one
 // of the inputs. Zero-sized work succeeds.
 //
-// Out of scope: the backward of MXFP4 weights; GLU gradients; e5m2, e3m2 and
-// e2m3 elements; MXFP4 activations; DDS / SSD / SDS / DSS; chaining the
+// Out of scope: the backward of MXFP4 weights; folding the gated gradient
+// into SddMx's epilogue, so that D is never written; e5m2, e3m2 and e2m3
+// elements; MXFP4 activations; DDS / SSD / SDS / DSS; chaining the
 // accumulator through the MFMA; a CPU model of the instruction's internal
-// sum; biases; a C++ example.
+// sum; caching the weights' backward layouts across micro-batches; biases; a
+// C++ example.
 #ifndef SPUTNIK_BLOCK_MX_H_
 #define SPUTNIK_BLOCK_MX_H_
 
@@ -242,6 +304,30 @@ hipError_t DsdMxWgrad(const BlockMatrix s, const uint8_t *s_scales,
                       const void *bq, const uint8_t *b_scales, Matrix c,
                       OutputType out, bool add, DataType dtype,
                       hipStream_t stream);
+
+// ---- Gradients of a gated expert (above). ----
+
+struct MxImages {
+  void *q;
+  uint8_t *scales;
+  void *qt;
+  uint8_t *scales_t;
+};
+
+hipError_t QuantizeBlocksMxGated(const BlockMatrix s, const void *gate,
+                                 Activation activation, MxImages h,
+                                 DataType dtype, hipStream_t stream);
+
+hipError_t QuantizeBlocksMxGatedGrad(const BlockMatrix d, const void *gate,
+                                     const void *up, Activation activation,
+                                     MxImages dg, MxImages du, DataType dtype,
+                                     hipStream_t stream);
+
+hipError_t DsdMxPair(const BlockMatrix s1, const uint8_t *s1_scales,
+                     const void *b1q, const uint8_t *b1_scales,
+                     const void *s2_data, const uint8_t *s2_scales,
+                     const void *b2q, const uint8_t *b2_scales, Matrix c,
+                     DataType dtype, hipStream_t stream);
 
 }  // namespace block
 }  // namespace sputnik

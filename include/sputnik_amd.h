@@ -788,6 +788,39 @@ int sputnik_dsd_mx_wgrad(const sputnik_block_matrix_t *s,
                          const uint8_t *s_scales, const void *bq,
                          const uint8_t *b_scales, const sputnik_matrix_t *c,
                          int out, int add, int dtype, void *stream);
+/* The MX gradients of a gated (GLU) expert (sputnik/block/mx.h has the table).
+ * Output pairs as sputnik_quantize_blocks_mx: (q, scales) in storage order,
+ * (qt, scales_t) in the transposed order; a pair may be null, not all of them.
+ *
+ *   sputnik_quantize_blocks_mx_gated
+ *                            the block values of s * act(gate), as
+ *                            sputnik_quantize_rows_mx (stage 2) evaluates it
+ *   sputnik_quantize_blocks_mx_gated_grad
+ *                            dG = d * up * act'(gate) and dU = d * act(gate)
+ *                            as sputnik_block_gate_grad stores them, from one
+ *                            read of d, gate and up (block values of one
+ *                            layout); four output pairs, dG's then dU's
+ *   sputnik_dsd_mx_pair      C = S1q . B1q + S2q . B2q (e4m3 weights) through
+ *                            one accumulator, rounded once: s1 holds the
+ *                            shared topology and the first pair's bytes,
+ *                            s2_data / s2_scales the second pair's; bit for
+ *                            bit sputnik_dsd_mx over [S1 | S2] . [B1; B2] */
+int sputnik_quantize_blocks_mx_gated(const sputnik_block_matrix_t *s,
+                                     const void *gate, int act, void *q,
+                                     uint8_t *scales, void *qt,
+                                     uint8_t *scales_t, int dtype,
+                                     void *stream);
+int sputnik_quantize_blocks_mx_gated_grad(
+    const sputnik_block_matrix_t *d, const void *gate, const void *up, int act,
+    void *dg_q, uint8_t *dg_scales, void *dg_qt, uint8_t *dg_scales_t,
+    void *du_q, uint8_t *du_scales, void *du_qt, uint8_t *du_scales_t,
+    int dtype, void *stream);
+int sputnik_dsd_mx_pair(const sputnik_block_matrix_t *s1,
+                        const uint8_t *s1_scales, const void *b1q,
+                        const uint8_t *b1_scales, const void *s2_data,
+                        const uint8_t *s2_scales, const void *b2q,
+                        const uint8_t *b2_scales, const sputnik_matrix_t *c,
+                        int dtype, void *stream);
 
 /* ---- Host-only queries (no GPU work; safe without a device) */
 /* 1 when the reference would accept the problem (same rules as

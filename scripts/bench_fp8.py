@@ -38,6 +38,12 @@ second run, so its arm clears that mark before each call: from the second
 call on it differentiates through dU in U's place, which moves the values and
 not the work.
 
+With --mx --glu --backward the same arms are the MX path's (DESIGN "MX GLU
+backward path"): QuantizeBlocksMxGatedGrad next to BlockGateGrad and two
+QuantizeBlocksMx, dsd_mx_pair next to two dsd_mx and a torch add, and the
+whole backward of ops.glu_mlp_mx next to those of ops.glu_mlp and of
+ops.glu_mlp_fp8 in the fast mode.
+
 Protocol: one process, HIP events, every arm warmed for at
 least --warm-ms of device time, then --rounds interleaved rounds, each window
 long enough to hold at least --load-ms of back-to-back calls; medians and
@@ -61,6 +67,8 @@ python scripts/bench_fp8.py --mx [--parent-lib PATH]
 python scripts/bench_fp8.py --mx --backward
                             [--out profiles/mx/bench_mx_grad.jsonl]
 python scripts/bench_fp8.py --glu [--out profiles/fp8/bench_fp8_glu.jsonl]
+python scripts/bench_fp8.py --mx --glu --backward
+                            [--out profiles/mx/bench_mx_glu.jsonl]
 """
 import argparse
 import ctypes
@@ -293,6 +301,38 @@ def main():
                 "glu_fp8_fast_backward": backward_of(glu_fp8("fast"), x, w1t,
                                                      v1t, w2),
             }
+        if a.glu and a.mx:
+            w1m_t = ops.quantize_weight_mx(w1t)   # [k = F, n = h]
+            v1m_t = ops.quantize_weight_mx(v1t)
+            dgm = ops.quantize_sparse_mx(topo.with_data(d16))
+            dum = ops.quantize_sparse_mx(topo.with_data(u16))
+
+            def gated_grad_mx_fused():
+                dg = ops._mx_images(blocks, True, True, "cuda")
+                du = ops._mx_images(blocks, True, True, "cuda")
+                sp.QuantizeBlocksMxGatedGrad(meta.descriptor(d16), g16.data,
+                                             u16, "silu", dg, du)
+                return dg, du
+
+            def gated_grad_mx_composed():
+                return [ops._quantize_blocks_mx(topo.with_data(t), None, None,
+                                                None, True, True)
+                        for t in sp.BlockGateGrad(d16, g16.data, u16, "silu")]
+
+            arms = {
+                "gated_grad_fused": gated_grad_mx_fused,
+                "gated_grad_composed": gated_grad_mx_composed,
+                "pair_fused": lambda: ops.dsd_mx_pair(dgm, w1m_t, dum, v1m_t,
+                                                      dt),
+                "pair_composed": lambda: ops.dsd_mx(dgm, w1m_t, dt)
+                + ops.dsd_mx(dum, v1m_t, dt),
+                "glu_bf16_backward": arms["glu_bf16_backward"],
+                "glu_fp8_fast_backward": arms["glu_fp8_fast_backward"],
+                "glu_mx_backward": backward_of(
+                    lambda x_, a_, b_, c_: ops.glu_mlp_mx(x_, a_, b_, c_,
+                                                          topo, "silu"),
+                    x, w1t, v1t, w2),
+            }
         calls = {}
         for name, fn in arms.items():
             fn()
@@ -354,7 +394,13 @@ def main():
             for fused in ("gated_grad", "pair"):
                 line[f"{fused}_fused_over_composed"] = round(
                     us[f"{fused}_fused"] / us[f"{fused}_composed"], 3)
-            for name in ("glu_fp8_backward", "glu_fp8_fast_backward"):
+            if a.mx:
+                line["pass"] = "mx glu backward"
+                for base in ("bf16", "fp8_fast"):
+                    line[f"glu_mx_backward_over_{base}"] = round(
+                        us["glu_mx_backward"] / us[f"glu_{base}_backward"], 3)
+            for name in () if a.mx else ("glu_fp8_backward",
+                                         "glu_fp8_fast_backward"):
                 line[f"{name}_over_bf16"] = round(
                     us[name] / us["glu_bf16_backward"], 3)
         elif a.backward and a.mx:

@@ -290,6 +290,15 @@ _SIGNATURES = {
                                    _P, _P, ctypes.c_int, _P],
     "sputnik_dsd_mx_wgrad": [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
                              ctypes.c_int, _P],
+    # a gated expert's: (s, gate, act, q, scales, qt, scales_t, dtype,
+    # stream); (d, gate, up, act, dG's four, dU's four, dtype, stream); (s1,
+    # s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q, b2_scales, c, dtype,
+    # stream)
+    "sputnik_quantize_blocks_mx_gated": [_P, _P, ctypes.c_int, _P, _P, _P, _P,
+                                         ctypes.c_int, _P],
+    "sputnik_quantize_blocks_mx_gated_grad": [_P, _P, _P, ctypes.c_int]
+    + [_P] * 8 + [ctypes.c_int, _P],
+    "sputnik_dsd_mx_pair": [_P] * 9 + [ctypes.c_int, _P],
     "sputnik_can_implement": [ctypes.c_int, _P, ctypes.c_int, _P, ctypes.c_int, _P],
     "sputnik_abi_block_matrix_size": [],
     "sputnik_abi_block_matrix_offset": [ctypes.c_int],
@@ -2404,9 +2413,101 @@ def DsdMxWgrad(s, s_scales, bq, b_scales, c, add=False, stream=None):  # noqa: N
         0 if f32 else _dtype_code(c.data), _stream(stream)), "DsdMxWgrad")
 
 
+def _mx_images(images, nb: int, what: str):
+    """The four pointers of an MxImages given as (q, scales, qt, scales_t),
+    None for a pair that is not asked for."""
+    q, scales, qt, scales_t = images
+    return (_mx_pair(q, scales, (nb, 128, 128), (nb * 128, 4), f"{what} row")
+            + _mx_pair(qt, scales_t, (nb, 128, 128), (nb * 128, 4),
+                       f"{what} column"))
+
+
+def QuantizeBlocksMxGated(s, gate, activation, q=None, scales=None, qt=None,  # noqa: N802
+                          scales_t=None, stream=None):
+    """QuantizeBlocksMx of H = s * act(gate) (`gate`: block values like
+    s.data), evaluated as QuantizeRowsMx(..., activation, gate) evaluates it:
+    the hidden matrix of a gated expert along either axis or both, the column
+    pair being the sparse operand of dW2 = H^T dY
+    (sputnik_quantize_blocks_mx_gated)."""
+    import torch
+
+    if not isinstance(s, BlockMatrix):
+        raise TypeError("QuantizeBlocksMxGated takes a BlockMatrix")
+    if s.data.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("QuantizeBlocksMxGated: s.data must be fp16 / bf16")
+    _fp8_buffer(gate, s.data.dtype, tuple(s.data.shape), "gate")
+    ptrs = _mx_images((q, scales, qt, scales_t), s.num_blocks,
+                      "QuantizeBlocksMxGated:")
+    if q is None and qt is None:
+        raise ValueError("QuantizeBlocksMxGated: no output")
+    cs = s._c()
+    _check(lib().sputnik_quantize_blocks_mx_gated(
+        ctypes.byref(cs), _ptr(gate), _act_code(activation), *ptrs,
+        _dtype_code(s.data), _stream(stream)), "QuantizeBlocksMxGated")
+
+
+def QuantizeBlocksMxGatedGrad(d, gate, up, activation, dg=(None,) * 4,  # noqa: N802
+                              du=(None,) * 4, stream=None):
+    """Both gradients of a gated expert's hidden stage as MXFP8, quantised
+    from one read: with D the block values of the BlockMatrix d, `gate` = G
+    and `up` = U (block values like d.data), dG = D * U * act'(G) and dU = D *
+    act(G) as BlockGateGrad stores them, never written as 16 bits. `dg` and
+    `du` are (q, scales, qt, scales_t) tuples with QuantizeBlocksMx' shapes
+    and meaning; a pair left None is not computed, all four None is an error
+    (sputnik_quantize_blocks_mx_gated_grad)."""
+    import torch
+
+    if not isinstance(d, BlockMatrix):
+        raise TypeError("QuantizeBlocksMxGatedGrad takes a BlockMatrix")
+    if d.data.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("QuantizeBlocksMxGatedGrad: d.data must be fp16 / "
+                        "bf16")
+    _fp8_buffer(gate, d.data.dtype, tuple(d.data.shape), "gate")
+    _fp8_buffer(up, d.data.dtype, tuple(d.data.shape), "up")
+    nb = d.num_blocks
+    ptrs = (_mx_images(dg, nb, "QuantizeBlocksMxGatedGrad: dG")
+            + _mx_images(du, nb, "QuantizeBlocksMxGatedGrad: dU"))
+    if all(p is None for p in ptrs):
+        raise ValueError("QuantizeBlocksMxGatedGrad: no output")
+    cd = d._c()
+    _check(lib().sputnik_quantize_blocks_mx_gated_grad(
+        ctypes.byref(cd), _ptr(gate), _ptr(up), _act_code(activation), *ptrs,
+        _dtype_code(d.data), _stream(stream)), "QuantizeBlocksMxGatedGrad")
+
+
+def DsdMxPair(s1, s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q,  # noqa: N802
+              b2_scales, c, stream=None):
+    """C (Matrix of fp16 / bf16, [s1.rows, n]) = S1q . B1q + S2q . B2q through
+    one accumulator, rounded once: s1 / s1_scales as DsdMx's sparse operand,
+    s2_data (e4m3, s1.data's shape) / s2_scales a second set of block values
+    on the same topology, b1q / b2q two e4m3 MX weights as DsdMx's. Bit for
+    bit DsdMx over the concatenated operands (sputnik_dsd_mx_pair)."""
+    import torch
+
+    if not isinstance(s1, BlockMatrix) or not isinstance(c, Matrix):
+        raise TypeError("DsdMxPair takes a BlockMatrix and writes a Matrix")
+    _, n, k = _mx_weight(b1q, b1_scales, "e4m3", "DsdMxPair")
+    if _mx_weight(b2q, b2_scales, "e4m3", "DsdMxPair")[1:] != (n, k):
+        raise ValueError("DsdMxPair: b1q and b2q differ in shape")
+    if k != s1.cols or n != c.cols or c.rows != s1.rows:
+        raise ValueError(f"DsdMxPair shapes [{s1.rows}, {s1.cols}] x [{k}, "
+                         f"{n}] -> [{c.rows}, {c.cols}]")
+    if getattr(s1.data, "dtype", None) != torch.float8_e4m3fn:
+        raise TypeError("DsdMxPair: s1.data must be torch.float8_e4m3fn")
+    _fp8_buffer(s2_data, torch.float8_e4m3fn, tuple(s1.data.shape), "s2_data")
+    _fp8_buffer(s1_scales, torch.uint8, (s1.num_blocks * 128, 4), "s1_scales")
+    _fp8_buffer(s2_scales, torch.uint8, (s1.num_blocks * 128, 4), "s2_scales")
+    cs, cc = s1._c(), c._c()
+    _check(lib().sputnik_dsd_mx_pair(
+        ctypes.byref(cs), _ptr(s1_scales), _ptr(b1q), _ptr(b1_scales),
+        _ptr(s2_data), _ptr(s2_scales), _ptr(b2q), _ptr(b2_scales),
+        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "DsdMxPair")
+
+
 __all__ = [
     "QuantizeRowsMx", "QuantizeWeightMx", "SddMx", "DsdMx", "MX_FORMATS",
     "QuantizeTilesMx", "QuantizeBlocksMx", "DsdMxWgrad",
+    "QuantizeBlocksMxGated", "QuantizeBlocksMxGatedGrad", "DsdMxPair",
     "AllocateBitmaskBuffers", "AllocateRowIndicesBuffer",
     "AllocateTransposeBuffers", "AsInt", "Bitmask", "FreeBitmaskBuffers",
     "build_hash", "capture_workspaces", "pair_errors", "sdd_plan", "sdd_kernel",

@@ -167,6 +167,17 @@ hipError_t LaunchMxWgrad(int dtype, bool out_f32, bool add, const void *s,
                          const uint8_t *b_scales, void *c, const int *offsets,
                          const short *indices, int m_blocks, int n_blocks,
                          int k_blocks, int nnz_blocks, hipStream_t stream);
+// The e4m3 DSD of LaunchMxGemm over two operand pairs of one topology through
+// one accumulator (DsdMxPair): s2 / s2_scales the second pair's blocks and
+// scale dwords in the same storage order, b2 / b2_scales its weight, shaped
+// as b1's.
+hipError_t LaunchMxPair(int dtype, const void *s1, const uint8_t *s1_scales,
+                        const void *b1, const uint8_t *b1_scales,
+                        const void *s2, const uint8_t *s2_scales,
+                        const void *b2, const uint8_t *b2_scales, void *c,
+                        const int *offsets, const short *indices, int m_blocks,
+                        int n_blocks, int k_blocks, int nnz_blocks,
+                        hipStream_t stream);
 
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.

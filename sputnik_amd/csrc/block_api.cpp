@@ -643,6 +643,38 @@ hipError_t DsdMxWgrad(const BlockMatrix s, const uint8_t *s_scales,
       s.cols / 128, s.nonzeros / (128 * 128), stream);
 }
 
+hipError_t DsdMxPair(const BlockMatrix s1, const uint8_t *s1_scales,
+                     const void *b1q, const uint8_t *b1_scales,
+                     const void *s2_data, const uint8_t *s2_scales,
+                     const void *b2q, const uint8_t *b2_scales, Matrix c,
+                     DataType dtype, hipStream_t stream) {
+  if (!Fp8SizesOk(s1, c.cols, (int)dtype) || c.rows != s1.rows)
+    return hipErrorInvalidValue;
+  if (c.rows == 0 || c.cols == 0) return hipSuccess;
+  const std::initializer_list<const void *> operands = {
+      (const void *)s1.data, (const void *)s1_scales, b1q,
+      (const void *)b1_scales, s2_data, (const void *)s2_scales, b2q,
+      (const void *)b2_scales};
+  if (c.data == nullptr || s1.offsets == nullptr) return hipErrorInvalidValue;
+  if (s1.nonzeros > 0) {
+    if (s1.indices == nullptr) return hipErrorInvalidValue;
+    for (const void *in : operands)
+      if (in == nullptr) return hipErrorInvalidValue;
+  }
+  for (const void *in : operands)
+    if (c.data == in) return hipErrorInvalidValue;
+  if (c.data == (const void *)s1.offsets || c.data == (const void *)s1.indices)
+    return hipErrorInvalidValue;
+  if (!Aligned16({s1.data, s2_data, b1q, b2q, c.data}) ||
+      !Aligned4({s1_scales, s2_scales, b1_scales, b2_scales}))
+    return hipErrorInvalidValue;
+  return sputnik_amd::LaunchMxPair(
+      (int)dtype, s1.data, s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q,
+      b2_scales, c.data, static_cast<const int *>(s1.offsets),
+      static_cast<const short *>(s1.indices), s1.rows / 128, c.cols / 128,
+      s1.cols / 128, s1.nonzeros / (128 * 128), stream);
+}
+
 hipError_t Transpose(BlockMatrix a, hipStream_t stream) {
   // transpose.cu:107-109 checks the three workspaces; with no nonzero block
   // the two per-block ones are legitimately empty.

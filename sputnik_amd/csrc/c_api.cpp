@@ -874,6 +874,45 @@ int sputnik_dsd_mx_wgrad(const sputnik_block_matrix_t *s,
       static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
 }
 
+// ... and a gated expert's.
+int sputnik_quantize_blocks_mx_gated(const sputnik_block_matrix_t *s,
+                                     const void *gate, int act, void *q,
+                                     uint8_t *scales, void *qt,
+                                     uint8_t *scales_t, int dtype,
+                                     void *stream) {
+  if (!s) return hipErrorInvalidValue;
+  return sputnik::block::QuantizeBlocksMxGated(
+      ToCpp(s), gate, static_cast<sputnik::block::Activation>(act),
+      {q, scales, qt, scales_t}, static_cast<DataType>(dtype),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_quantize_blocks_mx_gated_grad(
+    const sputnik_block_matrix_t *d, const void *gate, const void *up, int act,
+    void *dg_q, uint8_t *dg_scales, void *dg_qt, uint8_t *dg_scales_t,
+    void *du_q, uint8_t *du_scales, void *du_qt, uint8_t *du_scales_t,
+    int dtype, void *stream) {
+  if (!d) return hipErrorInvalidValue;
+  return sputnik::block::QuantizeBlocksMxGatedGrad(
+      ToCpp(d), gate, up, static_cast<sputnik::block::Activation>(act),
+      {dg_q, dg_scales, dg_qt, dg_scales_t},
+      {du_q, du_scales, du_qt, du_scales_t}, static_cast<DataType>(dtype),
+      static_cast<hipStream_t>(stream));
+}
+
+int sputnik_dsd_mx_pair(const sputnik_block_matrix_t *s1,
+                        const uint8_t *s1_scales, const void *b1q,
+                        const uint8_t *b1_scales, const void *s2_data,
+                        const uint8_t *s2_scales, const void *b2q,
+                        const uint8_t *b2_scales, const sputnik_matrix_t *c,
+                        int dtype, void *stream) {
+  if (!s1 || !c) return hipErrorInvalidValue;
+  return sputnik::block::DsdMxPair(
+      ToCpp(s1), s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q, b2_scales,
+      ToCpp(c), static_cast<DataType>(dtype),
+      static_cast<hipStream_t>(stream));
+}
+
 // MoE router and device sort (sputnik/block/router.h): moe_router.hip
 // validates.
 int sputnik_router_topk(const void *logits, int32_t *top_experts,

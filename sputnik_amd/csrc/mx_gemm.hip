@@ -66,6 +66,18 @@
 // C_old are row-contiguous. A block row without stored blocks is left alone
 // under `add` (neither read nor written) and is +0 otherwise. The kWgrad =
 // false instantiations keep their code.
+//
+// kPair (DsdMxPair) is the e4m3 DSD over two operand pairs that share one
+// topology, C = S1 B1 + S2 B2 through one accumulator: the step count doubles,
+// steps [0, blocks) walk the block row with the first pair's pointers and
+// steps [blocks, 2 blocks) walk it again with the second pair's, the indices
+// coming through the scalar cache a second time. Which pair a step takes is
+// wave-uniform and changes only the source addresses of issue(): the ring
+// keeps alternating (i % 2, so with an odd block count the second pair starts
+// in the other stage), compute() reads whatever stage i holds, and the +0
+// MFMA and the one fp32 add per step are the DSD's. Bit for bit DsdMx over
+// [S1 | S2] . [B1; B2], with no copy of either. The kPair = false
+// instantiations compile to what they were.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -137,12 +149,20 @@ struct MxGemmParams {
   const short *row_indices;  // SDD: C's
   int m_blocks, n_blocks, k_blocks, nnz_blocks;
   int out_f32, add;  // kWgrad: C holds fp32; C += (accumulate.h)
+  // kPair: the second pair's blocks, row scales, Bq and its scales
+  const char *a2;
+  const uint8_t *a2_scales;
+  const char *b2;
+  const uint8_t *b2_scales;
 };
 
-template <typename T, bool kDsd, bool kB4, bool kWgrad = false>
+template <typename T, bool kDsd, bool kB4, bool kWgrad = false,
+          bool kPair = false>
 __global__ void __launch_bounds__(kThreads)
     mx_gemm_kernel(const MxGemmParams p) {
   static_assert(!kWgrad || (kDsd && !kB4), "the wgrad is the e4m3 DSD");
+  static_assert(!kPair || (kDsd && !kB4 && !kWgrad),
+                "the paired product is the e4m3 DSD");
   constexpr int kStageBytes = StageBytes(kB4);
   constexpr int kBOff = kATileBytes;
   constexpr int kScaleOff = kATileBytes + BTileBytes(kB4);
@@ -169,10 +189,22 @@ __global__ void __launch_bounds__(kThreads)
     if (rb < 0 || rb >= p.m_blocks || nb < 0 || nb >= p.n_blocks) return;
     steps = p.k_blocks;
   }
+  // kPair: step i takes stored block i - blocks of the second pair once i
+  // has passed the row's blocks.
+  [[maybe_unused]] const int blocks = steps;
+  if constexpr (kPair) steps *= 2;
+  auto second = [&](int i) {
+    if constexpr (kPair) return i >= blocks;
+    return false;
+  };
+  auto stored = [&](int i) {
+    if constexpr (kPair) return i >= blocks ? i - blocks : i;
+    return i;
+  };
   // The k-block of step i, or -1 for a stored block to skip.
   auto k_block = [&](int i) {
     if constexpr (!kDsd) return i;
-    const int kb = scalar_short(p.indices + first + i);
+    const int kb = scalar_short(p.indices + first + stored(i));
     return kb >= 0 && kb < p.k_blocks ? kb : -1;
   };
 
@@ -185,9 +217,10 @@ __global__ void __launch_bounds__(kThreads)
     const uint8_t *a_scale;   // of row 0 of the tile, this step's dword
     long long a_scale_pitch;  // bytes between rows
     if constexpr (kDsd) {
-      a_tile = p.a + (long long)(first + i) * kATileBytes;
+      const long long at = first + stored(i);
+      a_tile = (second(i) ? p.a2 : p.a) + at * kATileBytes;
       a_pitch = kB;
-      a_scale = p.a_scales + (long long)(first + i) * kB * 4;
+      a_scale = (second(i) ? p.a2_scales : p.a_scales) + at * kB * 4;
       a_scale_pitch = 4;
     } else {
       a_tile = p.a + (long long)rb * kB * k_bytes + (long long)kb * kB;
@@ -195,8 +228,9 @@ __global__ void __launch_bounds__(kThreads)
       a_scale_pitch = (long long)p.k_blocks * 4;
       a_scale = p.a_scales + (long long)rb * kB * a_scale_pitch + kb * 4;
     }
-    const char *b_tile =
-        p.b + (long long)nb * kB * b_pitch + (long long)kb * kBRow;
+    const char *b_tile = (second(i) ? p.b2 : p.b) +
+                         (long long)nb * kB * b_pitch + (long long)kb * kBRow;
+    const uint8_t *b_scales = second(i) ? p.b2_scales : p.b_scales;
 #pragma unroll
     for (int pass = 0; pass < kATileBytes / (kThreads * 16); ++pass) {
       // (a wave's 64 x 16 bytes are 8 rows of the image)
@@ -230,7 +264,7 @@ __global__ void __launch_bounds__(kThreads)
     } else {
       const int col = (wave - kB / 64) * 64 + lane;
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX_GLOBAL(p.b_scales +
+          SPUTNIK_MX_GLOBAL(b_scales +
                             ((long long)(nb * kB + col) * p.k_blocks + kb) * 4),
           SPUTNIK_MX_LDS(stage + kScaleOff + wave * 256), 4, 0, 0);
     }
@@ -393,7 +427,7 @@ hipError_t LaunchMxGemm(bool dsd, bool b4, int dtype, const void *a,
   const MxGemmParams p{static_cast<const char *>(a), a_scales,
                        static_cast<const char *>(b), b_scales, c, offsets,
                        indices, row_indices, m_blocks, n_blocks, k_blocks,
-                       nnz_blocks, 0, 0};
+                       nnz_blocks, 0, 0, nullptr, nullptr, nullptr, nullptr};
   auto launch = [&](auto t, auto d, auto f) {
     hipLaunchKernelGGL((mx_gemm_kernel<decltype(t), decltype(d)::value,
                                        decltype(f)::value>),
@@ -422,9 +456,33 @@ hipError_t LaunchMxWgrad(int dtype, bool out_f32, bool add, const void *a,
   const MxGemmParams p{static_cast<const char *>(a), a_scales,
                        static_cast<const char *>(b), b_scales, c, offsets,
                        indices, nullptr, m_blocks, n_blocks, k_blocks,
-                       nnz_blocks, out_f32, add};
+                       nnz_blocks, out_f32, add, nullptr, nullptr, nullptr,
+                       nullptr};
   auto launch = [&](auto t) {
     hipLaunchKernelGGL((mx_gemm_kernel<decltype(t), true, false, true>),
+                       dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
+    return hipGetLastError();
+  };
+  return dtype == 1 ? launch(__bf16{}) : launch(_Float16{});
+}
+
+hipError_t LaunchMxPair(int dtype, const void *s1, const uint8_t *s1_scales,
+                        const void *b1, const uint8_t *b1_scales,
+                        const void *s2, const uint8_t *s2_scales,
+                        const void *b2, const uint8_t *b2_scales, void *c,
+                        const int *offsets, const short *indices, int m_blocks,
+                        int n_blocks, int k_blocks, int nnz_blocks,
+                        hipStream_t stream) {
+  const long long tiles = (long long)m_blocks * n_blocks;
+  if (tiles == 0) return hipSuccess;
+  if (tiles > INT_MAX) return hipErrorInvalidValue;
+  const MxGemmParams p{static_cast<const char *>(s1), s1_scales,
+                       static_cast<const char *>(b1), b1_scales, c, offsets,
+                       indices, nullptr, m_blocks, n_blocks, k_blocks,
+                       nnz_blocks, 0, 0, static_cast<const char *>(s2),
+                       s2_scales, static_cast<const char *>(b2), b2_scales};
+  auto launch = [&](auto t) {
+    hipLaunchKernelGGL((mx_gemm_kernel<decltype(t), true, false, false, true>),
                        dim3((unsigned)tiles), dim3(kThreads), 0, stream, p);
     return hipGetLastError();
   };

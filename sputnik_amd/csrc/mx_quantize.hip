@@ -18,7 +18,13 @@
 // pass's: one 128 x 128 tile per workgroup, read once with 16-byte loads,
 // quantised in 1 x 32 groups along the rows, in 32 x 1 groups down the
 // columns, or both. quantize_tile_mx has the thread map and the LDS bank
-// argument.
+// argument; its row pass (mx_row_chunk) and its column pass (mx_column_pass)
+// are helpers.
+//
+// quantize_gated_grad_mx_kernel (QuantizeBlocksMxGatedGrad) is the GLU
+// backward's: both gated gradients of a 128 x 128 block from one read of D, G
+// and U, each quantised along either axis or both through the same two
+// helpers, neither ever stored as 16 bits. Its comment has the staging.
 #include <climits>
 #include <cstdint>
 #include <initializer_list>
@@ -197,6 +203,83 @@ __device__ __forceinline__ void store16(uint8_t *p, const uint32_t *w,
   store_bytes(p, w, 4, false);
 }
 
+// The row pass on one chunk: lane `sub` of a row's 16 holds 8 elements; the 4
+// lanes of a 32-block meet for the amax, each lane stores its 8 bytes at `q`
+// and the row's first lane the row's scale dword at `scales`. Whole waves
+// call it.
+template <typename T>
+__device__ __forceinline__ void mx_row_chunk(act_t8<T> v, int sub, uint8_t *q,
+                                             uint8_t *scales, bool aligned,
+                                             bool scales_aligned) {
+  float amax = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float f = (float)v[i];
+    if (fp8_finite(f)) amax = fmaxf(amax, fabsf(f));
+  }
+  amax = fmaxf(amax, __shfl_xor(amax, 2));
+  amax = fmaxf(amax, __shfl_xor(amax, 1));
+  const float scale = mx_scale<false>(amax);
+  const uint32_t byte = mx_scale_byte(scale);
+  const int lane0 = (threadIdx.x & 63) & ~15;
+  const uint32_t dword = (uint32_t)__shfl((int)byte, lane0) |
+                         (uint32_t)__shfl((int)byte, lane0 + 4) << 8 |
+                         (uint32_t)__shfl((int)byte, lane0 + 8) << 16 |
+                         (uint32_t)__shfl((int)byte, lane0 + 12) << 24;
+  uint32_t w[2] = {0, 0};
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    w[i >> 2] |= fp8_quantize((float)v[i], scale) << (8 * (i & 3));
+  if (aligned) *reinterpret_cast<uint2 *>(q) = make_uint2(w[0], w[1]);
+  else store_bytes(q, w, 2, false);
+  if (sub == 0) store_bytes(scales, &dword, 1, scales_aligned);
+}
+
+// The column pass over a staged [128][128] image of T (quantize_tile_mx has
+// the map): `qt` / `scales_t` are the tile's first byte of each output,
+// the pitches the bytes between consecutive columns. Every thread of the
+// workgroup calls it, after the barrier that follows the staging.
+template <typename T>
+__device__ __forceinline__ void mx_column_pass(
+    const T *image, uint8_t *col_scales, uint8_t *qt, long long qt_pitch,
+    uint8_t *scales_t, long long scales_t_pitch, bool aligned_t,
+    bool scales_t_aligned) {
+  typedef T t2 __attribute__((ext_vector_type(2)));
+  const int u = threadIdx.x >> 6, pair = threadIdx.x & 63;
+  const T *from = image + u * kMxBlock * kTile + 2 * pair;
+  t2 v[kMxBlock];
+  float amax[2] = {0.0f, 0.0f};
+#pragma unroll
+  for (int i = 0; i < kMxBlock; ++i) {
+    v[i] = *reinterpret_cast<const t2 *>(from + i * kTile);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const float f = (float)v[i][j];
+      if (fp8_finite(f)) amax[j] = fmaxf(amax[j], fabsf(f));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = 2 * pair + j;
+    const float scale = mx_scale<false>(amax[j]);
+    col_scales[c * 4 + u] = (uint8_t)mx_scale_byte(scale);
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < kMxBlock; ++i)
+      w[i >> 2] |= fp8_quantize((float)v[i][j], scale) << (8 * (i & 3));
+    uint8_t *dst = qt + c * qt_pitch + u * kMxBlock;
+    store16(dst, w, aligned_t);
+    store16(dst + 16, w + 4, aligned_t);
+  }
+  __syncthreads();
+  if (threadIdx.x < kTile) {
+    const uint32_t dword = reinterpret_cast<const uint32_t *>(
+        col_scales)[threadIdx.x];
+    store_bytes(scales_t + threadIdx.x * scales_t_pitch, &dword, 1,
+                scales_t_aligned);
+  }
+}
+
 // A 128 x 128 tile of T at `x` (`pitch` elements between rows; z likewise
 // for kOutActGrad) -> both MXFP8 images, the body QuantizeTilesMx and
 // QuantizeBlocksMx share. Every thread of the workgroup calls it.
@@ -226,7 +309,6 @@ template <typename T, int kMode>
 __device__ __forceinline__ void quantize_tile_mx(
     const T *x, const T *z, long long pitch, int act, const MxTileSinks &o,
     const MxTileParams &p, T *image, uint8_t *col_scales) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
   const int sub = threadIdx.x & 15;
 #pragma unroll 2
   for (int pass = 0; pass < kTile * kTile / 8 / kThreads; ++pass) {
@@ -240,71 +322,17 @@ __device__ __forceinline__ void quantize_tile_mx(
       E::template apply8<T>(act, v, g, v, &h, &unused);
       v = h;
     }
-    if (o.q != nullptr) {
-      float amax = 0.0f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float f = (float)v[i];
-        if (fp8_finite(f)) amax = fmaxf(amax, fabsf(f));
-      }
-      amax = fmaxf(amax, __shfl_xor(amax, 2));
-      amax = fmaxf(amax, __shfl_xor(amax, 1));
-      const float scale = mx_scale<false>(amax);
-      const uint32_t byte = mx_scale_byte(scale);
-      const int lane0 = (threadIdx.x & 63) & ~15;
-      const uint32_t dword = (uint32_t)__shfl((int)byte, lane0) |
-                             (uint32_t)__shfl((int)byte, lane0 + 4) << 8 |
-                             (uint32_t)__shfl((int)byte, lane0 + 8) << 16 |
-                             (uint32_t)__shfl((int)byte, lane0 + 12) << 24;
-      uint32_t w[2] = {0, 0};
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        w[i >> 2] |= fp8_quantize((float)v[i], scale) << (8 * (i & 3));
-      uint8_t *dst = o.q + r * o.q_pitch + sub * 8;
-      if (p.aligned) *reinterpret_cast<uint2 *>(dst) = make_uint2(w[0], w[1]);
-      else store_bytes(dst, w, 2, false);
-      if (sub == 0)
-        store_bytes(o.scales + r * o.scales_pitch, &dword, 1,
-                    p.scales_aligned);
-    }
+    if (o.q != nullptr)
+      mx_row_chunk<T>(v, sub, o.q + r * o.q_pitch + sub * 8,
+                      o.scales + r * o.scales_pitch, p.aligned,
+                      p.scales_aligned);
     if (o.qt != nullptr)
       *reinterpret_cast<act_t8<T> *>(image + r * kTile + sub * 8) = v;
   }
   if (o.qt == nullptr) return;
   __syncthreads();
-  const int u = threadIdx.x >> 6, pair = threadIdx.x & 63;
-  const T *from = image + u * kMxBlock * kTile + 2 * pair;
-  t2 v[kMxBlock];
-  float amax[2] = {0.0f, 0.0f};
-#pragma unroll
-  for (int i = 0; i < kMxBlock; ++i) {
-    v[i] = *reinterpret_cast<const t2 *>(from + i * kTile);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float f = (float)v[i][j];
-      if (fp8_finite(f)) amax[j] = fmaxf(amax[j], fabsf(f));
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = 2 * pair + j;
-    const float scale = mx_scale<false>(amax[j]);
-    col_scales[c * 4 + u] = (uint8_t)mx_scale_byte(scale);
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < kMxBlock; ++i)
-      w[i >> 2] |= fp8_quantize((float)v[i][j], scale) << (8 * (i & 3));
-    uint8_t *dst = o.qt + c * o.qt_pitch + u * kMxBlock;
-    store16(dst, w, p.aligned_t);
-    store16(dst + 16, w + 4, p.aligned_t);
-  }
-  __syncthreads();
-  if (threadIdx.x < kTile) {
-    const uint32_t dword = reinterpret_cast<const uint32_t *>(
-        col_scales)[threadIdx.x];
-    store_bytes(o.scales_t + threadIdx.x * o.scales_t_pitch, &dword, 1,
-                p.scales_t_aligned);
-  }
+  mx_column_pass<T>(image, col_scales, o.qt, o.qt_pitch, o.scales_t,
+                    o.scales_t_pitch, p.aligned_t, p.scales_t_aligned);
 }
 
 template <typename T, int kMode>
@@ -350,6 +378,78 @@ __global__ void __launch_bounds__(kThreads)
   quantize_tile_mx<T, kMode>(static_cast<const T *>(p.x) + at,
                              z == nullptr ? nullptr : z + at, p.cols, p.act, o,
                              p, image, col_scales);
+}
+
+// QuantizeBlocksMxGatedGrad: one 128 x 128 block per workgroup. D, G and U are
+// each read once, in quantize_tile_mx's row map (8 passes of 16 rows, 16
+// lanes x 8 elements per row, 16-byte loads). The chunk's (dG, dU) come from
+// the trait MatmulGatedGrad's elementwise stage calls, rounded to T. Set 0 is
+// dG, set 1 dU. A set's row image is quantised from the registers by
+// mx_row_chunk; for its column image the chunk is staged in the set's own
+// unpadded [128][128] image of T and mx_column_pass walks it after one
+// barrier. 2 x 32 KiB of images and 2 x 512 bytes of col_scales are 65 KiB:
+// two workgroups still share a CU's 160 KiB.
+//
+// LDS banks: each image is written and read exactly as quantize_tile_mx's
+// (its comment has the argument): a wave's 16-byte writes are one contiguous
+// kilobyte, the column reads 64 consecutive dwords. The two images are 32 KiB
+// apart, a multiple of every bank period, and are never touched by the same
+// instruction, so they do not meet. A null pair is a workgroup-uniform test:
+// it costs neither its shuffles and stores nor, for a column pair, its
+// staging and its pass.
+struct MxGateGradParams {
+  const void *d, *g, *u;
+  uint8_t *q[2], *scales[2], *qt[2], *scales_t[2];
+  const int *block_offsets;
+  int nnz_blocks, act;
+  bool aligned, scales_aligned, aligned_t, scales_t_aligned;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+    quantize_gated_grad_mx_kernel(const MxGateGradParams p) {
+  __shared__ __attribute__((aligned(16))) T image[2][kTile * kTile];
+  __shared__ __attribute__((aligned(4))) uint8_t col_scales[2][kTile * 4];
+  static_assert(2 * (sizeof(image) + sizeof(col_scales)) <= 160 * 1024,
+                "two workgroups per CU");
+  const bool columns = p.qt[0] != nullptr || p.qt[1] != nullptr;
+  long long rb = blockIdx.x;
+  if (columns) {  // output block blockIdx.x is source block block_offsets[..]
+    const int b = p.block_offsets[blockIdx.x];
+    if (b < 0 || b >= p.nnz_blocks) return;
+    rb = b;
+  }
+  const T *d = static_cast<const T *>(p.d), *g = static_cast<const T *>(p.g),
+          *u = static_cast<const T *>(p.u);
+  const int sub = threadIdx.x & 15;
+#pragma unroll 2
+  for (int pass = 0; pass < kTile * kTile / 8 / kThreads; ++pass) {
+    const int r = pass * (kThreads / 16) + (threadIdx.x >> 4);
+    const long long row = rb * kTile + r, at = row * kTile + sub * 8;
+    act_t8<T> o[2];
+    SddEpilogue<kOutGateGrad>::template apply8<T>(
+        p.act, load8<T>(d + at, p.aligned), load8<T>(g + at, p.aligned),
+        load8<T>(u + at, p.aligned), &o[0], &o[1]);
+#pragma unroll
+    for (int set = 0; set < 2; ++set) {
+      if (p.q[set] != nullptr)
+        mx_row_chunk<T>(o[set], sub, p.q[set] + at, p.scales[set] + row * 4,
+                        p.aligned, p.scales_aligned);
+      if (p.qt[set] != nullptr)
+        *reinterpret_cast<act_t8<T> *>(image[set] + r * kTile + sub * 8) =
+            o[set];
+    }
+  }
+  if (!columns) return;
+  __syncthreads();
+#pragma unroll
+  for (int set = 0; set < 2; ++set)
+    if (p.qt[set] != nullptr)
+      mx_column_pass<T>(image[set], col_scales[set],
+                        p.qt[set] + (long long)blockIdx.x * kTile * kTile,
+                        kTile,
+                        p.scales_t[set] + (long long)blockIdx.x * kTile * 4, 4,
+                        p.aligned_t, p.scales_t_aligned);
 }
 
 bool Aligned(std::initializer_list<const void *> ps, uintptr_t mask) {
@@ -540,6 +640,87 @@ hipError_t QuantizeBlocksMx(const BlockMatrix s, MxBlockStage stage,
     default:
       return LaunchQuantizeTilesMx<kModeNone>(p, blocks, (int)dtype, stream);
   }
+}
+
+namespace {
+
+bool MxBlocksOk(const BlockMatrix &s, Activation activation, DataType dtype) {
+  const int act = (int)activation;
+  return s.block_size == BlockSize::k128 && s.nonzeros >= 0 &&
+         s.nonzeros % (kTile * kTile) == 0 &&
+         ((int)dtype == 0 || (int)dtype == 1) && act >= kActRelu &&
+         act <= kActSilu;
+}
+
+// Both pointers of each pair or neither, and `any`: one pair at least.
+bool MxImagesOk(const MxImages &o, bool *any) {
+  if ((o.q == nullptr) != (o.scales == nullptr) ||
+      (o.qt == nullptr) != (o.scales_t == nullptr))
+    return false;
+  *any = *any || o.q != nullptr || o.qt != nullptr;
+  return true;
+}
+
+}  // namespace
+
+hipError_t QuantizeBlocksMxGated(const BlockMatrix s, const void *gate,
+                                 Activation activation, MxImages h,
+                                 DataType dtype, hipStream_t stream) {
+  bool any = false;
+  if (!MxBlocksOk(s, activation, dtype) || !MxImagesOk(h, &any) || !any)
+    return hipErrorInvalidValue;
+  if (s.nonzeros == 0) return hipSuccess;
+  if (s.data == nullptr || gate == nullptr ||
+      (h.qt != nullptr && s.block_offsets == nullptr))
+    return hipErrorInvalidValue;
+  if (!Distinct({h.q, h.scales, h.qt, h.scales_t},
+                {s.data, gate, (const void *)s.block_offsets}))
+    return hipErrorInvalidValue;
+  const int blocks = s.nonzeros / (kTile * kTile);
+  MxTileParams p{s.data, gate, static_cast<uint8_t *>(h.q), h.scales,
+                 static_cast<uint8_t *>(h.qt), h.scales_t,
+                 static_cast<const int *>(s.block_offsets),
+                 (long long)blocks * kTile, kTile, blocks, (int)activation,
+                 true, false, false, false, false};
+  return LaunchQuantizeTilesMx<kOutGate>(p, blocks, (int)dtype, stream);
+}
+
+hipError_t QuantizeBlocksMxGatedGrad(const BlockMatrix d, const void *gate,
+                                     const void *up, Activation activation,
+                                     MxImages dg, MxImages du, DataType dtype,
+                                     hipStream_t stream) {
+  bool any = false;
+  if (!MxBlocksOk(d, activation, dtype) || !MxImagesOk(dg, &any) ||
+      !MxImagesOk(du, &any) || !any)
+    return hipErrorInvalidValue;
+  if (d.nonzeros == 0) return hipSuccess;
+  const bool columns = dg.qt != nullptr || du.qt != nullptr;
+  if (d.data == nullptr || gate == nullptr || up == nullptr ||
+      (columns && d.block_offsets == nullptr))
+    return hipErrorInvalidValue;
+  if (!Distinct({dg.q, dg.scales, dg.qt, dg.scales_t, du.q, du.scales, du.qt,
+                 du.scales_t},
+                {d.data, gate, up, (const void *)d.block_offsets}))
+    return hipErrorInvalidValue;
+  const MxGateGradParams p{
+      d.data, gate, up,
+      {static_cast<uint8_t *>(dg.q), static_cast<uint8_t *>(du.q)},
+      {dg.scales, du.scales},
+      {static_cast<uint8_t *>(dg.qt), static_cast<uint8_t *>(du.qt)},
+      {dg.scales_t, du.scales_t},
+      static_cast<const int *>(d.block_offsets),
+      d.nonzeros / (kTile * kTile), (int)activation,
+      Aligned({d.data, gate, up}, 15) && Aligned({dg.q, du.q}, 7),
+      Aligned({dg.scales, du.scales}, 3), Aligned({dg.qt, du.qt}, 15),
+      Aligned({dg.scales_t, du.scales_t}, 3)};
+  auto launch = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((quantize_gated_grad_mx_kernel<T>),
+                       dim3((unsigned)p.nnz_blocks), dim3(kThreads), 0, stream,
+                       p);
+    return hipGetLastError();
+  };
+  return (int)dtype == 1 ? launch(__bf16{}) : launch(_Float16{});
 }
 
 }  // namespace block

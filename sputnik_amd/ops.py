@@ -63,6 +63,9 @@ three products; its pieces are `quantize_tiles_mx` (1 x 32 row groups and 32 x
 1 column groups in one pass), `quantize_sparse_mx_t` (a sparse operand and its
 transpose, each scaled along its own k) and `dsd_mx_wgrad`, dsd_mx into a
 gradient sink.
+The MX path of a gated expert (mx.h, "Gradients of a gated expert") is
+`glu_mlp_mx(x, w1t, v1t, w2, topo, activation)` and `moe_glu_mlp_mx_train`
+around it; its dX is `dsd_mx_pair`, two MX products through one accumulator.
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -96,6 +99,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                QuantizeBlocksGated, QuantizeBlocksGatedGrad, DsdFp8Pair,
                QuantizeRowsMx, QuantizeWeightMx, SddMx, DsdMx, MX_FORMATS,
                QuantizeTilesMx, QuantizeBlocksMx, DsdMxWgrad,
+               QuantizeBlocksMxGated, QuantizeBlocksMxGatedGrad, DsdMxPair,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
                RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
                MOE_SORT_CHUNK, ROUTER_AUX_TOKENS, ROUTER_MAX_EXPERTS,
@@ -2549,7 +2553,8 @@ def mlp_mx(x: torch.Tensor, w1t: torch.Tensor, w2: torch.Tensor,
     16-bit inputs, in their dtype. A sink (`dw1t_out`, `dw2_out`: contiguous
     [F, h], x's dtype or fp32) receives sink += gradient, rounded once, in
     place of a returned gradient. What needs_input_grad does not ask for is
-    skipped. There are no biases, no GLU form and no MXFP4 weights."""
+    skipped. There are no biases and no MXFP4 weights; glu_mlp_mx is the
+    gated form."""
     _check_dtypes(x, w1t, w2)
     if not isinstance(topo, SparseMatrix) or topo.is_transposed():
         raise TypeError("mlp_mx: topo must be a SparseMatrix (not a .t() "
@@ -2590,6 +2595,218 @@ def moe_mlp_mx_train(x: torch.Tensor, top_experts: torch.Tensor,
                            route.rows // BLOCK, dtype=x.dtype)
     y = mlp_mx(xp, w1t, w2, topo, "gelu" if activation is None else
                activation, dw1t_out, dw2_out)
+    return padded_scatter(y, route, expert_weights)
+
+
+# ---- MX gradients of a gated expert (mx.h, "Gradients of a gated expert") ----
+
+def _mx_images(nb: int, rows: bool, cols: bool, dev):
+    """(q, scales, qt, scales_t) buffers of an MX block quantiser, None for a
+    pair that is not asked for."""
+    out = []
+    for want in (rows, cols):
+        out += [torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
+                            device=dev) if want else None,
+                torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=dev)
+                if want else None]
+    return tuple(out)
+
+
+def _mx_views(topo: SparseMatrix, images):
+    """(the MxSparseMatrix of topo's topology or None, that of the
+    transposed topology or None) over the images a block quantiser filled."""
+    q, s, qt, st = images
+    meta = topo._meta
+    by_rows = None if q is None else MxSparseMatrix(topo, q, s)
+    by_cols = None if qt is None else MxSparseMatrix(
+        SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
+                     meta.indices_t), qt, st)
+    return by_rows, by_cols
+
+
+def dsd_mx_pair(sq1: MxSparseMatrix, w1: MxWeight, sq2: MxSparseMatrix,
+                w2: MxWeight, out_dtype=torch.bfloat16) -> torch.Tensor:
+    """sq1 . w1 + sq2 . w2 as a dense [m, n] tensor of `out_dtype`, both
+    products in MXFP8 through one fp32 accumulator and rounded once: sq1 and
+    sq2 are quantised block values on one topology (the same metadata), w1
+    and w2 two e4m3 MxWeights of [k, n]. Bit for bit dsd_mx over the
+    concatenated operands [sq1 | sq2] . [w1; w2], which are never formed: a
+    block row takes sq1's blocks in storage order, then sq2's. The dX of a
+    gated expert. Forward only."""
+    if (not isinstance(sq1, MxSparseMatrix)
+            or not isinstance(sq2, MxSparseMatrix)):
+        raise TypeError("dsd_mx_pair: sq1 and sq2 must be MxSparseMatrix")
+    if sq1._meta is not sq2._meta or sq1.is_transposed() != sq2.is_transposed():
+        raise ValueError("dsd_mx_pair: sq1 and sq2 must share one topology")
+    if not isinstance(w1, MxWeight) or not isinstance(w2, MxWeight):
+        raise TypeError("dsd_mx_pair: w1 and w2 must be MxWeights")
+    if w1.format != "e4m3" or w2.format != "e4m3":
+        raise ValueError("dsd_mx_pair: the weights must be 'e4m3'")
+    _out_dtype(out_dtype, "dsd_mx_pair")
+    if sq1.shape[1] != w1.k or w1.shape != w2.shape:
+        raise ValueError(f"dsd_mx_pair shapes {sq1.shape} x {w1.shape} + "
+                         f"{sq2.shape} x {w2.shape}")
+    out = torch.empty(sq1.shape[0], w1.n, dtype=out_dtype, device=sq1.device)
+    DsdMxPair(sq1._descriptor(), sq1.scales, w1.q, w1.scales, sq2.data,
+              sq2.scales, w2.q, w2.scales,
+              Matrix(out.shape[0], out.shape[1], out))
+    return out
+
+
+class _GLUMLPMx(torch.autograd.Function):
+    """y = dsd_mx(quantize_sparse_mx(sdd_mx(x, v1t^T), act, gate=sdd_mx(x,
+    w1t^T)), w2) and the backward pass of mx.h's gated table. Keeps G, U, the
+    column quantisation of X and the 16-bit weights, whose backward layouts
+    are quantised in backward, as _MLPMx has it."""
+
+    @staticmethod
+    def forward(ctx, x, w1t, v1t, w2, topo, act, w1_sink, v1_sink, w2_sink):
+        need_x, need_w1, need_v1, need_w2 = ctx.needs_input_grad[:4]
+        need_w1 = need_w1 or w1_sink is not None
+        need_v1 = need_v1 or v1_sink is not None
+        need_w2 = need_w2 or w2_sink is not None
+        ctx.topo, ctx.act = topo, act
+        ctx.sinks = (w1_sink, v1_sink, w2_sink)
+        ctx.need = (need_x, need_w1, need_v1, need_w2)
+        w1q = quantize_weight_mx(w1t, transpose=True)           # [h, F]
+        v1q = quantize_weight_mx(v1t, transpose=True)           # [h, F]
+        w2q = quantize_weight_mx(w2)                            # [F, h]
+        xq, xs, xqt, xst = quantize_tiles_mx(x, cols=need_w1 or need_v1)
+        g = sdd_mx(xq, xs, w1q, topo, x.dtype)
+        u = sdd_mx(xq, xs, v1q, topo, x.dtype)
+        y = dsd_mx(quantize_sparse_mx(u, act, gate=g), w2q, x.dtype)
+        if any(ctx.need):
+            ctx.save_for_backward(g.data, u.data, xqt, xst,
+                                  w1t if need_x else None,
+                                  v1t if need_x else None,
+                                  w2 if any(ctx.need[:3]) else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        g_data, u_data, xqt, xst, w1t, v1t, w2 = ctx.saved_tensors
+        need_x, need_w1, need_v1, need_w2 = ctx.need
+        w1_sink, v1_sink, w2_sink = ctx.sinks
+        topo, act = ctx.topo, ctx.act
+        meta, nb, dt, dev = topo._meta, topo.nnz_blocks, g_data.dtype, dy.device
+        need_d = need_x or need_w1 or need_v1
+        dyq, dys, dyqt, dyst = quantize_tiles_mx(dy.contiguous(), rows=need_d,
+                                                 cols=need_w2)
+
+        def wgrad(st, bqt, bst, sink):
+            if sink is not None:
+                dsd_mx_wgrad(st, bqt, bst, sink, True)
+                return None
+            return dsd_mx_wgrad(st, bqt, bst, out_dtype=dt)
+
+        dx = dw1 = dv1 = dw2 = None
+        if need_w2:                                   # H^T dY
+            meta.ensure_transposed(u_data)
+            h = _mx_images(nb, False, True, dev)
+            if nb:
+                QuantizeBlocksMxGated(meta.descriptor(u_data), g_data, act, *h)
+            dw2 = wgrad(_mx_views(topo, h)[1], dyqt, dyst, w2_sink)
+            del h
+        if need_d:
+            # D = dY W2^T: W2 read as [n = F, k = h]
+            d = sdd_mx(dyq, dys, quantize_weight_mx(w2, transpose=True), topo,
+                       dt)
+            # dG = D U act'(G) and dU = D act(G), each along the axes its
+            # products read, from one pass over D, G and U
+            if need_w1 or need_v1:
+                meta.ensure_transposed(u_data)
+            dg = _mx_images(nb, need_x, need_w1, dev)
+            du = _mx_images(nb, need_x, need_v1, dev)
+            if nb:
+                QuantizeBlocksMxGatedGrad(meta.descriptor(d.data), g_data,
+                                          u_data, act, dg, du)
+            dgq, dgt = _mx_views(topo, dg)
+            duq, dut = _mx_views(topo, du)
+            if need_x:              # dG W1t + dU V1t: each [k = F, n = h]
+                dx = dsd_mx_pair(dgq, quantize_weight_mx(w1t), duq,
+                                 quantize_weight_mx(v1t), dt)
+            if need_w1:                               # dG^T X
+                dw1 = wgrad(dgt, xqt, xst, w1_sink)
+            if need_v1:                               # dU^T X
+                dv1 = wgrad(dut, xqt, xst, v1_sink)
+        return (dx, dw1, dv1, dw2) + (None,) * 5
+
+
+def _glu_mx_sinks(x, w2, sinks, what: str):
+    for sink, name in zip(sinks, ("dw1t_out", "dv1t_out", "dw2_out")):
+        if sink is not None:
+            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
+                        f"{what}: {name}")
+
+
+def glu_mlp_mx(x: torch.Tensor, w1t: torch.Tensor, v1t: torch.Tensor,
+               w2: torch.Tensor, topo: SparseMatrix, activation="silu",
+               dw1t_out: Optional[torch.Tensor] = None,
+               dv1t_out: Optional[torch.Tensor] = None,
+               dw2_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gated expert MLP with its four products in MXFP8, forward and
+    backward: y = ((x v1t^T) * act(x w1t^T) at topo's blocks) w2 over 16-bit
+    x [T, h], w1t, v1t and w2 [F, h], topo [T, F]. Forward is
+    quantize_weight_mx of the three weights, quantize_rows_mx -> two sdd_mx
+    -> quantize_sparse_mx with the gate -> dsd_mx: the bits of moe_mlp_mx's
+    expert chain with `v1q`. Backward (sputnik/block/mx.h, "Gradients of a
+    gated expert"): D = dY W2^T by sdd_mx; dG = D U act'(G) and dU = D act(G)
+    formed and quantised in one pass over D, G and U, never stored as 16
+    bits; dX = dG W1t + dU V1t by dsd_mx_pair, one accumulator and one
+    rounding; dW2 = H^T dY, dW1t = dG^T X and dV1t = dU^T X by dsd_mx_wgrad.
+    The weights' backward layouts are quantised from the 16-bit weights. The
+    gradients are straight-through, in the 16-bit dtype. A sink (`dw1t_out`,
+    `dv1t_out`, `dw2_out`: contiguous [F, h], x's dtype or fp32) receives
+    sink += gradient, rounded once, in place of a returned gradient. What
+    needs_input_grad and the sinks do not ask for is skipped. There are no
+    biases and no MXFP4 weights."""
+    _check_dtypes(x, w1t, v1t, w2)
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError("glu_mlp_mx: topo must be a SparseMatrix (not a "
+                        ".t() view)")
+    if (x.dim() != 2 or w1t.dim() != 2
+            or tuple(w1t.shape) != tuple(w2.shape)
+            or tuple(v1t.shape) != tuple(w2.shape)
+            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
+            or int(w1t.shape[1]) != int(x.shape[1])
+            or int(x.shape[1]) % BLOCK):
+        raise ValueError("glu_mlp_mx: x [T, h], w1t, v1t and w2 [F, h], "
+                         "topo [T, F], all multiples of 128")
+    _glu_mx_sinks(x, w2, (dw1t_out, dv1t_out, dw2_out), "glu_mlp_mx")
+    return _GLUMLPMx.apply(x.contiguous(), w1t.contiguous(),
+                           v1t.contiguous(), w2.contiguous(), topo,
+                           _act_code(activation), dw1t_out, dv1t_out, dw2_out)
+
+
+def moe_glu_mlp_mx_train(x: torch.Tensor, top_experts: torch.Tensor,
+                         expert_weights: torch.Tensor, w1t: torch.Tensor,
+                         v1t: torch.Tensor, w2: torch.Tensor,
+                         num_experts: int, activation=None,
+                         rows: Optional[int] = None,
+                         dw1t_out: Optional[torch.Tensor] = None,
+                         dv1t_out: Optional[torch.Tensor] = None,
+                         dw2_out: Optional[torch.Tensor] = None
+                         ) -> torch.Tensor:
+    """moe_mlp's gated form with the expert products in MXFP8 and gradients:
+    padded_gather -> glu_mlp_mx -> padded_scatter, the permutation with its
+    existing gradients. w1t, v1t and w2 are 16-bit [num_experts * ffn,
+    d_model]; the other arguments are moe_mlp's (activation None: "silu").
+    Differentiable in x, expert_weights, w1t, v1t and w2."""
+    for w, name in ((w1t, "w1t"), (v1t, "v1t")):
+        if not isinstance(w, torch.Tensor) or w.dim() != 2:
+            raise ValueError(f"moe_glu_mlp_mx_train: {name} is [E * ffn, "
+                             "d_model]")
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
+                              v1t.t(), num_experts, rows)
+    _glu_mx_sinks(x, w2, (dw1t_out, dv1t_out, dw2_out),
+                  "moe_glu_mlp_mx_train")
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    y = glu_mlp_mx(xp, w1t, v1t, w2, topo, "silu" if activation is None else
+                   activation, dw1t_out, dv1t_out, dw2_out)
     return padded_scatter(y, route, expert_weights)
 
 
