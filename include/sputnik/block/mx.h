@@ -236,6 +236,51 @@
 //                    |C - exact| <= 2^-p |exact|
 //                        + (eps_fast + (2 K / 128 + 1) 2^-23) sum |terms|
 //
+// Fused gated SDD (forward of a GLU expert, either weight format):
+//
+//   SddMxGated   both products of SddMx at c's stored blocks from one read of
+//                Aq, then the gate stage and QuantizeRowsMx, in one kernel:
+//                acc_g = Aq . gate^T and acc_u = Aq . up^T, each SddMx's
+//                arithmetic (the step, the +0 accumulator input, one fp32 add
+//                per step, k ascending). `gate_q` / `up_q` and their scales
+//                are two weights of `b_format` with n = c.cols logical rows;
+//                logical row n is physical row b_row_step n of its pointer,
+//                bytes and scales alike, b_row_step 1 or 2. Two separate
+//                weights: step 1. One tensor [2 n, k] with rows 2 f = gate
+//                and 2 f + 1 = up: gate = base, up = base + one row (k or k /
+//                2 bytes; k / 32 scale bytes), step 2; nothing is copied.
+//                `c` is the topology only (c.data is not read or written).
+//                Per element, fp32 with no contraction:
+//                  G = round_T((float(round_T(acc_g)) + float(gate_bias[col]))
+//                      + 0.0f), U likewise with up_bias: bias.h's rule; a null
+//                      bias skips the add, G = round_T(acc_g), SddMx's bits.
+//                  kPlain          H = round_T(float(U) act(float(G)) + 0.0f),
+//                                  MatmulGated's stage.
+//                  kClampedSwiglu  Gc = G > limit ? limit : G
+//                                  Uc = U > limit ? limit
+//                                       : (U < -limit ? -limit : U)
+//                                  s  = 1 / (1 + exp(-t)), t = alpha Gc held
+//                                       to [-100, 100], the sigmoid as silu
+//                                       evaluates it
+//                                  H  = round_T((Uc + 1.0f) (Gc s) + 0.0f)
+//                                  (a NaN in G or U passes through the
+//                                  comparisons and makes H NaN; `activation`
+//                                  is checked, not used).
+//                hq [nnz_blocks, 128, 128] e4m3 and h_scales [nnz_blocks 128,
+//                4] are QuantizeRowsMx(kNone) of H's block values, bit for
+//                bit, the Sq / s_scales of DsdMx. keep.g / keep.u / keep.h,
+//                each null or block values of T: G, U and H as above. With no
+//                bias and kPlain, hq / h_scales / keep.g / keep.u are bit for
+//                bit SddMx, SddMx, QuantizeRowsMx(kGated). No split-K, no
+//                atomics: the same inputs give the same bits. An out-of-range
+//                index leaves its block of every output unwritten. Error of G
+//                and U before the bias: SddMx's. Besides SddMx's checks,
+//                hipErrorInvalidValue for b_row_step outside {1, 2}, a kind or
+//                activation outside its enum, limit not > 0 or alpha not
+//                finite (kClampedSwiglu), a null hq / h_scales, misalignment
+//                (Aq, the weights, hq and keep.* 16 bytes, scales 4, biases
+//                2), or an output that is an input or another output.
+//
 // `dtype` is T, the 16-bit type. Every call is stream-ordered, allocates
 // nothing and never synchronises or aborts: hipErrorInvalidValue, with nothing
 // launched, for a null required buffer, a negative size, a dimension that is
@@ -248,8 +293,8 @@
 // into SddMx's epilogue, so that D is never written; e5m2, e3m2 and e2m3
 // elements; MXFP4 activations; DDS / SSD / SDS / DSS; chaining the
 // accumulator through the MFMA; a CPU model of the instruction's internal
-// sum; caching the weights' backward layouts across micro-batches; biases; a
-// C++ example.
+// sum; caching the weights' backward layouts across micro-batches; biases
+// outside SddMxGated (the training path, SddMx, DsdMx); a C++ example.
 #ifndef SPUTNIK_BLOCK_MX_H_
 #define SPUTNIK_BLOCK_MX_H_
 
@@ -283,6 +328,33 @@ hipError_t SddMx(const void *aq, const uint8_t *a_scales, int k,
 hipError_t DsdMx(const BlockMatrix s, const uint8_t *s_scales, const void *bq,
                  const uint8_t *b_scales, MxFormat b_format, Matrix c,
                  DataType dtype, hipStream_t stream);
+
+// ---- Fused gated SDD (above). ----
+
+enum class MxGluKind { kPlain = 0, kClampedSwiglu = 1 };
+
+// `activation` is kPlain's; `alpha` and `limit` are kClampedSwiglu's.
+struct MxGlu {
+  MxGluKind kind;
+  Activation activation;
+  float alpha;
+  float limit;
+};
+
+// Block values of T to keep beside the MXFP8 image; each may be null.
+struct MxGluKeep {
+  void *g;
+  void *u;
+  void *h;
+};
+
+hipError_t SddMxGated(const void *aq, const uint8_t *a_scales, int k,
+                      const void *gate_q, const uint8_t *gate_scales,
+                      const void *up_q, const uint8_t *up_scales,
+                      int b_row_step, MxFormat b_format, const void *gate_bias,
+                      const void *up_bias, MxGlu glu, BlockMatrix c, void *hq,
+                      uint8_t *h_scales, MxGluKeep keep, DataType dtype,
+                      hipStream_t stream);
 
 // ---- Gradients (above). ----
 

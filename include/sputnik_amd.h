@@ -756,6 +756,25 @@ int sputnik_dsd_mx(const sputnik_block_matrix_t *s, const uint8_t *s_scales,
                    const void *bq, const uint8_t *b_scales, int b_format,
                    const sputnik_matrix_t *c, int dtype, void *stream);
 
+/* The fused gated MX SDD (sputnik/block/mx.h, "Fused gated SDD", has the
+ * contract): G = Aq . gate^T and U = Aq . up^T at c's stored blocks, both
+ * sputnik_sdd_mx's arithmetic, their biases (T [c.cols] or null), the gate
+ * stage (`kind` 0: U * act(G); 1: the clamped SwiGLU with `alpha` and `limit`)
+ * and the MXFP8 image of H in one kernel. Logical weight row n is physical row
+ * b_row_step n (1 or 2) of gate_q / up_q and of their scales: an interleaved
+ * [2 n, k] tensor is gate = base, up = base + one row, step 2. hq [blocks, 128,
+ * 128] e4m3 and h_scales [blocks * 128, 4] are what sputnik_dsd_mx takes;
+ * g_out / u_out / h_out are block values of T or null. c is the topology
+ * (with row_indices); c.data is unused. */
+int sputnik_sdd_mx_gated(const void *aq, const uint8_t *a_scales, int k,
+                         const void *gate_q, const uint8_t *gate_scales,
+                         const void *up_q, const uint8_t *up_scales,
+                         int b_row_step, int b_format, const void *gate_bias,
+                         const void *up_bias, int kind, int act, float alpha,
+                         float limit, const sputnik_block_matrix_t *c, void *hq,
+                         uint8_t *h_scales, void *g_out, void *u_out,
+                         void *h_out, int dtype, void *stream);
+
 /* The MX gradients' pieces (sputnik/block/mx.h, "Gradients", has the contract
  * and the table of the backward pass). Elements are e4m3.
  *

@@ -44,6 +44,11 @@ QuantizeBlocksMx, dsd_mx_pair next to two dsd_mx and a torch add, and the
 whole backward of ops.glu_mlp_mx next to those of ops.glu_mlp and of
 ops.glu_mlp_fp8 in the fast mode.
 
+With --mx --gated the arms are those of the gated expert's first product in
+the MX forward path (DESIGN "MX forward path"), per weight format:
+glu_chain_*, the three launches sdd_mx, sdd_mx and quantize_sparse_mx with the
+gate, next to glu_fused_*, ops.sdd_mx_gated over the same operands.
+
 Protocol: one process, HIP events, every arm warmed for at
 least --warm-ms of device time, then --rounds interleaved rounds, each window
 long enough to hold at least --load-ms of back-to-back calls; medians and
@@ -64,6 +69,8 @@ python scripts/bench_fp8.py [--shapes c4,decode] [--parent-lib PATH]
                             [--out profiles/fp8/bench_fp8.jsonl]
 python scripts/bench_fp8.py --mx [--parent-lib PATH]
                             [--out profiles/mx/bench_mx.jsonl]
+python scripts/bench_fp8.py --mx --gated
+                            [--out profiles/mx/bench_mx_gated.jsonl]
 python scripts/bench_fp8.py --mx --backward
                             [--out profiles/mx/bench_mx_grad.jsonl]
 python scripts/bench_fp8.py --glu [--out profiles/fp8/bench_fp8_glu.jsonl]
@@ -101,6 +108,9 @@ def main():
                     help="time the MX products beside bf16 and fast fp8")
     ap.add_argument("--glu", action="store_true",
                     help="time the gated expert's backward pass")
+    ap.add_argument("--gated", action="store_true",
+                    help="with --mx: time the fused gated SDD next to its "
+                         "three-launch chain")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -333,6 +343,23 @@ def main():
                                                           topo, "silu"),
                     x, w1t, v1t, w2),
             }
+        if a.mx and a.gated:
+            v1 = rand(D_MODEL, hidden, scale=1 / 64)
+            mq, ms = ops.quantize_rows_mx(x)
+            arms = {}
+            for f in ("e4m3", "e2m1"):
+                gw = ops.quantize_weight_mx(w1, format=f)
+                uw = ops.quantize_weight_mx(v1, format=f)
+
+                def chain(gw=gw, uw=uw):
+                    g = ops.sdd_mx(mq, ms, gw, topo, dt)
+                    u = ops.sdd_mx(mq, ms, uw, topo, dt)
+                    return ops.quantize_sparse_mx(u, "silu", gate=g)
+                arms[f"glu_chain_{f}"] = chain
+                arms[f"glu_fused_{f}"] = (
+                    lambda w=ops.MxGluWeight(gw, uw): ops.sdd_mx_gated(
+                        mq, ms, w, topo, "silu", out_dtype=dt))
+            del v1
         calls = {}
         for name, fn in arms.items():
             fn()
@@ -389,7 +416,12 @@ def main():
                 arm["hbm_share"] = round(tbs / HBM_TBS, 3)
             line["arms"][name] = arm
         us = {name: arm["us"] for name, arm in line["arms"].items()}
-        if a.glu:
+        if a.mx and a.gated:
+            line["pass"] = "mx gated forward"
+            for f in ("e4m3", "e2m1"):
+                line[f"glu_fused_{f}_over_chain"] = round(
+                    us[f"glu_fused_{f}"] / us[f"glu_chain_{f}"], 3)
+        elif a.glu:
             line["pass"] = "glu backward"
             for fused in ("gated_grad", "pair"):
                 line[f"{fused}_fused_over_composed"] = round(
@@ -419,7 +451,8 @@ def main():
             for name in ("mlp_fp8_backward", "mlp_fp8_fast_backward"):
                 line[f"{name}_over_bf16"] = round(
                     us[name] / us["mlp_bf16_backward"], 3)
-        for op in ("sdd", "dsd") if a.mx and not a.backward else ():
+        for op in (("sdd", "dsd") if a.mx and not a.backward and not a.gated
+                   else ()):
             for f in ("e4m3", "e2m1"):
                 for base in ("bf16", "fp8_fast"):
                     line[f"{op}_mx_{f}_over_{base}"] = round(

@@ -281,6 +281,13 @@ _SIGNATURES = {
     "sputnik_sdd_mx": [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P,
                        ctypes.c_int, _P],
     "sputnik_dsd_mx": [_P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_int, _P],
+    # the fused gated SDD: (aq, a_scales, k, gate_q, gate_scales, up_q,
+    # up_scales, b_row_step, b_format, gate_bias, up_bias, kind, act, alpha,
+    # limit, c, hq, h_scales, g_out, u_out, h_out, dtype, stream)
+    "sputnik_sdd_mx_gated": [_P, _P, ctypes.c_int, _P, _P, _P, _P,
+                             ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int,
+                             ctypes.c_int, ctypes.c_float, ctypes.c_float]
+    + [_P] * 6 + [ctypes.c_int, _P],
     # their gradients' pieces: (x, rows, cols, q, scales, qt, scales_t, dtype,
     # stream); (s, stage, act, z, q, scales, qt, scales_t, dtype, stream); (s,
     # s_scales, bq, b_scales, c, out, add, dtype, stream)
@@ -2294,6 +2301,81 @@ def SddMx(aq, a_scales, bq, b_scales, c, format="e4m3", stream=None):  # noqa: N
         ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "SddMx")
 
 
+def _mx_rows(q, scales, step: int, code: int, what: str):
+    """(n, k) of the logical weight SddMxGated reads through `q` / `scales`
+    with row step `step`: a contiguous weight of n rows (step 1), or the view
+    base[0::2] / base[1::2] of a contiguous [2 n, ...] tensor (step 2), whose
+    first element is the pointer passed and whose rows lie two rows apart."""
+    import torch
+
+    want = torch.uint8 if code else torch.float8_e4m3fn
+    for t, dt, name in ((q, want, "q"), (scales, torch.uint8, "scales")):
+        if getattr(t, "dtype", None) != dt or t.dim() != 2:
+            raise TypeError(f"{what}: {name} must be a 2-D {dt} tensor")
+        if t.stride(1) != 1 or t.stride(0) != step * int(t.shape[1]):
+            raise ValueError(f"{what}: {name} must have rows {step} row(s) "
+                             "apart and contiguous")
+    n, k = int(q.shape[0]), int(q.shape[1]) * (2 if code else 1)
+    _fp8_tiles(n, f"{what}: n")
+    _fp8_tiles(k, f"{what}: k")
+    if tuple(scales.shape) != (n, k // 32):
+        raise ValueError(f"{what}: scales have shape {tuple(scales.shape)}, "
+                         f"expected {(n, k // 32)}")
+    return n, k
+
+
+def SddMxGated(aq, a_scales, gate_q, gate_scales, up_q, up_scales, c, hq,  # noqa: N802
+               h_scales, format="e4m3", activation="silu", clamp=None,
+               gate_bias=None, up_bias=None, g_out=None, u_out=None,
+               h_out=None, b_row_step=1, stream=None):
+    """The fused gated MX SDD (sputnik_sdd_mx_gated; sputnik/block/mx.h): G =
+    Aq . gate^T and U = Aq . up^T at c's stored blocks as SddMx computes them,
+    plus their biases (c.data's dtype, [c.cols]), then H = U * act(G) or, with
+    `clamp` = (alpha, limit), the clamped SwiGLU, quantised into hq (e4m3
+    [blocks, 128, 128]) and h_scales (uint8 [blocks * 128, 4]), DsdMx's
+    operand. gate_q / up_q with their scales are two MX weights of `format`
+    (b_row_step 1) or the views base[0::2] / base[1::2] of one interleaved
+    tensor (b_row_step 2). g_out / u_out / h_out, block values like c.data,
+    receive G, U and H when given. c is the topology (with row_indices); its
+    data tensor only fixes the 16-bit type."""
+    import torch
+
+    if not isinstance(c, BlockMatrix):
+        raise TypeError("SddMxGated takes the topology as a BlockMatrix")
+    if b_row_step not in (1, 2):
+        raise ValueError("SddMxGated: b_row_step is 1 or 2")
+    code = _mx_format(format, "SddMxGated")
+    n, k = _mx_rows(gate_q, gate_scales, b_row_step, code, "SddMxGated: gate")
+    if _mx_rows(up_q, up_scales, b_row_step, code, "SddMxGated: up") != (n, k):
+        raise ValueError("SddMxGated: gate and up differ in shape")
+    if n != c.cols:
+        raise ValueError(f"SddMxGated: the weights have {n} rows, C {c.cols} "
+                         "columns")
+    dtype = c.data.dtype
+    code_t = _dtype_code(c.data)
+    nb = c.num_blocks
+    _fp8_buffer(aq, torch.float8_e4m3fn, (c.rows, k), "aq")
+    _fp8_buffer(a_scales, torch.uint8, (c.rows, k // 32), "a_scales")
+    _fp8_buffer(hq, torch.float8_e4m3fn, (nb, 128, 128), "hq")
+    _fp8_buffer(h_scales, torch.uint8, (nb * 128, 4), "h_scales")
+    for t, name in ((gate_bias, "gate_bias"), (up_bias, "up_bias")):
+        if t is not None:
+            _fp8_buffer(t, dtype, (c.cols,), name)
+    for t, name in ((g_out, "g_out"), (u_out, "u_out"), (h_out, "h_out")):
+        if t is not None:
+            _fp8_buffer(t, dtype, (nb, 128, 128), name)
+    kind, alpha, limit = 0, 0.0, 0.0
+    if clamp is not None:
+        kind, (alpha, limit) = 1, (float(v) for v in clamp)
+    cc = c._c()
+    _check(lib().sputnik_sdd_mx_gated(
+        _ptr(aq), _ptr(a_scales), k, _ptr(gate_q), _ptr(gate_scales),
+        _ptr(up_q), _ptr(up_scales), b_row_step, code, _ptr(gate_bias),
+        _ptr(up_bias), kind, _act_code(activation), alpha, limit,
+        ctypes.byref(cc), _ptr(hq), _ptr(h_scales), _ptr(g_out), _ptr(u_out),
+        _ptr(h_out), code_t, _stream(stream)), "SddMxGated")
+
+
 def DsdMx(s, s_scales, bq, b_scales, c, format="e4m3", stream=None):  # noqa: N802
     """C (Matrix of fp16 / bf16, [s.rows, n]) = Sq . Bq: s a BlockMatrix whose
     data holds e4m3 block values with s_scales uint8 [blocks * 128, 4]
@@ -2506,6 +2588,7 @@ def DsdMxPair(s1, s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q,  # noqa: N
 
 __all__ = [
     "QuantizeRowsMx", "QuantizeWeightMx", "SddMx", "DsdMx", "MX_FORMATS",
+    "SddMxGated",
     "QuantizeTilesMx", "QuantizeBlocksMx", "DsdMxWgrad",
     "QuantizeBlocksMxGated", "QuantizeBlocksMxGatedGrad", "DsdMxPair",
     "AllocateBitmaskBuffers", "AllocateRowIndicesBuffer",

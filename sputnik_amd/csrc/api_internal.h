@@ -178,6 +178,22 @@ hipError_t LaunchMxPair(int dtype, const void *s1, const uint8_t *s1_scales,
                         const int *offsets, const short *indices, int m_blocks,
                         int n_blocks, int k_blocks, int nnz_blocks,
                         hipStream_t stream);
+// The fused gated MX SDD (SddMxGated, mx_gated_gemm.hip), arguments already
+// validated (block_api.cpp): a as LaunchMxGemm's SDD; gate / up and their
+// scales two weights whose logical row n is physical row b_row_step n; the
+// biases T [n] or null; `clamped` selects the clamped SwiGLU (alpha, limit)
+// over `act`; hq / h_scales the MXFP8 image of H, g_out / u_out / h_out block
+// values of T or null.
+hipError_t LaunchMxGated(bool b4, int dtype, const void *a,
+                         const uint8_t *a_scales, const void *gate,
+                         const uint8_t *gate_scales, const void *up,
+                         const uint8_t *up_scales, int b_row_step,
+                         const void *gate_bias, const void *up_bias,
+                         bool clamped, int act, float alpha, float limit,
+                         void *hq, uint8_t *h_scales, void *g_out, void *u_out,
+                         void *h_out, const short *indices,
+                         const short *row_indices, int m_blocks, int n_blocks,
+                         int k_blocks, int nnz_blocks, hipStream_t stream);
 
 // Per-(current device, stream) registration of caller memory (ptr null:
 // unregister); the plain entry points look it up.

@@ -1,5 +1,6 @@
 // sputnik-amd: the sputnik::block C++ overload set (drop-in for the
 // reference's), over the Run* entry points of dispatch.cpp.
+#include <cmath>
 #include <cstdint>
 #include <initializer_list>
 
@@ -587,6 +588,59 @@ hipError_t SddMx(const void *aq, const uint8_t *a_scales, int k,
   return sputnik_amd::LaunchMxGemm(
       false, b_format == MxFormat::kE2M1, (int)dtype, aq, a_scales, bq,
       b_scales, c.data, nullptr, static_cast<const short *>(c.indices),
+      static_cast<const short *>(c.row_indices), c.rows / 128, c.cols / 128,
+      k / 128, c.nonzeros / (128 * 128), stream);
+}
+
+hipError_t SddMxGated(const void *aq, const uint8_t *a_scales, int k,
+                      const void *gate_q, const uint8_t *gate_scales,
+                      const void *up_q, const uint8_t *up_scales,
+                      int b_row_step, MxFormat b_format, const void *gate_bias,
+                      const void *up_bias, MxGlu glu, BlockMatrix c, void *hq,
+                      uint8_t *h_scales, MxGluKeep keep, DataType dtype,
+                      hipStream_t stream) {
+  if (!MxFormatOk(b_format) || (b_row_step != 1 && b_row_step != 2))
+    return hipErrorInvalidValue;
+  if (glu.kind != MxGluKind::kPlain && glu.kind != MxGluKind::kClampedSwiglu)
+    return hipErrorInvalidValue;
+  if (glu.activation != Activation::kRelu &&
+      glu.activation != Activation::kGelu &&
+      glu.activation != Activation::kSilu)
+    return hipErrorInvalidValue;
+  if (glu.kind == MxGluKind::kClampedSwiglu &&
+      (!(glu.limit > 0.0f) || !std::isfinite(glu.alpha)))
+    return hipErrorInvalidValue;
+  if (!Fp8SizesOk(c, k, (int)dtype)) return hipErrorInvalidValue;
+  if (c.nonzeros == 0) return hipSuccess;
+  if (c.indices == nullptr || c.row_indices == nullptr || hq == nullptr ||
+      h_scales == nullptr ||
+      (k > 0 && (aq == nullptr || a_scales == nullptr || gate_q == nullptr ||
+                 gate_scales == nullptr || up_q == nullptr ||
+                 up_scales == nullptr)))
+    return hipErrorInvalidValue;
+  const void *outs[] = {hq, h_scales, keep.g, keep.u, keep.h};
+  for (int i = 0; i < 5; ++i) {
+    if (outs[i] == nullptr) continue;
+    for (const void *in : {aq, (const void *)a_scales, gate_q,
+                           (const void *)gate_scales, up_q,
+                           (const void *)up_scales, gate_bias, up_bias,
+                           (const void *)c.indices,
+                           (const void *)c.row_indices})
+      if (outs[i] == in) return hipErrorInvalidValue;
+    for (int j = 0; j < i; ++j)
+      if (outs[i] == outs[j]) return hipErrorInvalidValue;
+  }
+  if (!Aligned16({aq, gate_q, up_q, hq, keep.g, keep.u, keep.h}) ||
+      !Aligned4({a_scales, gate_scales, up_scales, h_scales}) ||
+      ((reinterpret_cast<uintptr_t>(gate_bias) |
+        reinterpret_cast<uintptr_t>(up_bias)) & 1) != 0)
+    return hipErrorInvalidValue;
+  return sputnik_amd::LaunchMxGated(
+      b_format == MxFormat::kE2M1, (int)dtype, aq, a_scales, gate_q,
+      gate_scales, up_q, up_scales, b_row_step, gate_bias, up_bias,
+      glu.kind == MxGluKind::kClampedSwiglu, (int)glu.activation, glu.alpha,
+      glu.limit, hq, h_scales, keep.g, keep.u, keep.h,
+      static_cast<const short *>(c.indices),
       static_cast<const short *>(c.row_indices), c.rows / 128, c.cols / 128,
       k / 128, c.nonzeros / (128 * 128), stream);
 }

@@ -843,6 +843,24 @@ int sputnik_dsd_mx(const sputnik_block_matrix_t *s, const uint8_t *s_scales,
       static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
 }
 
+int sputnik_sdd_mx_gated(const void *aq, const uint8_t *a_scales, int k,
+                         const void *gate_q, const uint8_t *gate_scales,
+                         const void *up_q, const uint8_t *up_scales,
+                         int b_row_step, int b_format, const void *gate_bias,
+                         const void *up_bias, int kind, int act, float alpha,
+                         float limit, const sputnik_block_matrix_t *c, void *hq,
+                         uint8_t *h_scales, void *g_out, void *u_out,
+                         void *h_out, int dtype, void *stream) {
+  if (!c) return hipErrorInvalidValue;
+  return sputnik::block::SddMxGated(
+      aq, a_scales, k, gate_q, gate_scales, up_q, up_scales, b_row_step,
+      static_cast<sputnik::block::MxFormat>(b_format), gate_bias, up_bias,
+      {static_cast<sputnik::block::MxGluKind>(kind),
+       static_cast<sputnik::block::Activation>(act), alpha, limit},
+      ToCpp(c), hq, h_scales, {g_out, u_out, h_out},
+      static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
+}
+
 // ... and their gradients' pieces.
 int sputnik_quantize_tiles_mx(const void *x, int rows, int cols, void *q,
                               uint8_t *scales, void *qt, uint8_t *scales_t,

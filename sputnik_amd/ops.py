@@ -66,6 +66,11 @@ gradient sink.
 The MX path of a gated expert (mx.h, "Gradients of a gated expert") is
 `glu_mlp_mx(x, w1t, v1t, w2, topo, activation)` and `moe_glu_mlp_mx_train`
 around it; its dX is `dsd_mx_pair`, two MX products through one accumulator.
+The MX forward path of a gated expert in one kernel is `sdd_mx_gated(xq, xs,
+w, topo, activation)` over an `MxGluWeight` (two MxWeights, or one interleaved
+[2 n, k] checkpoint tensor used as it is), with the projections' biases and
+the clamped SwiGLU (`clamp=(alpha, limit)`) in its epilogue; `moe_glu_mx` is
+the layer around it.
 Every product runs on
 libsputnik.so through the C-ABI on the current torch stream; there is no
 dense or CPU fallback (a missing library raises).
@@ -98,7 +103,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                QuantizeTiles, QuantizeBlocks, TransposeWeightFp8, DsdFp8Wgrad,
                QuantizeBlocksGated, QuantizeBlocksGatedGrad, DsdFp8Pair,
                QuantizeRowsMx, QuantizeWeightMx, SddMx, DsdMx, MX_FORMATS,
-               QuantizeTilesMx, QuantizeBlocksMx, DsdMxWgrad,
+               SddMxGated, QuantizeTilesMx, QuantizeBlocksMx, DsdMxWgrad,
                QuantizeBlocksMxGated, QuantizeBlocksMxGatedGrad, DsdMxPair,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
                RouterTopKAuxGrad, RouterTopKGrad, RowIndices, Transpose,
@@ -1862,6 +1867,152 @@ def moe_mlp_mx(x: torch.Tensor, top_experts: torch.Tensor,
         u = sdd_mx(xq, xs, v1q, topo, x.dtype)
         hq = quantize_sparse_mx(u, "silu" if act is None else act, gate=g)
     return padded_scatter(dsd_mx(hq, w2q, x.dtype), route, expert_weights)
+
+
+class MxGluWeight:
+    """The gate and up projections [k, n] of a GLU expert layer in one MX
+    format, as sdd_mx_gated reads them: `MxGluWeight(gate, up)` from two
+    MxWeights of equal shape and format, or `from_interleaved` from one
+    checkpoint tensor whose rows alternate gate, up. Nothing is copied:
+    `row_step` (1 or 2) is the distance of consecutive logical rows in
+    `gate_q` / `up_q` and their scales."""
+
+    def __init__(self, gate: MxWeight, up: MxWeight):
+        if not isinstance(gate, MxWeight) or not isinstance(up, MxWeight):
+            raise TypeError("MxGluWeight: gate and up are MxWeights")
+        if gate.shape != up.shape or gate.format != up.format:
+            raise ValueError(f"MxGluWeight: gate {gate.shape} {gate.format} "
+                             f"and up {up.shape} {up.format} differ")
+        self.gate_q, self.gate_scales = gate.q, gate.scales
+        self.up_q, self.up_scales = up.q, up.scales
+        self.k, self.n, self.format, self.row_step = (gate.k, gate.n,
+                                                      gate.format, 1)
+
+    @property
+    def shape(self):
+        return (self.k, self.n)
+
+    def dim(self) -> int:
+        return 2
+
+    @classmethod
+    def from_interleaved(cls, q: torch.Tensor, scales: torch.Tensor,
+                         format: str = "e4m3") -> "MxGluWeight":
+        """One tensor `q` [2 n, k] (e2m1: [2 n, k / 2]) with `scales` [2 n,
+        k / 32], row 2 f the gate row and row 2 f + 1 the up row of hidden
+        column f, the experts concatenated along the rows: the gpt-oss
+        layout. Dtypes as MxWeight.from_tensors; the tensor is held as it
+        is."""
+        both = MxWeight.from_tensors(q, scales, format)
+        if both.n % (2 * BLOCK):
+            raise ValueError(f"MxGluWeight: {both.n} interleaved rows are not "
+                             "twice a multiple of 128")
+        self = cls.__new__(cls)
+        self.gate_q, self.up_q = both.q[0::2], both.q[1::2]
+        self.gate_scales, self.up_scales = both.scales[0::2], both.scales[1::2]
+        self.k, self.n, self.format, self.row_step = (both.k, both.n // 2,
+                                                      format, 2)
+        return self
+
+
+def _clamp(clamp, what: str):
+    """`clamp` as (alpha, limit) floats, or None."""
+    if clamp is None:
+        return None
+    try:
+        alpha, limit = (float(v) for v in clamp)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: clamp is an (alpha, limit) pair") from None
+    if not math.isfinite(alpha) or not limit > 0.0:
+        raise ValueError(f"{what}: clamp needs a finite alpha and a limit > "
+                         f"0, not {clamp!r}")
+    return alpha, limit
+
+
+def sdd_mx_gated(xq: torch.Tensor, xs: torch.Tensor, w: MxGluWeight,
+                 topo: SparseMatrix, activation="silu", *, clamp=None,
+                 b1: Optional[torch.Tensor] = None,
+                 bv1: Optional[torch.Tensor] = None, keep: bool = False,
+                 out_dtype=torch.bfloat16):
+    """The MXFP8 image of H = U * act(G) at topo's nonzero blocks, G = xq .
+    gate + b1 and U = xq . up + bv1, from one kernel: sdd_mx twice,
+    the biases as sdd_bias adds them, and quantize_sparse_mx(u, activation,
+    gate=g), with neither G nor U written (`keep`: also returns them, (hq, g,
+    u)). With `clamp` = (alpha, limit) H is the clamped SwiGLU (min(U, limit)
+    clamped below at -limit, + 1) * g' * sigmoid(alpha g'), g' = min(G,
+    limit), gpt-oss's with (1.702, 7.0). `b1` / `bv1` are [n] of `out_dtype`,
+    the type G, U and H are rounded to. Without biases and clamp the bits are
+    the three-call chain's. Forward only."""
+    if not isinstance(w, MxGluWeight):
+        raise TypeError("sdd_mx_gated: w must be an MxGluWeight")
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError("sdd_mx_gated: topo must be a SparseMatrix (not a "
+                        ".t() view)")
+    _out_dtype(out_dtype, "sdd_mx_gated")
+    act = _act_code(activation)
+    clamp = _clamp(clamp, "sdd_mx_gated")
+    if (not isinstance(xq, torch.Tensor) or xq.dim() != 2
+            or (int(xq.shape[0]), w.n) != tuple(topo.shape)
+            or int(xq.shape[1]) != w.k):
+        raise ValueError(f"sdd_mx_gated shapes "
+                         f"{tuple(getattr(xq, 'shape', ()))} x {w.shape} -> "
+                         f"{topo.shape}")
+    for name, b in (("b1", b1), ("bv1", bv1)):
+        if b is not None:
+            if (not isinstance(b, torch.Tensor) or b.dtype != out_dtype
+                    or tuple(b.shape) != (w.n,)):
+                raise ValueError(f"sdd_mx_gated: {name} must be [{w.n}] of "
+                                 f"{out_dtype}")
+            _no_grad("sdd_mx_gated", b)
+    b1 = None if b1 is None else b1.contiguous()
+    bv1 = None if bv1 is None else bv1.contiguous()
+    nb, dev = topo.nnz_blocks, xq.device
+    hq = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn, device=dev)
+    hs = torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=dev)
+    g = u = None
+    if keep:
+        g = torch.empty(nb, BLOCK, BLOCK, dtype=out_dtype, device=dev)
+        u = torch.empty_like(g)
+    # (the descriptor's data tensor names the 16-bit type; it is not written)
+    kind = g if keep else torch.empty(0, dtype=out_dtype, device=dev)
+    topo._meta.ensure_row_indices(kind)
+    SddMxGated(xq, xs, w.gate_q, w.gate_scales, w.up_q, w.up_scales,
+               topo._meta.descriptor(kind), hq, hs, w.format, act, clamp, b1,
+               bv1, g, u, None, w.row_step)
+    h = MxSparseMatrix(topo, hq, hs)
+    return (h, topo.with_data(g), topo.with_data(u)) if keep else h
+
+
+def moe_glu_mx(x: torch.Tensor, top_experts: torch.Tensor,
+               expert_weights: torch.Tensor, w1v1: MxGluWeight, w2q: MxWeight,
+               num_experts: int, activation="silu",
+               rows: Optional[int] = None, *, clamp=None,
+               b1: Optional[torch.Tensor] = None,
+               bv1: Optional[torch.Tensor] = None,
+               b2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A GLU MoE layer with MX expert products and the fused first product:
+    padded_gather -> quantize_rows_mx -> sdd_mx_gated with `w1v1` -> dsd_mx
+    with `w2q` -> padded_scatter_bias. `b1` / `bv1` [E * ffn] are the biases
+    of the gate and up projections, `b2` [E, d_model] the output bias, `clamp`
+    as sdd_mx_gated has it: a gpt-oss layer is from_interleaved weights, all
+    three biases and clamp=(1.702, 7.0). Forward only."""
+    _no_grad("moe_glu_mx", x, expert_weights, b1, bv1, b2)
+    if not isinstance(w1v1, MxGluWeight):
+        raise TypeError("moe_glu_mx: w1v1 must be an MxGluWeight")
+    w1 = MxWeight(w1v1.gate_q, w1v1.gate_scales, w1v1.k, w1v1.n, w1v1.format)
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1, w2q, None,
+                              num_experts, rows, mx=True)
+    _check_moe_biases(x, w1, w1, num_experts, (b1, bv1, b2), "moe_glu_mx")
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    xq, xs = quantize_rows_mx(xp)
+    hq = sdd_mx_gated(xq, xs, w1v1, topo, activation, clamp=clamp, b1=b1,
+                      bv1=bv1, out_dtype=x.dtype)
+    return padded_scatter_bias(dsd_mx(hq, w2q, x.dtype), route,
+                               expert_weights, bias=b2)
 
 
 # ---- FP8 gradients (sputnik/block/fp8.h, "Gradients") ------------------------
