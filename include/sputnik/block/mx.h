@@ -49,7 +49,8 @@
 //           `b_format`; m = c.rows, n = c.cols.
 //   DsdMx   C [m, n] (T) = Sq (BCSR, e4m3 bytes in s.data) . Bq: s_scales
 //           [nnz_blocks 128, 4] as QuantizeRowsMx leaves them, k = s.cols.
-//   A / S is always e4m3. Shapes, index checks, the skipping of out-of-range
+//   A / S is e4m3 in these two ("MXFP4 activations", below, has the e2m1 A /
+//   S). Shapes, index checks, the skipping of out-of-range
 //   blocks, +0 rows for empty block rows and alias rejection follow SddFp8 /
 //   DsdFp8; Aq / Sq / Bq / C are 16-byte and the scale arrays 4-byte aligned
 //   (a step's four scale bytes of a row are fetched as one dword).
@@ -281,6 +282,51 @@
 //                (Aq, the weights, hq and keep.* 16 bytes, scales 4, biases
 //                2), or an output that is an input or another output.
 //
+// MXFP4 activations (A4W4: both operands e2m1, the form of the instruction
+// with half the passes of any form that has an fp8 operand; forward only):
+//
+//   QuantizeRowsMxFp4  QuantizeRowsMx with e2m1 elements: x [rows, cols] of T,
+//                cols a multiple of 128 -> q [rows, cols / 2] bytes, two codes
+//                per byte, low nibble first, and scales uint8 [rows, cols /
+//                32]. Scale, element and non-finite rules are the e2m1 rules
+//                above (QuantizeWeightMx's): a non-finite element turns its
+//                block's scale byte into 0xFF and the block's codes into 0.
+//                The stages evaluate H exactly as QuantizeRowsMx does, rounded
+//                to T before it is quantised. Block values go in as
+//                [nnz_blocks 128, 128]: q [nnz_blocks, 128, 64] and one scale
+//                dword per stored-block row. Any alignment.
+//   SddMxFp4     SddMx with Aq [m, k / 2] e2m1 bytes.
+//   DsdMxFp4     DsdMx with s.data [nnz_blocks, 128, 64] e2m1 bytes, s_scales
+//                [nnz_blocks 128, 4] (s.nonzeros still counts elements: 128 x
+//                128 per stored block).
+//   B is always an e2m1 weight, as QuantizeWeightMx(kE2M1) or a checkpoint
+//   leaves it; there is no e2m1 A against an e4m3 B. The arithmetic is the one
+//   above, unchanged: per k-block of 128, P is the instruction's result from
+//   a +0 accumulator (cbsz 4, blgp 4), lane (r, g) passing k = 32 g .. 32 g +
+//   31 of its row / column in registers 0 - 3 and scale byte g, for both
+//   operands; acc = acc + P, one fp32 add per k-block in k order (SDD) or the
+//   row's storage order (DSD); C = round_T(acc), rounded once. No split-K, no
+//   atomics: the same inputs give the same bits, and SDD on a full topology
+//   and DSD over the same bytes give the same bits. A 0xFF scale byte of A /
+//   S makes NaN exactly its row of the step's tile, one of B exactly its
+//   column. Shape and index checks, the skipping of out-of-range blocks, +0
+//   rows for empty block rows, alias rejection and the alignments (operands
+//   and C 16 bytes, scales 4) are SddMx / DsdMx's.
+//   Error: the bound above with eps_fast. Every e2m1 value is an e4m3 value
+//   and the scales are the same e8m0, so the characterised families cover
+//   these operands, provided the fp4 form of the instruction sums as the fp8
+//   form does. Measured on SddMxFp4 / DsdMxFp4 (tests/test_gpu_mx_fp4.py, K =
+//   640, bytes quantised from normal data with block scales over 16 binades,
+//   the rounding to T beyond 2^-p |exact| left out): worst |C - exact| / sum
+//   |terms| 0 for SDD (fp16 and bf16) and for DSD in bf16 (an earlier draw of
+//   the same family gave 2^-26.2 and 2^-29.5), and 2^-9.9 for DSD in fp16,
+//   which is no accumulation error: block rows with one or two stored blocks
+//   under small scales give results in fp16's subnormal range, and round_fp16
+//   of the exact result alone gives the same 2^-9.90 on the host. An e2m1 x
+//   e2m1 product has two significant bits, and the fp4 form lost nothing
+//   measurable beside what fp32 adds lose: it sums no worse than the fp8 form.
+//   The tests assert eps_fast / 2 = 2^-8 on their data.
+//
 // `dtype` is T, the 16-bit type. Every call is stream-ordered, allocates
 // nothing and never synchronises or aborts: hipErrorInvalidValue, with nothing
 // launched, for a null required buffer, a negative size, a dimension that is
@@ -291,10 +337,11 @@
 //
 // Out of scope: the backward of MXFP4 weights; folding the gated gradient
 // into SddMx's epilogue, so that D is never written; e5m2, e3m2 and e2m3
-// elements; MXFP4 activations; DDS / SSD / SDS / DSS; chaining the
-// accumulator through the MFMA; a CPU model of the instruction's internal
-// sum; caching the weights' backward layouts across micro-batches; biases
-// outside SddMxGated (the training path, SddMx, DsdMx); a C++ example.
+// elements; the backward pass with e2m1 operands; an e2m1-A variant of
+// SddMxGated; biases on the MXFP4-activation path; DDS / SSD / SDS / DSS;
+// chaining the accumulator through the MFMA; a CPU model of the instruction's
+// internal sum; caching the weights' backward layouts across micro-batches;
+// biases outside SddMxGated (the training path, SddMx, DsdMx); a C++ example.
 #ifndef SPUTNIK_BLOCK_MX_H_
 #define SPUTNIK_BLOCK_MX_H_
 
@@ -328,6 +375,21 @@ hipError_t SddMx(const void *aq, const uint8_t *a_scales, int k,
 hipError_t DsdMx(const BlockMatrix s, const uint8_t *s_scales, const void *bq,
                  const uint8_t *b_scales, MxFormat b_format, Matrix c,
                  DataType dtype, hipStream_t stream);
+
+// ---- MXFP4 activations (above). ----
+
+hipError_t QuantizeRowsMxFp4(const void *x, const void *gate, int rows,
+                             int cols, MxStage stage, Activation activation,
+                             void *q, uint8_t *scales, DataType dtype,
+                             hipStream_t stream);
+
+hipError_t SddMxFp4(const void *aq, const uint8_t *a_scales, int k,
+                    const void *bq, const uint8_t *b_scales, BlockMatrix c,
+                    DataType dtype, hipStream_t stream);
+
+hipError_t DsdMxFp4(const BlockMatrix s, const uint8_t *s_scales,
+                    const void *bq, const uint8_t *b_scales, Matrix c,
+                    DataType dtype, hipStream_t stream);
 
 // ---- Fused gated SDD (above). ----
 

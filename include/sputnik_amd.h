@@ -756,6 +756,31 @@ int sputnik_dsd_mx(const sputnik_block_matrix_t *s, const uint8_t *s_scales,
                    const void *bq, const uint8_t *b_scales, int b_format,
                    const sputnik_matrix_t *c, int dtype, void *stream);
 
+/* MXFP4 activations (sputnik/block/mx.h, "MXFP4 activations"): the calls
+ * above with an e2m1 A / S against an e2m1 weight, both operands on the FP4
+ * form of the matrix instruction. Forward only.
+ *
+ *   sputnik_quantize_rows_mx_fp4  as sputnik_quantize_rows_mx -> q [rows,
+ *                                 cols / 2] bytes, two e2m1 codes each, low
+ *                                 nibble first; scales uint8 [rows, cols / 32]
+ *                                 (0xFF for a block with a non-finite element)
+ *   sputnik_sdd_mx_fp4   sputnik_sdd_mx with aq [c.rows, k / 2]
+ *   sputnik_dsd_mx_fp4   sputnik_dsd_mx with s.data [blocks, 128, 64] bytes
+ *
+ * bq / b_scales are a weight of format 1 (e2m1). Arithmetic, order, checks and
+ * alignments as sputnik_sdd_mx / sputnik_dsd_mx. */
+int sputnik_quantize_rows_mx_fp4(const void *x, const void *gate, int rows,
+                                 int cols, int stage, int act, void *q,
+                                 uint8_t *scales, int dtype, void *stream);
+int sputnik_sdd_mx_fp4(const void *aq, const uint8_t *a_scales, int k,
+                       const void *bq, const uint8_t *b_scales,
+                       const sputnik_block_matrix_t *c, int dtype,
+                       void *stream);
+int sputnik_dsd_mx_fp4(const sputnik_block_matrix_t *s,
+                       const uint8_t *s_scales, const void *bq,
+                       const uint8_t *b_scales, const sputnik_matrix_t *c,
+                       int dtype, void *stream);
+
 /* The fused gated MX SDD (sputnik/block/mx.h, "Fused gated SDD", has the
  * contract): G = Aq . gate^T and U = Aq . up^T at c's stored blocks, both
  * sputnik_sdd_mx's arithmetic, their biases (T [c.cols] or null), the gate

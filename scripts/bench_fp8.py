@@ -49,6 +49,11 @@ the MX forward path (DESIGN "MX forward path"), per weight format:
 glu_chain_*, the three launches sdd_mx, sdd_mx and quantize_sparse_mx with the
 gate, next to glu_fused_*, ops.sdd_mx_gated over the same operands.
 
+With --mx --fp4 the arms are those of the MXFP4-activation path (DESIGN "MX
+forward path", A4W4): sdd_mx_fp4 and dsd_mx_fp4 next to sdd_mx and dsd_mx
+with the same MXFP4 weights (the route those weights took before), and
+quantize_rows_mx_fp4 next to quantize_rows_mx.
+
 Protocol: one process, HIP events, every arm warmed for at
 least --warm-ms of device time, then --rounds interleaved rounds, each window
 long enough to hold at least --load-ms of back-to-back calls; medians and
@@ -71,6 +76,8 @@ python scripts/bench_fp8.py --mx [--parent-lib PATH]
                             [--out profiles/mx/bench_mx.jsonl]
 python scripts/bench_fp8.py --mx --gated
                             [--out profiles/mx/bench_mx_gated.jsonl]
+python scripts/bench_fp8.py --mx --fp4
+                            [--out profiles/mx/bench_mx_fp4.jsonl]
 python scripts/bench_fp8.py --mx --backward
                             [--out profiles/mx/bench_mx_grad.jsonl]
 python scripts/bench_fp8.py --glu [--out profiles/fp8/bench_fp8_glu.jsonl]
@@ -111,6 +118,9 @@ def main():
     ap.add_argument("--gated", action="store_true",
                     help="with --mx: time the fused gated SDD next to its "
                          "three-launch chain")
+    ap.add_argument("--fp4", action="store_true",
+                    help="with --mx: time the MXFP4-activation products and "
+                         "quantiser next to the MXFP8-activation ones")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -360,6 +370,21 @@ def main():
                     lambda w=ops.MxGluWeight(gw, uw): ops.sdd_mx_gated(
                         mq, ms, w, topo, "silu", out_dtype=dt))
             del v1
+        if a.mx and a.fp4:
+            m1, m2 = (ops.quantize_weight_mx(w, format="e2m1")
+                      for w in (w1, w2))
+            mq, ms = ops.quantize_rows_mx(x)
+            fq, fs = ops.quantize_rows_mx_fp4(x)
+            hmx = ops.quantize_sparse_mx(g16, "gelu")
+            hfp4 = ops.quantize_sparse_mx_fp4(g16, "gelu")
+            arms = {
+                "sdd_mx_e2m1": lambda: ops.sdd_mx(mq, ms, m1, topo, dt),
+                "sdd_mx_fp4": lambda: ops.sdd_mx_fp4(fq, fs, m1, topo, dt),
+                "dsd_mx_e2m1": lambda: ops.dsd_mx(hmx, m2, dt),
+                "dsd_mx_fp4": lambda: ops.dsd_mx_fp4(hfp4, m2, dt),
+                "quantize_rows_mx": lambda: ops.quantize_rows_mx(x),
+                "quantize_rows_mx_fp4": lambda: ops.quantize_rows_mx_fp4(x),
+            }
         calls = {}
         for name, fn in arms.items():
             fn()
@@ -387,6 +412,8 @@ def main():
         # per 128; the activation gradient reads Z as well)
         moved = {"quantize_rows": rows * D_MODEL * 3 + rows * D_MODEL // 32,
                  "quantize_rows_mx": rows * D_MODEL * 3
+                 + rows * D_MODEL // 32,
+                 "quantize_rows_mx_fp4": rows * D_MODEL * 5 // 2
                  + rows * D_MODEL // 32,
                  "quantize_sparse_gelu": blocks * 16384 * 3 + blocks * 512,
                  "quantize_tiles": rows * D_MODEL * 4 + rows * D_MODEL // 16,
@@ -416,7 +443,14 @@ def main():
                 arm["hbm_share"] = round(tbs / HBM_TBS, 3)
             line["arms"][name] = arm
         us = {name: arm["us"] for name, arm in line["arms"].items()}
-        if a.mx and a.gated:
+        if a.mx and a.fp4:
+            line["pass"] = "mx fp4 forward"
+            for op in ("sdd", "dsd"):
+                line[f"{op}_mx_fp4_over_e2m1"] = round(
+                    us[f"{op}_mx_fp4"] / us[f"{op}_mx_e2m1"], 3)
+            line["quantize_rows_mx_fp4_over_mx"] = round(
+                us["quantize_rows_mx_fp4"] / us["quantize_rows_mx"], 3)
+        elif a.mx and a.gated:
             line["pass"] = "mx gated forward"
             for f in ("e4m3", "e2m1"):
                 line[f"glu_fused_{f}_over_chain"] = round(
@@ -452,7 +486,7 @@ def main():
                 line[f"{name}_over_bf16"] = round(
                     us[name] / us["mlp_bf16_backward"], 3)
         for op in (("sdd", "dsd") if a.mx and not a.backward and not a.gated
-                   else ()):
+                   and not a.fp4 else ()):
             for f in ("e4m3", "e2m1"):
                 for base in ("bf16", "fp8_fast"):
                     line[f"{op}_mx_{f}_over_{base}"] = round(

@@ -281,6 +281,12 @@ _SIGNATURES = {
     "sputnik_sdd_mx": [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P,
                        ctypes.c_int, _P],
     "sputnik_dsd_mx": [_P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_int, _P],
+    # MXFP4 activations: the first, third and fourth without b_format
+    "sputnik_quantize_rows_mx_fp4": [_P, _P, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, _P, _P,
+                                     ctypes.c_int, _P],
+    "sputnik_sdd_mx_fp4": [_P, _P, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P],
+    "sputnik_dsd_mx_fp4": [_P, _P, _P, _P, _P, ctypes.c_int, _P],
     # the fused gated SDD: (aq, a_scales, k, gate_q, gate_scales, up_q,
     # up_scales, b_row_step, b_format, gate_bias, up_bias, kind, act, alpha,
     # limit, c, hq, h_scales, g_out, u_out, h_out, dtype, stream)
@@ -2398,6 +2404,71 @@ def DsdMx(s, s_scales, bq, b_scales, c, format="e4m3", stream=None):  # noqa: N8
         ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "DsdMx")
 
 
+def QuantizeRowsMxFp4(x, q, scales, activation=None, gate=None, stream=None):  # noqa: N802
+    """QuantizeRowsMx as MXFP4: q uint8 [rows, cols / 2], two e2m1 codes per
+    byte, low nibble first, and scales uint8 [rows, cols / 32] of x [rows,
+    cols]; a block with a non-finite element gets scale byte 0xFF and codes 0
+    (sputnik_quantize_rows_mx_fp4)."""
+    import torch
+
+    _moe_matrix(x, None, None, "x")
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    _fp8_tiles(cols, "QuantizeRowsMxFp4: cols")
+    _fp8_buffer(q, torch.uint8, (rows, cols // 2), "q")
+    _fp8_buffer(scales, torch.uint8, (rows, cols // 32), "scales")
+    if gate is not None:
+        if activation is None:
+            raise ValueError("QuantizeRowsMxFp4: a gate needs its activation")
+        _fp8_buffer(gate, x.dtype, (rows, cols), "gate")
+    act = 0 if activation is None else _act_code(activation)
+    stage = 2 if gate is not None else 0 if activation is None else 1
+    _check(lib().sputnik_quantize_rows_mx_fp4(
+        _ptr(x), None if gate is None else _ptr(gate), rows, cols, stage, act,
+        _ptr(q), _ptr(scales), _dtype_code(x), _stream(stream)),
+        "QuantizeRowsMxFp4")
+
+
+def SddMxFp4(aq, a_scales, bq, b_scales, c, stream=None):  # noqa: N802
+    """SddMx with MXFP4 activations: aq uint8 [c.rows, k / 2] with a_scales
+    uint8 [c.rows, k / 32] (QuantizeRowsMxFp4), bq / b_scales an e2m1 MX
+    weight. Both operands on the FP4 form of the scaled MFMA
+    (sputnik_sdd_mx_fp4)."""
+    import torch
+
+    if not isinstance(c, BlockMatrix):
+        raise TypeError("SddMxFp4 writes a BlockMatrix")
+    _, n, k = _mx_weight(bq, b_scales, "e2m1", "SddMxFp4")
+    if n != c.cols:
+        raise ValueError(f"SddMxFp4: bq has {n} rows, C {c.cols} columns")
+    _fp8_buffer(aq, torch.uint8, (c.rows, k // 2), "aq")
+    _fp8_buffer(a_scales, torch.uint8, (c.rows, k // 32), "a_scales")
+    cc = c._c()
+    _check(lib().sputnik_sdd_mx_fp4(
+        _ptr(aq), _ptr(a_scales), k, _ptr(bq), _ptr(b_scales),
+        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "SddMxFp4")
+
+
+def DsdMxFp4(s, s_scales, bq, b_scales, c, stream=None):  # noqa: N802
+    """DsdMx with MXFP4 activations: s a BlockMatrix whose data holds uint8
+    [blocks, 128, 64] e2m1 pairs with s_scales uint8 [blocks * 128, 4]
+    (QuantizeRowsMxFp4 over the block values as [blocks * 128, 128]); bq /
+    b_scales an e2m1 MX weight, k = s.cols (sputnik_dsd_mx_fp4)."""
+    import torch
+
+    if not isinstance(s, BlockMatrix) or not isinstance(c, Matrix):
+        raise TypeError("DsdMxFp4 takes a BlockMatrix and writes a Matrix")
+    _, n, k = _mx_weight(bq, b_scales, "e2m1", "DsdMxFp4")
+    if k != s.cols or n != c.cols or c.rows != s.rows:
+        raise ValueError(f"DsdMxFp4 shapes [{s.rows}, {s.cols}] x [{k}, {n}] "
+                         f"-> [{c.rows}, {c.cols}]")
+    _fp8_buffer(s.data, torch.uint8, (s.num_blocks, 128, 64), "s.data")
+    _fp8_buffer(s_scales, torch.uint8, (s.num_blocks * 128, 4), "s_scales")
+    cs, cc = s._c(), c._c()
+    _check(lib().sputnik_dsd_mx_fp4(
+        ctypes.byref(cs), _ptr(s_scales), _ptr(bq), _ptr(b_scales),
+        ctypes.byref(cc), _dtype_code(c.data), _stream(stream)), "DsdMxFp4")
+
+
 def _mx_pair(q, scales, q_shape, s_shape, what: str):
     """An output pair of an MX tile quantiser: both given or both None."""
     import torch
@@ -2588,7 +2659,7 @@ def DsdMxPair(s1, s1_scales, b1q, b1_scales, s2_data, s2_scales, b2q,  # noqa: N
 
 __all__ = [
     "QuantizeRowsMx", "QuantizeWeightMx", "SddMx", "DsdMx", "MX_FORMATS",
-    "SddMxGated",
+    "SddMxGated", "QuantizeRowsMxFp4", "SddMxFp4", "DsdMxFp4",
     "QuantizeTilesMx", "QuantizeBlocksMx", "DsdMxWgrad",
     "QuantizeBlocksMxGated", "QuantizeBlocksMxGatedGrad", "DsdMxPair",
     "AllocateBitmaskBuffers", "AllocateRowIndicesBuffer",

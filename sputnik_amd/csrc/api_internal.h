@@ -160,6 +160,16 @@ hipError_t LaunchMxGemm(bool dsd, bool b4, int dtype, const void *a,
                         const short *indices, const short *row_indices,
                         int m_blocks, int n_blocks, int k_blocks,
                         int nnz_blocks, hipStream_t stream);
+// The A4W4 block GEMM (mx4_gemm.hip), arguments already validated by
+// SddMxFp4 / DsdMxFp4 (block_api.cpp): LaunchMxGemm's operands with an e2m1 A
+// (a = Aq [m, k / 2] or, DSD, stored blocks of [128][64] bytes) and an e2m1
+// B.
+hipError_t LaunchMx4Gemm(bool dsd, int dtype, const void *a,
+                         const uint8_t *a_scales, const void *b,
+                         const uint8_t *b_scales, void *c, const int *offsets,
+                         const short *indices, const short *row_indices,
+                         int m_blocks, int n_blocks, int k_blocks,
+                         int nnz_blocks, hipStream_t stream);
 // The e4m3 DSD of LaunchMxGemm into a gradient sink (DsdMxWgrad): c holds T
 // or, with `out_f32`, fp32; `add` accumulates into it.
 hipError_t LaunchMxWgrad(int dtype, bool out_f32, bool add, const void *s,

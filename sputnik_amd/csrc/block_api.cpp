@@ -670,6 +670,54 @@ hipError_t DsdMx(const BlockMatrix s, const uint8_t *s_scales, const void *bq,
       c.cols / 128, s.cols / 128, s.nonzeros / (128 * 128), stream);
 }
 
+// MXFP4 activations: SddMx / DsdMx's checks (s.nonzeros counts elements, 128 x
+// 128 a block, whatever their width), then the A4W4 kernel.
+hipError_t SddMxFp4(const void *aq, const uint8_t *a_scales, int k,
+                    const void *bq, const uint8_t *b_scales, BlockMatrix c,
+                    DataType dtype, hipStream_t stream) {
+  if (!Fp8SizesOk(c, k, (int)dtype)) return hipErrorInvalidValue;
+  if (c.nonzeros == 0) return hipSuccess;
+  if (c.data == nullptr || c.indices == nullptr || c.row_indices == nullptr ||
+      (k > 0 && (aq == nullptr || a_scales == nullptr || bq == nullptr ||
+                 b_scales == nullptr)))
+    return hipErrorInvalidValue;
+  for (const void *in : {aq, (const void *)a_scales, bq,
+                         (const void *)b_scales, (const void *)c.indices,
+                         (const void *)c.row_indices})
+    if (c.data == in) return hipErrorInvalidValue;
+  if (!Aligned16({aq, bq, c.data}) || !Aligned4({a_scales, b_scales}))
+    return hipErrorInvalidValue;
+  return sputnik_amd::LaunchMx4Gemm(
+      false, (int)dtype, aq, a_scales, bq, b_scales, c.data, nullptr,
+      static_cast<const short *>(c.indices),
+      static_cast<const short *>(c.row_indices), c.rows / 128, c.cols / 128,
+      k / 128, c.nonzeros / (128 * 128), stream);
+}
+
+hipError_t DsdMxFp4(const BlockMatrix s, const uint8_t *s_scales,
+                    const void *bq, const uint8_t *b_scales, Matrix c,
+                    DataType dtype, hipStream_t stream) {
+  if (!Fp8SizesOk(s, c.cols, (int)dtype) || c.rows != s.rows)
+    return hipErrorInvalidValue;
+  if (c.rows == 0 || c.cols == 0) return hipSuccess;
+  if (c.data == nullptr || s.offsets == nullptr ||
+      (s.nonzeros > 0 && (s.data == nullptr || s.indices == nullptr ||
+                          s_scales == nullptr || bq == nullptr ||
+                          b_scales == nullptr)))
+    return hipErrorInvalidValue;
+  for (const void *in : {(const void *)s.data, (const void *)s_scales, bq,
+                         (const void *)b_scales, (const void *)s.offsets,
+                         (const void *)s.indices})
+    if (c.data == in) return hipErrorInvalidValue;
+  if (!Aligned16({s.data, bq, c.data}) || !Aligned4({s_scales, b_scales}))
+    return hipErrorInvalidValue;
+  return sputnik_amd::LaunchMx4Gemm(
+      true, (int)dtype, s.data, s_scales, bq, b_scales, c.data,
+      static_cast<const int *>(s.offsets),
+      static_cast<const short *>(s.indices), nullptr, s.rows / 128,
+      c.cols / 128, s.cols / 128, s.nonzeros / (128 * 128), stream);
+}
+
 hipError_t DsdMxWgrad(const BlockMatrix s, const uint8_t *s_scales,
                       const void *bq, const uint8_t *b_scales, Matrix c,
                       OutputType out, bool add, DataType dtype,

@@ -843,6 +843,35 @@ int sputnik_dsd_mx(const sputnik_block_matrix_t *s, const uint8_t *s_scales,
       static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
 }
 
+int sputnik_quantize_rows_mx_fp4(const void *x, const void *gate, int rows,
+                                 int cols, int stage, int act, void *q,
+                                 uint8_t *scales, int dtype, void *stream) {
+  return sputnik::block::QuantizeRowsMxFp4(
+      x, gate, rows, cols, static_cast<sputnik::block::MxStage>(stage),
+      static_cast<sputnik::block::Activation>(act), q, scales,
+      static_cast<DataType>(dtype), static_cast<hipStream_t>(stream));
+}
+
+int sputnik_sdd_mx_fp4(const void *aq, const uint8_t *a_scales, int k,
+                       const void *bq, const uint8_t *b_scales,
+                       const sputnik_block_matrix_t *c, int dtype,
+                       void *stream) {
+  if (!c) return hipErrorInvalidValue;
+  return sputnik::block::SddMxFp4(aq, a_scales, k, bq, b_scales, ToCpp(c),
+                                  static_cast<DataType>(dtype),
+                                  static_cast<hipStream_t>(stream));
+}
+
+int sputnik_dsd_mx_fp4(const sputnik_block_matrix_t *s,
+                       const uint8_t *s_scales, const void *bq,
+                       const uint8_t *b_scales, const sputnik_matrix_t *c,
+                       int dtype, void *stream) {
+  if (!s || !c) return hipErrorInvalidValue;
+  return sputnik::block::DsdMxFp4(ToCpp(s), s_scales, bq, b_scales, ToCpp(c),
+                                  static_cast<DataType>(dtype),
+                                  static_cast<hipStream_t>(stream));
+}
+
 int sputnik_sdd_mx_gated(const void *aq, const uint8_t *a_scales, int k,
                          const void *gate_q, const uint8_t *gate_scales,
                          const void *up_q, const uint8_t *up_scales,

@@ -9,6 +9,9 @@
 // act_math.h's SddEpilogue table is applied first, through the same apply8, so
 // the bytes are the quantisation of the H the 16-bit path stores.
 //
+// quantize_rows_mx_fp4_kernel: the same rows as MXFP4 (its comment has the
+// steps).
+//
 // quantize_weight_mx_kernel: runs at load time. One workgroup per 128 x 128
 // block through an LDS image in [n][k] order (the 2-byte transpose when the
 // source is [k, n]); then one thread per (row n, 32-block): amax, scale byte,
@@ -60,6 +63,15 @@ __device__ __forceinline__ void store_bytes(uint8_t *p, const uint32_t *w,
   for (int i = 0; i < 4 * words; ++i) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
 }
 
+__device__ __forceinline__ void store16(uint8_t *p, const uint32_t *w,
+                                        bool aligned) {
+  if (aligned) {
+    *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    return;
+  }
+  store_bytes(p, w, 4, false);
+}
+
 template <typename T, int kMode>
 __global__ void __launch_bounds__(kThreads)
     quantize_rows_mx_kernel(const T *x, const T *gate, uint8_t *q,
@@ -109,6 +121,90 @@ __global__ void __launch_bounds__(kThreads)
         w[i >> 2] |= fp8_quantize((float)v[i], scale) << (8 * (i & 3));
       if (aligned) *reinterpret_cast<uint2 *>(q + at) = make_uint2(w[0], w[1]);
       else store_bytes(q + at, w, 2, false);
+      if (sub == 0) store_bytes(scales + tile * 4, &dword, 1, scales_aligned);
+    }
+  }
+}
+
+// The e8m0 byte of an e2m1 32-block from its finite amax, mx_scale<true>'s
+// rule on the bits: amax = 1.M 2^(E - 127) = m 2^(E - 126) with m = 1.M / 2,
+// so m <= 0.75 is M <= 0x400000 and the scale's exponent is E - 126 - 3 (or -
+// 2), floored at -126: byte max(E - 2 + (M > 0x400000), 1). A subnormal or
+// zero amax has E = 0 and lands on the floor.
+__device__ __forceinline__ uint32_t mx_e2m1_scale_byte(float amax) {
+  const uint32_t bits = __float_as_uint(amax);
+  const int e = (int)(bits >> 23) - 2 + ((bits & 0x7FFFFFu) > 0x400000u ? 1 : 0);
+  return (uint32_t)(e > 1 ? e : 1);
+}
+
+// quantize_rows_mx_fp4_kernel (QuantizeRowsMxFp4): quantize_rows_mx_kernel's
+// lane layout, loads and stage, so H is the same 16-bit value; then the e2m1
+// rules. A lane's 8 elements are 8 codes, one dword. No division: the scale
+// is 2^(byte - 127) with byte in 1 .. 253, its reciprocal the normal float
+// with exponent field 254 - byte, and x times it is the exact quotient (at
+// most 6 in magnitude, at least 2^-7 times the smallest subnormal of T). A
+// non-finite element is met across the 32-block's four lanes like the amax:
+// scale byte 0xFF, codes 0. The four dwords of a 32-block meet in its first
+// lane and leave as one 16-byte store; the row tile's four scale bytes leave
+// as one dword.
+template <typename T, int kMode>
+__global__ void __launch_bounds__(kThreads)
+    quantize_rows_mx_fp4_kernel(const T *x, const T *gate, uint8_t *q,
+                                uint8_t *scales, long long tiles, int act,
+                                bool aligned, bool q_aligned,
+                                bool scales_aligned) {
+  const int sub = threadIdx.x & 15;
+  const long long step = (long long)gridDim.x * (kThreads / 16);
+  // (every lane of a wave runs the same trips: the cross-lane steps below are
+  // executed by whole waves)
+  for (long long base = (long long)blockIdx.x * (kThreads / 16); base < tiles;
+       base += step) {
+    const long long tile = base + (threadIdx.x >> 4);
+    const bool live = tile < tiles;
+    const long long at = tile * kTile + sub * 8;
+    act_t8<T> v{};
+    if (live) {
+      v = load8<T>(x + at, aligned);
+      if constexpr (kMode != kModeNone) {
+        using E = SddEpilogue<kMode>;
+        act_t8<T> g = v, h, unused;
+        if constexpr (E::kSideInputs >= 1) g = load8<T>(gate + at, aligned);
+        E::template apply8<T>(act, v, g, v, &h, &unused);
+        v = h;
+      }
+    }
+    float amax = 0.0f;
+    int finite = 1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float f = (float)v[i];
+      if (fp8_finite(f)) amax = fmaxf(amax, fabsf(f));
+      else finite = 0;
+    }
+    // the 32-block: lanes sub & ~3 .. sub | 3
+    amax = fmaxf(amax, __shfl_xor(amax, 2));
+    amax = fmaxf(amax, __shfl_xor(amax, 1));
+    finite &= __shfl_xor(finite, 2);
+    finite &= __shfl_xor(finite, 1);
+    const uint32_t byte = finite ? mx_e2m1_scale_byte(amax) : kE8m0Nan;
+    uint32_t w = 0;
+    if (finite) {
+      const float inverse = __uint_as_float((254u - byte) << 23);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        w |= mx_encode_e2m1((float)v[i] * inverse) << (4 * i);
+    }
+    const int lane0 = (threadIdx.x & 63) & ~15;
+    const uint32_t dword = (uint32_t)__shfl((int)byte, lane0) |
+                           (uint32_t)__shfl((int)byte, lane0 + 4) << 8 |
+                           (uint32_t)__shfl((int)byte, lane0 + 8) << 16 |
+                           (uint32_t)__shfl((int)byte, lane0 + 12) << 24;
+    const uint32_t block[4] = {w, (uint32_t)__shfl_down((int)w, 1),
+                               (uint32_t)__shfl_down((int)w, 2),
+                               (uint32_t)__shfl_down((int)w, 3)};
+    if (live) {
+      if ((sub & 3) == 0)
+        store16(q + tile * (kTile / 2) + sub * 4, block, q_aligned);
       if (sub == 0) store_bytes(scales + tile * 4, &dword, 1, scales_aligned);
     }
   }
@@ -193,15 +289,6 @@ struct MxTileSinks {
   uint8_t *q, *scales, *qt, *scales_t;
   long long q_pitch, scales_pitch, qt_pitch, scales_t_pitch;
 };
-
-__device__ __forceinline__ void store16(uint8_t *p, const uint32_t *w,
-                                        bool aligned) {
-  if (aligned) {
-    *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    return;
-  }
-  store_bytes(p, w, 4, false);
-}
 
 // The row pass on one chunk: lane `sub` of a row's 16 holds 8 elements; the 4
 // lanes of a 32-block meet for the amax, each lane stores its 8 bytes at `q`
@@ -527,6 +614,34 @@ hipError_t QuantizeRowsMxImpl(const void *x, const void *gate, int rows,
   return dtype == 1 ? launch(__bf16{}) : launch(_Float16{});
 }
 
+template <int kMode>
+hipError_t QuantizeRowsMxFp4Impl(const void *x, const void *gate, int rows,
+                                 int cols, int act, void *q, uint8_t *scales,
+                                 int dtype, hipStream_t stream) {
+  if (rows < 0 || cols < 0 || cols % kTile != 0 || (dtype != 0 && dtype != 1))
+    return hipErrorInvalidValue;
+  if (kMode != kModeNone && (act < kActRelu || act > kActSilu))
+    return hipErrorInvalidValue;
+  if (rows == 0 || cols == 0) return hipSuccess;
+  if (x == nullptr || q == nullptr || scales == nullptr ||
+      (kMode == kOutGate && gate == nullptr))
+    return hipErrorInvalidValue;
+  if (!Distinct({q, scales}, {x, gate})) return hipErrorInvalidValue;
+  const long long tiles = (long long)rows * (cols / kTile);
+  const long long want = (tiles + kThreads / 16 - 1) / (kThreads / 16);
+  const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
+  auto launch = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((quantize_rows_mx_fp4_kernel<T, kMode>), dim3(grid),
+                       dim3(kThreads), 0, stream, static_cast<const T *>(x),
+                       static_cast<const T *>(gate), static_cast<uint8_t *>(q),
+                       scales, tiles, act, Aligned({x, gate}, 15),
+                       Aligned({q}, 15), Aligned({scales}, 3));
+    return hipGetLastError();
+  };
+  return dtype == 1 ? launch(__bf16{}) : launch(_Float16{});
+}
+
 }  // namespace
 }  // namespace sputnik_amd
 
@@ -551,6 +666,26 @@ hipError_t QuantizeRowsMx(const void *x, const void *gate, int rows, int cols,
     case MxStage::kGated:
       return QuantizeRowsMxImpl<kOutGate>(x, gate, rows, cols, (int)activation,
                                           q, scales, (int)dtype, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t QuantizeRowsMxFp4(const void *x, const void *gate, int rows,
+                             int cols, MxStage stage, Activation activation,
+                             void *q, uint8_t *scales, DataType dtype,
+                             hipStream_t stream) {
+  switch (stage) {
+    case MxStage::kNone:
+      return QuantizeRowsMxFp4Impl<kModeNone>(x, nullptr, rows, cols, 0, q,
+                                              scales, (int)dtype, stream);
+    case MxStage::kActivation:
+      return QuantizeRowsMxFp4Impl<kOutAct>(x, nullptr, rows, cols,
+                                            (int)activation, q, scales,
+                                            (int)dtype, stream);
+    case MxStage::kGated:
+      return QuantizeRowsMxFp4Impl<kOutGate>(x, gate, rows, cols,
+                                             (int)activation, q, scales,
+                                             (int)dtype, stream);
   }
   return hipErrorInvalidValue;
 }

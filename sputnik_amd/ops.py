@@ -103,6 +103,7 @@ from . import (BlockActivation, BlockActivationGrad, BlockGate, BlockGateGrad,
                QuantizeTiles, QuantizeBlocks, TransposeWeightFp8, DsdFp8Wgrad,
                QuantizeBlocksGated, QuantizeBlocksGatedGrad, DsdFp8Pair,
                QuantizeRowsMx, QuantizeWeightMx, SddMx, DsdMx, MX_FORMATS,
+               QuantizeRowsMxFp4, SddMxFp4, DsdMxFp4,
                SddMxGated, QuantizeTilesMx, QuantizeBlocksMx, DsdMxWgrad,
                QuantizeBlocksMxGated, QuantizeBlocksMxGatedGrad, DsdMxPair,
                RouterScoreTopK, RouterScoreTopKGrad, RouterTopKAux,
@@ -1869,6 +1870,158 @@ def moe_mlp_mx(x: torch.Tensor, top_experts: torch.Tensor,
     return padded_scatter(dsd_mx(hq, w2q, x.dtype), route, expert_weights)
 
 
+# ---- MXFP4 activations (A4W4): the chain above with e2m1 on both sides ------
+
+class MxFp4SparseMatrix(SparseMatrix):
+    """A SparseMatrix whose block values are e2m1 codes, uint8 [nnz_blocks,
+    128, 64] (two per byte, low nibble first), with `scales` uint8
+    [nnz_blocks * 128, 4] (quantize_sparse_mx_fp4). The operand of
+    dsd_mx_fp4."""
+
+    def __init__(self, topo: SparseMatrix, q: torch.Tensor,
+                 scales: torch.Tensor):
+        # (a stored block is 128 x 64 bytes here, which SparseMatrix's own
+        # constructor does not take: the fields are set directly)
+        m = topo._meta
+        if (q.dtype != torch.uint8
+                or tuple(q.shape) != (m.nb, BLOCK, BLOCK // 2)):
+            raise ValueError(f"data must be uint8 [{m.nb}, 128, 64]")
+        self.data, self._meta, self._transposed = q, m, False
+        self.scales = scales
+
+
+def _e2m1_weight(w, what: str) -> None:
+    if not isinstance(w, MxWeight):
+        raise TypeError(f"{what}: w must be an MxWeight")
+    if w.format != "e2m1":
+        raise ValueError(f"{what}: MXFP4 activations take an 'e2m1' weight, "
+                         f"not {w.format!r}")
+
+
+def quantize_rows_mx_fp4(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(q, scales) of x [rows, cols] (fp16 / bf16, cols a multiple of 128) as
+    MXFP4: q uint8 [rows, cols / 2], two e2m1 codes per byte, low nibble
+    first; scales uint8 [rows, cols / 32]. A 32-block with a non-finite
+    element gets scale byte 0xFF (NaN). Forward only."""
+    _check_dtypes(x)
+    _no_grad("quantize_rows_mx_fp4", x)
+    if x.dim() != 2 or int(x.shape[1]) % BLOCK:
+        raise ValueError("quantize_rows_mx_fp4: x is [rows, a multiple of "
+                         "128]")
+    x = x.contiguous()
+    q = torch.empty(x.shape[0], x.shape[1] // 2, dtype=torch.uint8,
+                    device=x.device)
+    scales = torch.empty(x.shape[0], x.shape[1] // 32, dtype=torch.uint8,
+                         device=x.device)
+    QuantizeRowsMxFp4(x, q, scales)
+    return q, scales
+
+
+def quantize_sparse_mx_fp4(sparse: SparseMatrix, activation=None,
+                           gate: Optional[SparseMatrix] = None
+                           ) -> MxFp4SparseMatrix:
+    """quantize_sparse_mx in MXFP4: the block values of `sparse` (or of
+    act(sparse), or of sparse * act(gate)), evaluated as quantize_sparse_mx
+    evaluates them, as e2m1 codes. Forward only."""
+    if not isinstance(sparse, SparseMatrix) or sparse.is_transposed():
+        raise TypeError("quantize_sparse_mx_fp4 takes a SparseMatrix (not a "
+                        ".t() view)")
+    _check_dtypes(sparse.data)
+    _no_grad("quantize_sparse_mx_fp4", sparse.data,
+             None if gate is None else gate.data)
+    g = None
+    if gate is not None:
+        if (not isinstance(gate, SparseMatrix)
+                or gate._meta is not sparse._meta or gate.is_transposed()
+                or gate.dtype != sparse.dtype):
+            raise ValueError("quantize_sparse_mx_fp4: gate must share "
+                             "sparse's topology and dtype")
+        if activation is None:
+            raise ValueError("quantize_sparse_mx_fp4: a gate needs its "
+                             "activation")
+        g = gate.data.contiguous().view(-1, BLOCK)
+    nb = sparse.nnz_blocks
+    x = sparse.data.contiguous().view(nb * BLOCK, BLOCK)
+    q = torch.empty(nb, BLOCK, BLOCK // 2, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=x.device)
+    QuantizeRowsMxFp4(x, q.view(nb * BLOCK, BLOCK // 2), scales,
+                      None if activation is None else _act_code(activation), g)
+    return MxFp4SparseMatrix(sparse, q, scales)
+
+
+def sdd_mx_fp4(xq: torch.Tensor, xs: torch.Tensor, w: MxWeight,
+               topo: SparseMatrix, out_dtype=torch.bfloat16) -> SparseMatrix:
+    """sdd_mx with MXFP4 activations: xq / xs from quantize_rows_mx_fp4, w an
+    'e2m1' MxWeight of [k, n] (ValueError otherwise), topo [m, n]. Both
+    operands go through the FP4 form of the scaled MFMA; arithmetic, order and
+    rounding are sdd_mx's. Bitwise reproducible. Forward only."""
+    _e2m1_weight(w, "sdd_mx_fp4")
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError("sdd_mx_fp4: topo must be a SparseMatrix (not a .t() "
+                        "view)")
+    _out_dtype(out_dtype, "sdd_mx_fp4")
+    if (not isinstance(xq, torch.Tensor) or xq.dim() != 2
+            or (int(xq.shape[0]), w.n) != tuple(topo.shape)
+            or int(xq.shape[1]) * 2 != w.k):
+        raise ValueError(f"sdd_mx_fp4 shapes "
+                         f"{tuple(getattr(xq, 'shape', ()))} (two codes per "
+                         f"byte) x {w.shape} -> {topo.shape}")
+    data = torch.empty(topo.nnz_blocks, BLOCK, BLOCK, dtype=out_dtype,
+                       device=xq.device)
+    topo._meta.ensure_row_indices(data)
+    SddMxFp4(xq, xs, w.q, w.scales, topo._meta.descriptor(data))
+    return topo.with_data(data)
+
+
+def dsd_mx_fp4(sq: MxFp4SparseMatrix, w: MxWeight,
+               out_dtype=torch.bfloat16) -> torch.Tensor:
+    """dsd_mx with MXFP4 activations: sq from quantize_sparse_mx_fp4, w an
+    'e2m1' MxWeight of [k, n] (ValueError otherwise). A block row without
+    blocks gives +0 rows. Forward only."""
+    if not isinstance(sq, MxFp4SparseMatrix):
+        raise TypeError("dsd_mx_fp4: sq must come from quantize_sparse_mx_fp4")
+    _e2m1_weight(w, "dsd_mx_fp4")
+    _out_dtype(out_dtype, "dsd_mx_fp4")
+    if sq.shape[1] != w.k:
+        raise ValueError(f"dsd_mx_fp4 shapes {sq.shape} x {w.shape}")
+    out = torch.empty(sq.shape[0], w.n, dtype=out_dtype, device=sq.device)
+    DsdMxFp4(sq._descriptor(), sq.scales, w.q, w.scales,
+             Matrix(out.shape[0], out.shape[1], out))
+    return out
+
+
+def moe_mlp_mx_fp4(x: torch.Tensor, top_experts: torch.Tensor,
+                   expert_weights: torch.Tensor, w1q: MxWeight, w2q: MxWeight,
+                   num_experts: int, activation=None,
+                   v1q: Optional[MxWeight] = None,
+                   rows: Optional[int] = None) -> torch.Tensor:
+    """moe_mlp_mx with MXFP4 activations against MXFP4 weights (A4W4):
+    padded_gather -> quantize_rows_mx_fp4 -> sdd_mx_fp4 with `w1q` (and with
+    `v1q` for a GLU) -> quantize_sparse_mx_fp4 with the activation (or the
+    gate) -> dsd_mx_fp4 with `w2q` -> padded_scatter. Every weight is an
+    'e2m1' MxWeight, as a published MXFP4 checkpoint stores it. Forward
+    only."""
+    _no_grad("moe_mlp_mx_fp4", x, expert_weights)
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1q, w2q, v1q,
+                              num_experts, rows, mx=True)
+    for w in (w1q, w2q) if v1q is None else (w1q, v1q, w2q):
+        _e2m1_weight(w, "moe_mlp_mx_fp4")
+    act = None if activation is None else _act_code(activation)
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    xq, xs = quantize_rows_mx_fp4(xp)
+    g = sdd_mx_fp4(xq, xs, w1q, topo, x.dtype)
+    if v1q is None:
+        hq = quantize_sparse_mx_fp4(g, "gelu" if act is None else act)
+    else:
+        u = sdd_mx_fp4(xq, xs, v1q, topo, x.dtype)
+        hq = quantize_sparse_mx_fp4(u, "silu" if act is None else act, gate=g)
+    return padded_scatter(dsd_mx_fp4(hq, w2q, x.dtype), route, expert_weights)
+
+
 class MxGluWeight:
     """The gate and up projections [k, n] of a GLU expert layer in one MX
     format, as sdd_mx_gated reads them: `MxGluWeight(gate, up)` from two
@@ -3445,4 +3598,7 @@ __all__ = ["MoeAux", "MoeRoute", "SparseMatrix", "dds", "dds_acc", "dsd", "dsd_a
            "MxWeight", "MxSparseMatrix", "quantize_rows_mx",
            "quantize_sparse_mx", "quantize_weight_mx", "sdd_mx", "dsd_mx",
            "moe_mlp_mx",
+           "MxFp4SparseMatrix", "quantize_rows_mx_fp4",
+           "quantize_sparse_mx_fp4", "sdd_mx_fp4", "dsd_mx_fp4",
+           "moe_mlp_mx_fp4",
            "topology_from_mask"]
