@@ -231,8 +231,9 @@ def main():
 
             arms = {
                 "quantize_tiles": lambda: ops.quantize_tiles(dy),
-                "quantize_blocks_gelu_grad": lambda: ops._quantize_blocks(
-                    dh16, "act_grad", 1, g16.data, True, True, False),
+                "quantize_blocks_gelu_grad": lambda: ops._lowp_quantize_blocks(
+                    ops._FP8, dh16, "act_grad", 1, g16.data, True, True,
+                    pow2=False),
                 "wgrad_bf16": lambda: ops._dsd(h16.t(), dy),
                 "wgrad_fp8": lambda: ops.dsd_fp8_wgrad(ht, dyqt, dyst,
                                                        out_dtype=dt),
@@ -256,8 +257,8 @@ def main():
             arms = {
                 "quantize_tiles_mx": lambda: ops.quantize_tiles_mx(dy),
                 "quantize_blocks_mx_gelu_grad":
-                    lambda: ops._quantize_blocks_mx(dh16, "act_grad", 1,
-                                                    g16.data, True, True),
+                    lambda: ops._lowp_quantize_blocks(
+                        ops._MX, dh16, "act_grad", 1, g16.data, True, True),
                 "wgrad_mx": lambda: ops.dsd_mx_wgrad(hmt, myqt, myst,
                                                      out_dtype=dt),
                 **{k: arms[k] for k in keep},
@@ -279,15 +280,16 @@ def main():
             duq = ops.quantize_sparse(topo.with_data(u16))
 
             def gated_grad_fused():
-                dg = ops._fp8_images(blocks, True, True, "cuda")
-                du = ops._fp8_images(blocks, True, True, "cuda")
+                dg = ops._lowp_images(ops._FP8, blocks, True, True, "cuda")
+                du = ops._lowp_images(ops._FP8, blocks, True, True, "cuda")
                 sp.QuantizeBlocksGatedGrad(meta.descriptor(d16), g16.data,
                                            u16, "silu", dg, du)
                 return dg, du
 
             def gated_grad_composed():
-                return [ops._quantize_blocks(topo.with_data(t), None, None,
-                                             None, True, True, False)
+                return [ops._lowp_quantize_blocks(
+                            ops._FP8, topo.with_data(t), None, None, None,
+                            True, True, pow2=False)
                         for t in sp.BlockGateGrad(d16, g16.data, u16, "silu")]
 
             def backward_of(fn, *leaves, rerun=False):
@@ -328,15 +330,16 @@ def main():
             dum = ops.quantize_sparse_mx(topo.with_data(u16))
 
             def gated_grad_mx_fused():
-                dg = ops._mx_images(blocks, True, True, "cuda")
-                du = ops._mx_images(blocks, True, True, "cuda")
+                dg = ops._lowp_images(ops._MX, blocks, True, True, "cuda")
+                du = ops._lowp_images(ops._MX, blocks, True, True, "cuda")
                 sp.QuantizeBlocksMxGatedGrad(meta.descriptor(d16), g16.data,
                                              u16, "silu", dg, du)
                 return dg, du
 
             def gated_grad_mx_composed():
-                return [ops._quantize_blocks_mx(topo.with_data(t), None, None,
-                                                None, True, True)
+                return [ops._lowp_quantize_blocks(
+                            ops._MX, topo.with_data(t), None, None, None,
+                            True, True)
                         for t in sp.BlockGateGrad(d16, g16.data, u16, "silu")]
 
             arms = {

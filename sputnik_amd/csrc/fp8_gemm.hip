@@ -70,12 +70,15 @@
 #include <type_traits>
 
 #include "api_internal.h"
+#include "lowp_tile.h"
 
 namespace sputnik_amd {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kB = 128;                  // block edge = scale interval
+// kThreads, kB (the block edge = scale interval), the vector types, the
+// scalar loads and the swizzle keys: lowp_tile.h.
+using namespace lowp;
+
 constexpr int kTileBytes = kB * kB;      // one e4m3 operand tile
 constexpr int kScaleBytes = kB * 4;      // the row scales of an A tile
 // (kWgrad: the column scales of the B tile follow the row scales)
@@ -88,39 +91,11 @@ constexpr int StageBytes(bool wgrad) {
 constexpr int kStages = 2;
 constexpr int LdsBytes(bool wgrad) { return kStages * StageBytes(wgrad); }
 static_assert(kB * kB * 2 <= LdsBytes(false), "the output tile reuses the ring");
-// (the wgrad's fp32 image: four floats of padding per row put the four row
-// groups of a wave's store on different banks)
-constexpr int kImagePitch = kB + 4;
 static_assert(kB * kImagePitch * 4 <= LdsBytes(true), "... as fp32 too");
 static_assert(2 * LdsBytes(true) <= 160 * 1024, "two workgroups per CU");
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-#define SPUTNIK_FP8_LDS(p) ((__attribute__((address_space(3))) void *)(p))
-#define SPUTNIK_FP8_GLOBAL(p) \
-  ((const __attribute__((address_space(1))) void *)(p))
-
-// Wave-uniform loads through the scalar cache: metadata and weight scales
-// are read-only for the whole launch.
-__device__ __forceinline__ int scalar_int(const int *p) {
-  return *(const __attribute__((address_space(4))) int *)p;
-}
-__device__ __forceinline__ float scalar_float(const float *p) {
-  return *(const __attribute__((address_space(4))) float *)p;
-}
-// (an int16 entry from its aligned dword: any 2-byte-aligned base works)
-__device__ __forceinline__ int scalar_short(const short *p) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const int v = *reinterpret_cast<const __attribute__((address_space(4))) int *>(
-      a & ~uintptr_t(3));
-  return (short)((a & 2) ? (v >> 16) : v);
-}
-
-__device__ __forceinline__ int swizzle_key(int row) { return (row >> 1) & 7; }
 
 // 8 e4m3 bytes as 8 fp16 values, exactly (NaN bytes stay NaN).
 __device__ __forceinline__ f16x8 e4m3_to_f16x8(int lo, int hi) {
@@ -264,25 +239,25 @@ __global__ void __launch_bounds__(kThreads)
       // (a wave's 64 x 16 bytes are 8 rows of the image)
       const int piece = pass * (kThreads * 16) + wave * 1024;
       const int row = (piece >> 7) + (lane >> 3);
-      const int chunk = (lane & 7) ^ swizzle_key(row);
+      const int chunk = (lane & 7) ^ key8(row);
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_FP8_GLOBAL(a_tile + row * a_pitch + chunk * 16),
-          SPUTNIK_FP8_LDS(stage + piece), 16, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(a_tile + row * a_pitch + chunk * 16),
+          SPUTNIK_LOWP_LDS(stage + piece), 16, 0, 0);
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_FP8_GLOBAL(b_tile + row * k_bytes + chunk * 16),
-          SPUTNIK_FP8_LDS(stage + kTileBytes + piece), 16, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(b_tile + row * k_bytes + chunk * 16),
+          SPUTNIK_LOWP_LDS(stage + kTileBytes + piece), 16, 0, 0);
     }
     if (wave < kB / 64) {
       const int row = wave * 64 + lane;
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_FP8_GLOBAL(a_scale + row * a_scale_stride),
-          SPUTNIK_FP8_LDS(stage + 2 * kTileBytes + wave * 256), 4, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(a_scale + row * a_scale_stride),
+          SPUTNIK_LOWP_LDS(stage + 2 * kTileBytes + wave * 256), 4, 0, 0);
     } else if constexpr (kWgrad) {
       const int col = (wave - kB / 64) * 64 + lane;
       const long long n = (long long)p.n_blocks * kB;
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_FP8_GLOBAL(p.b_scales + kb * n + (long long)nb * kB + col),
-          SPUTNIK_FP8_LDS(stage + 2 * kTileBytes + wave * 256), 4, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(p.b_scales + kb * n + (long long)nb * kB + col),
+          SPUTNIK_LOWP_LDS(stage + 2 * kTileBytes + wave * 256), 4, 0, 0);
     }
   };
 
@@ -299,7 +274,7 @@ __global__ void __launch_bounds__(kThreads)
   auto fragment = [&](const char *image, int row0) {
     const int row = row0 + r;
     const char *at = image + row * kB;
-    const int key = swizzle_key(row);
+    const int key = key8(row);
     const i32x4 lo = *reinterpret_cast<const i32x4 *>(at + ((g ^ key) << 4));
     const i32x4 hi =
         *reinterpret_cast<const i32x4 *>(at + (((g + 4) ^ key) << 4));

@@ -63,12 +63,15 @@
 #include <type_traits>
 
 #include "api_internal.h"
+#include "lowp_tile.h"
 
 namespace sputnik_amd {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kB = 128;               // block edge = one k-block
+// kThreads, kB (the block edge = one k-block), the vector types, the
+// scalar loads and the swizzle keys: lowp_tile.h.
+using namespace lowp;
+
 constexpr int kHalfRow = kB / 2;      // bytes of a k-block in an e2m1 row
 constexpr int kImageBytes = kB * kB;  // 128 rows x two k-blocks of 64 bytes
 constexpr int kScaleBytes = kB * 2 * 4;  // two dwords per row (column)
@@ -81,29 +84,6 @@ constexpr int kLdsBytes = kStages * kStageBytes;
 static_assert(kStageBytes == 34 * 1024, "the stage size of the header");
 static_assert(2 * kLdsBytes <= 160 * 1024, "two workgroups per CU");
 static_assert(kB * kB * 2 <= kLdsBytes, "the output tile reuses the ring");
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define SPUTNIK_MX4_LDS(p) ((__attribute__((address_space(3))) void *)(p))
-#define SPUTNIK_MX4_GLOBAL(p) \
-  ((const __attribute__((address_space(1))) void *)(p))
-
-// Wave-uniform loads through the scalar cache: the metadata is read-only for
-// the whole launch.
-__device__ __forceinline__ int scalar_int(const int *p) {
-  return *(const __attribute__((address_space(4))) int *)p;
-}
-// (an int16 entry from its aligned dword: any 2-byte-aligned base works)
-__device__ __forceinline__ int scalar_short(const short *p) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const int v = *reinterpret_cast<const __attribute__((address_space(4))) int *>(
-      a & ~uintptr_t(3));
-  return (short)((a & 2) ? (v >> 16) : v);
-}
-
-__device__ __forceinline__ int key8(int row) { return (row >> 1) & 7; }
 
 struct Mx4GemmParams {
   const char *a;            // SDD: Aq [m, k / 2]; DSD: the stored blocks of Sq
@@ -191,11 +171,11 @@ __global__ void __launch_bounds__(kThreads)
       const bool second = chunk >= 4;
       const int at = (chunk & 3) * 16;
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX4_GLOBAL((second ? h1.a : h0.a) + row * a_pitch + at),
-          SPUTNIK_MX4_LDS(stage + piece), 16, 0, 0);
+          SPUTNIK_LOWP_GLOBAL((second ? h1.a : h0.a) + row * a_pitch + at),
+          SPUTNIK_LOWP_LDS(stage + piece), 16, 0, 0);
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX4_GLOBAL((second ? h1.b : h0.b) + row * row_bytes + at),
-          SPUTNIK_MX4_LDS(stage + kBOff + piece), 16, 0, 0);
+          SPUTNIK_LOWP_GLOBAL((second ? h1.b : h0.b) + row * row_bytes + at),
+          SPUTNIK_LOWP_LDS(stage + kBOff + piece), 16, 0, 0);
     }
     // Scale dwords, [half][row]: waves 0, 1 the first half's, 2, 3 the
     // second's; an absent half's are not fetched.
@@ -203,11 +183,11 @@ __global__ void __launch_bounds__(kThreads)
       const Mx4Half &h = wave < 2 ? h0 : h1;
       const int row = (wave & 1) * 64 + lane;
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX4_GLOBAL(h.a_scale + row * a_scale_pitch),
-          SPUTNIK_MX4_LDS(stage + kAScaleOff + wave * 256), 4, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(h.a_scale + row * a_scale_pitch),
+          SPUTNIK_LOWP_LDS(stage + kAScaleOff + wave * 256), 4, 0, 0);
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX4_GLOBAL(h.b_scale + row * scale_row),
-          SPUTNIK_MX4_LDS(stage + kBScaleOff + wave * 256), 4, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(h.b_scale + row * scale_row),
+          SPUTNIK_LOWP_LDS(stage + kBScaleOff + wave * 256), 4, 0, 0);
     }
   };
 

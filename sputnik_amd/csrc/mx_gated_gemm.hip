@@ -73,13 +73,16 @@
 
 #include "act_math.h"
 #include "api_internal.h"
+#include "lowp_tile.h"
 #include "mx_math.h"
 
 namespace sputnik_amd {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kB = 128;                  // block edge = one step of k
+// kThreads, kB (the block edge = one step of k), the vector types, the
+// scalar loads and the swizzle keys: lowp_tile.h.
+using namespace lowp;
+
 constexpr int kATileBytes = kB * kB;
 constexpr int BTileBytes(bool b4) { return b4 ? kB * kB / 2 : kB * kB; }
 constexpr int kScaleBytes = kB * 4;      // one dword per row (column)
@@ -98,25 +101,6 @@ static_assert(StageBytes(false) % 256 == 0 && StageBytes(true) % 256 == 0 &&
                   BTileBytes(true) % 256 == 0,
               "every tile starts on a bank row");
 static_assert(kB * kB * 2 <= LdsBytes(true), "the output image reuses the ring");
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define SPUTNIK_MXG_LDS(p) ((__attribute__((address_space(3))) void *)(p))
-#define SPUTNIK_MXG_GLOBAL(p) \
-  ((const __attribute__((address_space(1))) void *)(p))
-
-// (an int16 entry through the scalar cache, from its aligned dword)
-__device__ __forceinline__ int scalar_short(const short *p) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const int v = *reinterpret_cast<const __attribute__((address_space(4))) int *>(
-      a & ~uintptr_t(3));
-  return (short)((a & 2) ? (v >> 16) : v);
-}
-
-__device__ __forceinline__ int key8(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ int key4(int row) { return (row >> 2) & 3; }
 
 struct MxGatedParams {
   const char *a;            // Aq [m, k]
@@ -176,8 +160,8 @@ __global__ void __launch_bounds__(kThreads)
       const int row = (piece >> 7) + (lane >> 3);
       const int chunk = (lane & 7) ^ key8(row);
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MXG_GLOBAL(a_tile + row * k_bytes + chunk * 16),
-          SPUTNIK_MXG_LDS(stage + piece), 16, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(a_tile + row * k_bytes + chunk * 16),
+          SPUTNIK_LOWP_LDS(stage + piece), 16, 0, 0);
     }
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
@@ -196,8 +180,8 @@ __global__ void __launch_bounds__(kThreads)
           chunk = (lane & 7) ^ key8(row);
         }
         __builtin_amdgcn_global_load_lds(
-            SPUTNIK_MXG_GLOBAL(b_tile + row * b_pitch + chunk * 16),
-            SPUTNIK_MXG_LDS(to + piece), 16, 0, 0);
+            SPUTNIK_LOWP_GLOBAL(b_tile + row * b_pitch + chunk * 16),
+            SPUTNIK_LOWP_LDS(to + piece), 16, 0, 0);
       }
     }
     // Scale units of 64 dwords: 0, 1 the A rows, 2, 3 the gate columns, 4, 5
@@ -216,8 +200,8 @@ __global__ void __launch_bounds__(kThreads)
               (long long)(nb * kB + at) * b_scale_pitch + kb * 4;
       }
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MXG_GLOBAL(src),
-          SPUTNIK_MXG_LDS(stage + kScaleOff + unit * 256), 4, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(src),
+          SPUTNIK_LOWP_LDS(stage + kScaleOff + unit * 256), 4, 0, 0);
     }
   };
 

@@ -14,8 +14,9 @@
 //   staging  16-byte LDS-DMA (global_load_lds) for the tiles, 4-byte for the
 //            scale dwords (waves 0, 1: rows; waves 2, 3: columns), so the loop
 //            has no register-destination load. The DMA's LDS image is
-//            lane-linear, so the swizzle sits on the source address: the lane
-//            that lands on 16-byte slot p of row r fetches chunk p ^ key(r).
+//            lane-linear, so the swizzle sits on the source address
+//            (lowp_tile.h has the keys and why the reads below are
+//            conflict-free).
 //   reads    lane l (r = l % 16, g = l / 16) of a 16-row fragment. The k map
 //            of the instruction, measured (mx.h): an e4m3 operand wants k =
 //            16 g .. 16 g + 15 in registers 0 - 3 and k = 64 + 16 g .. 64 +
@@ -54,15 +55,8 @@
 // the adds are the DSD's, untouched: only the epilogue differs. The sink may
 // hold fp32 and may be added into, and round_out(acc + float(C_old)) needs
 // the unrounded acc next to C_old, so the tile leaves the registers as an
-// fp32 image. 128 rows of 512 bytes are 64 KiB; the 66 KiB ring leaves
-// exactly 16 bytes of padding per row (pitch 132 dwords). A wave's store of
-// acc[ti][tj][e] puts lane (r, g) at row 4 g + e, column r of a 16 x 16 tile:
-// dword 132 (4 g) + r, bank (16 g + r) % 64: 64 lanes, 64 banks, once each (in
-// halves of 32 lanes on a 32-bank view: banks r and 16 + r). Without the
-// padding the four lane groups would meet on one bank. The image then leaves
-// as 16-byte pieces of the output type: a lane reads 16 (fp32: 4 x f32) or 32
-// (T: 8 x f32 -> 8 x T) consecutive bytes of an image row, consecutive lanes
-// consecutive pieces, so both the LDS reads and the global accesses of C and
+// fp32 image at pitch kImagePitch (lowp_tile.h has the bank argument) and
+// then as 16-byte pieces of the output type, so the global accesses of C and
 // C_old are row-contiguous. A block row without stored blocks is left alone
 // under `add` (neither read nor written) and is +0 otherwise. The kWgrad =
 // false instantiations keep their code.
@@ -85,12 +79,15 @@
 #include <type_traits>
 
 #include "api_internal.h"
+#include "lowp_tile.h"
 
 namespace sputnik_amd {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kB = 128;                  // block edge = one step of k
+// kThreads, kB (the block edge = one step of k), the vector types, the
+// scalar loads and the swizzle keys: lowp_tile.h.
+using namespace lowp;
+
 constexpr int kATileBytes = kB * kB;
 constexpr int BTileBytes(bool b4) { return b4 ? kB * kB / 2 : kB * kB; }
 constexpr int kScaleBytes = kB * 4;      // one dword per row (column)
@@ -108,35 +105,8 @@ static_assert(3 * StageBytes(false) * 2 > 160 * 1024,
               "a third e4m3 stage would cost the second workgroup");
 static_assert(kB * kB * 2 <= LdsBytes(false) && kB * kB * 2 <= LdsBytes(true),
               "the output tile reuses the ring");
-// (the wgrad's fp32 image: four floats of padding per row put the four row
-// groups of a 16 x 16 accumulator store on different banks)
-constexpr int kImagePitch = kB + 4;
 static_assert(kB * kImagePitch * 4 <= LdsBytes(false),
               "the fp32 image of the wgrad reuses the e4m3 ring");
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define SPUTNIK_MX_LDS(p) ((__attribute__((address_space(3))) void *)(p))
-#define SPUTNIK_MX_GLOBAL(p) \
-  ((const __attribute__((address_space(1))) void *)(p))
-
-// Wave-uniform loads through the scalar cache: the metadata is read-only for
-// the whole launch.
-__device__ __forceinline__ int scalar_int(const int *p) {
-  return *(const __attribute__((address_space(4))) int *)p;
-}
-// (an int16 entry from its aligned dword: any 2-byte-aligned base works)
-__device__ __forceinline__ int scalar_short(const short *p) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const int v = *reinterpret_cast<const __attribute__((address_space(4))) int *>(
-      a & ~uintptr_t(3));
-  return (short)((a & 2) ? (v >> 16) : v);
-}
-
-__device__ __forceinline__ int key8(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ int key4(int row) { return (row >> 2) & 3; }
 
 struct MxGemmParams {
   const char *a;            // SDD: Aq [m, k]; DSD: the stored blocks of Sq
@@ -238,8 +208,8 @@ __global__ void __launch_bounds__(kThreads)
       const int row = (piece >> 7) + (lane >> 3);
       const int chunk = (lane & 7) ^ key8(row);
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX_GLOBAL(a_tile + row * a_pitch + chunk * 16),
-          SPUTNIK_MX_LDS(stage + piece), 16, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(a_tile + row * a_pitch + chunk * 16),
+          SPUTNIK_LOWP_LDS(stage + piece), 16, 0, 0);
     }
 #pragma unroll
     for (int pass = 0; pass < BTileBytes(kB4) / (kThreads * 16); ++pass) {
@@ -253,20 +223,20 @@ __global__ void __launch_bounds__(kThreads)
         chunk = (lane & 7) ^ key8(row);
       }
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX_GLOBAL(b_tile + row * b_pitch + chunk * 16),
-          SPUTNIK_MX_LDS(stage + kBOff + piece), 16, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(b_tile + row * b_pitch + chunk * 16),
+          SPUTNIK_LOWP_LDS(stage + kBOff + piece), 16, 0, 0);
     }
     if (wave < kB / 64) {
       const int row = wave * 64 + lane;
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX_GLOBAL(a_scale + row * a_scale_pitch),
-          SPUTNIK_MX_LDS(stage + kScaleOff + wave * 256), 4, 0, 0);
+          SPUTNIK_LOWP_GLOBAL(a_scale + row * a_scale_pitch),
+          SPUTNIK_LOWP_LDS(stage + kScaleOff + wave * 256), 4, 0, 0);
     } else {
       const int col = (wave - kB / 64) * 64 + lane;
       __builtin_amdgcn_global_load_lds(
-          SPUTNIK_MX_GLOBAL(b_scales +
+          SPUTNIK_LOWP_GLOBAL(b_scales +
                             ((long long)(nb * kB + col) * p.k_blocks + kb) * 4),
-          SPUTNIK_MX_LDS(stage + kScaleOff + wave * 256), 4, 0, 0);
+          SPUTNIK_LOWP_LDS(stage + kScaleOff + wave * 256), 4, 0, 0);
     }
   };
 

@@ -87,7 +87,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Callable, Optional, Tuple
 
 import torch
 
@@ -2168,7 +2168,85 @@ def moe_glu_mx(x: torch.Tensor, top_experts: torch.Tensor,
                                expert_weights, bias=b2)
 
 
-# ---- FP8 gradients (sputnik/block/fp8.h, "Gradients") ------------------------
+# ---- FP8 and MXFP8 gradients: one expert chain over a format record ----------
+# (sputnik/block/fp8.h and mx.h, "Gradients" and "Gradients of a gated expert")
+
+@dataclass(frozen=True)
+class _Lowp:
+    """One low-precision format of the expert chain below. The chain's
+    options travel as two dicts, `qopt` to the quantisers and `popt` to the
+    products: {"pow2": ...} and {"accumulate": ...} for FP8, empty for MX."""
+
+    scale_dtype: torch.dtype
+    row_scales: Callable      # (m, n) -> shape of the scales of q [m, n]
+    col_scales: Callable      # (m, n) -> shape of the scales of qt [n, m]
+    block_scales: Callable    # nb -> shape of the scales of nb blocks
+    sparse: type
+    weight: type
+    QuantizeTiles: Callable
+    QuantizeBlocks: Callable
+    QuantizeBlocksGated: Callable
+    QuantizeBlocksGatedGrad: Callable
+    DsdWgrad: Callable
+    DsdPair: Callable
+    sdd: Callable
+    dsd: Callable
+    quantize_weight: Callable
+    quantize_sparse: Callable
+    # (the public names the messages carry)
+    tiles: str
+    sparse_t: str
+    wgrad: str
+    pair: str
+    # How backward obtains the transposed weights. FP8: the exact byte
+    # transposes of the forward weights, made in forward and kept on ctx. MX:
+    # an MX weight has no exact transpose, so the 16-bit weights are saved
+    # and quantised again in backward.
+    keeps_transposes: bool
+    contiguous_dy: bool       # backward passes dy.contiguous() on
+
+
+_E4M3 = torch.float8_e4m3fn
+
+_FP8 = _Lowp(
+    torch.float32, lambda m, n: (m, n // BLOCK), lambda m, n: (m // BLOCK, n),
+    lambda nb: (nb * BLOCK,), Fp8SparseMatrix, Fp8Weight, QuantizeTiles,
+    QuantizeBlocks, QuantizeBlocksGated, QuantizeBlocksGatedGrad, DsdFp8Wgrad,
+    DsdFp8Pair, sdd_fp8, dsd_fp8, quantize_weight, quantize_sparse,
+    "quantize_tiles", "quantize_sparse_t", "dsd_fp8_wgrad", "dsd_fp8_pair",
+    keeps_transposes=True, contiguous_dy=False)
+
+_MX = _Lowp(
+    torch.uint8, lambda m, n: (m, n // 32), lambda m, n: (n, m // 32),
+    lambda nb: (nb * BLOCK, 4), MxSparseMatrix, MxWeight, QuantizeTilesMx,
+    QuantizeBlocksMx, QuantizeBlocksMxGated, QuantizeBlocksMxGatedGrad,
+    DsdMxWgrad, DsdMxPair, sdd_mx, dsd_mx, quantize_weight_mx,
+    quantize_sparse_mx, "quantize_tiles_mx", "quantize_sparse_mx_t",
+    "dsd_mx_wgrad", "dsd_mx_pair", keeps_transposes=False, contiguous_dy=True)
+
+
+def _quantize_tiles(fmt: _Lowp, x, rows: bool, cols: bool, **qopt):
+    what = fmt.tiles
+    _check_dtypes(x)
+    _no_grad(what, x)
+    if x.dim() != 2 or int(x.shape[0]) % BLOCK or int(x.shape[1]) % BLOCK:
+        raise ValueError(f"{what}: x is 2-D with multiples of 128")
+    if not (rows or cols):
+        raise ValueError(f"{what}: no output asked for")
+    x = x.contiguous()
+    m, n = int(x.shape[0]), int(x.shape[1])
+    q = s = qt = st = None
+    if rows:
+        q = torch.empty(m, n, dtype=_E4M3, device=x.device)
+        s = torch.empty(fmt.row_scales(m, n), dtype=fmt.scale_dtype,
+                        device=x.device)
+    if cols:
+        qt = torch.empty(n, m, dtype=_E4M3, device=x.device)
+        st = torch.empty(fmt.col_scales(m, n), dtype=fmt.scale_dtype,
+                         device=x.device)
+    fmt.QuantizeTiles(x, q, s, qt, st, **qopt)
+    return q, s, qt, st
+
 
 def quantize_tiles(x: torch.Tensor, rows: bool = True, cols: bool = True,
                    pow2: bool = False):
@@ -2177,53 +2255,79 @@ def quantize_tiles(x: torch.Tensor, rows: bool = True, cols: bool = True,
     qt torch.float8_e4m3fn [cols, rows] and scales_t fp32 [rows / 128, cols]
     with one scale per 128 x 1 column tile, the dense operand of
     dsd_fp8_wgrad. A pair that is not asked for is (None, None)."""
-    _check_dtypes(x)
-    _no_grad("quantize_tiles", x)
-    if x.dim() != 2 or int(x.shape[0]) % BLOCK or int(x.shape[1]) % BLOCK:
-        raise ValueError("quantize_tiles: x is 2-D with multiples of 128")
-    if not (rows or cols):
-        raise ValueError("quantize_tiles: no output asked for")
-    x = x.contiguous()
-    m, n = int(x.shape[0]), int(x.shape[1])
-    q = s = qt = st = None
-    if rows:
-        q = torch.empty(m, n, dtype=torch.float8_e4m3fn, device=x.device)
-        s = torch.empty(m, n // BLOCK, dtype=torch.float32, device=x.device)
-    if cols:
-        qt = torch.empty(n, m, dtype=torch.float8_e4m3fn, device=x.device)
-        st = torch.empty(m // BLOCK, n, dtype=torch.float32, device=x.device)
-    QuantizeTiles(x, q, s, qt, st, pow2)
-    return q, s, qt, st
+    return _quantize_tiles(_FP8, x, rows, cols, pow2=pow2)
 
 
-def _quantize_blocks(sparse: SparseMatrix, stage, act, z, rows: bool,
-                     cols: bool, pow2: bool):
-    """QuantizeBlocks over sparse's block values: (the Fp8SparseMatrix of
-    sparse's topology or None, the Fp8SparseMatrix of the transposed
-    topology or None)."""
+def quantize_tiles_mx(x: torch.Tensor, rows: bool = True, cols: bool = True):
+    """(q, scales, qt, scales_t) of x [rows, cols] (fp16 / bf16, both
+    multiples of 128) as MXFP8, read once: q / scales as quantize_rows_mx,
+    bit for bit; qt torch.float8_e4m3fn [cols, rows] and scales_t uint8
+    [cols, rows / 32], one e8m0 byte per column and 32 rows: x^T as an MX
+    weight, the dense operand of dsd_mx_wgrad. A pair that is not asked for
+    is (None, None)."""
+    return _quantize_tiles(_MX, x, rows, cols)
+
+
+def _lowp_images(fmt: _Lowp, nb: int, rows: bool, cols: bool, dev):
+    """(q, scales, qt, scales_t) buffers of fmt's block quantisers, None for
+    a pair that is not asked for."""
+    out = []
+    for want in (rows, cols):
+        out += [torch.empty(nb, BLOCK, BLOCK, dtype=_E4M3, device=dev)
+                if want else None,
+                torch.empty(fmt.block_scales(nb), dtype=fmt.scale_dtype,
+                            device=dev) if want else None]
+    return tuple(out)
+
+
+def _lowp_views(fmt: _Lowp, topo: SparseMatrix, images):
+    """(fmt's sparse matrix of topo's topology or None, that of the
+    transposed topology or None) over the images a block quantiser filled."""
+    q, s, qt, st = images
+    meta = topo._meta
+    by_rows = None if q is None else fmt.sparse(topo, q, s)
+    by_cols = None if qt is None else fmt.sparse(
+        SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
+                     meta.indices_t), qt, st)
+    return by_rows, by_cols
+
+
+def _lowp_quantize_blocks(fmt: _Lowp, sparse: SparseMatrix, stage, act, z,
+                          rows: bool, cols: bool, **qopt):
+    """fmt.QuantizeBlocks over sparse's block values: (fmt's sparse matrix of
+    sparse's topology or None, that of the transposed topology or None)."""
     meta, nb = sparse._meta, sparse.nnz_blocks
     data = sparse.data.contiguous()
-    dev = data.device
-    q = s = qt = st = None
-    if rows:
-        q = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
-                        device=dev)
-        s = torch.empty(nb * BLOCK, dtype=torch.float32, device=dev)
     if cols:
         meta.ensure_transposed(data)
-        qt = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
-                         device=dev)
-        st = torch.empty(nb * BLOCK, dtype=torch.float32, device=dev)
+    images = _lowp_images(fmt, nb, rows, cols, data.device)
     if nb:
-        QuantizeBlocks(meta.descriptor(data), q, s, qt, st, stage, act,
-                       None if z is None else z.contiguous(), pow2)
-    by_rows = Fp8SparseMatrix(sparse, q, s) if rows else None
-    by_cols = None
-    if cols:
-        by_cols = Fp8SparseMatrix(
-            SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
-                         meta.indices_t), qt, st)
-    return by_rows, by_cols
+        fmt.QuantizeBlocks(meta.descriptor(data), *images, stage, act,
+                           None if z is None else z.contiguous(), **qopt)
+    return _lowp_views(fmt, sparse, images)
+
+
+def _quantize_sparse_t(fmt: _Lowp, sparse, activation, z, rows: bool, **qopt):
+    what = fmt.sparse_t
+    if not isinstance(sparse, SparseMatrix) or sparse.is_transposed():
+        raise TypeError(f"{what} takes a SparseMatrix (not a .t() view)")
+    _check_dtypes(sparse.data)
+    _no_grad(what, sparse.data, None if z is None else z.data)
+    stage = None
+    if z is not None:
+        if (not isinstance(z, SparseMatrix) or z._meta is not sparse._meta
+                or z.is_transposed() or z.dtype != sparse.dtype):
+            raise ValueError(f"{what}: z must share sparse's topology and "
+                             "dtype")
+        if activation is None:
+            raise ValueError(f"{what}: z needs its activation")
+        stage = "act_grad"
+    elif activation is not None:
+        stage = "act"
+    act = None if activation is None else _act_code(activation)
+    return _lowp_quantize_blocks(fmt, sparse, stage, act,
+                                 None if z is None else z.data, rows, True,
+                                 **qopt)
 
 
 def quantize_sparse_t(sparse: SparseMatrix, activation=None,
@@ -2236,26 +2340,53 @@ def quantize_sparse_t(sparse: SparseMatrix, activation=None,
     quantize_sparse does it; with `z` (same topology and dtype) sparse *
     act'(z), as sdd_act's gradient evaluates it, rounded to sparse's dtype
     first."""
-    if not isinstance(sparse, SparseMatrix) or sparse.is_transposed():
-        raise TypeError("quantize_sparse_t takes a SparseMatrix (not a .t() "
-                        "view)")
-    _check_dtypes(sparse.data)
-    _no_grad("quantize_sparse_t", sparse.data, None if z is None else z.data)
-    stage = None
-    if z is not None:
-        if (not isinstance(z, SparseMatrix) or z._meta is not sparse._meta
-                or z.is_transposed() or z.dtype != sparse.dtype):
-            raise ValueError("quantize_sparse_t: z must share sparse's "
-                             "topology and dtype")
-        if activation is None:
-            raise ValueError("quantize_sparse_t: z needs its activation")
-        stage = "act_grad"
-    elif activation is not None:
-        stage = "act"
-    act = None if activation is None else _act_code(activation)
-    return _quantize_blocks(sparse, stage, act,
-                            None if z is None else z.data, False, True,
-                            pow2)[1]
+    return _quantize_sparse_t(_FP8, sparse, activation, z, False,
+                              pow2=pow2)[1]
+
+
+def quantize_sparse_mx_t(sparse: SparseMatrix, activation=None,
+                         z: Optional[SparseMatrix] = None
+                         ) -> Tuple[MxSparseMatrix, MxSparseMatrix]:
+    """(the MxSparseMatrix of `sparse`, the MxSparseMatrix of sparse^T) from
+    one pass over the block values. The first is quantize_sparse_mx's, bit
+    for bit, the operand of dsd_mx; the second holds sparse's blocks
+    transposed and in the transposed order, scaled per source column and 32
+    source rows, the sparse operand of dsd_mx_wgrad. With `activation` alone
+    act(sparse) is quantised; with `z` (same topology and dtype) sparse *
+    act'(z), as sdd_act's gradient evaluates it, rounded to sparse's dtype
+    first."""
+    return _quantize_sparse_t(_MX, sparse, activation, z, True)
+
+
+def _dsd_wgrad(fmt: _Lowp, st, bqt, bst, out=None, add=False,
+               out_dtype=torch.bfloat16, **popt):
+    what = fmt.wgrad
+    if not isinstance(st, fmt.sparse):
+        raise TypeError(f"{what}: st must come from {fmt.sparse_t}")
+    if not isinstance(bqt, torch.Tensor) or bqt.dim() != 2:
+        raise TypeError(f"{what}: bqt is {fmt.tiles}' qt")
+    m, n = st.shape[0], int(bqt.shape[0])
+    if st.shape[1] != int(bqt.shape[1]):
+        raise ValueError(f"{what} shapes {st.shape} x "
+                         f"{(int(bqt.shape[1]), n)}")
+    kinds = (torch.float16, torch.bfloat16, torch.float32)
+    if out is None:
+        if add:
+            raise ValueError(f"{what}: add needs `out`")
+        if out_dtype not in kinds:
+            raise TypeError(f"{what}: out_dtype must be torch.float16, "
+                            "torch.bfloat16 or torch.float32")
+        out = torch.empty(m, n, dtype=out_dtype, device=bqt.device)
+    else:
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != (m, n)
+                or not out.is_contiguous()):
+            raise ValueError(f"{what}: out must be a contiguous {(m, n)} "
+                             "tensor")
+        if out.dtype not in kinds:
+            raise TypeError(f"{what}: out must be fp16, bf16 or fp32")
+    fmt.DsdWgrad(st._descriptor(), st.scales, bqt, bst, Matrix(m, n, out),
+                 add=add, **popt)
+    return out
 
 
 def dsd_fp8_wgrad(st: Fp8SparseMatrix, bqt: torch.Tensor, bst: torch.Tensor,
@@ -2271,94 +2402,276 @@ def dsd_fp8_wgrad(st: Fp8SparseMatrix, bqt: torch.Tensor, bst: torch.Tensor,
     round(acc + out), rounded once, and rows that meet no block of st are
     left untouched. Bitwise reproducible."""
     _accumulate(accumulate, "dsd_fp8_wgrad")
-    if not isinstance(st, Fp8SparseMatrix):
-        raise TypeError("dsd_fp8_wgrad: st must come from quantize_sparse_t")
-    if not isinstance(bqt, torch.Tensor) or bqt.dim() != 2:
-        raise TypeError("dsd_fp8_wgrad: bqt is quantize_tiles' qt")
-    m, n = st.shape[0], int(bqt.shape[0])
-    if st.shape[1] != int(bqt.shape[1]):
-        raise ValueError(f"dsd_fp8_wgrad shapes {st.shape} x "
-                         f"{(int(bqt.shape[1]), n)}")
-    if out is None:
-        if add:
-            raise ValueError("dsd_fp8_wgrad: add needs `out`")
-        if out_dtype not in (torch.float16, torch.bfloat16, torch.float32):
-            raise TypeError("dsd_fp8_wgrad: out_dtype must be torch.float16, "
-                            "torch.bfloat16 or torch.float32")
-        out = torch.empty(m, n, dtype=out_dtype, device=bqt.device)
-    else:
-        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != (m, n)
-                or not out.is_contiguous()):
-            raise ValueError(f"dsd_fp8_wgrad: out must be a contiguous "
-                             f"{(m, n)} tensor")
-        if out.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-            raise TypeError("dsd_fp8_wgrad: out must be fp16, bf16 or fp32")
-    DsdFp8Wgrad(st._descriptor(), st.scales, bqt, bst, Matrix(m, n, out),
-                add=add, accumulate=accumulate)
+    return _dsd_wgrad(_FP8, st, bqt, bst, out, add, out_dtype,
+                      accumulate=accumulate)
+
+
+def dsd_mx_wgrad(st: MxSparseMatrix, bqt: torch.Tensor, bst: torch.Tensor,
+                 out: Optional[torch.Tensor] = None, add: bool = False,
+                 out_dtype=torch.bfloat16) -> torch.Tensor:
+    """st . B as a dense [m, n] tensor, the weight-gradient product in MXFP8:
+    st the transposed half of quantize_sparse_mx_t ([m, k], k the token
+    dimension), B [k, n] given as quantize_tiles_mx' column pair bqt [n, k],
+    bst [n, k / 32]. dsd_mx's arithmetic. Writes `out` (contiguous [m, n],
+    fp16 / bf16 / fp32) or a new tensor of `out_dtype` (the same three); with
+    `add`, out = round(acc + out), rounded once, and rows that meet no block
+    of st are left untouched. Bitwise reproducible."""
+    return _dsd_wgrad(_MX, st, bqt, bst, out, add, out_dtype)
+
+
+def _dsd_pair(fmt: _Lowp, sq1, w1, sq2, w2, out_dtype, **popt):
+    what, sparse, weight = fmt.pair, fmt.sparse.__name__, fmt.weight.__name__
+    if not isinstance(sq1, fmt.sparse) or not isinstance(sq2, fmt.sparse):
+        raise TypeError(f"{what}: sq1 and sq2 must be {sparse}")
+    if sq1._meta is not sq2._meta or sq1.is_transposed() != sq2.is_transposed():
+        raise ValueError(f"{what}: sq1 and sq2 must share one topology")
+    if not isinstance(w1, fmt.weight) or not isinstance(w2, fmt.weight):
+        raise TypeError(f"{what}: w1 and w2 must be {weight}s")
+    # (an MxWeight names its element format; an Fp8Weight has the one)
+    if any(getattr(w, "format", "e4m3") != "e4m3" for w in (w1, w2)):
+        raise ValueError(f"{what}: the weights must be 'e4m3'")
+    _out_dtype(out_dtype, what)
+    if sq1.shape[1] != w1.k or w1.shape != w2.shape:
+        raise ValueError(f"{what} shapes {sq1.shape} x {w1.shape} + "
+                         f"{sq2.shape} x {w2.shape}")
+    out = torch.empty(sq1.shape[0], w1.n, dtype=out_dtype, device=sq1.device)
+    fmt.DsdPair(sq1._descriptor(), sq1.scales, w1.q, w1.scales, sq2.data,
+                sq2.scales, w2.q, w2.scales,
+                Matrix(out.shape[0], out.shape[1], out), **popt)
     return out
 
 
-class _MLPFp8(torch.autograd.Function):
-    """y = dsd_fp8(quantize_sparse(sdd_fp8(x, w1t^T), act), w2) and the
-    backward pass of fp8.h's table. Keeps Z, the column quantisation of X
-    (bytes, not the 16-bit X) and the backward layouts of the two weights."""
+def dsd_fp8_pair(sq1: Fp8SparseMatrix, w1: Fp8Weight, sq2: Fp8SparseMatrix,
+                 w2: Fp8Weight, out_dtype=torch.bfloat16,
+                 accumulate: str = "fp32") -> torch.Tensor:
+    """sq1 . w1 + sq2 . w2 as a dense [m, n] tensor of `out_dtype`, both
+    products in fp8 through one fp32 accumulator and rounded once: sq1 and
+    sq2 are quantised block values on one topology (the same metadata), w1
+    and w2 two Fp8Weights of [k, n]. Bit for bit dsd_fp8 over the
+    concatenated operands [sq1 | sq2] . [w1; w2], which are never formed: a
+    block row takes sq1's blocks in storage order, then sq2's. The dX of a
+    gated expert. Forward only. `accumulate` as sdd_fp8."""
+    _accumulate(accumulate, "dsd_fp8_pair")
+    return _dsd_pair(_FP8, sq1, w1, sq2, w2, out_dtype, accumulate=accumulate)
+
+
+def dsd_mx_pair(sq1: MxSparseMatrix, w1: MxWeight, sq2: MxSparseMatrix,
+                w2: MxWeight, out_dtype=torch.bfloat16) -> torch.Tensor:
+    """sq1 . w1 + sq2 . w2 as a dense [m, n] tensor of `out_dtype`, both
+    products in MXFP8 through one fp32 accumulator and rounded once: sq1 and
+    sq2 are quantised block values on one topology (the same metadata), w1
+    and w2 two e4m3 MxWeights of [k, n]. Bit for bit dsd_mx over the
+    concatenated operands [sq1 | sq2] . [w1; w2], which are never formed: a
+    block row takes sq1's blocks in storage order, then sq2's. The dX of a
+    gated expert. Forward only."""
+    return _dsd_pair(_MX, sq1, w1, sq2, w2, out_dtype)
+
+
+def _keep_weights(ctx, fmt: _Lowp, weights):
+    """What backward will make the transposed layouts from, for `weights` =
+    (quantised weight, 16-bit weight, needed) in the order backward's
+    launches want them: (FP8) the transposes themselves on ctx.wt, or (MX)
+    the 16-bit weights, returned for save_for_backward."""
+    if fmt.keeps_transposes:
+        ctx.wt = [wq.t() if need else None for wq, _, need in weights]
+        return ()
+    ctx.wt = None
+    return tuple(w if need else None for _, w, need in weights)
+
+
+def _kept_weight(ctx, fmt: _Lowp, saved, i: int, transpose: bool):
+    """Weight i of _keep_weights in its backward layout; `transpose` as
+    quantize_weight's, for the 16-bit weight."""
+    if fmt.keeps_transposes:
+        return ctx.wt[i]
+    return fmt.quantize_weight(saved[i], transpose=transpose)
+
+
+def _wgrad_to(fmt: _Lowp, st, bqt, bst, sink, dt, popt):
+    """sink += st . B and None, or the product as a new tensor of dt."""
+    if sink is not None:
+        _dsd_wgrad(fmt, st, bqt, bst, sink, True, **popt)
+        return None
+    return _dsd_wgrad(fmt, st, bqt, bst, out_dtype=dt, **popt)
+
+
+class _LowpMLP(torch.autograd.Function):
+    """y = dsd(quantize_sparse(sdd(x, w1t^T), act), w2) in fmt and the
+    backward pass of fp8.h's / mx.h's table. Keeps Z, the column quantisation
+    of X (bytes, not the 16-bit X) and what _keep_weights keeps."""
 
     @staticmethod
-    def forward(ctx, x, w1t, w2, topo, act, accumulate, pow2, w1_sink,
+    def forward(ctx, x, w1t, w2, topo, act, fmt, qopt, popt, w1_sink,
                 w2_sink):
         need_x, need_w1, need_w2 = ctx.needs_input_grad[:3]
         need_w1 = need_w1 or w1_sink is not None
         need_w2 = need_w2 or w2_sink is not None
-        ctx.topo, ctx.act, ctx.mode, ctx.pow2 = topo, act, accumulate, pow2
+        ctx.topo, ctx.act, ctx.fmt = topo, act, fmt
+        ctx.qopt, ctx.popt = qopt, popt
         ctx.w1_sink, ctx.w2_sink = w1_sink, w2_sink
         ctx.need = (need_x, need_w1, need_w2)
-        w1q = quantize_weight(w1t, transpose=True, pow2=pow2)   # [h, F]
-        w2q = quantize_weight(w2, pow2=pow2)                    # [F, h]
-        xq, xs, xqt, xst = quantize_tiles(x, cols=need_w1, pow2=pow2)
-        z = sdd_fp8(xq, xs, w1q, topo, x.dtype, accumulate)
-        y = dsd_fp8(quantize_sparse(z, act, pow2=pow2), w2q, x.dtype,
-                    accumulate)
+        w1q = fmt.quantize_weight(w1t, transpose=True, **qopt)  # [h, F]
+        w2q = fmt.quantize_weight(w2, **qopt)                   # [F, h]
+        xq, xs, xqt, xst = _quantize_tiles(fmt, x, True, need_w1, **qopt)
+        z = fmt.sdd(xq, xs, w1q, topo, x.dtype, **popt)
+        y = fmt.dsd(fmt.quantize_sparse(z, act, **qopt), w2q, x.dtype, **popt)
         if any(ctx.need):
             # (dH = dY W2^T and dX = dZ W1t take the transposed layouts)
-            ctx.w2q_t = w2q.t() if need_x or need_w1 else None
-            ctx.w1q_t = w1q.t() if need_x else None
-            ctx.save_for_backward(z.data, xqt, xst)
+            kept = _keep_weights(ctx, fmt, ((w2q, w2, need_x or need_w1),
+                                            (w1q, w1t, need_x)))
+            ctx.save_for_backward(z.data, xqt, xst, *kept)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        z_data, xqt, xst = ctx.saved_tensors
+        z_data, xqt, xst, *kept = ctx.saved_tensors
         need_x, need_w1, need_w2 = ctx.need
-        topo, act, mode, pow2 = ctx.topo, ctx.act, ctx.mode, ctx.pow2
+        topo, act, fmt, qopt, popt = (ctx.topo, ctx.act, ctx.fmt, ctx.qopt,
+                                      ctx.popt)
         z = topo.with_data(z_data)
         dt = z_data.dtype
         dx = dw1 = dw2 = None
         need_dz = need_x or need_w1
-        dyq, dys, dyqt, dyst = quantize_tiles(dy, rows=need_dz, cols=need_w2,
-                                              pow2=pow2)
+        if fmt.contiguous_dy:
+            dy = dy.contiguous()
+        dyq, dys, dyqt, dyst = _quantize_tiles(fmt, dy, need_dz, need_w2,
+                                               **qopt)
         if need_w2:                                   # H^T dY
-            ht = _quantize_blocks(z, "act", act, None, False, True, pow2)[1]
-            if ctx.w2_sink is not None:
-                dsd_fp8_wgrad(ht, dyqt, dyst, ctx.w2_sink, True,
-                              accumulate=mode)
-            else:
-                dw2 = dsd_fp8_wgrad(ht, dyqt, dyst, out_dtype=dt,
-                                    accumulate=mode)
+            ht = _lowp_quantize_blocks(fmt, z, "act", act, None, False, True,
+                                       **qopt)[1]
+            dw2 = _wgrad_to(fmt, ht, dyqt, dyst, ctx.w2_sink, dt, popt)
             del ht
         if need_dz:
-            dh = sdd_fp8(dyq, dys, ctx.w2q_t, topo, dt, mode)   # dY W2^T
+            # dY W2^T: W2 read as [n = F, k = h]
+            dh = fmt.sdd(dyq, dys, _kept_weight(ctx, fmt, kept, 0, True),
+                         topo, dt, **popt)
             # dZ = dH * act'(Z), quantised along both axes in one pass
-            dzq, dzt = _quantize_blocks(dh, "act_grad", act, z_data, need_x,
-                                        need_w1, pow2)
-            if need_x:
-                dx = dsd_fp8(dzq, ctx.w1q_t, dt, mode)          # dZ W1t
-            if ctx.w1_sink is not None:                         # dZ^T X
-                dsd_fp8_wgrad(dzt, xqt, xst, ctx.w1_sink, True,
-                              accumulate=mode)
-            elif need_w1:
-                dw1 = dsd_fp8_wgrad(dzt, xqt, xst, out_dtype=dt,
-                                    accumulate=mode)
-        return dx, dw1, dw2, None, None, None, None, None, None
+            dzq, dzt = _lowp_quantize_blocks(fmt, dh, "act_grad", act, z_data,
+                                             need_x, need_w1, **qopt)
+            if need_x:                                # dZ W1t: [k = F, n = h]
+                dx = fmt.dsd(dzq, _kept_weight(ctx, fmt, kept, 1, False), dt,
+                             **popt)
+            if need_w1:                               # dZ^T X
+                dw1 = _wgrad_to(fmt, dzt, xqt, xst, ctx.w1_sink, dt, popt)
+        return (dx, dw1, dw2) + (None,) * 7
+
+
+class _LowpGLUMLP(torch.autograd.Function):
+    """y = dsd(quantize_sparse(sdd(x, v1t^T), act, gate=sdd(x, w1t^T)), w2)
+    in fmt and the backward pass of fp8.h's / mx.h's gated table. Keeps G, U,
+    the column quantisation of X and what _keep_weights keeps."""
+
+    @staticmethod
+    def forward(ctx, x, w1t, v1t, w2, topo, act, fmt, qopt, popt, w1_sink,
+                v1_sink, w2_sink):
+        need_x, need_w1, need_v1, need_w2 = ctx.needs_input_grad[:4]
+        need_w1 = need_w1 or w1_sink is not None
+        need_v1 = need_v1 or v1_sink is not None
+        need_w2 = need_w2 or w2_sink is not None
+        ctx.topo, ctx.act, ctx.fmt = topo, act, fmt
+        ctx.qopt, ctx.popt = qopt, popt
+        ctx.sinks = (w1_sink, v1_sink, w2_sink)
+        ctx.need = (need_x, need_w1, need_v1, need_w2)
+        w1q = fmt.quantize_weight(w1t, transpose=True, **qopt)  # [h, F]
+        v1q = fmt.quantize_weight(v1t, transpose=True, **qopt)  # [h, F]
+        w2q = fmt.quantize_weight(w2, **qopt)                   # [F, h]
+        xq, xs, xqt, xst = _quantize_tiles(fmt, x, True, need_w1 or need_v1,
+                                           **qopt)
+        g = fmt.sdd(xq, xs, w1q, topo, x.dtype, **popt)
+        u = fmt.sdd(xq, xs, v1q, topo, x.dtype, **popt)
+        y = fmt.dsd(fmt.quantize_sparse(u, act, gate=g, **qopt), w2q, x.dtype,
+                    **popt)
+        if any(ctx.need):
+            # (D = dY W2^T and dX = dG W1t + dU V1t take the transposed
+            # layouts)
+            kept = _keep_weights(ctx, fmt, ((w2q, w2, any(ctx.need[:3])),
+                                            (w1q, w1t, need_x),
+                                            (v1q, v1t, need_x)))
+            ctx.save_for_backward(g.data, u.data, xqt, xst, *kept)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        g_data, u_data, xqt, xst, *kept = ctx.saved_tensors
+        need_x, need_w1, need_v1, need_w2 = ctx.need
+        w1_sink, v1_sink, w2_sink = ctx.sinks
+        topo, act, fmt, qopt, popt = (ctx.topo, ctx.act, ctx.fmt, ctx.qopt,
+                                      ctx.popt)
+        meta, nb, dt, dev = topo._meta, topo.nnz_blocks, g_data.dtype, dy.device
+        need_d = need_x or need_w1 or need_v1
+        if fmt.contiguous_dy:
+            dy = dy.contiguous()
+        dyq, dys, dyqt, dyst = _quantize_tiles(fmt, dy, need_d, need_w2,
+                                               **qopt)
+        dx = dw1 = dv1 = dw2 = None
+        if need_w2:                                   # H^T dY
+            meta.ensure_transposed(u_data)
+            h = _lowp_images(fmt, nb, False, True, dev)
+            if nb:
+                fmt.QuantizeBlocksGated(meta.descriptor(u_data), g_data, act,
+                                        *h, **qopt)
+            dw2 = _wgrad_to(fmt, _lowp_views(fmt, topo, h)[1], dyqt, dyst,
+                            w2_sink, dt, popt)
+            del h
+        if need_d:
+            # D = dY W2^T: W2 read as [n = F, k = h]
+            d = fmt.sdd(dyq, dys, _kept_weight(ctx, fmt, kept, 0, True), topo,
+                        dt, **popt)
+            # dG = D U act'(G) and dU = D act(G), each along the axes its
+            # products read, from one pass over D, G and U
+            if need_w1 or need_v1:
+                meta.ensure_transposed(u_data)
+            dg = _lowp_images(fmt, nb, need_x, need_w1, dev)
+            du = _lowp_images(fmt, nb, need_x, need_v1, dev)
+            if nb:
+                fmt.QuantizeBlocksGatedGrad(meta.descriptor(d.data), g_data,
+                                            u_data, act, dg, du, **qopt)
+            dgq, dgt = _lowp_views(fmt, topo, dg)
+            duq, dut = _lowp_views(fmt, topo, du)
+            if need_x:              # dG W1t + dU V1t: each [k = F, n = h]
+                dx = _dsd_pair(fmt, dgq,
+                               _kept_weight(ctx, fmt, kept, 1, False), duq,
+                               _kept_weight(ctx, fmt, kept, 2, False), dt,
+                               **popt)
+            if need_w1:                               # dG^T X
+                dw1 = _wgrad_to(fmt, dgt, xqt, xst, w1_sink, dt, popt)
+            if need_v1:                               # dU^T X
+                dv1 = _wgrad_to(fmt, dut, xqt, xst, v1_sink, dt, popt)
+        return (dx, dw1, dv1, dw2) + (None,) * 8
+
+
+_FP8_SINKS = ("w1t_grad_out", "v1t_grad_out", "w2_grad_out")
+_MX_SINKS = ("dw1t_out", "dv1t_out", "dw2_out")
+
+
+def _check_sinks(x, w2, sinks, names, what: str):
+    for sink, name in zip(sinks, names):
+        if sink is not None:
+            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
+                        f"{what}: {name}")
+
+
+def _lowp_mlp(fmt: _Lowp, what: str, x, w1t, v1t, w2, topo, activation, qopt,
+              popt, sinks, names):
+    """mlp_* (v1t None) and glu_mlp_*: the argument checks and the chain."""
+    gated = v1t is not None
+    ws = (w1t, v1t, w2) if gated else (w1t, w2)
+    _check_dtypes(x, *ws)
+    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
+        raise TypeError(f"{what}: topo must be a SparseMatrix (not a .t() "
+                        "view)")
+    if (x.dim() != 2 or w1t.dim() != 2
+            or any(tuple(w.shape) != tuple(w2.shape) for w in ws[:-1])
+            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
+            or int(w1t.shape[1]) != int(x.shape[1])
+            or int(x.shape[1]) % BLOCK):
+        raise ValueError(f"{what}: x [T, h], "
+                         + ("w1t, v1t and w2" if gated else "w1t and w2")
+                         + " [F, h], topo [T, F], all multiples of 128")
+    _check_sinks(x, w2, sinks, names, what)
+    chain = _LowpGLUMLP if gated else _LowpMLP
+    return chain.apply(x.contiguous(), *(w.contiguous() for w in ws), topo,
+                       _act_code(activation), fmt, qopt, popt, *sinks)
 
 
 def mlp_fp8(x: torch.Tensor, w1t: torch.Tensor, w2: torch.Tensor,
@@ -2380,196 +2693,33 @@ def mlp_fp8(x: torch.Tensor, w1t: torch.Tensor, w2: torch.Tensor,
     returned gradient. What needs_input_grad does not ask for is skipped.
     There are no biases; glu_mlp_fp8 is the gated form."""
     _accumulate(accumulate, "mlp_fp8")
-    _check_dtypes(x, w1t, w2)
-    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
-        raise TypeError("mlp_fp8: topo must be a SparseMatrix (not a .t() "
-                        "view)")
-    if (x.dim() != 2 or w1t.dim() != 2 or tuple(w1t.shape) != tuple(w2.shape)
-            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
-            or int(w1t.shape[1]) != int(x.shape[1])
-            or int(x.shape[1]) % BLOCK):
-        raise ValueError("mlp_fp8: x [T, h], w1t and w2 [F, h], topo [T, F], "
-                         "all multiples of 128")
-    for sink, what in ((w1t_grad_out, "w1t_grad_out"),
-                       (w2_grad_out, "w2_grad_out")):
-        if sink is not None:
-            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
-                        f"mlp_fp8: {what}")
-    return _MLPFp8.apply(x.contiguous(), w1t.contiguous(), w2.contiguous(),
-                         topo, _act_code(activation), accumulate, bool(pow2),
-                         w1t_grad_out, w2_grad_out)
+    return _lowp_mlp(_FP8, "mlp_fp8", x, w1t, None, w2, topo, activation,
+                     {"pow2": bool(pow2)}, {"accumulate": accumulate},
+                     (w1t_grad_out, w2_grad_out),
+                     ("w1t_grad_out", "w2_grad_out"))
 
 
-def moe_mlp_fp8_train(x: torch.Tensor, top_experts: torch.Tensor,
-                      expert_weights: torch.Tensor, w1t: torch.Tensor,
-                      w2: torch.Tensor, num_experts: int, activation=None,
-                      rows: Optional[int] = None, accumulate: str = "fp32",
-                      pow2: bool = False,
-                      w1t_grad_out: Optional[torch.Tensor] = None,
-                      w2_grad_out: Optional[torch.Tensor] = None
-                      ) -> torch.Tensor:
-    """moe_mlp with the expert products in fp8 and gradients: padded_gather
-    -> mlp_fp8 -> padded_scatter, the permutation with its existing
-    gradients. w1t and w2 are 16-bit [num_experts * ffn, d_model]; the other
-    arguments are moe_mlp's (activation None: "gelu"). Differentiable in x,
-    expert_weights, w1t and w2."""
-    _accumulate(accumulate, "moe_mlp_fp8_train")
-    if not isinstance(w1t, torch.Tensor) or w1t.dim() != 2:
-        raise ValueError("moe_mlp_fp8_train: w1t is [E * ffn, d_model]")
-    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
-                              None, num_experts, rows)
-    if route is None:
-        route = moe_route(top_experts, num_experts, rows)
-    xp = padded_gather(x, route)
-    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
-                           route.rows // BLOCK, dtype=x.dtype)
-    y = mlp_fp8(xp, w1t, w2, topo, "gelu" if activation is None else
-                activation, accumulate, pow2, w1t_grad_out, w2_grad_out)
-    return padded_scatter(y, route, expert_weights)
-
-
-# ---- FP8 gradients of a gated expert (fp8.h, "Gradients of a gated expert") ---
-
-def _fp8_images(nb: int, rows: bool, cols: bool, dev):
-    """(q, scales, qt, scales_t) buffers of a block quantiser, None for a
-    pair that is not asked for."""
-    out = []
-    for want in (rows, cols):
-        out += [torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
-                            device=dev) if want else None,
-                torch.empty(nb * BLOCK, dtype=torch.float32, device=dev)
-                if want else None]
-    return tuple(out)
-
-
-def _fp8_views(topo: SparseMatrix, images):
-    """(the Fp8SparseMatrix of topo's topology or None, that of the
-    transposed topology or None) over the images a block quantiser filled."""
-    q, s, qt, st = images
-    meta = topo._meta
-    by_rows = None if q is None else Fp8SparseMatrix(topo, q, s)
-    by_cols = None if qt is None else Fp8SparseMatrix(
-        SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
-                     meta.indices_t), qt, st)
-    return by_rows, by_cols
-
-
-def dsd_fp8_pair(sq1: Fp8SparseMatrix, w1: Fp8Weight, sq2: Fp8SparseMatrix,
-                 w2: Fp8Weight, out_dtype=torch.bfloat16,
-                 accumulate: str = "fp32") -> torch.Tensor:
-    """sq1 . w1 + sq2 . w2 as a dense [m, n] tensor of `out_dtype`, both
-    products in fp8 through one fp32 accumulator and rounded once: sq1 and
-    sq2 are quantised block values on one topology (the same metadata), w1
-    and w2 two Fp8Weights of [k, n]. Bit for bit dsd_fp8 over the
-    concatenated operands [sq1 | sq2] . [w1; w2], which are never formed: a
-    block row takes sq1's blocks in storage order, then sq2's. The dX of a
-    gated expert. Forward only. `accumulate` as sdd_fp8."""
-    _accumulate(accumulate, "dsd_fp8_pair")
-    if (not isinstance(sq1, Fp8SparseMatrix)
-            or not isinstance(sq2, Fp8SparseMatrix)):
-        raise TypeError("dsd_fp8_pair: sq1 and sq2 must be Fp8SparseMatrix")
-    if sq1._meta is not sq2._meta or sq1.is_transposed() != sq2.is_transposed():
-        raise ValueError("dsd_fp8_pair: sq1 and sq2 must share one topology")
-    if not isinstance(w1, Fp8Weight) or not isinstance(w2, Fp8Weight):
-        raise TypeError("dsd_fp8_pair: w1 and w2 must be Fp8Weights")
-    _out_dtype(out_dtype, "dsd_fp8_pair")
-    if sq1.shape[1] != w1.k or w1.shape != w2.shape:
-        raise ValueError(f"dsd_fp8_pair shapes {sq1.shape} x {w1.shape} + "
-                         f"{sq2.shape} x {w2.shape}")
-    out = torch.empty(sq1.shape[0], w1.n, dtype=out_dtype, device=sq1.device)
-    DsdFp8Pair(sq1._descriptor(), sq1.scales, w1.q, w1.scales, sq2.data,
-               sq2.scales, w2.q, w2.scales,
-               Matrix(out.shape[0], out.shape[1], out), accumulate=accumulate)
-    return out
-
-
-class _GLUMLPFp8(torch.autograd.Function):
-    """y = dsd_fp8(quantize_sparse(sdd_fp8(x, v1t^T), act, gate=sdd_fp8(x,
-    w1t^T)), w2) and the backward pass of fp8.h's gated table. Keeps G, U,
-    the column quantisation of X and the backward layouts of the weights."""
-
-    @staticmethod
-    def forward(ctx, x, w1t, v1t, w2, topo, act, accumulate, pow2, w1_sink,
-                v1_sink, w2_sink):
-        need_x, need_w1, need_v1, need_w2 = ctx.needs_input_grad[:4]
-        need_w1 = need_w1 or w1_sink is not None
-        need_v1 = need_v1 or v1_sink is not None
-        need_w2 = need_w2 or w2_sink is not None
-        ctx.topo, ctx.act, ctx.mode, ctx.pow2 = topo, act, accumulate, pow2
-        ctx.sinks = (w1_sink, v1_sink, w2_sink)
-        ctx.need = (need_x, need_w1, need_v1, need_w2)
-        w1q = quantize_weight(w1t, transpose=True, pow2=pow2)   # [h, F]
-        v1q = quantize_weight(v1t, transpose=True, pow2=pow2)   # [h, F]
-        w2q = quantize_weight(w2, pow2=pow2)                    # [F, h]
-        xq, xs, xqt, xst = quantize_tiles(x, cols=need_w1 or need_v1,
-                                          pow2=pow2)
-        g = sdd_fp8(xq, xs, w1q, topo, x.dtype, accumulate)
-        u = sdd_fp8(xq, xs, v1q, topo, x.dtype, accumulate)
-        y = dsd_fp8(quantize_sparse(u, act, gate=g, pow2=pow2), w2q, x.dtype,
-                    accumulate)
-        if any(ctx.need):
-            # (D = dY W2^T and dX = dG W1t + dU V1t take the transposed
-            # layouts)
-            ctx.w2q_t = w2q.t() if any(ctx.need[:3]) else None
-            ctx.w1q_t = w1q.t() if need_x else None
-            ctx.v1q_t = v1q.t() if need_x else None
-            ctx.save_for_backward(g.data, u.data, xqt, xst)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        g_data, u_data, xqt, xst = ctx.saved_tensors
-        need_x, need_w1, need_v1, need_w2 = ctx.need
-        w1_sink, v1_sink, w2_sink = ctx.sinks
-        topo, act, mode, pow2 = ctx.topo, ctx.act, ctx.mode, ctx.pow2
-        meta, nb, dt, dev = topo._meta, topo.nnz_blocks, g_data.dtype, dy.device
-        need_d = need_x or need_w1 or need_v1
-        dyq, dys, dyqt, dyst = quantize_tiles(dy, rows=need_d, cols=need_w2,
-                                              pow2=pow2)
-
-        def wgrad(st, bqt, bst, sink):
-            if sink is not None:
-                dsd_fp8_wgrad(st, bqt, bst, sink, True, accumulate=mode)
-                return None
-            return dsd_fp8_wgrad(st, bqt, bst, out_dtype=dt, accumulate=mode)
-
-        dx = dw1 = dv1 = dw2 = None
-        if need_w2:                                   # H^T dY
-            meta.ensure_transposed(u_data)
-            h = _fp8_images(nb, False, True, dev)
-            if nb:
-                QuantizeBlocksGated(meta.descriptor(u_data), g_data, act, *h,
-                                    pow2=pow2)
-            dw2 = wgrad(_fp8_views(topo, h)[1], dyqt, dyst, w2_sink)
-            del h
-        if need_d:
-            d = sdd_fp8(dyq, dys, ctx.w2q_t, topo, dt, mode)    # dY W2^T
-            # dG = D U act'(G) and dU = D act(G), each along the axes its
-            # products read, from one pass over D, G and U
-            if need_w1 or need_v1:
-                meta.ensure_transposed(u_data)
-            dg = _fp8_images(nb, need_x, need_w1, dev)
-            du = _fp8_images(nb, need_x, need_v1, dev)
-            if nb:
-                QuantizeBlocksGatedGrad(meta.descriptor(d.data), g_data,
-                                        u_data, act, dg, du, pow2)
-            dgq, dgt = _fp8_views(topo, dg)
-            duq, dut = _fp8_views(topo, du)
-            if need_x:                                # dG W1t + dU V1t
-                dx = dsd_fp8_pair(dgq, ctx.w1q_t, duq, ctx.v1q_t, dt, mode)
-            if need_w1:                               # dG^T X
-                dw1 = wgrad(dgt, xqt, xst, w1_sink)
-            if need_v1:                               # dU^T X
-                dv1 = wgrad(dut, xqt, xst, v1_sink)
-        return (dx, dw1, dv1, dw2) + (None,) * 7
-
-
-def _glu_fp8_sinks(x, w2, sinks, what: str):
-    for sink, name in zip(sinks, ("w1t_grad_out", "v1t_grad_out",
-                                  "w2_grad_out")):
-        if sink is not None:
-            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
-                        f"{what}: {name}")
+def mlp_mx(x: torch.Tensor, w1t: torch.Tensor, w2: torch.Tensor,
+           topo: SparseMatrix, activation="gelu",
+           dw1t_out: Optional[torch.Tensor] = None,
+           dw2_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The expert MLP with its three products in MXFP8, forward and backward:
+    y = act(x w1t^T at topo's blocks) w2 over 16-bit x [T, h], w1t [F, h] and
+    w2 [F, h] (MegaBlocks' orientation), topo [T, F]. Forward quantises the
+    weights (quantize_weight_mx) and runs quantize_rows_mx -> sdd_mx ->
+    quantize_sparse_mx(activation) -> dsd_mx, bit for bit. Backward
+    (sputnik/block/mx.h, "Gradients"): dH = dY W2^T by sdd_mx, dZ = dH *
+    act'(Z) fused into the quantiser, dX = dZ W1t by dsd_mx, and dW2 = H^T
+    dY, dW1t = dZ^T X by dsd_mx_wgrad with both operands scaled per 32 tokens
+    x 1 column; the weights' backward layouts are quantised from the 16-bit
+    weights. The gradients are straight-through: taken with respect to the
+    16-bit inputs, in their dtype. A sink (`dw1t_out`, `dw2_out`: contiguous
+    [F, h], x's dtype or fp32) receives sink += gradient, rounded once, in
+    place of a returned gradient. What needs_input_grad does not ask for is
+    skipped. There are no biases and no MXFP4 weights; glu_mlp_mx is the
+    gated form."""
+    return _lowp_mlp(_MX, "mlp_mx", x, w1t, None, w2, topo, activation, {},
+                     {}, (dw1t_out, dw2_out), ("dw1t_out", "dw2_out"))
 
 
 def glu_mlp_fp8(x: torch.Tensor, w1t: torch.Tensor, v1t: torch.Tensor,
@@ -2594,453 +2744,10 @@ def glu_mlp_fp8(x: torch.Tensor, w1t: torch.Tensor, v1t: torch.Tensor,
     needs_input_grad and the sinks do not ask for is skipped. There are no
     biases."""
     _accumulate(accumulate, "glu_mlp_fp8")
-    _check_dtypes(x, w1t, v1t, w2)
-    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
-        raise TypeError("glu_mlp_fp8: topo must be a SparseMatrix (not a "
-                        ".t() view)")
-    if (x.dim() != 2 or w1t.dim() != 2
-            or tuple(w1t.shape) != tuple(w2.shape)
-            or tuple(v1t.shape) != tuple(w2.shape)
-            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
-            or int(w1t.shape[1]) != int(x.shape[1])
-            or int(x.shape[1]) % BLOCK):
-        raise ValueError("glu_mlp_fp8: x [T, h], w1t, v1t and w2 [F, h], "
-                         "topo [T, F], all multiples of 128")
-    _glu_fp8_sinks(x, w2, (w1t_grad_out, v1t_grad_out, w2_grad_out),
-                   "glu_mlp_fp8")
-    return _GLUMLPFp8.apply(x.contiguous(), w1t.contiguous(),
-                            v1t.contiguous(), w2.contiguous(), topo,
-                            _act_code(activation), accumulate, bool(pow2),
-                            w1t_grad_out, v1t_grad_out, w2_grad_out)
-
-
-def moe_glu_mlp_fp8_train(x: torch.Tensor, top_experts: torch.Tensor,
-                          expert_weights: torch.Tensor, w1t: torch.Tensor,
-                          v1t: torch.Tensor, w2: torch.Tensor,
-                          num_experts: int, activation=None,
-                          rows: Optional[int] = None,
-                          accumulate: str = "fp32", pow2: bool = False,
-                          w1t_grad_out: Optional[torch.Tensor] = None,
-                          v1t_grad_out: Optional[torch.Tensor] = None,
-                          w2_grad_out: Optional[torch.Tensor] = None
-                          ) -> torch.Tensor:
-    """moe_mlp's gated form with the expert products in fp8 and gradients:
-    padded_gather -> glu_mlp_fp8 -> padded_scatter, the permutation with its
-    existing gradients. w1t, v1t and w2 are 16-bit [num_experts * ffn,
-    d_model]; the other arguments are moe_mlp's (activation None: "silu").
-    Differentiable in x, expert_weights, w1t, v1t and w2."""
-    _accumulate(accumulate, "moe_glu_mlp_fp8_train")
-    for w, name in ((w1t, "w1t"), (v1t, "v1t")):
-        if not isinstance(w, torch.Tensor) or w.dim() != 2:
-            raise ValueError(f"moe_glu_mlp_fp8_train: {name} is [E * ffn, "
-                             "d_model]")
-    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
-                              v1t.t(), num_experts, rows)
-    _glu_fp8_sinks(x, w2, (w1t_grad_out, v1t_grad_out, w2_grad_out),
-                   "moe_glu_mlp_fp8_train")
-    if route is None:
-        route = moe_route(top_experts, num_experts, rows)
-    xp = padded_gather(x, route)
-    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
-                           route.rows // BLOCK, dtype=x.dtype)
-    y = glu_mlp_fp8(xp, w1t, v1t, w2, topo, "silu" if activation is None else
-                    activation, accumulate, pow2, w1t_grad_out, v1t_grad_out,
-                    w2_grad_out)
-    return padded_scatter(y, route, expert_weights)
-
-
-# ---- MoE router -------------------------------------------------------------
-
-# ---- MX gradients (sputnik/block/mx.h, "Gradients") --------------------------
-
-def quantize_tiles_mx(x: torch.Tensor, rows: bool = True, cols: bool = True):
-    """(q, scales, qt, scales_t) of x [rows, cols] (fp16 / bf16, both
-    multiples of 128) as MXFP8, read once: q / scales as quantize_rows_mx,
-    bit for bit; qt torch.float8_e4m3fn [cols, rows] and scales_t uint8
-    [cols, rows / 32], one e8m0 byte per column and 32 rows: x^T as an MX
-    weight, the dense operand of dsd_mx_wgrad. A pair that is not asked for
-    is (None, None)."""
-    _check_dtypes(x)
-    _no_grad("quantize_tiles_mx", x)
-    if x.dim() != 2 or int(x.shape[0]) % BLOCK or int(x.shape[1]) % BLOCK:
-        raise ValueError("quantize_tiles_mx: x is 2-D with multiples of 128")
-    if not (rows or cols):
-        raise ValueError("quantize_tiles_mx: no output asked for")
-    x = x.contiguous()
-    m, n = int(x.shape[0]), int(x.shape[1])
-    q = s = qt = st = None
-    if rows:
-        q = torch.empty(m, n, dtype=torch.float8_e4m3fn, device=x.device)
-        s = torch.empty(m, n // 32, dtype=torch.uint8, device=x.device)
-    if cols:
-        qt = torch.empty(n, m, dtype=torch.float8_e4m3fn, device=x.device)
-        st = torch.empty(n, m // 32, dtype=torch.uint8, device=x.device)
-    QuantizeTilesMx(x, q, s, qt, st)
-    return q, s, qt, st
-
-
-def _quantize_blocks_mx(sparse: SparseMatrix, stage, act, z, rows: bool,
-                        cols: bool):
-    """QuantizeBlocksMx over sparse's block values: (the MxSparseMatrix of
-    sparse's topology or None, the MxSparseMatrix of the transposed topology
-    or None)."""
-    meta, nb = sparse._meta, sparse.nnz_blocks
-    data = sparse.data.contiguous()
-    dev = data.device
-    q = s = qt = st = None
-    if rows:
-        q = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
-                        device=dev)
-        s = torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=dev)
-    if cols:
-        meta.ensure_transposed(data)
-        qt = torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
-                         device=dev)
-        st = torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=dev)
-    if nb:
-        QuantizeBlocksMx(meta.descriptor(data), q, s, qt, st, stage, act,
-                         None if z is None else z.contiguous())
-    by_rows = MxSparseMatrix(sparse, q, s) if rows else None
-    by_cols = None
-    if cols:
-        by_cols = MxSparseMatrix(
-            SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
-                         meta.indices_t), qt, st)
-    return by_rows, by_cols
-
-
-def quantize_sparse_mx_t(sparse: SparseMatrix, activation=None,
-                         z: Optional[SparseMatrix] = None
-                         ) -> Tuple[MxSparseMatrix, MxSparseMatrix]:
-    """(the MxSparseMatrix of `sparse`, the MxSparseMatrix of sparse^T) from
-    one pass over the block values. The first is quantize_sparse_mx's, bit
-    for bit, the operand of dsd_mx; the second holds sparse's blocks
-    transposed and in the transposed order, scaled per source column and 32
-    source rows, the sparse operand of dsd_mx_wgrad. With `activation` alone
-    act(sparse) is quantised; with `z` (same topology and dtype) sparse *
-    act'(z), as sdd_act's gradient evaluates it, rounded to sparse's dtype
-    first."""
-    if not isinstance(sparse, SparseMatrix) or sparse.is_transposed():
-        raise TypeError("quantize_sparse_mx_t takes a SparseMatrix (not a "
-                        ".t() view)")
-    _check_dtypes(sparse.data)
-    _no_grad("quantize_sparse_mx_t", sparse.data,
-             None if z is None else z.data)
-    stage = None
-    if z is not None:
-        if (not isinstance(z, SparseMatrix) or z._meta is not sparse._meta
-                or z.is_transposed() or z.dtype != sparse.dtype):
-            raise ValueError("quantize_sparse_mx_t: z must share sparse's "
-                             "topology and dtype")
-        if activation is None:
-            raise ValueError("quantize_sparse_mx_t: z needs its activation")
-        stage = "act_grad"
-    elif activation is not None:
-        stage = "act"
-    act = None if activation is None else _act_code(activation)
-    return _quantize_blocks_mx(sparse, stage, act,
-                               None if z is None else z.data, True, True)
-
-
-def dsd_mx_wgrad(st: MxSparseMatrix, bqt: torch.Tensor, bst: torch.Tensor,
-                 out: Optional[torch.Tensor] = None, add: bool = False,
-                 out_dtype=torch.bfloat16) -> torch.Tensor:
-    """st . B as a dense [m, n] tensor, the weight-gradient product in MXFP8:
-    st the transposed half of quantize_sparse_mx_t ([m, k], k the token
-    dimension), B [k, n] given as quantize_tiles_mx' column pair bqt [n, k],
-    bst [n, k / 32]. dsd_mx's arithmetic. Writes `out` (contiguous [m, n],
-    fp16 / bf16 / fp32) or a new tensor of `out_dtype` (the same three); with
-    `add`, out = round(acc + out), rounded once, and rows that meet no block
-    of st are left untouched. Bitwise reproducible."""
-    if not isinstance(st, MxSparseMatrix):
-        raise TypeError("dsd_mx_wgrad: st must come from "
-                        "quantize_sparse_mx_t")
-    if not isinstance(bqt, torch.Tensor) or bqt.dim() != 2:
-        raise TypeError("dsd_mx_wgrad: bqt is quantize_tiles_mx' qt")
-    m, n = st.shape[0], int(bqt.shape[0])
-    if st.shape[1] != int(bqt.shape[1]):
-        raise ValueError(f"dsd_mx_wgrad shapes {st.shape} x "
-                         f"{(int(bqt.shape[1]), n)}")
-    kinds = (torch.float16, torch.bfloat16, torch.float32)
-    if out is None:
-        if add:
-            raise ValueError("dsd_mx_wgrad: add needs `out`")
-        if out_dtype not in kinds:
-            raise TypeError("dsd_mx_wgrad: out_dtype must be torch.float16, "
-                            "torch.bfloat16 or torch.float32")
-        out = torch.empty(m, n, dtype=out_dtype, device=bqt.device)
-    else:
-        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != (m, n)
-                or not out.is_contiguous()):
-            raise ValueError(f"dsd_mx_wgrad: out must be a contiguous "
-                             f"{(m, n)} tensor")
-        if out.dtype not in kinds:
-            raise TypeError("dsd_mx_wgrad: out must be fp16, bf16 or fp32")
-    DsdMxWgrad(st._descriptor(), st.scales, bqt, bst, Matrix(m, n, out),
-               add=add)
-    return out
-
-
-class _MLPMx(torch.autograd.Function):
-    """y = dsd_mx(quantize_sparse_mx(sdd_mx(x, w1t^T), act), w2) and the
-    backward pass of mx.h's table. Keeps Z, the column quantisation of X
-    (bytes, not the 16-bit X) and the 16-bit weights: an MX weight has no
-    exact transpose, so the backward layouts are quantised in backward."""
-
-    @staticmethod
-    def forward(ctx, x, w1t, w2, topo, act, w1_sink, w2_sink):
-        need_x, need_w1, need_w2 = ctx.needs_input_grad[:3]
-        need_w1 = need_w1 or w1_sink is not None
-        need_w2 = need_w2 or w2_sink is not None
-        ctx.topo, ctx.act = topo, act
-        ctx.w1_sink, ctx.w2_sink = w1_sink, w2_sink
-        ctx.need = (need_x, need_w1, need_w2)
-        w1q = quantize_weight_mx(w1t, transpose=True)           # [h, F]
-        w2q = quantize_weight_mx(w2)                            # [F, h]
-        xq, xs, xqt, xst = quantize_tiles_mx(x, cols=need_w1)
-        z = sdd_mx(xq, xs, w1q, topo, x.dtype)
-        y = dsd_mx(quantize_sparse_mx(z, act), w2q, x.dtype)
-        if any(ctx.need):
-            ctx.save_for_backward(z.data, xqt, xst,
-                                  w1t if need_x else None,
-                                  w2 if need_x or need_w1 else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        z_data, xqt, xst, w1t, w2 = ctx.saved_tensors
-        need_x, need_w1, need_w2 = ctx.need
-        topo, act = ctx.topo, ctx.act
-        z = topo.with_data(z_data)
-        dt = z_data.dtype
-        dx = dw1 = dw2 = None
-        need_dz = need_x or need_w1
-        dyq, dys, dyqt, dyst = quantize_tiles_mx(dy.contiguous(), rows=need_dz,
-                                                 cols=need_w2)
-        if need_w2:                                   # H^T dY
-            ht = _quantize_blocks_mx(z, "act", act, None, False, True)[1]
-            if ctx.w2_sink is not None:
-                dsd_mx_wgrad(ht, dyqt, dyst, ctx.w2_sink, True)
-            else:
-                dw2 = dsd_mx_wgrad(ht, dyqt, dyst, out_dtype=dt)
-            del ht
-        if need_dz:
-            # dY W2^T: W2 read as [n = F, k = h]
-            dh = sdd_mx(dyq, dys, quantize_weight_mx(w2, transpose=True),
-                        topo, dt)
-            # dZ = dH * act'(Z), quantised along both axes in one pass
-            dzq, dzt = _quantize_blocks_mx(dh, "act_grad", act, z_data,
-                                           need_x, need_w1)
-            if need_x:                                # dZ W1t: [k = F, n = h]
-                dx = dsd_mx(dzq, quantize_weight_mx(w1t), dt)
-            if ctx.w1_sink is not None:               # dZ^T X
-                dsd_mx_wgrad(dzt, xqt, xst, ctx.w1_sink, True)
-            elif need_w1:
-                dw1 = dsd_mx_wgrad(dzt, xqt, xst, out_dtype=dt)
-        return dx, dw1, dw2, None, None, None, None
-
-
-def mlp_mx(x: torch.Tensor, w1t: torch.Tensor, w2: torch.Tensor,
-           topo: SparseMatrix, activation="gelu",
-           dw1t_out: Optional[torch.Tensor] = None,
-           dw2_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The expert MLP with its three products in MXFP8, forward and backward:
-    y = act(x w1t^T at topo's blocks) w2 over 16-bit x [T, h], w1t [F, h] and
-    w2 [F, h] (MegaBlocks' orientation), topo [T, F]. Forward quantises the
-    weights (quantize_weight_mx) and runs quantize_rows_mx -> sdd_mx ->
-    quantize_sparse_mx(activation) -> dsd_mx, bit for bit. Backward
-    (sputnik/block/mx.h, "Gradients"): dH = dY W2^T by sdd_mx, dZ = dH *
-    act'(Z) fused into the quantiser, dX = dZ W1t by dsd_mx, and dW2 = H^T
-    dY, dW1t = dZ^T X by dsd_mx_wgrad with both operands scaled per 32 tokens
-    x 1 column; the weights' backward layouts are quantised from the 16-bit
-    weights. The gradients are straight-through: taken with respect to the
-    16-bit inputs, in their dtype. A sink (`dw1t_out`, `dw2_out`: contiguous
-    [F, h], x's dtype or fp32) receives sink += gradient, rounded once, in
-    place of a returned gradient. What needs_input_grad does not ask for is
-    skipped. There are no biases and no MXFP4 weights; glu_mlp_mx is the
-    gated form."""
-    _check_dtypes(x, w1t, w2)
-    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
-        raise TypeError("mlp_mx: topo must be a SparseMatrix (not a .t() "
-                        "view)")
-    if (x.dim() != 2 or w1t.dim() != 2 or tuple(w1t.shape) != tuple(w2.shape)
-            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
-            or int(w1t.shape[1]) != int(x.shape[1])
-            or int(x.shape[1]) % BLOCK):
-        raise ValueError("mlp_mx: x [T, h], w1t and w2 [F, h], topo [T, F], "
-                         "all multiples of 128")
-    for sink, what in ((dw1t_out, "dw1t_out"), (dw2_out, "dw2_out")):
-        if sink is not None:
-            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
-                        f"mlp_mx: {what}")
-    return _MLPMx.apply(x.contiguous(), w1t.contiguous(), w2.contiguous(),
-                        topo, _act_code(activation), dw1t_out, dw2_out)
-
-
-def moe_mlp_mx_train(x: torch.Tensor, top_experts: torch.Tensor,
-                     expert_weights: torch.Tensor, w1t: torch.Tensor,
-                     w2: torch.Tensor, num_experts: int, activation=None,
-                     rows: Optional[int] = None,
-                     dw1t_out: Optional[torch.Tensor] = None,
-                     dw2_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """moe_mlp with the expert products in MXFP8 and gradients: padded_gather
-    -> mlp_mx -> padded_scatter, the permutation with its existing gradients.
-    w1t and w2 are 16-bit [num_experts * ffn, d_model]; the other arguments
-    are moe_mlp's (activation None: "gelu"). Differentiable in x,
-    expert_weights, w1t and w2."""
-    if not isinstance(w1t, torch.Tensor) or w1t.dim() != 2:
-        raise ValueError("moe_mlp_mx_train: w1t is [E * ffn, d_model]")
-    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
-                              None, num_experts, rows)
-    if route is None:
-        route = moe_route(top_experts, num_experts, rows)
-    xp = padded_gather(x, route)
-    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
-                           route.rows // BLOCK, dtype=x.dtype)
-    y = mlp_mx(xp, w1t, w2, topo, "gelu" if activation is None else
-               activation, dw1t_out, dw2_out)
-    return padded_scatter(y, route, expert_weights)
-
-
-# ---- MX gradients of a gated expert (mx.h, "Gradients of a gated expert") ----
-
-def _mx_images(nb: int, rows: bool, cols: bool, dev):
-    """(q, scales, qt, scales_t) buffers of an MX block quantiser, None for a
-    pair that is not asked for."""
-    out = []
-    for want in (rows, cols):
-        out += [torch.empty(nb, BLOCK, BLOCK, dtype=torch.float8_e4m3fn,
-                            device=dev) if want else None,
-                torch.empty(nb * BLOCK, 4, dtype=torch.uint8, device=dev)
-                if want else None]
-    return tuple(out)
-
-
-def _mx_views(topo: SparseMatrix, images):
-    """(the MxSparseMatrix of topo's topology or None, that of the
-    transposed topology or None) over the images a block quantiser filled."""
-    q, s, qt, st = images
-    meta = topo._meta
-    by_rows = None if q is None else MxSparseMatrix(topo, q, s)
-    by_cols = None if qt is None else MxSparseMatrix(
-        SparseMatrix((meta.cols, meta.rows), qt, meta.offsets_t,
-                     meta.indices_t), qt, st)
-    return by_rows, by_cols
-
-
-def dsd_mx_pair(sq1: MxSparseMatrix, w1: MxWeight, sq2: MxSparseMatrix,
-                w2: MxWeight, out_dtype=torch.bfloat16) -> torch.Tensor:
-    """sq1 . w1 + sq2 . w2 as a dense [m, n] tensor of `out_dtype`, both
-    products in MXFP8 through one fp32 accumulator and rounded once: sq1 and
-    sq2 are quantised block values on one topology (the same metadata), w1
-    and w2 two e4m3 MxWeights of [k, n]. Bit for bit dsd_mx over the
-    concatenated operands [sq1 | sq2] . [w1; w2], which are never formed: a
-    block row takes sq1's blocks in storage order, then sq2's. The dX of a
-    gated expert. Forward only."""
-    if (not isinstance(sq1, MxSparseMatrix)
-            or not isinstance(sq2, MxSparseMatrix)):
-        raise TypeError("dsd_mx_pair: sq1 and sq2 must be MxSparseMatrix")
-    if sq1._meta is not sq2._meta or sq1.is_transposed() != sq2.is_transposed():
-        raise ValueError("dsd_mx_pair: sq1 and sq2 must share one topology")
-    if not isinstance(w1, MxWeight) or not isinstance(w2, MxWeight):
-        raise TypeError("dsd_mx_pair: w1 and w2 must be MxWeights")
-    if w1.format != "e4m3" or w2.format != "e4m3":
-        raise ValueError("dsd_mx_pair: the weights must be 'e4m3'")
-    _out_dtype(out_dtype, "dsd_mx_pair")
-    if sq1.shape[1] != w1.k or w1.shape != w2.shape:
-        raise ValueError(f"dsd_mx_pair shapes {sq1.shape} x {w1.shape} + "
-                         f"{sq2.shape} x {w2.shape}")
-    out = torch.empty(sq1.shape[0], w1.n, dtype=out_dtype, device=sq1.device)
-    DsdMxPair(sq1._descriptor(), sq1.scales, w1.q, w1.scales, sq2.data,
-              sq2.scales, w2.q, w2.scales,
-              Matrix(out.shape[0], out.shape[1], out))
-    return out
-
-
-class _GLUMLPMx(torch.autograd.Function):
-    """y = dsd_mx(quantize_sparse_mx(sdd_mx(x, v1t^T), act, gate=sdd_mx(x,
-    w1t^T)), w2) and the backward pass of mx.h's gated table. Keeps G, U, the
-    column quantisation of X and the 16-bit weights, whose backward layouts
-    are quantised in backward, as _MLPMx has it."""
-
-    @staticmethod
-    def forward(ctx, x, w1t, v1t, w2, topo, act, w1_sink, v1_sink, w2_sink):
-        need_x, need_w1, need_v1, need_w2 = ctx.needs_input_grad[:4]
-        need_w1 = need_w1 or w1_sink is not None
-        need_v1 = need_v1 or v1_sink is not None
-        need_w2 = need_w2 or w2_sink is not None
-        ctx.topo, ctx.act = topo, act
-        ctx.sinks = (w1_sink, v1_sink, w2_sink)
-        ctx.need = (need_x, need_w1, need_v1, need_w2)
-        w1q = quantize_weight_mx(w1t, transpose=True)           # [h, F]
-        v1q = quantize_weight_mx(v1t, transpose=True)           # [h, F]
-        w2q = quantize_weight_mx(w2)                            # [F, h]
-        xq, xs, xqt, xst = quantize_tiles_mx(x, cols=need_w1 or need_v1)
-        g = sdd_mx(xq, xs, w1q, topo, x.dtype)
-        u = sdd_mx(xq, xs, v1q, topo, x.dtype)
-        y = dsd_mx(quantize_sparse_mx(u, act, gate=g), w2q, x.dtype)
-        if any(ctx.need):
-            ctx.save_for_backward(g.data, u.data, xqt, xst,
-                                  w1t if need_x else None,
-                                  v1t if need_x else None,
-                                  w2 if any(ctx.need[:3]) else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        g_data, u_data, xqt, xst, w1t, v1t, w2 = ctx.saved_tensors
-        need_x, need_w1, need_v1, need_w2 = ctx.need
-        w1_sink, v1_sink, w2_sink = ctx.sinks
-        topo, act = ctx.topo, ctx.act
-        meta, nb, dt, dev = topo._meta, topo.nnz_blocks, g_data.dtype, dy.device
-        need_d = need_x or need_w1 or need_v1
-        dyq, dys, dyqt, dyst = quantize_tiles_mx(dy.contiguous(), rows=need_d,
-                                                 cols=need_w2)
-
-        def wgrad(st, bqt, bst, sink):
-            if sink is not None:
-                dsd_mx_wgrad(st, bqt, bst, sink, True)
-                return None
-            return dsd_mx_wgrad(st, bqt, bst, out_dtype=dt)
-
-        dx = dw1 = dv1 = dw2 = None
-        if need_w2:                                   # H^T dY
-            meta.ensure_transposed(u_data)
-            h = _mx_images(nb, False, True, dev)
-            if nb:
-                QuantizeBlocksMxGated(meta.descriptor(u_data), g_data, act, *h)
-            dw2 = wgrad(_mx_views(topo, h)[1], dyqt, dyst, w2_sink)
-            del h
-        if need_d:
-            # D = dY W2^T: W2 read as [n = F, k = h]
-            d = sdd_mx(dyq, dys, quantize_weight_mx(w2, transpose=True), topo,
-                       dt)
-            # dG = D U act'(G) and dU = D act(G), each along the axes its
-            # products read, from one pass over D, G and U
-            if need_w1 or need_v1:
-                meta.ensure_transposed(u_data)
-            dg = _mx_images(nb, need_x, need_w1, dev)
-            du = _mx_images(nb, need_x, need_v1, dev)
-            if nb:
-                QuantizeBlocksMxGatedGrad(meta.descriptor(d.data), g_data,
-                                          u_data, act, dg, du)
-            dgq, dgt = _mx_views(topo, dg)
-            duq, dut = _mx_views(topo, du)
-            if need_x:              # dG W1t + dU V1t: each [k = F, n = h]
-                dx = dsd_mx_pair(dgq, quantize_weight_mx(w1t), duq,
-                                 quantize_weight_mx(v1t), dt)
-            if need_w1:                               # dG^T X
-                dw1 = wgrad(dgt, xqt, xst, w1_sink)
-            if need_v1:                               # dU^T X
-                dv1 = wgrad(dut, xqt, xst, v1_sink)
-        return (dx, dw1, dv1, dw2) + (None,) * 5
-
-
-def _glu_mx_sinks(x, w2, sinks, what: str):
-    for sink, name in zip(sinks, ("dw1t_out", "dv1t_out", "dw2_out")):
-        if sink is not None:
-            _check_sink(sink, int(w2.shape[0]), int(w2.shape[1]), x.dtype,
-                        f"{what}: {name}")
+    return _lowp_mlp(_FP8, "glu_mlp_fp8", x, w1t, v1t, w2, topo, activation,
+                     {"pow2": bool(pow2)}, {"accumulate": accumulate},
+                     (w1t_grad_out, v1t_grad_out, w2_grad_out),
+                     _FP8_SINKS)
 
 
 def glu_mlp_mx(x: torch.Tensor, w1t: torch.Tensor, v1t: torch.Tensor,
@@ -3064,22 +2771,96 @@ def glu_mlp_mx(x: torch.Tensor, w1t: torch.Tensor, v1t: torch.Tensor,
     sink += gradient, rounded once, in place of a returned gradient. What
     needs_input_grad and the sinks do not ask for is skipped. There are no
     biases and no MXFP4 weights."""
-    _check_dtypes(x, w1t, v1t, w2)
-    if not isinstance(topo, SparseMatrix) or topo.is_transposed():
-        raise TypeError("glu_mlp_mx: topo must be a SparseMatrix (not a "
-                        ".t() view)")
-    if (x.dim() != 2 or w1t.dim() != 2
-            or tuple(w1t.shape) != tuple(w2.shape)
-            or tuple(v1t.shape) != tuple(w2.shape)
-            or tuple(topo.shape) != (int(x.shape[0]), int(w1t.shape[0]))
-            or int(w1t.shape[1]) != int(x.shape[1])
-            or int(x.shape[1]) % BLOCK):
-        raise ValueError("glu_mlp_mx: x [T, h], w1t, v1t and w2 [F, h], "
-                         "topo [T, F], all multiples of 128")
-    _glu_mx_sinks(x, w2, (dw1t_out, dv1t_out, dw2_out), "glu_mlp_mx")
-    return _GLUMLPMx.apply(x.contiguous(), w1t.contiguous(),
-                           v1t.contiguous(), w2.contiguous(), topo,
-                           _act_code(activation), dw1t_out, dv1t_out, dw2_out)
+    return _lowp_mlp(_MX, "glu_mlp_mx", x, w1t, v1t, w2, topo, activation,
+                     {}, {}, (dw1t_out, dv1t_out, dw2_out), _MX_SINKS)
+
+
+def _moe_lowp_train(what: str, expert, x, top_experts, expert_weights, w1t,
+                    v1t, w2, num_experts, activation, rows, sinks, names):
+    """moe_*_train: padded_gather -> expert(xp, topo, activation) ->
+    padded_scatter; v1t None for the plain expert."""
+    gated = v1t is not None
+    for w, name in ((w1t, "w1t"), (v1t, "v1t"))[:1 + gated]:
+        if not isinstance(w, torch.Tensor) or w.dim() != 2:
+            raise ValueError(f"{what}: {name} is [E * ffn, d_model]")
+    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
+                              v1t.t() if gated else None, num_experts, rows)
+    if gated:
+        _check_sinks(x, w2, sinks, names, what)
+    if route is None:
+        route = moe_route(top_experts, num_experts, rows)
+    xp = padded_gather(x, route)
+    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
+                           route.rows // BLOCK, dtype=x.dtype)
+    if activation is None:
+        activation = "silu" if gated else "gelu"
+    return padded_scatter(expert(xp, topo, activation), route, expert_weights)
+
+
+def moe_mlp_fp8_train(x: torch.Tensor, top_experts: torch.Tensor,
+                      expert_weights: torch.Tensor, w1t: torch.Tensor,
+                      w2: torch.Tensor, num_experts: int, activation=None,
+                      rows: Optional[int] = None, accumulate: str = "fp32",
+                      pow2: bool = False,
+                      w1t_grad_out: Optional[torch.Tensor] = None,
+                      w2_grad_out: Optional[torch.Tensor] = None
+                      ) -> torch.Tensor:
+    """moe_mlp with the expert products in fp8 and gradients: padded_gather
+    -> mlp_fp8 -> padded_scatter, the permutation with its existing
+    gradients. w1t and w2 are 16-bit [num_experts * ffn, d_model]; the other
+    arguments are moe_mlp's (activation None: "gelu"). Differentiable in x,
+    expert_weights, w1t and w2."""
+    _accumulate(accumulate, "moe_mlp_fp8_train")
+    return _moe_lowp_train(
+        "moe_mlp_fp8_train",
+        lambda xp, topo, act: mlp_fp8(xp, w1t, w2, topo, act, accumulate,
+                                      pow2, w1t_grad_out, w2_grad_out),
+        x, top_experts, expert_weights, w1t, None, w2, num_experts,
+        activation, rows, (), ())
+
+
+def moe_mlp_mx_train(x: torch.Tensor, top_experts: torch.Tensor,
+                     expert_weights: torch.Tensor, w1t: torch.Tensor,
+                     w2: torch.Tensor, num_experts: int, activation=None,
+                     rows: Optional[int] = None,
+                     dw1t_out: Optional[torch.Tensor] = None,
+                     dw2_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moe_mlp with the expert products in MXFP8 and gradients: padded_gather
+    -> mlp_mx -> padded_scatter, the permutation with its existing gradients.
+    w1t and w2 are 16-bit [num_experts * ffn, d_model]; the other arguments
+    are moe_mlp's (activation None: "gelu"). Differentiable in x,
+    expert_weights, w1t and w2."""
+    return _moe_lowp_train(
+        "moe_mlp_mx_train",
+        lambda xp, topo, act: mlp_mx(xp, w1t, w2, topo, act, dw1t_out,
+                                     dw2_out),
+        x, top_experts, expert_weights, w1t, None, w2, num_experts,
+        activation, rows, (), ())
+
+
+def moe_glu_mlp_fp8_train(x: torch.Tensor, top_experts: torch.Tensor,
+                          expert_weights: torch.Tensor, w1t: torch.Tensor,
+                          v1t: torch.Tensor, w2: torch.Tensor,
+                          num_experts: int, activation=None,
+                          rows: Optional[int] = None,
+                          accumulate: str = "fp32", pow2: bool = False,
+                          w1t_grad_out: Optional[torch.Tensor] = None,
+                          v1t_grad_out: Optional[torch.Tensor] = None,
+                          w2_grad_out: Optional[torch.Tensor] = None
+                          ) -> torch.Tensor:
+    """moe_mlp's gated form with the expert products in fp8 and gradients:
+    padded_gather -> glu_mlp_fp8 -> padded_scatter, the permutation with its
+    existing gradients. w1t, v1t and w2 are 16-bit [num_experts * ffn,
+    d_model]; the other arguments are moe_mlp's (activation None: "silu").
+    Differentiable in x, expert_weights, w1t, v1t and w2."""
+    _accumulate(accumulate, "moe_glu_mlp_fp8_train")
+    sinks = (w1t_grad_out, v1t_grad_out, w2_grad_out)
+    return _moe_lowp_train(
+        "moe_glu_mlp_fp8_train",
+        lambda xp, topo, act: glu_mlp_fp8(xp, w1t, v1t, w2, topo, act,
+                                          accumulate, pow2, *sinks),
+        x, top_experts, expert_weights, w1t, v1t, w2, num_experts,
+        activation, rows, sinks, _FP8_SINKS)
 
 
 def moe_glu_mlp_mx_train(x: torch.Tensor, top_experts: torch.Tensor,
@@ -3096,23 +2877,15 @@ def moe_glu_mlp_mx_train(x: torch.Tensor, top_experts: torch.Tensor,
     existing gradients. w1t, v1t and w2 are 16-bit [num_experts * ffn,
     d_model]; the other arguments are moe_mlp's (activation None: "silu").
     Differentiable in x, expert_weights, w1t, v1t and w2."""
-    for w, name in ((w1t, "w1t"), (v1t, "v1t")):
-        if not isinstance(w, torch.Tensor) or w.dim() != 2:
-            raise ValueError(f"moe_glu_mlp_mx_train: {name} is [E * ffn, "
-                             "d_model]")
-    route, hidden = _moe_args(x, top_experts, expert_weights, w1t.t(), w2,
-                              v1t.t(), num_experts, rows)
-    _glu_mx_sinks(x, w2, (dw1t_out, dv1t_out, dw2_out),
-                  "moe_glu_mlp_mx_train")
-    if route is None:
-        route = moe_route(top_experts, num_experts, rows)
-    xp = padded_gather(x, route)
-    topo = expert_topology(route.padded_bins, hidden // num_experts // BLOCK,
-                           route.rows // BLOCK, dtype=x.dtype)
-    y = glu_mlp_mx(xp, w1t, v1t, w2, topo, "silu" if activation is None else
-                   activation, dw1t_out, dv1t_out, dw2_out)
-    return padded_scatter(y, route, expert_weights)
+    sinks = (dw1t_out, dv1t_out, dw2_out)
+    return _moe_lowp_train(
+        "moe_glu_mlp_mx_train",
+        lambda xp, topo, act: glu_mlp_mx(xp, w1t, v1t, w2, topo, act, *sinks),
+        x, top_experts, expert_weights, w1t, v1t, w2, num_experts,
+        activation, rows, sinks, _MX_SINKS)
 
+
+# ---- MoE router -------------------------------------------------------------
 
 def _router_forward(ctx, logits, top_k, normalize, dtype):
     """What _Router and _RouterAux begin with: (contiguous logits, top,

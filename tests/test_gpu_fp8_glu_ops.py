@@ -145,7 +145,8 @@ def test_glu_mlp_fp8_forward_and_every_backward_stage(dtype, act, mode):
     meta.ensure_transposed(u.data)
     meta.ensure_row_indices(u.data)
     s = meta.descriptor(u.data)
-    images = lambda: ops._fp8_images(nb, True, True, "cuda")   # noqa: E731
+    images = lambda: ops._lowp_images(      # noqa: E731
+        ops._FP8, nb, True, True, "cuda")
     dense = lambda: torch.empty(rows, D_MODEL, dtype=td, device="cuda")  # noqa: E731
     w2q_t, w1q_t, v1q_t = w2q.t(), w1q.t(), v1q.t()
     dyq, dys, dyqt, dyst = ops.quantize_tiles(dy)

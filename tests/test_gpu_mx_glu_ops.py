@@ -73,7 +73,8 @@ def test_glu_mlp_mx_forward_and_every_backward_stage(dtype, act):
     def q8(*shape):
         return torch.empty(*shape, dtype=torch.float8_e4m3fn, device="cuda")
 
-    images = lambda: ops._mx_images(nb, True, True, "cuda")    # noqa: E731
+    images = lambda: ops._lowp_images(      # noqa: E731
+        ops._MX, nb, True, True, "cuda")
     w2q_t, w2s_t = q8(HIDDEN, D_MODEL), u8(HIDDEN, D_MODEL // 32)
     sp.QuantizeWeightMx(w2, w2q_t, w2s_t, True)     # [n = F, k = h]
     wq = [(q8(D_MODEL, HIDDEN), u8(D_MODEL, HIDDEN // 32)) for _ in range(2)]
